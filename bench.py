@@ -5,6 +5,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N --dry-launch      rendezvous + bucketed all-reduce only (gloo on a CPU-only box)
+    python bench.py ... --dump-outputs DIR     also write what the last timed step computed as DIR/<name>.npy
 
 One "step" = one full optimisation step (forward + losses + backward + [all-reduce] + clip + Adam,
 train.py:604-785) of builder=deepvoice3 preset=deepvoice3_ljspeech (BASELINE.json configs[1]) on a synthetic
@@ -37,8 +38,9 @@ accumulate; 1e-4 parity with the fp32 reference at the preset sizes), bf16x3, f3
   input_pipeline      the same step fed by data.Prefetcher (rank-sharded length-bucketed sampler, pinned
                       staging, H2D + device-side collate on a side stream) instead of a resident batch
   host_buffers        the step rate if the boundary is handed pinned host tensors synchronously (never `value`)
-  cpu_baseline        the reference's own train.train() on the host cores when the reference tree is present
-                      (kind "reference"), else the CPU oracle port of the same step (kind "port"); bounded sample
+  cpu_baseline        the reference's own train.train() on the host cores when DV3_REFERENCE_ROOT names a reference
+                      tree (kind "reference"), else the CPU oracle port of the same step (kind "port"); bounded sample
+  dump_outputs        --dump-outputs DIR: the files written (dump_outputs() says what they hold)
 """
 import argparse
 import json
@@ -86,6 +88,9 @@ MFMA_RANDOM_OPERANDS_TF = 1681.0      # measured, profiles/r03_mfma_power.txt (z
 PEAK_F32_MFMA_TF = 157.3    # /opt/skills/guides/MI355X_MICROARCH.md: fp32 matrix peak (= vector peak)
 PEAK_16BIT_MFMA_TF = 2500.0  # same guide: dense bf16 / fp16 MFMA peak
 PEAK_HBM_GBS = 8000.0
+SETTLE_MAX_STEPS = 200          # most settle steps TrainRun.measure() runs before --warmup (all of them under --dump-outputs)
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 1 << 22           # ... of which a fixed, seeded sample of this many elements per arena
 
 DTYPE_NOTE = {
     "f16x3": "fp32 operands as scaled fp16 hi+lo (forward GEMMs) / bf16 hi+lo (gradient GEMMs) on the matrix cores, "
@@ -487,8 +492,9 @@ def cpu_baseline_port(B, Tt, n_frames, max_seconds=25.0):
 
 
 def cpu_baseline(B, Tt, n_frames, max_seconds=25.0):
+    # the reference tree is opt-in (DV3_REFERENCE_ROOT): by default the run reads nothing outside the repository
     from oracle import refimport
-    if refimport.available():
+    if os.environ.get("DV3_REFERENCE_ROOT") and refimport.available():
         try:
             return cpu_baseline_reference(B, Tt, n_frames, max_seconds)
         except Exception as e:      # the reference tree is there but does not import here: say so, use the port
@@ -751,9 +757,12 @@ class TrainRun(object):
             return self.runner.step(batch)      # a fresh batch is copied into the captured one first
         return self.trainer.step(batch if batch is not None else self.batch)
 
-    def measure(self, steps, warmup, feed=None, settle_s=0.0):
+    def measure(self, steps, warmup, feed=None, settle_s=0.0, on_last=None):
         """W untimed steps, then exactly K steps bracketed by barrier + synchronize; max over ranks.
-        feed: an iterator of device batches (data.Prefetcher) used instead of the resident batch."""
+        feed: an iterator of device batches (data.Prefetcher) used instead of the resident batch.
+        on_last(trainer, scalars): called once the K timed steps are done and timed, before any further step runs.  It
+        also makes the settle phase a fixed number of steps, so that the state the timed steps start from (and their
+        dropout masks) does not depend on how fast the settle steps ran."""
         pg, dev = self.pg, self.dev
         nxt = (lambda: next(feed)) if feed is not None else (lambda: None)
         comm = self.trainer.comm
@@ -765,7 +774,8 @@ class TrainRun(object):
                 scal = self.step(nxt())
             torch.cuda.synchronize()
             per = max((time.perf_counter() - t_s) / 2, 1e-4)
-            n_settle = torch.tensor([int(min(200, max(0, settle_s / per - 2)))], dtype=torch.int32, device=dev)
+            n_fix = SETTLE_MAX_STEPS - 2 if on_last is not None else settle_s / per - 2
+            n_settle = torch.tensor([int(min(SETTLE_MAX_STEPS, max(0, n_fix)))], dtype=torch.int32, device=dev)
             if pg is not None:
                 torch.distributed.all_reduce(n_settle, op=torch.distributed.ReduceOp.MAX)
             for _ in range(int(n_settle.item())):
@@ -788,6 +798,8 @@ class TrainRun(object):
             torch.distributed.barrier()
         dt = time.perf_counter() - t0
         power = sampler.stop() if sampler is not None else None
+        if on_last is not None:
+            on_last(self.trainer, scal)
         # Host time to issue ONE step into an idle queue.  (t_host above also contains back-pressure: once the host
         # is a few steps ahead the runtime makes it wait -- a replayed hipGraph cannot be launched again while it is
         # in flight, and eager launches block when the queue's kernarg ring is full -- so over a long loop it
@@ -833,6 +845,34 @@ class TrainRun(object):
         self.runner = self.trainer = self.model = self.batch = None
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
+
+
+def dump_outputs(out_dir, trainer, scal, sample=DUMP_SAMPLE, seed=0):
+    """--dump-outputs: what the last timed step computed, as out_dir/<name>.npy, for comparing two builds output for output.
+      <scalar>.npy   every scalar the step returned (loss terms, grad_norm, ...), float64 of shape (1,)
+      params.npy     the parameters the step's clip + Adam wrote (the flat fp32 arena), float32
+      grads.npy      the gradients the step's backward produced (the flat fp32 gradient arena), float32
+    An arena larger than `sample` elements is written as the same fixed, seeded sample of element indices (ascending)
+    every run; the inputs, the initial weights and the dropout seed are seeded too.  Returns the result line's entry."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for k, v in sorted(scal.items()):
+        if torch.is_tensor(v) and v.numel() == 1:
+            arrays[k] = v.detach().reshape(1).double().cpu().numpy()
+    a = trainer.arena
+    idx = None
+    if a.total > sample:
+        idx = np.sort(np.random.RandomState(seed).choice(a.total, sample, replace=False))
+    for name, t in (("params", a.flat), ("grads", a.grad)):
+        h = t.detach().cpu().numpy()
+        arrays[name] = np.ascontiguousarray(h[idx] if idx is not None else h, dtype=np.float32)
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d byte budget" % (total, DUMP_MAX_BYTES))
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return dict(dir=out_dir, files=sorted(n + ".npy" for n in arrays), bytes=int(total), arena_elements=int(a.total),
+                arena_sample=None if idx is None else dict(elements=int(sample), seed=seed))
 
 
 def launch_mode(args, world=1):
@@ -1220,10 +1260,18 @@ def main():
     ap.add_argument("--force-group", action="store_true",
                     help="--gpus 1 only: run the headline step itself under a world-size-1 nccl (RCCL) process group "
                          "(gradient buckets armed); without it the same measurement appears under configs.ddp_world1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (train mode)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="start the N ranks, rendezvous and run the bucketed all-reduce only (no HIP compute; gloo "
                          "on a CPU-only box)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and (args.mode != "train" or args.dry_launch):
+        ap.error("--dump-outputs writes the outputs of the train step (--mode train, no --dry-launch)")
 
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) <= 1:
         # no launcher around us: start the N ranks ourselves (the driver runs `python bench.py --gpus N`)
@@ -1273,7 +1321,17 @@ def main():
         return
 
     run = TrainRun(dev, pg, rank, world, args.preset, gemm, args.batch, args.text_len, args.frames, launch_mode(args, world))
-    m = run.measure(args.steps, args.warmup, settle_s=args.settle)
+    dumped = {}
+    on_last = None
+    if args.dump_outputs and rank == 0:
+        def on_last(trainer, scal):
+            dumped.update(dump_outputs(args.dump_outputs, trainer, scal))
+    elif args.dump_outputs:
+        def on_last(trainer, scal):      # (same fixed settle phase on every rank; rank 0 writes)
+            pass
+    m = run.measure(args.steps, args.warmup, settle_s=args.settle, on_last=on_last)
+    if dumped:
+        dumped.update(hipgraph=bool(run.use_graph), graph_form=run.graph_form())
     m_eager = None
     if run.use_graph and not args.no_extras:
         # the same step launched eagerly: host enqueue time and the all-reduce time left exposed are only observable there
@@ -1304,6 +1362,8 @@ def main():
                                launch_bound=bool(m["host_enqueue_ms_per_step"] > 0.97 * m["ms_per_step"]),
                                settle_s=args.settle),
                    step_flop_frac=m["step_flop_frac"])
+        if dumped:
+            out["dump_outputs"] = dumped
         if pg is not None:
             import torch.distributed as tdist
             out["rccl_ranks"] = tdist.get_world_size(pg)
@@ -1461,8 +1521,20 @@ def main():
                                                            "hbm_frac", "variant")}
     if not args.no_cpu_baseline and world == 1 and args.preset == "deepvoice3_ljspeech":
         out["cpu_baseline"] = cpu_baseline(args.batch, args.text_len, args.frames)
+    _flush_native_stdout()      # the result line is the last line of stdout
     print(json.dumps(out), flush=True)
     _shutdown(pg)
+
+
+def _flush_native_stdout():
+    """flush what native libraries (RCCL's version banner) left in the C stdio buffer: it would otherwise reach a piped
+    stdout only at exit, after the result line"""
+    sys.stdout.flush()
+    try:
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+    except (OSError, AttributeError):
+        pass
 
 
 def _shutdown(pg):

@@ -793,6 +793,33 @@ def test_bench_probes_the_launch_mode_on_every_world_size(monkeypatch):
     assert bench.launch_mode(argparse.Namespace(no_graph=False, graph=True), 8) is True
 
 
+def test_bench_dump_outputs_is_seeded_and_bounded(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): one float .npy per returned scalar plus the parameter and gradient arenas,
+    a larger arena as the same seeded sample of elements every run, the whole within the 64 MB budget"""
+    import bench
+    from deepvoice3_pytorch_amd.train_step import FlatArena
+    torch.manual_seed(0)
+    arena = FlatArena([torch.nn.Parameter(torch.randn(1000)), torch.nn.Parameter(torch.randn(37, 3))])
+    arena.grad.copy_(torch.arange(arena.total, dtype=torch.float32))
+    trainer = type("T", (), {"arena": arena})()
+    scal = dict(loss=torch.tensor(1.5), grad_norm=torch.tensor([0.25]), f16_range_events=torch.zeros(1, dtype=torch.int32))
+    a = bench.dump_outputs(str(tmp_path / "a"), trainer, scal, sample=500)
+    b = bench.dump_outputs(str(tmp_path / "b"), trainer, scal, sample=500)
+    assert a["files"] == ["f16_range_events.npy", "grad_norm.npy", "grads.npy", "loss.npy", "params.npy"]
+    assert a["bytes"] <= bench.DUMP_MAX_BYTES and a["arena_sample"]["elements"] == 500
+    for f in a["files"]:
+        x, y = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    assert float(np.load(str(tmp_path / "a" / "loss.npy"))[0]) == 1.5
+    g = np.load(str(tmp_path / "a" / "grads.npy"))          # the sampled element indices, ascending and distinct
+    assert g.shape == (500,) and np.all(np.diff(g) > 0) and g.max() < arena.total
+    assert np.array_equal(np.load(str(tmp_path / "a" / "params.npy")), arena.flat.numpy()[g.astype(np.int64)])
+    full = bench.dump_outputs(str(tmp_path / "c"), trainer, scal)            # small arena: written whole
+    assert full["arena_sample"] is None and np.load(str(tmp_path / "c" / "params.npy")).shape == (arena.total,)
+    # the largest default dump (DUMP_SAMPLE elements of two arenas) fits the budget
+    assert 2 * 4 * bench.DUMP_SAMPLE + 64 * 8 <= bench.DUMP_MAX_BYTES
+
+
 @pytest.mark.parametrize("n", [2, 8])
 def test_bench_self_launches_its_ranks_dry(n):
     """`python bench.py --gpus N` with no launcher around it must start N ranks itself (the driver's command
