@@ -83,6 +83,51 @@ class MultiSpeakerTTSModel(nn.Module):
         return mel, linear, alignments, done
 
 
+    def synthesize_batch(self, text_sequences, text_lengths, speaker_ids=None):
+        """Per-utterance batched synthesis: every item of a ragged batch comes back as if it had been synthesised alone
+        (the reference's synthesis.tts at B = 1, synthesis.py:42-73, model part).  text_sequences (B, Tt) int ids on
+        the device, padded past each item's text_lengths[b]; positions are 1..text_lengths[b].  The encoder and the
+        post-net zero each item's columns past its own length after every layer (ops.ItemLengths), the decoder runs in
+        its per-utterance mode (Decoder.incremental_forward(text_lengths=...)).  Inference only.
+        -> (mel (B, T, mel_dim), linear (B, T * upsampling, linear_dim), alignments, done, frame_lengths): frame_lengths
+        (int64[B], host) are each item's mel frames (decoder steps x r); everything past them is zero."""
+        from . import ops
+        if self.training:
+            raise RuntimeError("synthesize_batch: eval mode only")
+        dev = text_sequences.device
+        B, Tt = text_sequences.shape
+        tl = torch.as_tensor(text_lengths).reshape(-1).to(torch.int64).cpu()
+        if tl.numel() != B or int(tl.min()) < 1 or int(tl.max()) > Tt:
+            raise ValueError("synthesize_batch: %d text lengths in [1, %d] expected, got %s" % (B, Tt, tl.tolist()))
+        tl_dev = tl.to(torch.int32).to(dev)
+        pos = torch.arange(1, Tt + 1, device=dev)[None, :].expand(B, Tt)
+        text_positions = torch.where(pos <= tl_dev[:, None].long(), pos, torch.zeros_like(pos))
+        speaker_embed = None
+        if speaker_ids is not None:
+            assert self.n_speakers > 1
+            speaker_embed = self.embed_speakers(speaker_ids)
+        enc, dec = self.seq2seq.encoder, self.seq2seq.decoder
+        prev, vl = ops.valid, ops.ItemLengths(tl, Tt, dev)
+        ops.valid = vl
+        try:
+            with torch.no_grad():
+                memory = enc(text_sequences, lengths=None, speaker_embed=speaker_embed)
+                dec.start_fresh_sequence()
+                kw = dict(speaker_embed=speaker_embed) if speaker_embed is not None else {}
+                mel, alignments, done, states, steps = dec.incremental_forward(memory, text_positions,
+                                                                               text_lengths=tl, **kw)
+                Td = mel.size(1)
+                mel = mel.reshape(B, -1, self.mel_dim)
+                post_in = states.view(B, mel.size(1), -1) if self.use_decoder_state_for_postnet_input else mel
+                vl.set_dec(steps, Td)
+                linear = self.postnet(post_in, speaker_embed).contiguous()
+                ops.zero_frames(linear, vl.dec_len, int(steps.min()), linear.size(1) // Td)
+        finally:
+            ops.valid = prev
+        assert linear.size(-1) == self.linear_dim
+        return mel, linear, alignments, done, steps * (mel.size(1) // Td)
+
+
 class AttentionSeq2Seq(nn.Module):
     """Encoder -> attention Decoder pair (reference __init__.py:100-126)."""
 

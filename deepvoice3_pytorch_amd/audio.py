@@ -111,11 +111,26 @@ def magnitudes(linear_outputs, cfg):
     return mag
 
 
-def istft(mag, phasor, hop, convention="torch", window_scale=None):
-    """mag (B,T,513), phasor (B,T,513,2) or None -> y (B, hop*(T-1)); lws framing: (B, (T+1)*hop - 1024)."""
+def num_samples(T, hop, convention):
+    """samples the inverse makes of T frames: (T + 1) * hop - 1024 on the lws framing, hop * (T - 1) on the torch one"""
+    return lws_num_samples(T, hop) if convention == "lws" else hop * (T - 1)
+
+
+def istft(mag, phasor, hop, convention="torch", window_scale=None, tlen=None):
+    """mag (B,T,513), phasor (B,T,513,2) or None -> y (B, hop*(T-1)); lws framing: (B, (T+1)*hop - 1024).
+    tlen (device int32[B]): item b has only its first tlen[b] frames -- its own signal, zeros after it."""
     B, T, F = mag.shape
     assert F == N_BIN
     frames = torch.empty((B, T, N_FFT), dtype=torch.float32, device=mag.device)
+    if tlen is not None:
+        lws = convention == "lws"
+        swin = lws_windows(mag.device, hop, window_scale)[1] if lws else None
+        _lib.call("dv3_gl_istft_items_f32", mag.data_ptr(), phasor.data_ptr() if phasor is not None else None,
+                  swin.data_ptr() if lws else None, frames.data_ptr(), B, T, hop, tlen.data_ptr(), int(lws), _stream())
+        y = torch.empty((B, num_samples(T, hop, convention)), dtype=torch.float32, device=mag.device)
+        _lib.call("dv3_overlap_add_items_f32", frames.data_ptr(), y.data_ptr(), B, T, hop, tlen.data_ptr(), int(lws),
+                  _stream())
+        return y
     if convention == "lws":
         _, swin = lws_windows(mag.device, hop, window_scale)
         _lib.call("dv3_lws_istft_frames_f32", mag.data_ptr(), phasor.data_ptr() if phasor is not None else None,
@@ -225,9 +240,10 @@ def melspectrogram_batch(wav, cfg=None, num_mels=80, fmin=125.0, fmax=7600.0):
     return _db_norm(mel, cfg)
 
 
-def griffin_lim(mag, hop, n_iter, init_phasor=None, convention="torch", window_scale=None):
-    """Griffin & Lim: alternate projections between the given magnitudes and consistent STFTs."""
-    y = istft(mag, init_phasor, hop, convention, window_scale)
+def griffin_lim(mag, hop, n_iter, init_phasor=None, convention="torch", window_scale=None, tlen=None):
+    """Griffin & Lim: alternate projections between the given magnitudes and consistent STFTs.  tlen (device int32[B]):
+    per-item frame counts -- item b iterates on its own first tlen[b] frames and signal (see istft)."""
+    y = istft(mag, init_phasor, hop, convention, window_scale, tlen)
     B, T, _ = mag.shape
     if n_iter > 0:
         frames = torch.empty((B, T, N_FFT), dtype=torch.float32, device=mag.device)
@@ -236,6 +252,14 @@ def griffin_lim(mag, hop, n_iter, init_phasor=None, convention="torch", window_s
         if lws:
             awin, swin = lws_windows(mag.device, hop, window_scale)
         for _ in range(n_iter):
+            if tlen is not None:
+                _lib.call("dv3_gl_project_items_f32", y.data_ptr(), mag.data_ptr(), awin.data_ptr() if lws else None,
+                          swin.data_ptr() if lws else None, frames.data_ptr(), B, T, hop, tlen.data_ptr(), int(lws),
+                          _stream())
+                _lib.call("dv3_overlap_add_items_f32", frames.data_ptr(), y2.data_ptr(), B, T, hop, tlen.data_ptr(),
+                          int(lws), _stream())
+                y, y2 = y2, y
+                continue
             # stft -> unit phase -> x magnitude -> inverse FFT -> window in one launch (the phasors never reach HBM)
             if lws:
                 _lib.call("dv3_lws_gl_project_f32", y.data_ptr(), mag.data_ptr(), awin.data_ptr(), swin.data_ptr(),
@@ -255,10 +279,15 @@ def inv_preemphasis_(y, coef):
     return out
 
 
-def inv_spectrogram_batch(linear_outputs, cfg=None, init_phasor=None):
+def inv_spectrogram_batch(linear_outputs, cfg=None, init_phasor=None, frame_lengths=None):
     """(B, T, 513) device tensor (model linear_outputs) -> waveforms on the device: (B, (T+1)*hop - 1024) on the lws
-    framing (what the reference's processor.istft returns for T frames), (B, hop*(T-1)) on the torch framing."""
+    framing (what the reference's processor.istft returns for T frames), (B, hop*(T-1)) on the torch framing.
+    frame_lengths (B host ints): a batch of utterances padded to T frames; item b is inverted from its own first
+    frame_lengths[b] frames exactly as its B = 1 call on the trimmed spectrogram, its samples past its own length are
+    zero.  -> (waveforms, sample lengths (int64[B], host)) in that case."""
     cfg = cfg or AudioConfig()
+    if frame_lengths is not None:
+        return _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths)
     mag = magnitudes(linear_outputs, cfg)
     y = griffin_lim(mag, cfg.hop_size, cfg.griffin_lim_iters, init_phasor, cfg.convention, cfg.window_scale)
     return inv_preemphasis_(y, cfg.preemphasis)
@@ -269,3 +298,23 @@ def inv_spectrogram(spectrogram, cfg=None, device="cuda:0"):
     s = torch.as_tensor(np.ascontiguousarray(np.asarray(spectrogram, dtype=np.float32).T)).unsqueeze(0)
     y = inv_spectrogram_batch(s.to(device), cfg)
     return y[0].cpu().numpy()
+
+
+def _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths):
+    B, T = linear_outputs.shape[0], linear_outputs.shape[1]
+    fl = torch.as_tensor(frame_lengths).reshape(-1).to(torch.int64).cpu()
+    hop = cfg.hop_size
+    tmin = 2
+    while num_samples(tmin, hop, cfg.convention) <= (0 if cfg.convention == "lws" else N_FFT // 2):
+        tmin += 1
+    if fl.numel() != B or int(fl.min()) < tmin or int(fl.max()) > T:
+        raise ValueError("inv_spectrogram_batch: %d frame lengths in [%d, %d] expected, got %s" % (
+            B, tmin, T, fl.tolist()))
+    tlen = fl.to(torch.int32).to(linear_outputs.device)
+    mag = magnitudes(linear_outputs, cfg)
+    y = griffin_lim(mag, hop, cfg.griffin_lim_iters, init_phasor, cfg.convention, cfg.window_scale, tlen)
+    lengths = torch.tensor([num_samples(int(n), hop, cfg.convention) for n in fl], dtype=torch.int64)
+    out = torch.empty_like(y)
+    _lib.call("dv3_deemphasis_items_f32", y.data_ptr(), out.data_ptr(), B, y.shape[1],
+              lengths.to(torch.int32).to(y.device).data_ptr(), float(cfg.preemphasis), _stream())
+    return out, lengths

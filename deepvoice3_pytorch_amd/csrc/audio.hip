@@ -28,6 +28,14 @@ __device__ __forceinline__ cplx cmul(cplx a, cplx b) { return {a.x * b.x - a.y *
 __device__ __forceinline__ cplx cadd(cplx a, cplx b) { return {a.x + b.x, a.y + b.y}; }
 __device__ __forceinline__ cplx csub(cplx a, cplx b) { return {a.x - b.x, a.y - b.y}; }
 
+// per-item frame count (the *_items entry points): tlen[b] clamped to [tlo, T], tlo = the fewest frames the framing takes
+// at this hop (the host's bound: no read outside the item's own signal whatever the device array holds); NULL: T
+__device__ __forceinline__ int item_frames(const int32_t* tlen, int b, int T, int tlo) {
+  return tlen ? min(max(tlen[b], tlo), T) : T;
+}
+template <bool LWS>
+__device__ __forceinline__ int item_samples(int Tb, int hop) { return LWS ? (Tb + 1) * hop - NFFT : hop * (Tb - 1); }
+
 __device__ __forceinline__ float hann(int n) { return 0.5f - 0.5f * cospif(2.0f * (float)n / (float)NFFT); }
 
 // W[j] = exp(+2 pi i j / 1024), filled once per workgroup (4 sincospif per thread instead of 3 per butterfly and
@@ -99,10 +107,12 @@ __global__ void gl_prepare_kernel(const float* __restrict__ lin, float* __restri
 template <bool LWS>
 __global__ __launch_bounds__(256) void istft_frames_kernel(const float* __restrict__ mag,
                                                            const float* __restrict__ phasor,
-                                                           float* __restrict__ frames, const float* __restrict__ sw) {
+                                                           float* __restrict__ frames, const float* __restrict__ sw,
+                                                           const int32_t* __restrict__ tlen, int T, int tlo) {
   __shared__ cplx A[NFFT], Bf[NFFT];
   const int tid = threadIdx.x;
   const int64_t fr = blockIdx.x;
+  if (tlen && (int)(fr % T) >= item_frames(tlen, (int)(fr / T), T, tlo)) return;   // past the item's own frames
   const float* m = mag + fr * NBIN;
   const float* ph = phasor ? phasor + fr * NBIN * 2 : nullptr;
   for (int k = tid; k <= NFFT / 2; k += 256) {
@@ -119,15 +129,21 @@ __global__ __launch_bounds__(256) void istft_frames_kernel(const float* __restri
 
 // y[b][i] = sum_t frames[b][t][p - t*hop] / sum_t hann^2[p - t*hop],  p = i + NFFT/2, i < hop*(T-1)
 // LWS: p = i + (NFFT - hop) (the zero padding lws strips), no division (the synthesis window carries the normaliser)
+// tlen (per item): item b overlap-adds its own Tb frames into its own item_samples(Tb) samples, zeros after them
 template <bool LWS>
 __global__ void ola_kernel(const float* __restrict__ frames, float* __restrict__ y, int T, int hop,
-                           int L) {
+                           int L, const int32_t* __restrict__ tlen, int tlo) {
   const int b = blockIdx.y;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= L) return;
+  const int Tb = item_frames(tlen, b, T, tlo);
+  if (tlen && i >= item_samples<LWS>(Tb, hop)) {
+    y[(int64_t)b * L + i] = 0.f;
+    return;
+  }
   const int p = i + (LWS ? NFFT - hop : NFFT / 2);
   int t_hi = p / hop;
-  if (t_hi > T - 1) t_hi = T - 1;
+  if (t_hi > Tb - 1) t_hi = Tb - 1;
   int t_lo = (p - NFFT + hop) / hop;  // smallest t with p - t*hop <= NFFT-1  (ceil((p-NFFT+1)/hop))
   if (p - NFFT + 1 <= 0) t_lo = 0;
   float acc = 0.f, wsum = 0.f;
@@ -230,12 +246,16 @@ __global__ __launch_bounds__(256) void gl_project_kernel(const float* __restrict
 template <bool LWS>
 __global__ __launch_bounds__(256) void gl_project2_kernel(const float* __restrict__ y, const float* __restrict__ mag,
                                                           float* __restrict__ frames, int T, int hop, int L, int TP,
-                                                          const float* __restrict__ aw, const float* __restrict__ sw) {
+                                                          const float* __restrict__ aw, const float* __restrict__ sw,
+                                                          const int32_t* __restrict__ tlen, int tlo) {
   __shared__ cplx A[NFFT], Bf[NFFT], W[NFFT];
   const int tid = threadIdx.x;
   const int b = blockIdx.x / TP, t1 = 2 * (blockIdx.x - b * TP);
-  const bool two = t1 + 1 < T;
-  const float* yb = y + (int64_t)b * L;
+  const float* yb = y + (int64_t)b * L;      // rows L apart; item b's own signal is its first Lb samples
+  const int Tb = item_frames(tlen, b, T, tlo);
+  if (t1 >= Tb) return;                      // a pair past the item's own frames (workgroup-uniform, before any barrier)
+  const bool two = t1 + 1 < Tb;
+  L = tlen ? item_samples<LWS>(Tb, hop) : L;
   fill_twiddles(W, tid);
   __syncthreads();
   for (int n = tid; n < NFFT; n += 256) {
@@ -283,11 +303,18 @@ __global__ __launch_bounds__(256) void gl_project2_kernel(const float* __restric
 
 // y[n] = x[n] + coef * y[n-1] per row (scipy.signal.lfilter([1], [1, -coef]); audio.py:26-28), in
 // place.  One workgroup per row: 256 contiguous segments scanned locally, carries chained in LDS.
-__global__ __launch_bounds__(256) void deemphasis_kernel(float* __restrict__ y, int L, float coef) {
+// lens (per item): row b filters its own first lens[b] samples and is zero after them
+__global__ __launch_bounds__(256) void deemphasis_kernel(float* __restrict__ y, int L, float coef,
+                                                         const int32_t* __restrict__ lens) {
   __shared__ float seg_end[256];
   __shared__ float carry[256];
   const int tid = threadIdx.x;
   float* row = y + (int64_t)blockIdx.x * L;
+  if (lens) {
+    const int Lb = min(max(lens[blockIdx.x], 0), L);
+    for (int i = Lb + tid; i < L; i += 256) row[i] = 0.f;
+    L = Lb;
+  }
   const int len = (L + 255) / 256;
   const int lo = min(tid * len, L), hi = min(lo + len, L);
   float v = 0.f;
@@ -369,14 +396,14 @@ extern "C" int dv3_istft_frames_f32(const float* mag, const float* phasor, float
                                     int32_t T, void* stream) {
   DV3_REQUIRE(mag && frames && B > 0 && T > 0, "istft_frames: bad arguments");
   hipLaunchKernelGGL(istft_frames_kernel<false>, dim3((unsigned)((int64_t)B * T)), dim3(256), 0,
-                     (hipStream_t)stream, mag, phasor, frames, (const float*)nullptr);
+                     (hipStream_t)stream, mag, phasor, frames, (const float*)nullptr, (const int32_t*)nullptr, (int)T, 1);
   return dv3_check_launch("istft_frames");
 }
 extern "C" int dv3_lws_istft_frames_f32(const float* mag, const float* phasor, const float* swin, float* frames, int32_t B,
                                         int32_t T, void* stream) {
   DV3_REQUIRE(mag && frames && swin && B > 0 && T > 0, "lws_istft_frames: bad arguments");
   hipLaunchKernelGGL(istft_frames_kernel<true>, dim3((unsigned)((int64_t)B * T)), dim3(256), 0,
-                     (hipStream_t)stream, mag, phasor, frames, swin);
+                     (hipStream_t)stream, mag, phasor, frames, swin, (const int32_t*)nullptr, (int)T, 1);
   return dv3_check_launch("lws_istft_frames");
 }
 
@@ -385,7 +412,7 @@ extern "C" int dv3_overlap_add_f32(const float* frames, float* y, int32_t B, int
   DV3_REQUIRE(frames && y && B > 0 && T > 1 && hop > 0 && hop <= 1024, "overlap_add: bad arguments");
   const int L = hop * (T - 1);
   hipLaunchKernelGGL(ola_kernel<false>, dim3(dv3_cdiv(L, 256), B), dim3(256), 0, (hipStream_t)stream, frames, y,
-                     T, hop, L);
+                     T, hop, L, (const int32_t*)nullptr, 1);
   return dv3_check_launch("overlap_add");
 }
 
@@ -394,7 +421,8 @@ static inline int lws_len(int T, int hop) { return (T + 1) * hop - NFFT; }
 extern "C" int dv3_lws_overlap_add_f32(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, void* stream) {
   DV3_REQUIRE(frames && y && B > 0 && T > 1 && hop > 0 && hop <= 1024 && lws_len(T, hop) > 0, "lws_overlap_add: bad arguments");
   const int L = lws_len(T, hop);
-  hipLaunchKernelGGL(ola_kernel<true>, dim3(dv3_cdiv(L, 256), B), dim3(256), 0, (hipStream_t)stream, frames, y, T, hop, L);
+  hipLaunchKernelGGL(ola_kernel<true>, dim3(dv3_cdiv(L, 256), B), dim3(256), 0, (hipStream_t)stream, frames, y, T, hop, L,
+                     (const int32_t*)nullptr, 1);
   return dv3_check_launch("lws_overlap_add");
 }
 extern "C" int dv3_lws_stft_f32(const float* y, const float* awin, float* phasor, float* spec, float* mag_bct, int32_t B,
@@ -412,7 +440,7 @@ extern "C" int dv3_lws_gl_project_f32(const float* y, const float* mag, const fl
               "lws_gl_project: bad arguments");
   const int TP = (T + 1) / 2;
   hipLaunchKernelGGL(gl_project2_kernel<true>, dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
-                     frames, T, hop, lws_len(T, hop), TP, awin, swin);
+                     frames, T, hop, lws_len(T, hop), TP, awin, swin, (const int32_t*)nullptr, 1);
   return dv3_check_launch("lws_gl_project");
 }
 
@@ -433,7 +461,7 @@ extern "C" int dv3_gl_project_f32(const float* y, const float* mag, float* frame
   DV3_REQUIRE(L > 512, "gl_project: signal shorter than the reflect padding");
   const int TP = (T + 1) / 2;     // two real frames per complex FFT
   hipLaunchKernelGGL(gl_project2_kernel<false>, dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
-                     frames, T, hop, L, TP, (const float*)nullptr, (const float*)nullptr);
+                     frames, T, hop, L, TP, (const float*)nullptr, (const float*)nullptr, (const int32_t*)nullptr, 1);
   return dv3_check_launch("gl_project");
 }
 
@@ -446,13 +474,18 @@ extern "C" int dv3_gl_project_f32(const float* y, const float* mag, float* frame
 constexpr int DEEMPH_W = 1024, DEEMPH_CH = 3072, DEEMPH_E = (DEEMPH_W + DEEMPH_CH) / 256;
 static_assert(DEEMPH_E == 16, "sixteen samples per thread");
 __global__ __launch_bounds__(256) void deemphasis_chunk_kernel(const float* __restrict__ x, float* __restrict__ y, int L,
-                                                               float coef) {
+                                                               float coef, const int32_t* __restrict__ lens) {
   __shared__ float seg_end[256];
   __shared__ float carry[256];
   const int tid = threadIdx.x;
   const float* xr = x + (int64_t)blockIdx.y * L;
   float* yr = y + (int64_t)blockIdx.y * L;
   const int out0 = blockIdx.x * DEEMPH_CH;                    // first output of the chunk
+  if (lens) {                                                 // per item: its own first lens[b] samples, zeros after them
+    const int Lb = min(max(lens[blockIdx.y], 0), L);
+    for (int i = max(out0, Lb) + tid; i < min(out0 + DEEMPH_CH, L); i += 256) yr[i] = 0.f;
+    L = Lb;
+  }
   const int i0 = out0 - DEEMPH_W + tid * DEEMPH_E;            // this thread's first sample (may lie before the row)
   float v[DEEMPH_E];
   const bool vec = i0 >= 0 && i0 + DEEMPH_E <= L && ((((uintptr_t)(xr + i0)) & 15) == 0);
@@ -511,7 +544,8 @@ extern "C" int dv3_deemphasis_f32(const float* x, float* y, int32_t B, int32_t L
   const float a = fabsf(coef);
   const bool chunked = a < 1.f && (a == 0.f || DEEMPH_W * logf(a) <= logf(1e-9f * (1.f - a))) && x != y;
   if (chunked) {
-    hipLaunchKernelGGL(deemphasis_chunk_kernel, dim3(dv3_cdiv(L, DEEMPH_CH), B), dim3(256), 0, (hipStream_t)stream, x, y, L, coef);
+    hipLaunchKernelGGL(deemphasis_chunk_kernel, dim3(dv3_cdiv(L, DEEMPH_CH), B), dim3(256), 0, (hipStream_t)stream, x, y, L, coef,
+                       (const int32_t*)nullptr);
     return dv3_check_launch("deemphasis");
   }
   if (x != y) {
@@ -521,6 +555,74 @@ extern "C" int dv3_deemphasis_f32(const float* x, float* y, int32_t B, int32_t L
       return DV3_ELAUNCH;
     }
   }
-  hipLaunchKernelGGL(deemphasis_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, y, L, coef);
+  hipLaunchKernelGGL(deemphasis_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, y, L, coef, (const int32_t*)nullptr);
   return dv3_check_launch("deemphasis");
+}
+
+// ---- per-item frame counts (ABI 44, include/dv3hip.h: dv3_gl_istft_items_f32 ...): a batch of utterances of different
+// lengths, each item's inverse exactly its B = 1 call on its own trimmed spectrogram ----
+// the fewest frames a framing takes at this hop: lws needs a positive signal length, torch one longer than the reflect pad
+static int items_tlo(int lws, int hop) {
+  int t = 2;
+  while (lws ? lws_len(t, hop) <= 0 : hop * (t - 1) <= NFFT / 2) ++t;
+  return t;
+}
+extern "C" int dv3_gl_istft_items_f32(const float* mag, const float* phasor, const float* swin, float* frames, int32_t B,
+                                      int32_t T, int32_t hop, const int32_t* tlen, int32_t lws, void* stream) {
+  DV3_REQUIRE(mag && frames && tlen && (!lws || swin) && B > 0 && T > 1 && hop > 0 && hop <= 1024 &&
+              T >= items_tlo(lws, hop), "gl_istft_items: bad arguments");
+  if (lws)
+    hipLaunchKernelGGL(istft_frames_kernel<true>, dim3((unsigned)((int64_t)B * T)), dim3(256), 0, (hipStream_t)stream, mag,
+                       phasor, frames, swin, tlen, (int)T, items_tlo(lws, hop));
+  else
+    hipLaunchKernelGGL(istft_frames_kernel<false>, dim3((unsigned)((int64_t)B * T)), dim3(256), 0, (hipStream_t)stream, mag,
+                       phasor, frames, (const float*)nullptr, tlen, (int)T, items_tlo(lws, hop));
+  return dv3_check_launch("gl_istft_items");
+}
+extern "C" int dv3_overlap_add_items_f32(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, const int32_t* tlen,
+                                         int32_t lws, void* stream) {
+  DV3_REQUIRE(frames && y && tlen && B > 0 && T > 1 && hop > 0 && hop <= 1024 && T >= items_tlo(lws, hop),
+              "overlap_add_items: bad arguments");
+  const int L = lws ? lws_len(T, hop) : hop * (T - 1);
+  if (lws)
+    hipLaunchKernelGGL(ola_kernel<true>, dim3(dv3_cdiv(L, 256), B), dim3(256), 0, (hipStream_t)stream, frames, y, T, hop, L,
+                       tlen, items_tlo(lws, hop));
+  else
+    hipLaunchKernelGGL(ola_kernel<false>, dim3(dv3_cdiv(L, 256), B), dim3(256), 0, (hipStream_t)stream, frames, y, T, hop, L,
+                       tlen, items_tlo(lws, hop));
+  return dv3_check_launch("overlap_add_items");
+}
+extern "C" int dv3_gl_project_items_f32(const float* y, const float* mag, const float* awin, const float* swin, float* frames,
+                                        int32_t B, int32_t T, int32_t hop, const int32_t* tlen, int32_t lws, void* stream) {
+  DV3_REQUIRE(y && mag && frames && tlen && (!lws || (awin && swin)) && B > 0 && T > 1 && hop > 0 && hop <= 1024 &&
+              T >= items_tlo(lws, hop), "gl_project_items: bad arguments");
+  const int TP = (T + 1) / 2;
+  const int L = lws ? lws_len(T, hop) : hop * (T - 1);
+  if (lws)
+    hipLaunchKernelGGL(gl_project2_kernel<true>, dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
+                       frames, T, hop, L, TP, awin, swin, tlen, items_tlo(lws, hop));
+  else
+    hipLaunchKernelGGL(gl_project2_kernel<false>, dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
+                       frames, T, hop, L, TP, (const float*)nullptr, (const float*)nullptr, tlen, items_tlo(lws, hop));
+  return dv3_check_launch("gl_project_items");
+}
+extern "C" int dv3_deemphasis_items_f32(const float* x, float* y, int32_t B, int32_t L, const int32_t* lens, float coef,
+                                        void* stream) {
+  DV3_REQUIRE(x && y && lens && B > 0 && L > 0, "deemphasis_items: bad arguments");
+  const float a = fabsf(coef);
+  const bool chunked = a < 1.f && (a == 0.f || DEEMPH_W * logf(a) <= logf(1e-9f * (1.f - a))) && x != y;
+  if (chunked) {
+    hipLaunchKernelGGL(deemphasis_chunk_kernel, dim3(dv3_cdiv(L, DEEMPH_CH), B), dim3(256), 0, (hipStream_t)stream, x, y, L,
+                       coef, lens);
+    return dv3_check_launch("deemphasis_items");
+  }
+  if (x != y) {
+    hipError_t e = hipMemcpyAsync(y, x, (size_t)B * L * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) {
+      dv3_set_error("deemphasis_items: %s", hipGetErrorString(e));
+      return DV3_ELAUNCH;
+    }
+  }
+  hipLaunchKernelGGL(deemphasis_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, y, L, coef, lens);
+  return dv3_check_launch("deemphasis_items");
 }

@@ -295,14 +295,19 @@ __device__ __forceinline__ void attn_step_item(const dv3_attn_step_desc& p, cons
                                                float* red, int* redi) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int E = p.E, Tk = p.Tk;
+  // per-utterance mode: this item's own key count s (the stride stays Tk); keys n >= s never enter the window, so
+  // their probabilities come out as exact zeros and every partial sum / max is the one of a B = 1 call at Tk = s
+  const bool items = p.key_len != nullptr;
+  const int s = items ? min(max(p.key_len[b], 1), Tk) : Tk;
+  int32_t* const la_rd = p.last_attended ? p.last_attended + (items ? (t & 1) * p.B + b : (t & 1)) : nullptr;
   float* q = lds;
   float* sc = lds + E;
-  int lo = 0, hi = Tk;
-  if (p.last_attended) {       // deepvoice3.py:150-156
-    const int la = p.last_attended[t & 1];
+  int lo = 0, hi = s;
+  if (la_rd) {                 // deepvoice3.py:150-156
+    const int la = *la_rd;
     const int back = la - p.win_back, ahead = la + p.win_ahead;
     if (back > 0) lo = back;
-    if (ahead < Tk) hi = ahead;
+    if (ahead < s) hi = ahead;
   }
   for (int e = tid; e < E; e += 256) q[e] = p.q[(int64_t)b * p.q_bs + e];
   __syncthreads();
@@ -354,7 +359,7 @@ __device__ __forceinline__ void attn_step_item(const dv3_attn_step_desc& p, cons
   }
   __syncthreads();
   // context (deepvoice3.py:167-171): sum_n p[n] v[e][n] * (Tk * sqrt(1/Tk))
-  const float scale = (float)Tk * sqrtf(1.0f / (float)Tk);
+  const float scale = (float)s * sqrtf(1.0f / (float)s);
   const float* __restrict__ vb = p.v + (int64_t)b * E * Tk;
   for (int e = tid; e < E; e += 256) {
     float c = 0.f;
@@ -369,8 +374,8 @@ __device__ __forceinline__ void attn_step_item(const dv3_attn_step_desc& p, cons
     for (; n < hi; ++n) c = fmaf(sc[n], vb[(int64_t)n * ns + (int64_t)e * es], c);
     p.ctx[(int64_t)b * p.ctx_bs + e] = c * scale;
   }
-  // next step's window: argmax of batch item 0 (deepvoice3.py:445), first maximum
-  if (b == 0 && p.last_attended) {
+  // next step's window: argmax of batch item 0 (deepvoice3.py:445) -- of every item in per-utterance mode --, first maximum
+  if ((b == 0 || items) && p.last_attended) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
       const float ov = __shfl_xor(best, off, 64);
@@ -382,7 +387,7 @@ __device__ __forceinline__ void attn_step_item(const dv3_attn_step_desc& p, cons
     if (tid == 0) {
       for (int w = 1; w < 4; ++w)
         if (red[w] > best || (red[w] == best && redi[w] < bi)) { best = red[w]; bi = redi[w]; }
-      p.last_attended[(t + 1) & 1] = bi;
+      p.last_attended[items ? ((t + 1) & 1) * p.B + b : ((t + 1) & 1)] = bi;
     }
   }
 }
@@ -609,6 +614,9 @@ extern "C" int dv3_decode_program_run(const dv3_decode_program* d, void* stream)
     DV3_REQUIRE(en.kind == 0 || en.kind == 1, "decode_program: entry %d has kind %d", e, en.kind);
     const int rc = en.kind == 0 ? conv_step_check(&en.conv, false, &l) : attn_step_check(&en.attn, false, &l);
     if (rc != DV3_OK) return rc;
+    DV3_REQUIRE(en.kind == 0 || !en.attn.key_len,
+                "decode_program: per-utterance attention (key_len) is not taken by the persistent program, whose stop "
+                "rule is one flag per batch; use dv3_decode_program_launch");
     DV3_REQUIRE((en.kind == 0 ? en.conv.B : en.attn.B) == d->B, "decode_program: entry %d has another batch size", e);
     if (l > lds_max) lds_max = l;
   }

@@ -1072,3 +1072,35 @@ extern "C" int dv3_zero_tail_b32(void* x, int64_t rows, int32_t T, int32_t words
                      (int)words, t_valid, (int)mult, (int)max_tail);
   return dv3_check_launch("zero_tail_b32");
 }
+
+// Per-utterance zero tails (ABI 44, include/dv3hip.h: dv3_zero_tail_items_b32): the same sweep over the last max_tail
+// columns of every row, the valid length read per batch item (rows_per_item consecutive rows share one).
+namespace {
+__global__ __launch_bounds__(256) void zero_tail_items_kernel(uint32_t* __restrict__ x, int64_t rows, int64_t rows_per_item,
+                                                              int T, int words, const int32_t* __restrict__ len, int mult,
+                                                              int max_tail) {
+  const int64_t per_row = (int64_t)max_tail * words;
+  const int64_t n = rows * per_row;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int64_t row = i / per_row;
+    const int64_t k = i - row * per_row;
+    const int64_t tv64 = (int64_t)len[row / rows_per_item] * mult;
+    const int tv = tv64 < 0 ? 0 : (tv64 > T ? T : (int)tv64);
+    const int col = T - max_tail + (int)(k / words);
+    if (col >= tv && col >= 0) x[(row * T + col) * words + (k % words)] = 0u;
+  }
+}
+}  // namespace
+extern "C" int dv3_zero_tail_items_b32(void* x, int32_t B, int64_t rows_per_item, int32_t T, int32_t words,
+                                       const int32_t* len, int32_t mult, int32_t max_tail, void* stream) {
+  DV3_REQUIRE(x && len && B >= 0 && rows_per_item >= 0 && T > 0 && words > 0 && mult > 0 && max_tail >= 0,
+              "zero_tail_items: bad args");
+  if (max_tail > T) max_tail = T;
+  const int64_t rows = (int64_t)B * rows_per_item;
+  if (rows == 0 || max_tail == 0) return DV3_OK;
+  int64_t blocks = (rows * max_tail * words + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(zero_tail_items_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (uint32_t*)x, rows,
+                     rows_per_item, (int)T, (int)words, len, (int)mult, (int)max_tail);
+  return dv3_check_launch("zero_tail_items_b32");
+}

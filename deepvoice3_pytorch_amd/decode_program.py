@@ -17,12 +17,41 @@ from . import ops
 from ._lib import STRUCTS
 
 
+def item_stops(done_rows, t0, min_steps, max_steps, stops):
+    """The reference's B = 1 stop rule (deepvoice3.py:469-473) applied to every item of a per-utterance batch: item b
+    stops after the first step n > min_steps whose done_b > 0.5, or after step max_steps + 1.  done_rows: the host
+    rows (one per step, steps t0 + 1, t0 + 2, ...) of B booleans done > 0.5; stops: one entry per item, 0 while the
+    item runs, updated in place to its number of steps.  -> True once every item has stopped (the batch then ends at
+    max(stops) steps)."""
+    for k, row in enumerate(done_rows):
+        n = t0 + k + 1
+        for b, d in enumerate(row):
+            if stops[b] == 0 and ((n > min_steps and d) or n > max_steps):
+                stops[b] = n
+    return all(stops)
+
+
+def item_results(stops, outputs, alignments, dones, states):
+    """the per-utterance decode's results with every frame past item b's own step count stops[b] set to zero (in place
+    where the tensor allows) -> (outputs, alignments, dones, states, frame_lengths int64[B] on the host)"""
+    lengths = torch.tensor(stops, dtype=torch.int32)
+    dev = outputs.device
+    ld = lengths.to(dev)
+    n = min(stops)
+    outputs, alignments, states = (ops.zero_frames(x.contiguous(), ld, n) for x in (outputs, alignments, states))
+    if dones:
+        d = ops.zero_frames(torch.cat([x.reshape(x.size(0), 1, 1) for x in dones], dim=1), ld, n)
+        dones = [d[:, i:i + 1] for i in range(d.size(1))]
+    return outputs, alignments, dones, states, lengths.long()
+
+
 class StepProgram(object):
     def __init__(self, B, device):
         self.B, self.dev = B, device
         self.f32 = dict(dtype=torch.float32, device=device)
         self.t_dev = torch.zeros(1, dtype=torch.int32, device=device)      # the step counter every launch reads
         self.keep, self.prog = [self.t_dev], []
+        self.per_item = False         # an attention entry reads per-utterance key lengths (attn_step(key_len=...))
 
     def buffer(self, *shape):
         t = torch.zeros(*shape, **self.f32)
@@ -75,12 +104,13 @@ class StepProgram(object):
         self.prog.append(("dv3_conv_step_f32", d))
         return y
 
-    def attn_step(self, q, k, v, window_backward, window_ahead, monotonic, attn_seq=None):
-        """one attention read over (B, E, Tk) keys / values (deepvoice3.py:143-171 at Tq = 1, no padding mask)"""
+    def attn_step(self, q, k, v, window_backward, window_ahead, monotonic, attn_seq=None, key_len=None):
+        """one attention read over (B, E, Tk) keys / values (deepvoice3.py:143-171 at Tq = 1, no padding mask);
+        key_len (device int32[B]): per-utterance mode -- item b reads its own keys n < key_len[b] with its own window"""
         B = self.B
         E, Tk = k.size(1), k.size(2)
         ctx = torch.empty(B, E, **self.f32)
-        la = self.buffer(2).to(torch.int32) if monotonic else None
+        la = self.buffer(2 * B if key_len is not None else 2).to(torch.int32) if monotonic else None
         if la is not None:
             self.keep.append(la)
         # one-frame reads want a key / value ROW contiguous: (B, Tk, E), transposed once per utterance batch
@@ -94,7 +124,11 @@ class StepProgram(object):
         if attn_seq is not None:
             a.attn_seq, a.attn_seq_ts = attn_seq.data_ptr(), attn_seq.stride(0)
         a.B, a.E, a.Tk = B, E, Tk
-        self.keep.extend([q, k, v, ctx, attn_seq])
+        if key_len is not None:
+            key_len = key_len.to(device=self.dev, dtype=torch.int32).contiguous()
+            a.key_len = key_len.data_ptr()
+            self.per_item = True
+        self.keep.extend([q, k, v, ctx, attn_seq, key_len])
         self.prog.append(("dv3_attn_step_f32", a))
         return ctx
 
@@ -163,10 +197,11 @@ class StepProgram(object):
         self.t_dev.fill_(t)
         return t
 
-    def decode_launched(self, cur_in, test_inputs, dones_seq, min_steps, max_steps, chunk=8):
+    def decode_launched(self, cur_in, test_inputs, dones_seq, min_steps, max_steps, chunk=8, stops=None):
         """the loop with the launches issued by the library (dv3_decode_program_launch: one call per chunk of steps, the
         step index in the descriptors).  Free running, the done flags are read once per chunk and the steps after the
-        stopping one are dropped -- later steps never change earlier outputs.  -> number of steps taken"""
+        stopping one are dropped -- later steps never change earlier outputs.  stops (a list of B zeros): the
+        per-utterance rule instead (item_stops), each item's step count stored there.  -> number of steps taken"""
         Prog = STRUCTS["dv3_decode_program"]
         arr, ti = self._entries(cur_in, test_inputs)
         p = Prog()
@@ -177,12 +212,19 @@ class StepProgram(object):
             p.t0, p.n_steps = 0, ti.size(1)
             if p.n_steps > 0:
                 ops._lib.call("dv3_decode_program_launch", ctypes.byref(p), stream)
+            if stops is not None:
+                stops[:] = [int(ti.size(1))] * self.B
             return int(ti.size(1))
         limit, t = max_steps + 1, 0
         while True:
             n = min(min_steps + 1 if t == 0 else chunk, limit - t)
             p.t0, p.n_steps = t, n
             ops._lib.call("dv3_decode_program_launch", ctypes.byref(p), stream)
+            if stops is not None:
+                if item_stops((dones_seq[t:t + n].reshape(n, -1) > 0.5).tolist(), t, min_steps, max_steps, stops):
+                    return max(stops)
+                t += n
+                continue
             done = (dones_seq[t:t + n].reshape(n, -1) > 0.5).all(dim=1).tolist()
             for k in range(n):
                 if t + k + 1 > min_steps and done[k]:
@@ -191,7 +233,8 @@ class StepProgram(object):
             if t >= limit:
                 return t
 
-    def decode(self, cur_in, test_inputs, dones_seq, min_steps, max_steps, use_graph, persistent=None, launched=None):
+    def decode(self, cur_in, test_inputs, dones_seq, min_steps, max_steps, use_graph, persistent=None, launched=None,
+               stops=None):
         """the decoder loop (deepvoice3.py:397-473 / nyanko.py:277-331): teacher-forced over test_inputs (B, n, D), or
         free running until every item's done flag passed 0.5 after min_steps, at most max_steps + 1 steps.
         -> number of steps taken.  Default (launched): one launch per program entry per step, issued by the library in
@@ -201,15 +244,22 @@ class StepProgram(object):
         DV3_DECODE_PERSISTENT=1): ONE launch for the whole loop -- bit-identical, and the host drops out entirely,
         but on MI355X the device-wide barrier between layers (agent-scope release + acquire: L2 write-back /
         invalidate across the 8 XCDs, ~3.5 us) costs more than a kernel boundary does (scripts/decode_time.py), so
-        it is opt-in."""
+        it is opt-in.  Per-utterance mode (attention entries with key_len): pass stops = [0] * B; every item stops by
+        its own done flag (item_stops), the loop runs until all have, and stops holds each item's step count; the
+        persistent program does not take this mode."""
+        if self.per_item and stops is None:
+            raise RuntimeError("decode program: per-utterance attention entries need the per-item stop rule (stops=)")
         if persistent is None:
             persistent = os.environ.get("DV3_DECODE_PERSISTENT", "0") == "1"
         if persistent:
+            if stops is not None:
+                raise RuntimeError("decode program: the persistent program does not take per-utterance decoding "
+                                   "(its stop rule is one flag per batch); use the launched or Python-driven loop")
             return self.decode_persistent(cur_in, test_inputs, dones_seq, min_steps, max_steps)
         if launched is None:
             launched = os.environ.get("DV3_DECODE_LAUNCHED", "1") != "0"
         if launched:
-            return self.decode_launched(cur_in, test_inputs, dones_seq, min_steps, max_steps)
+            return self.decode_launched(cur_in, test_inputs, dones_seq, min_steps, max_steps, stops=stops)
         free_running = test_inputs is None
         B = self.B
         graphed = bool(use_graph) and free_running
@@ -228,11 +278,16 @@ class StepProgram(object):
             else:
                 self.run_step()
             t += 1
-            if free_running:
+            if free_running and stops is not None:
+                if item_stops([(dones_seq[t - 1].reshape(-1) > 0.5).tolist()], t - 1, min_steps, max_steps, stops):
+                    break
+            elif free_running:
                 if t > min_steps and bool((dones_seq[t - 1] > 0.5).all()):
                     break
                 elif t > max_steps:
                     break
+        if stops is not None and not free_running:
+            stops[:] = [t] * B
         return t
 
 
@@ -242,8 +297,9 @@ class StepTrace(object):
     shape of what the step program writes on the device -- so the loops end with three slices instead of three lists of
     per-step tensors to squeeze, stack and transpose.  `stop` is the reference's rule (deepvoice3.py:469-473)."""
 
-    def __init__(self, min_steps, max_steps, teacher_forced):
+    def __init__(self, min_steps, max_steps, teacher_forced, stops=None):
         self.min_steps, self.max_steps, self.teacher_forced = min_steps, max_steps, teacher_forced
+        self.stops = stops            # per-utterance mode: a list of B zeros, each item's step count once it stopped
         self.n = 0
         self.dones = []
         self._bufs = None
@@ -270,7 +326,12 @@ class StepTrace(object):
     def stop(self, done):
         """after push: the free-running loop ends once every item signalled done past min_steps, or past max_steps"""
         if self.teacher_forced:
+            if self.stops is not None:
+                self.stops[:] = [self.n] * len(self.stops)
             return False
+        if self.stops is not None:
+            return item_stops([(done.reshape(-1) > 0.5).tolist()], self.n - 1, self.min_steps, self.max_steps,
+                              self.stops)
         return bool((done > 0.5).all() and self.n > self.min_steps) or self.n > self.max_steps
 
     def result(self):

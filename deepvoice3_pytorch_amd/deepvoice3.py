@@ -20,7 +20,7 @@ from . import ops
 from .modules import Conv1d, ConvTranspose1d, Embedding, Linear
 from .modules import key_lengths_i32, get_mask_from_lengths, SinusoidalEncoding, Conv1dGLU
 from . import conv as _conv
-from .decode_program import StepTrace
+from .decode_program import StepTrace, item_results
 
 
 def expand_speaker_embed(inputs_btc, speaker_embed=None, tdim=1):
@@ -405,18 +405,25 @@ class Decoder(nn.Module):
         return outputs, torch.stack(alignments), done, decoder_states
 
     def incremental_forward(self, encoder_out, text_positions, speaker_embed=None, initial_input=None,
-                            test_inputs=None):
+                            test_inputs=None, text_lengths=None):
         """Greedy autoregressive decode (deepvoice3.py:367-485).  The reference's quirks are
         kept: last_attended comes from batch item 0 (:445), no padding mask, and the running
         `ave_alignment + ave_alignment` (:449).  last_attended stays on the device (no host sync
-        per attention layer); the stop rule is checked on the host like the reference does."""
+        per attention layer); the stop rule is checked on the host like the reference does.
+        text_lengths (B,) ints: per-utterance mode -- item b decodes as if it were alone (its own keys, window,
+        context scale and stop, as the reference at B = 1); the result then carries a fifth entry, each item's
+        number of decoder steps, and every frame past it is zero."""
         keys, values = encoder_out
         B = keys.size(0)
         dev = keys.device
         if self.training:
             raise RuntimeError('incremental_forward only supports eval mode')
+        key_len = _item_key_len(text_lengths, B, keys.size(1), dev)
+        stops = [0] * B if key_len is not None else None
         if getattr(self, "fast_decode", False) and keys.is_cuda and self._fast_decode_eligible(keys.size(1)):
-            return self._incremental_fast(encoder_out, text_positions, speaker_embed, initial_input, test_inputs)
+            res = self._incremental_fast(encoder_out, text_positions, speaker_embed, initial_input, test_inputs,
+                                         key_len, stops)
+            return res if stops is None else item_results(stops, *res)
         w = self._rate(self.key_position_rate, self.speaker_proj1, speaker_embed)
         keys_bct = self.embed_keys_positions.forward_bct(text_positions, w,
                                                          base=keys.transpose(1, 2).contiguous())
@@ -432,9 +439,10 @@ class Decoder(nn.Module):
             v = att.value_projection.forward_bct(values_bct) if att.value_projection is not None else values_bct
             proj.append((k, v))
 
-        trace = StepTrace(self.min_decoder_steps, self.max_decoder_steps, test_inputs is not None)
-        last_attended = [torch.zeros(1, dtype=torch.int32, device=dev) if v else None
+        trace = StepTrace(self.min_decoder_steps, self.max_decoder_steps, test_inputs is not None, stops)
+        last_attended = [torch.zeros(1 if key_len is None else 2 * B, dtype=torch.int32, device=dev) if v else None
                          for v in self.force_monotonic_attention]
+        t_dev = torch.zeros(1, dtype=torch.int32, device=dev)      # per-utterance mode: the attention step's counter
         num_attention_layers = sum([layer is not None for layer in self.attention])
         wq = self._rate(self.query_position_rate, self.speaker_proj2, speaker_embed)
         if initial_input is None:
@@ -452,11 +460,15 @@ class Decoder(nn.Module):
                     xq = x.transpose(1, 2) + frame_pos_embed                       # (B, C, 1)
                     k, v = proj[idx]
                     q = attention.query_projection.forward_bct(xq.contiguous())
-                    ctx, alignment = ops.attention_core(q, k, v, None, last_attended[idx], 0.0, False,
-                                                        attention.window_backward, attention.window_ahead)
+                    if key_len is not None:       # the step program's attention kernel, per item
+                        ctx, alignment = ops.attn_step_items(q, k, v, key_len, last_attended[idx], t_dev,
+                                                             attention.window_backward, attention.window_ahead)
+                    else:
+                        ctx, alignment = ops.attention_core(q, k, v, None, last_attended[idx], 0.0, False,
+                                                            attention.window_backward, attention.window_ahead)
                     xo = attention.out_projection.forward_bct(ctx, r=xq.contiguous())
                     x = xo.transpose(1, 2)
-                    if self.force_monotonic_attention[idx]:
+                    if self.force_monotonic_attention[idx] and key_len is None:
                         ops._lib.call("dv3_attn_argmax_i32", alignment.data_ptr(), Tk,
                                       last_attended[idx].data_ptr(), ops._stream())
                     if ave_alignment is None:
@@ -467,6 +479,8 @@ class Decoder(nn.Module):
             decoder_state = x
             x = self.last_conv.incremental_forward(x)
             ave_alignment = ave_alignment / num_attention_layers
+            if key_len is not None:
+                t_dev.add_(1)
             return torch.sigmoid(x), torch.sigmoid(self.fc(x)), decoder_state, ave_alignment
 
         # Free-running decode can replay ONE captured hipGraph per step (~100 launches): every address in
@@ -508,7 +522,7 @@ class Decoder(nn.Module):
             t += 1
             if trace.stop(done):
                 break
-        return trace.result()
+        return trace.result() if stops is None else item_results(stops, *trace.result())
 
     def _fast_decode_eligible(self, Tk):
         """What the fused step program (csrc/decode_step.hip) takes; anything else runs the module-by-module
@@ -539,7 +553,7 @@ class Decoder(nn.Module):
 
     # -- the same decode on the fused step kernels (csrc/decode_step.hip) -------------------------------
     def _incremental_fast(self, encoder_out, text_positions, speaker_embed=None, initial_input=None,
-                          test_inputs=None):
+                          test_inputs=None, key_len=None, stops=None):
         """incremental_forward as a flat per-step program (decode_program.StepProgram): one conv-step entry per conv /
         projection layer and one attention-step entry per attention read (17 per step for the ljspeech preset instead
         of ~100 module calls), walked by ONE persistent launch for the whole utterance (or launch by launch):
@@ -614,7 +628,8 @@ class Decoder(nn.Module):
                 q = P.conv_step(attention.query_projection, xq, ops.EPI_LINEAR, attention.query_projection.out_features)
                 # ave_alignment = the FIRST layer's alignment * 2^(n-1)/n (the reference's `ave + ave`)
                 ctx = P.attn_step(q, kp, vp, attention.window_backward, attention.window_ahead,
-                                  self.force_monotonic_attention[idx], attn_seq=aligns if first_att else None)
+                                  self.force_monotonic_attention[idx], attn_seq=aligns if first_att else None,
+                                  key_len=key_len)
                 first_att = False
                 x = P.conv_step(attention.out_projection, ctx, ops.EPI_LINEAR, attention.out_projection.out_features,
                                 r=xq, r2=residual, out_seq=st)
@@ -622,7 +637,7 @@ class Decoder(nn.Module):
             P.conv_step(self.fc, pre, ops.EPI_SIGMOID, 1, out_seq=dones_seq)
             t = P.decode(cur_in, test_inputs, dones_seq, self.min_decoder_steps, self.max_decoder_steps,
                          getattr(self, "use_step_graph", False), getattr(self, "persistent_decode", None),
-                         getattr(self, "launched_decode", None))
+                         getattr(self, "launched_decode", None), stops=stops)
             scale = float(2 ** (n_att - 1)) / n_att if n_att else 1.0
             alignments = aligns[:t].transpose(0, 1)
             if scale != 1.0:
@@ -655,6 +670,17 @@ class Decoder(nn.Module):
         _clear_modules(self.preattention)
         _clear_modules(self.convolutions)
         self.last_conv.clear_buffer()
+
+
+def _item_key_len(text_lengths, B, Tk, device):
+    """Decoder.incremental_forward(text_lengths=...): each item's key count as a device int32[B] (None: reference mode)"""
+    if text_lengths is None:
+        return None
+    tl = torch.as_tensor(text_lengths).reshape(-1).to(torch.int64).cpu()
+    if tl.numel() != B or int(tl.min()) < 1 or int(tl.max()) > Tk:
+        raise ValueError("text_lengths: %d lengths in [1, %d] expected for a batch of %d, got %s" % (
+            B, Tk, B, tl.tolist()))
+    return tl.to(torch.int32).to(device)
 
 
 def _clear_modules(modules):

@@ -14,8 +14,8 @@ from . import conv as _conv
 from .modules import Embedding, Linear, Conv1d, ConvTranspose1d
 from .modules import HighwayConv1d, get_mask_from_lengths, key_lengths_i32
 from .modules import position_encoding_init
-from .deepvoice3 import AttentionLayer, _c8_enter, _c8_leave, _conv1d_c8
-from .decode_program import StepTrace
+from .deepvoice3 import AttentionLayer, _c8_enter, _c8_leave, _conv1d_c8, _item_key_len
+from .decode_program import StepTrace, item_results
 
 
 def _run_seq(mods, x, valid_axis=None):
@@ -226,7 +226,8 @@ class Decoder(nn.Module):
         E = self.attention.query_projection.out_features
         return (E + Tk) * 4 <= 64 * 1024 and fits(self.last_conv)
 
-    def _incremental_fast(self, encoder_out, text_positions, initial_input=None, test_inputs=None):
+    def _incremental_fast(self, encoder_out, text_positions, initial_input=None, test_inputs=None, key_len=None,
+                          stops=None):
         """incremental_forward (nyanko.py:250-338) as a flat per-step launch program (decode_program.StepProgram):
         28 conv-step launches + one attention-step launch per decoder step instead of ~150 module calls; the
         concat [R, Q] (nyanko.py:308) is one (B, 2D) buffer both producers write into."""
@@ -283,27 +284,31 @@ class Decoder(nn.Module):
             run(self.audio_encoder_modules, cur_in, dict(y=xq, post_add=pe_all, y_pre=cat[:, D:]))
             q = P.conv_step(att.query_projection, xq, ops.EPI_LINEAR, att.query_projection.out_features)
             ctx = P.attn_step(q, k, v, att.window_backward, att.window_ahead, self.force_monotonic_attention,
-                              attn_seq=aligns)
+                              attn_seq=aligns, key_len=key_len)
             P.conv_step(att.out_projection, ctx, ops.EPI_LINEAR, att.out_projection.out_features, r=xq, y=cat[:, :D])
             x = run(self.audio_decoder_modules, cat, dict(out_seq=states))
             pre = P.conv_step(self.last_conv, x, ops.EPI_LINEAR, F, y_act=nxt_in, out_seq=outs)
             P.conv_step(self.fc, pre, ops.EPI_SIGMOID, 1, out_seq=dones_seq)
             t = P.decode(cur_in, test_inputs, dones_seq, self.min_decoder_steps, self.max_decoder_steps,
                          getattr(self, "use_step_graph", False), getattr(self, "persistent_decode", None),
-                         getattr(self, "launched_decode", None))
+                         getattr(self, "launched_decode", None), stops=stops)
             alignments = aligns[:t].transpose(0, 1)
             decoder_states = states[:t].transpose(0, 1).contiguous()
             outputs = outs[:t].transpose(0, 1).contiguous()
             dones = [dones_seq[i].view(B, 1, 1) for i in range(t)]
         return outputs, alignments, dones, decoder_states
 
-    def incremental_forward(self, encoder_out, text_positions, initial_input=None, test_inputs=None):
-        """nyanko.py:250-338."""
+    def incremental_forward(self, encoder_out, text_positions, initial_input=None, test_inputs=None,
+                            text_lengths=None):
+        """nyanko.py:250-338.  text_lengths: per-utterance mode, as deepvoice3.Decoder.incremental_forward."""
         keys, values = encoder_out
-        if getattr(self, "fast_decode", True) and keys.is_cuda and self._fast_decode_eligible(keys.size(1)):
-            return self._incremental_fast(encoder_out, text_positions, initial_input, test_inputs)
         B = keys.size(0)
         dev = keys.device
+        key_len = _item_key_len(text_lengths, B, keys.size(1), dev)
+        stops = [0] * B if key_len is not None else None
+        if getattr(self, "fast_decode", True) and keys.is_cuda and self._fast_decode_eligible(keys.size(1)):
+            res = self._incremental_fast(encoder_out, text_positions, initial_input, test_inputs, key_len, stops)
+            return res if stops is None else item_results(stops, *res)
         keys_bct = keys.transpose(1, 2).contiguous()
         if text_positions is not None:
             keys_bct = ops.add_position_encoding(keys_bct, text_positions, self.embed_keys_positions.weight,
@@ -314,12 +319,14 @@ class Decoder(nn.Module):
         k = att.key_projection.forward_bct(keys_bct) if att.key_projection is not None else keys_bct
         v = att.value_projection.forward_bct(values_bct) if att.value_projection is not None else values_bct
 
-        trace = StepTrace(self.min_decoder_steps, self.max_decoder_steps, test_inputs is not None)
-        last_attended = torch.zeros(1, dtype=torch.int32, device=dev) if self.force_monotonic_attention else None
+        trace = StepTrace(self.min_decoder_steps, self.max_decoder_steps, test_inputs is not None, stops)
+        last_attended = (torch.zeros(1 if key_len is None else 2 * B, dtype=torch.int32, device=dev)
+                         if self.force_monotonic_attention else None)
         if initial_input is None:
             initial_input = keys.new_zeros(B, 1, self.in_dim * self.r)
         n_forced = test_inputs.size(1) if test_inputs is not None else None
         t = 0
+        t_dev = torch.zeros(1, dtype=torch.int32, device=dev)      # per-utterance mode: the attention step's counter
         while n_forced is None or t < n_forced:
             frame_pos = torch.full((B, 1), t + 1, dtype=torch.long, device=dev)
             if n_forced is not None:
@@ -331,10 +338,15 @@ class Decoder(nn.Module):
             xq = ops.add_position_encoding(x.transpose(1, 2).contiguous(), frame_pos,
                                            self.embed_query_positions.weight, None, False)
             q = att.query_projection.forward_bct(xq)
-            ctx, alignment = ops.attention_core(q, k, v, None, last_attended, 0.0, False,
-                                                att.window_backward, att.window_ahead)
+            if key_len is not None:               # the step program's attention kernel, per item
+                ctx, alignment = ops.attn_step_items(q, k, v, key_len, last_attended, t_dev, att.window_backward,
+                                                     att.window_ahead)
+                t_dev.add_(1)
+            else:
+                ctx, alignment = ops.attention_core(q, k, v, None, last_attended, 0.0, False,
+                                                    att.window_backward, att.window_ahead)
             R = att.out_projection.forward_bct(ctx, r=xq).transpose(1, 2)
-            if self.force_monotonic_attention:
+            if self.force_monotonic_attention and key_len is None:
                 ops._lib.call("dv3_attn_argmax_i32", alignment.data_ptr(), Tk, last_attended.data_ptr(),
                               ops._stream())
             x = torch.cat((R, Q), dim=-1)
@@ -346,7 +358,7 @@ class Decoder(nn.Module):
             t += 1
             if trace.stop(done):
                 break
-        return trace.result()
+        return trace.result() if stops is None else item_results(stops, *trace.result())
 
     def start_fresh_sequence(self):
         """forget the incremental state of every layer that keeps one (nyanko.py:340-343)"""

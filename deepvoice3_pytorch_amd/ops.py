@@ -2251,6 +2251,47 @@ class ValidLengths(object):
         raise RuntimeError("ValidLengths: no time axis of the padded batch has %d columns" % T)
 
 
+class ItemLengths(ValidLengths):
+    """The per-utterance form of ValidLengths (synthesis of a ragged batch, MultiSpeakerTTSModel.synthesize_batch): every
+    pointer is a device int32[B] -- each item's OWN length -- instead of the batch maximum, so that zero_tail zeroes
+    item b beyond its own last column, as a lone utterance's non-causal convolution sees its own zero padding.
+
+      text_len  int32[B]: each item's text length (the encoder axis)
+      dec_len   int32[B]: each item's decoder steps, set once the decode has ended (set_dec); the converter's axes are
+                dec_len x r x its upsampling, so axis_for hands out (dec_len, tail, T // t_dec)"""
+
+    def __init__(self, text_len, t_in, device="cpu"):
+        """text_len: the B text lengths on the host (the tails come from them: no device read)"""
+        text_len = torch.as_tensor(text_len).reshape(-1).to(torch.int32)
+        self.text_len = text_len.to(device)
+        self.t_in = int(t_in)
+        self.tail_in = self.t_in - int(text_len.min())
+        self.dec_len, self.t_dec, self.tail_dec = None, 0, 0
+
+    def set_dec(self, dec_len, t_dec):
+        """dec_len: each item's decoder steps on the host, t_dec: decoder steps of the padded batch"""
+        dec_len = torch.as_tensor(dec_len).reshape(-1).to(torch.int32)
+        self.dec_len = dec_len.to(self.text_len.device)
+        self.t_dec = int(t_dec)
+        self.tail_dec = self.t_dec - int(dec_len.min())
+
+    def clone(self):
+        raise RuntimeError("ItemLengths: a synthesis-time object, not captured into training steps")
+
+    def text(self):
+        return self.text_len, self.tail_in
+
+    def dec(self):
+        return self.dec_len, self.tail_dec
+
+    def axis_for(self, T):
+        """(per-item pointer, tail, mult) of a converter activation with T = t_dec * mult columns"""
+        if self.dec_len is None or T % self.t_dec:
+            raise RuntimeError("ItemLengths: no time axis of the decoded batch has %d columns" % T)
+        mult = T // self.t_dec
+        return self.dec_len, self.tail_dec * mult, mult
+
+
 valid = None      # a ValidLengths, set by the trainer for the duration of a step on a batch padded beyond its maxima
 
 
@@ -2265,6 +2306,13 @@ def _zero_tail_raw(x, ptr, mult, max_tail):
         rows = x.numel() // T
     if not x.is_contiguous():
         raise RuntimeError("zero_tail: contiguous tensors only")
+    if ptr.numel() > 1:         # one length per batch item (ItemLengths)
+        B = x.shape[0]
+        if ptr.numel() != B or ptr.dtype != torch.int32:
+            raise RuntimeError("zero_tail: %d per-item lengths for a batch of %d" % (ptr.numel(), B))
+        _lib.call("dv3_zero_tail_items_b32", x.data_ptr(), B, rows // B, T, words, ptr.data_ptr(), int(mult),
+                  int(max_tail), _stream())
+        return
     _lib.call("dv3_zero_tail_b32", x.data_ptr(), rows, T, words, ptr.data_ptr(), int(mult), int(max_tail), _stream())
 
 
@@ -2288,7 +2336,7 @@ class _ZeroTailFn(torch.autograd.Function):
 
 
 def zero_tail(x, ptr, max_tail, mult=1):
-    """see ValidLengths; ptr: device int32[1] = valid columns at mult 1"""
+    """see ValidLengths; ptr: device int32[1] = valid columns at mult 1, or int32[B]: item b's (ItemLengths)"""
     if max_tail <= 0:
         return x
     out = _ZeroTailFn.apply(x, ptr, mult, max_tail)
@@ -2296,6 +2344,42 @@ def zero_tail(x, ptr, max_tail, mult=1):
     if c is not None:
         out._dv3_C = c          # a channel-blocked tensor remembers its channel count
     return out
+
+
+def zero_frames(x, lengths, min_length, mult=1):
+    """x (B, T, D) fp32 contiguous, in place: frames t >= lengths[b] * mult of item b to zero (lengths device int32[B],
+    min_length their minimum as a host int; the per-item results of a ragged synthesis batch)"""
+    _chk(x, "x")
+    if not x.is_contiguous():
+        raise RuntimeError("zero_frames: contiguous tensors only")
+    B, T = x.shape[0], x.shape[1]
+    if B == 0 or T == 0 or x.numel() == 0:
+        return x
+    words = x.numel() // (B * T)
+    tail = T - int(min_length) * mult
+    _lib.call("dv3_zero_tail_items_b32", x.data_ptr(), B, 1, T, words, lengths.data_ptr(), int(mult), max(tail, 0),
+              _stream())
+    return x
+
+
+def attn_step_items(q, k, v, key_len, last_attended, t, win_back, win_ahead):
+    """one per-utterance attention read at step t (dv3_attn_step_f32 with key_len, include/dv3hip.h): q (B, E, 1), k and
+    v (B, E, Tk) fp32; key_len int32[B], last_attended int32[2, B] or None (slot t & 1 read, (t + 1) & 1 written);
+    t the device int32[1] step counter (a captured step replays with the counter it reads)
+    -> ctx (B, E, 1), attn (B, 1, Tk) with zeros at keys n >= key_len[b]"""
+    B, E, Tk = k.shape
+    q, k, v = _c(q), _c(k), _c(v)
+    ctx = torch.empty(B, E, 1, dtype=torch.float32, device=q.device)
+    attn = torch.empty(B, 1, Tk, dtype=torch.float32, device=q.device)
+    d = STRUCTS["dv3_attn_step_desc"]()
+    d.q, d.q_bs, d.k, d.v, d.kv_tke = q.data_ptr(), E, k.data_ptr(), v.data_ptr(), 0
+    d.last_attended = _ptr(last_attended)
+    d.win_back, d.win_ahead, d.t = win_back, win_ahead, t.data_ptr()
+    d.ctx, d.ctx_bs, d.attn = ctx.data_ptr(), E, attn.data_ptr()
+    d.B, d.E, d.Tk = B, E, Tk
+    d.key_len = key_len.data_ptr()
+    _lib.call("dv3_attn_step_f32", ctypes.byref(d), _stream())
+    return ctx, attn
 
 
 # ----------------------------------------------------------------------------------------------

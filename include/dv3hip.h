@@ -30,7 +30,7 @@ extern "C" {
 #define DV3_ELAUNCH (-2)  /* hipLaunch / runtime error        */
 
 /* ABI version, bumped on any struct change; checked by the Python loader. */
-#define DV3_ABI_VERSION 43
+#define DV3_ABI_VERSION 44
 int dv3_abi_version(void);
 const char* dv3_last_error(void);
 /* Fills name (<=255 chars) of device `dev`, number of CUs; returns 0/err. */
@@ -589,6 +589,13 @@ int dv3_memset_rows_b8(void* p, int32_t value, int64_t rows, int64_t row_bytes, 
  * that by zeroing the activations -- and, in backward, the activation gradients -- beyond the batch's own maximum.  */
 int dv3_zero_tail_b32(void* x, int64_t rows, int32_t T, int32_t words, const int32_t* t_valid, int32_t mult,
                       int32_t max_tail, void* stream);
+/* ABI 44 (per-utterance synthesis).  The same per batch item: x holds B items of rows_per_item rows of [T] elements of
+ * `words` 32-bit words (fp32 (B, C, T): rows_per_item = C, words = 1; channel-blocked bf16 [B][C8][T][8]: rows_per_item
+ * = C8, words = 4); columns t >= len[b] * mult of item b's rows are set to zero, len a device int32[B]; the host
+ * promises T - len[b] * mult <= max_tail for every b.  A lone utterance's non-causal convolution sees its own zero
+ * padding beyond its last frame (modules.py:139-143); in a ragged batch each item keeps that.  */
+int dv3_zero_tail_items_b32(void* x, int32_t B, int64_t rows_per_item, int32_t T, int32_t words, const int32_t* len,
+                            int32_t mult, int32_t max_tail, void* stream);
 /* Embedding gather into BCT with optional dropout: out[b][c][t] = W[idx[b][t]][c]
  * (deepvoice3.py:74-75, nyanko.py:63).  Backward: dense scatter-add into dW.           */
 int dv3_embedding_bct_f32(const int64_t* idx, const float* w, float* out,
@@ -714,6 +721,12 @@ int dv3_clip_adam_f32(float* p, const float* g, float* m, float* v, int64_t n,
  *   [last-win_back, last+win_ahead) (all keys when last_attended is NULL), softmax, ctx = P v * Tk*sqrt(1/Tk);
  *   attn (B, Tk) and / or attn_seq [t][b][n]; last_attended is a PAIR of device ints: slot t&1 is read, the
  *   argmax of batch item 0 (deepvoice3.py:445) is stored in slot (t+1)&1.
+ *   ABI 44, per-utterance mode (key_len != NULL): item b reads only its own keys n < s = key_len[b] (clamped to
+ *   [1, Tk]; Tk stays the row stride of k, v, attn and attn_seq): its window clamps to s, its softmax runs over
+ *   those keys (probabilities of n >= s are written as 0) and its context scale is s * sqrt(1 / s) -- exactly what
+ *   the reference computes for that utterance alone at B = 1.  last_attended is then [2][B] (slot t&1 row read,
+ *   slot (t+1)&1 row written) and EVERY item stores its own first-maximum argmax.  Not taken by
+ *   dv3_decode_program_run (its device-side stop rule is one flag per batch): refused there.
  * ------------------------------------------------------------------------------------ */
 typedef struct dv3_conv_step_desc {
   const float* x; int64_t x_bs;
@@ -760,6 +773,7 @@ typedef struct dv3_attn_step_desc {
   int32_t t_value;                           /* the step index when `t` is NULL             */
   int32_t kv_tke, reserved;                  /* 1: k and v are (B, Tk, E) -- the reference's own layout (deepvoice3.py:
                                                 132-141), a key / value row is contiguous: coalesced for a one-frame read */
+  const int32_t* key_len;                    /* [B] device ints: per-utterance mode (ABI 44), or NULL           */
 } dv3_attn_step_desc;
 int dv3_attn_step_f32(const dv3_attn_step_desc* d, void* stream);
 
@@ -858,6 +872,22 @@ int dv3_lws_istft_frames_f32(const float* mag, const float* phasor /* NULL: zero
 int dv3_lws_overlap_add_f32(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, void* stream);
 int dv3_lws_gl_project_f32(const float* y, const float* mag, const float* awin, const float* swin, float* frames, int32_t B,
                            int32_t T, int32_t hop, void* stream);
+
+/* ABI 44 (per-utterance synthesis): the same inverse on a batch padded to T frames whose item b has only tlen[b] frames
+ * (device int32[B]); lws = 1: the lws framing (swin / awin as above), 0: the torch framing.  Item b uses its own frames,
+ * its own signal end (L_b = (tlen[b] + 1) * hop - 1024, or hop * (tlen[b] - 1)) for the reflection / zero padding and its
+ * own overlap-add normaliser: exactly its B = 1 call on its own trimmed spectrogram.  Rows stay L(T) samples apart;
+ * samples from L_b on are written as zeros; frames past tlen[b] are neither written nor read.  tlen[b] is clamped into
+ * [fewest frames the framing takes at this hop, T] (T must be at least that).  */
+int dv3_gl_istft_items_f32(const float* mag, const float* phasor /* NULL: zero phase */, const float* swin, float* frames,
+                           int32_t B, int32_t T, int32_t hop, const int32_t* tlen, int32_t lws, void* stream);
+int dv3_overlap_add_items_f32(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, const int32_t* tlen,
+                              int32_t lws, void* stream);
+int dv3_gl_project_items_f32(const float* y, const float* mag, const float* awin, const float* swin, float* frames,
+                             int32_t B, int32_t T, int32_t hop, const int32_t* tlen, int32_t lws, void* stream);
+/* de-emphasis of row b over its own first lens[b] samples (device int32[B]); the rest of the row is written as zeros */
+int dv3_deemphasis_items_f32(const float* x, float* y, int32_t B, int32_t L, const int32_t* lens, float coef,
+                             void* stream);
 
 #ifdef __cplusplus
 }
