@@ -318,3 +318,104 @@ def _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths):
     _lib.call("dv3_deemphasis_items_f32", y.data_ptr(), out.data_ptr(), B, y.shape[1],
               lengths.to(torch.int32).to(y.device).data_ptr(), float(cfg.preemphasis), _stream())
     return out, lengths
+
+
+# ---------------------------------------------------------------------------------------------
+# ragged forward analysis: features of utterances of different lengths in one launch (preprocessing,
+# on-the-fly training features; audio.py:31-35,46-51 as ljspeech.py:40-76 calls them)
+# ---------------------------------------------------------------------------------------------
+_MEL_CACHE = {}
+
+
+def mel_tables(device, sample_rate=22050, num_mels=80, fmin=125.0, fmax=7600.0):
+    """(basis (num_mels, 513) float32, band int32 (num_mels, 2)) on `device`: band[m] = [first, last + 1) of filter m's
+    nonzero bins (the kernel's dot skips the bins outside it -- exact zeros, so the fp32 sum is the same)"""
+    key = (str(device), int(sample_rate), int(num_mels), float(fmin), float(fmax))
+    if key not in _MEL_CACHE:
+        w = mel_basis(sample_rate, N_FFT, num_mels, fmin, fmax)
+        band = np.zeros((num_mels, 2), dtype=np.int32)
+        for m in range(num_mels):
+            nz = np.nonzero(w[m])[0]
+            band[m] = (nz[0], nz[-1] + 1) if nz.size else (0, 0)
+        _MEL_CACHE[key] = (torch.from_numpy(w).to(device), torch.from_numpy(band).to(device))
+    return _MEL_CACHE[key]
+
+
+def _check_lws(cfg, what):
+    if cfg.convention != "lws":
+        raise ValueError("%s: only the lws framing (the reference's features) is supported; the torch framing has no "
+                         "ragged rule for its reflect padding" % what)
+
+
+def item_gains(wav_flat, lengths, rescaling_max, device_offsets=None):
+    """hparams.rescaling (ljspeech.py:59-60) per item: device float32[B], gain[b] = rescaling_max / max|x_b| in fp32
+    (1 for a silent item).  The host formula: np.float32(rescaling_max) / np.abs(x_b).max()."""
+    wav_flat = _c(_chk(wav_flat, "wav_flat"))
+    soff = device_offsets if device_offsets is not None else _sample_offsets(lengths, wav_flat.device)
+    B = len(lengths)
+    gain = torch.empty(B, dtype=torch.float32, device=wav_flat.device)
+    _lib.call("dv3_item_gain_f32", wav_flat.data_ptr(), soff.data_ptr(), B, float(rescaling_max), gain.data_ptr(),
+              _stream())
+    return gain
+
+
+def _sample_offsets(lengths, device):
+    return torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(device, non_blocking=True)
+
+
+def features_items(wav_flat, lengths, cfg=None, num_mels=80, fmin=125, fmax=7600, rescaling=None):
+    """Linear and mel features of B utterances packed back to back in `wav_flat` (a 1-D float32 device tensor; item b
+    is the next lengths[b] samples) -> (lin (sum T_b, 513), mel (sum T_b, num_mels), frames int64[B] on the host),
+    T_b = lws_num_frames(lengths[b], hop): the rows of PackedBatch.lin / .mel (data.py), item b's at
+    frames[:b].sum() ... frames[:b + 1].sum().  Each row depends on its own item only: the linear rows are bit for bit
+    spectrogram_batch(item[None])[0].T, and the mel rows are a fixed-order sum (see include/dv3hip.h:
+    dv3_analysis_items_f32).  rescaling: None / False, or rescaling_max (hparams.rescaling_max) -- item b is analysed
+    as x_b * item_gains(...)[b]."""
+    cfg = cfg or AudioConfig()
+    _check_lws(cfg, "features_items")
+    wav_flat = _c(_chk(wav_flat, "wav_flat"))
+    if wav_flat.dim() != 1:
+        raise ValueError("features_items: wav_flat must be 1-D (the items back to back)")
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    B = lengths.size
+    if B == 0 or int(lengths.min()) < 1 or int(lengths.sum()) != wav_flat.numel():
+        raise ValueError("features_items: %d samples do not split into items of lengths %s (each >= 1)"
+                         % (wav_flat.numel(), lengths.tolist()))
+    hop = cfg.hop_size
+    frames = np.array([lws_num_frames(int(n), hop) for n in lengths], dtype=np.int64)
+    nf = int(frames.sum())
+    if nf >= 2 ** 31 or int(lengths.max()) >= 2 ** 31 - N_FFT:
+        raise ValueError("features_items: batch too large for one launch (%d frames)" % nf)
+    dev = wav_flat.device
+    soff = _sample_offsets(lengths, dev)
+    foff = torch.from_numpy(np.concatenate([[0], np.cumsum(frames)]).astype(np.int32)).to(dev, non_blocking=True)
+    awin, _ = lws_windows(dev, hop, cfg.window_scale)
+    basis, band = mel_tables(dev, cfg.sample_rate, num_mels, fmin, fmax)
+    gain = item_gains(wav_flat, lengths, rescaling, soff) if rescaling else None
+    lin = torch.empty((nf, N_BIN), dtype=torch.float32, device=dev)
+    mel = torch.empty((nf, num_mels), dtype=torch.float32, device=dev)
+    _lib.call("dv3_analysis_items_f32", wav_flat.data_ptr(), soff.data_ptr(), foff.data_ptr(), B, nf, hop,
+              float(cfg.preemphasis), awin.data_ptr(), gain.data_ptr() if gain is not None else None, basis.data_ptr(),
+              band.data_ptr(), num_mels, float(cfg.min_level_db), float(cfg.ref_level_db), lin.data_ptr(),
+              mel.data_ptr(), _stream())
+    return lin, mel, frames
+
+
+def pack_waveforms(wavs, pin=None):
+    """[1-D float arrays] -> (one flat float32 host tensor, pinned when CUDA is present; lengths int64[B])"""
+    lengths = np.array([len(w) for w in wavs], dtype=np.int64)
+    if pin is None:
+        pin = torch.cuda.is_available()
+    flat = torch.empty(int(lengths.sum()), dtype=torch.float32, pin_memory=bool(pin))
+    fv = flat.numpy()
+    o = 0
+    for w, n in zip(wavs, lengths):
+        fv[o:o + n] = w
+        o += n
+    return flat, lengths
+
+
+def features_from_arrays(wavs, cfg=None, device="cuda:0", **kw):
+    """features_items for a list of 1-D host waveforms: one pinned staging buffer, one host-to-device copy."""
+    flat, lengths = pack_waveforms(wavs)
+    return features_items(flat.to(device, non_blocking=True), lengths, cfg, **kw)

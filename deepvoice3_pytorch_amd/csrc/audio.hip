@@ -38,6 +38,39 @@ __device__ __forceinline__ int item_samples(int Tb, int hop) { return LWS ? (Tb 
 
 __device__ __forceinline__ float hann(int n) { return 0.5f - 0.5f * cospif(2.0f * (float)n / (float)NFFT); }
 
+// ---- forward-analysis steps shared by the batch path (preemphasis_kernel, stft_phase_kernel<true>,
+// amp_to_db_norm_kernel) and the ragged one (analysis_items_kernel).  Each states its roundings explicitly (fmaf, or
+// contraction off): whether the compiler contracts a * b + c depends on the code around it, and the two paths must round
+// alike.  The forms are the ones the batch kernels compiled to before they shared them. ----
+// y[i] = x[i] - coef * x[i-1] (one rounding), y[0] = x[0]   (nnmnkwii.preprocessing.preemphasis, audio.py:21-23)
+__device__ __forceinline__ float preemph(float cur, float prev, float coef) { return fmaf(-coef, prev, cur); }
+__device__ __forceinline__ float preemph_at(const float* x, int i, float coef) { return i ? preemph(x[i], x[i - 1], coef) : x[0]; }
+// x * gain rounded on its own (never contracted into the preemphasis that reads it): the product a host computes
+// in fp32 before it hands the rescaled signal to the batch path
+__device__ __forceinline__ float gain_mul(float x, float g) {
+#pragma clang fp contract(off)
+  return x * g;
+}
+// the lws framing of frame t into A: aw[n] * sample(t * hop + n - (NFFT - hop)) inside [0, L), zeros outside
+template <class Sample>
+__device__ __forceinline__ void lws_frame(cplx* A, int t, int hop, int L, const float* aw, int tid, Sample sample) {
+  for (int n = tid; n < NFFT; n += 256) {
+    const int i = t * hop + n - (NFFT - hop);
+    A[n] = cplx{(i >= 0 && i < L) ? sample(i) * aw[n] : 0.f, 0.f};
+  }
+}
+// |z| = sqrt(rn(x^2) + rn(y^2)): both squares rounded, no fused multiply-add
+__device__ __forceinline__ float cabs_f(cplx z) {
+#pragma clang fp contract(off)
+  return sqrtf(z.x * z.x + z.y * z.y);
+}
+// amp_to_db_norm: clip((20*log10(max(min_level, x)) - ref_db - min_db) / -min_db, 0, 1)   audio.py:34-35,79-89
+__device__ __forceinline__ float db_min_level(float min_db) { return exp2f(min_db * 0.05f * 3.32192809488736234787f); }
+__device__ __forceinline__ float db_norm(float x, float min_level, float min_db, float ref_db) {
+  const float db = fmaf(20.0f, log10f(fmaxf(min_level, x)), -ref_db);
+  return fminf(fmaxf((db - min_db) / (-min_db), 0.f), 1.f);
+}
+
 // W[j] = exp(+2 pi i j / 1024), filled once per workgroup (4 sincospif per thread instead of 3 per butterfly and
 // pass: the transcendental calls were most of a frame's instructions).  hann(n) = 0.5 - 0.5 * Re W[n].
 __device__ __forceinline__ void fill_twiddles(cplx* W, int tid) {
@@ -177,11 +210,10 @@ __global__ __launch_bounds__(256) void stft_phase_kernel(const float* __restrict
   const int tid = threadIdx.x;
   const int b = blockIdx.x / T, t = blockIdx.x - b * T;
   const float* yb = y + (int64_t)b * L;
-  for (int n = tid; n < NFFT; n += 256) {
-    if constexpr (LWS) {
-      const int i = t * hop + n - (NFFT - hop);
-      A[n] = cplx{(i >= 0 && i < L) ? yb[i] * aw[n] : 0.f, 0.f};
-    } else {
+  if constexpr (LWS) {
+    lws_frame(A, t, hop, L, aw, tid, [=](int i) { return yb[i]; });
+  } else {
+    for (int n = tid; n < NFFT; n += 256) {
       int i = t * hop + n - NFFT / 2;  // index into the un-padded signal
       if (i < 0) i = -i;
       if (i >= L) i = 2 * (L - 1) - i;
@@ -196,9 +228,9 @@ __global__ __launch_bounds__(256) void stft_phase_kernel(const float* __restrict
       spec[(fr * NBIN + k) * 2] = z.x;
       spec[(fr * NBIN + k) * 2 + 1] = z.y;
     }
-    if (mag_bct) mag_bct[((int64_t)b * NBIN + k) * T + t] = sqrtf(z.x * z.x + z.y * z.y);
+    if (mag_bct) mag_bct[((int64_t)b * NBIN + k) * T + t] = cabs_f(z);
     if (phasor) {
-      const float inv = 1.0f / fmaxf(sqrtf(z.x * z.x + z.y * z.y), 1e-8f);
+      const float inv = 1.0f / fmaxf(cabs_f(z), 1e-8f);
       phasor[(fr * NBIN + k) * 2] = z.x * inv;
       phasor[(fr * NBIN + k) * 2 + 1] = z.y * inv;
     }
@@ -348,8 +380,7 @@ __global__ void preemphasis_kernel(const float* __restrict__ x, float* __restric
   const int b = blockIdx.y;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= L) return;
-  const float* xr = x + (int64_t)b * L;
-  y[(int64_t)b * L + i] = i ? xr[i] - coef * xr[i - 1] : xr[0];
+  y[(int64_t)b * L + i] = preemph_at(x + (int64_t)b * L, i, coef);
 }
 
 // out = clip((20*log10(max(min_level, x)) - ref_db - min_db) / -min_db, 0, 1)   audio.py:34-35,79-89
@@ -357,10 +388,75 @@ __global__ void amp_to_db_norm_kernel(const float* __restrict__ x, float* __rest
                                       float min_db, float ref_db) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const float min_level = exp2f(min_db * 0.05f * 3.32192809488736234787f);
-  for (; i < n; i += stride) {
-    const float db = 20.0f * log10f(fmaxf(min_level, x[i])) - ref_db;
-    out[i] = fminf(fmaxf((db - min_db) / (-min_db), 0.f), 1.f);
+  const float min_level = db_min_level(min_db);
+  for (; i < n; i += stride) out[i] = db_norm(x[i], min_level, min_db, ref_db);
+}
+
+// ---- ragged forward analysis (ABI 45, include/dv3hip.h: dv3_analysis_items_f32) ----
+// gain[b] = rescaling_max / max|x_b| over item b's own samples, 1 for a silent item.  One workgroup per item; fmaxf is
+// exact, so the reduction order does not show in the result.
+__global__ __launch_bounds__(256) void item_gain_kernel(const float* __restrict__ x, const int64_t* __restrict__ soff,
+                                                        float rescaling_max, float* __restrict__ gain) {
+  __shared__ float red[256];
+  const int tid = threadIdx.x;
+  const int64_t lo = soff[blockIdx.x], hi = soff[blockIdx.x + 1];
+  float m = 0.f;
+  for (int64_t i = lo + tid; i < hi; i += 256) m = fmaxf(m, fabsf(x[i]));
+  red[tid] = m;
+  for (int s = 128; s > 0; s >>= 1) {
+    __syncthreads();
+    if (tid < s) red[tid] = fmaxf(red[tid], red[tid + s]);
+  }
+  if (tid == 0) gain[blockIdx.x] = red[0] > 0.f ? rescaling_max / red[0] : 1.f;
+}
+
+// One workgroup per OUTPUT ROW g of the packed result: frame t = g - foff[b] of item b (foff[b] <= g < foff[b+1]).
+// preemphasis (optionally of gain[b] * x) inline -> lws framing of item b's own samples [0, L_b) -> 1024-point FFT in
+// LDS -> |X| -> lin row (dB-normalised) and, from the magnitudes left in LDS, the mel row: one lane per filter, a
+// fixed-order fmaf chain over the filter's ascending nonzero bins [band[2m], band[2m+1]).  Nothing of the row depends
+// on another item, on B or on the grid: the row is what item b alone gives.  The linear row takes the same steps, in
+// the same expressions, as preemphasis_kernel -> stft_phase_kernel<true> -> amp_to_db_norm_kernel.
+template <bool GAIN>
+__global__ __launch_bounds__(256) void analysis_items_kernel(
+    const float* __restrict__ x, const int64_t* __restrict__ soff, const int32_t* __restrict__ foff, int B, int hop,
+    float coef, const float* __restrict__ aw, const float* __restrict__ gain, const float* __restrict__ basis,
+    const int32_t* __restrict__ band, int n_mels, float min_db, float ref_db, float* __restrict__ lin,
+    float* __restrict__ mel) {
+  __shared__ cplx A[NFFT], Bf[NFFT];
+  const int tid = threadIdx.x;
+  const int g = blockIdx.x;
+  int lo = 0, hi = B;                                 // the item: largest b with foff[b] <= g
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (foff[mid] <= g) lo = mid; else hi = mid;
+  }
+  const int b = lo, t = g - foff[b];
+  const float* xb = x + soff[b];
+  const int L = (int)(soff[b + 1] - soff[b]);
+  if constexpr (GAIN) {
+    const float gb = gain[b];
+    lws_frame(A, t, hop, L, aw, tid, [=](int i) {
+      return i ? preemph(gain_mul(xb[i], gb), gain_mul(xb[i - 1], gb), coef) : gain_mul(xb[0], gb);
+    });
+  } else {
+    lws_frame(A, t, hop, L, aw, tid, [=](int i) { return preemph_at(xb, i, coef); });
+  }
+  fft1024<-1>(A, Bf, tid);                            // ends with a barrier; the spectrum is in Bf, A is free
+  float* Ms = reinterpret_cast<float*>(A);
+  const float min_level = db_min_level(min_db);
+  for (int k = tid; k < NBIN; k += 256) {
+    const float m = cabs_f(Bf[k]);
+    Ms[k] = m;
+    if (lin) lin[(int64_t)g * NBIN + k] = db_norm(m, min_level, min_db, ref_db);
+  }
+  if (!mel) return;                                   // workgroup-uniform
+  __syncthreads();
+  for (int m = tid; m < n_mels; m += 256) {
+    const float* w = basis + (int64_t)m * NBIN;
+    const int k0 = band ? max(band[2 * m], 0) : 0, k1 = band ? min(band[2 * m + 1], NBIN) : NBIN;
+    float acc = 0.f;
+    for (int k = k0; k < k1; ++k) acc = fmaf(w[k], Ms[k], acc);
+    mel[(int64_t)g * n_mels + m] = db_norm(acc, min_level, min_db, ref_db);
   }
 }
 
@@ -625,4 +721,26 @@ extern "C" int dv3_deemphasis_items_f32(const float* x, float* y, int32_t B, int
   }
   hipLaunchKernelGGL(deemphasis_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, y, L, coef, lens);
   return dv3_check_launch("deemphasis_items");
+}
+
+extern "C" int dv3_item_gain_f32(const float* x, const int64_t* soff, int32_t B, float rescaling_max, float* gain,
+                                 void* stream) {
+  DV3_REQUIRE(x && soff && gain && B > 0 && rescaling_max > 0.f, "item_gain: bad arguments");
+  hipLaunchKernelGGL(item_gain_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x, soff, rescaling_max, gain);
+  return dv3_check_launch("item_gain");
+}
+
+extern "C" int dv3_analysis_items_f32(const float* x, const int64_t* soff, const int32_t* foff, int32_t B,
+                                      int32_t n_frames, int32_t hop, float preemphasis, const float* awin,
+                                      const float* gain, const float* mel_basis, const int32_t* mel_band, int32_t n_mels,
+                                      float min_level_db, float ref_level_db, float* lin, float* mel, void* stream) {
+  DV3_REQUIRE(x && soff && foff && awin && B > 0 && n_frames > 0 && hop > 0 && hop <= 1024 && (lin || mel) &&
+              (!mel || (mel_basis && n_mels > 0)) && min_level_db < 0.f, "analysis_items: bad arguments");
+  if (gain)
+    hipLaunchKernelGGL(analysis_items_kernel<true>, dim3(n_frames), dim3(256), 0, (hipStream_t)stream, x, soff, foff, B,
+                       hop, preemphasis, awin, gain, mel_basis, mel_band, n_mels, min_level_db, ref_level_db, lin, mel);
+  else
+    hipLaunchKernelGGL(analysis_items_kernel<false>, dim3(n_frames), dim3(256), 0, (hipStream_t)stream, x, soff, foff, B,
+                       hop, preemphasis, awin, gain, mel_basis, mel_band, n_mels, min_level_db, ref_level_db, lin, mel);
+  return dv3_check_launch("analysis_items");
 }

@@ -235,6 +235,77 @@ class PreprocessedDataset(torch.utils.data.Dataset):
         return text, mel, spec
 
 
+def read_audio_config(root):
+    """the audio constants a preprocessed directory was made with (its audio_config.json, written by
+    preprocess.build_from_path: convention, window_scale, hop / fft size, sample rate, preemphasis, dB levels, mel
+    parameters, rescaling) as a dict, or None for a directory without one (the reference's preprocess.py writes none)"""
+    import json
+    import os
+    path = os.path.join(root, "audio_config.json")
+    if not os.path.exists(path):
+        return None
+    with open(path) as f:
+        return json.load(f)
+
+
+class WaveformDataset(torch.utils.data.Dataset):
+    """Utterances as waveforms, for features made on the GPU per batch (waveform_collate) instead of read from a
+    preprocessed directory.  rows: [(wav path, text[, speaker id])]; items are (text ids, float32 wav[, speaker id]),
+    `text_to_sequence` being the caller's text frontend as in PreprocessedDataset.  frame_lengths are the frame counts
+    the features will have (audio.lws_num_frames of the sample count in each wav header, read without decoding), so
+    LengthBucketedSampler buckets exactly as it does on the preprocessed train.txt of the same corpus."""
+
+    def __init__(self, rows, text_to_sequence, hop_size=256, sample_rate=22050):
+        from . import audio, preprocess
+        self.rows = [tuple(r) for r in rows]
+        if not self.rows or len(self.rows[0]) not in (2, 3):
+            raise ValueError("WaveformDataset: rows are (wav path, text[, speaker id])")
+        self.multi_speaker = len(self.rows[0]) == 3
+        self.text_to_sequence, self.sample_rate = text_to_sequence, sample_rate
+        self.num_samples = [preprocess.wav_num_samples(r[0]) for r in self.rows]
+        self.frame_lengths = [audio.lws_num_frames(n, hop_size) for n in self.num_samples]
+
+    @classmethod
+    def from_ljspeech(cls, in_dir, text_to_sequence, min_text=20, hop_size=256, sample_rate=22050):
+        """the utterances preprocess.build_from_path would write, in its order (metadata.csv, min_text filter)"""
+        from . import preprocess
+        return cls([(p, text) for _, p, text in preprocess.read_metadata(in_dir, min_text)], text_to_sequence,
+                   hop_size, sample_rate)
+
+    def __len__(self):
+        return len(self.rows)
+
+    def __getitem__(self, i):
+        from . import preprocess
+        r = self.rows[i]
+        text = np.asarray(self.text_to_sequence(r[1]), dtype=np.int32)
+        wav = preprocess.load_wav(r[0], self.sample_rate)
+        if self.multi_speaker:
+            return text, wav, int(r[2])
+        return text, wav
+
+
+def waveform_collate(items, device, outputs_per_step=1, downsample_step=4, cfg=None, lattice=None, num_mels=80,
+                     fmin=125, fmax=7600, rescaling=None):
+    """[(text ids, wav[, speaker id])] -> train_step.Batch on `device`, features made on the way: the waveforms go to
+    the device in one pinned copy, audio.features_items turns them into the packed lin / mel rows, and device_collate
+    pads them as it pads a PackedBatch read from disk.  The same utterances preprocessed by preprocess.build_from_path
+    (same cfg, mel parameters and rescaling) give a bit-identical Batch: the feature rows do not depend on how the
+    utterances were batched."""
+    from . import audio
+    in_len = np.array([len(it[0]) for it in items], dtype=np.int64)
+    pin = torch.cuda.is_available()
+    text = torch.from_numpy(np.concatenate([np.asarray(it[0], dtype=np.int64) for it in items]))
+    if pin:
+        text = text.pin_memory()
+    wav, lengths = audio.pack_waveforms([it[1] for it in items], pin=pin)
+    lin, mel, frames = audio.features_items(wav.to(device, non_blocking=True), lengths, cfg, num_mels, fmin, fmax,
+                                            rescaling)
+    spk = np.array([it[2] for it in items], dtype=np.int64) if len(items[0]) == 3 else None
+    packed = PackedBatch(text, mel, lin, in_len, frames, spk)
+    return device_collate(packed, device, outputs_per_step, downsample_step, lattice=lattice)
+
+
 class ListDataset(torch.utils.data.Dataset):
     """Items held in host memory (synthetic benchmarks, tests); `repeat` makes the list appear that many
     times longer without copying."""
