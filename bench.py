@@ -6,6 +6,7 @@
            --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N --dry-launch      rendezvous + bucketed all-reduce only (gloo on a CPU-only box)
     python bench.py ... --dump-outputs DIR     also write what the last timed step computed as DIR/<name>.npy
+    python bench.py ... --full                 also measure everything beyond the headline (the fields listed below)
 
 One "step" = one full optimisation step (forward + losses + backward + [all-reduce] + clip + Adam,
 train.py:604-785) of builder=deepvoice3 preset=deepvoice3_ljspeech (BASELINE.json configs[1]) on a synthetic
@@ -13,34 +14,44 @@ LJSpeech-shaped batch resident in HBM.  value = sum over ranks of un-padded targ
 time per step (max over ranks).  GEMM arithmetic --gemm: f16x3 (default: fp32 operands split into scaled fp16
 hi+lo for the forward GEMMs and bf16 hi+lo for the gradient GEMMs, three 16-bit MFMAs per product, fp32
 accumulate; 1e-4 parity with the fp32 reference at the preset sizes), bf16x3, f32 (exact fp32 MFMA), bf16.
-`dtype` names that arithmetic.  Rank 0 prints ONE JSON line; beside the contract's fields it carries
+`dtype` names that arithmetic.  Rank 0 prints ONE JSON line.
 
+A plain run does only what that headline needs: it sets up (model, batch, launch-mode probe), settles the clocks,
+runs the W warm-up and the K timed steps, writes --dump-outputs and prints the line.  Beside the contract's fields
+the line carries
+
+  config              the workload, and how the timed step was issued: hipgraph / graph_form (a chain of segment
+                      hipGraphs with the weight-gradient branch replayed on a real second stream, or one hipGraph,
+                      or eager launches), launch_probe (both timed for a few steps, the faster kept), host issue time
+  step_flop_frac      whole step: algorithmic FLOPs per mel-frame (SURVEY.md 8d) x frames / step time vs the
+                      MFMA roof of the mode (three 16-bit MFMAs per product: 2500/3 TF; f32: 157.3 TF)
+  power               shader clock and socket power sampled during the timed loop (when the node exposes them)
+  dump_outputs        --dump-outputs DIR: the files written (dump_outputs() says what they hold)
+
+Everything else the benchmark measures runs only under --full (off by default; --no-extras, --no-roofline and
+--no-cpu-baseline leave out parts of it), where the line also carries
+
+  eager               the headline step launched eagerly, when the headline replays a hipGraph
   roofline            the dominant kernel (forward tap-GEMM, Conv1dGLU at the north-star shape B=64 x 256ch x
                       1024T, k=3) timed with HIP events on its launch stream; bound "mfma": algorithmic FLOPs /
-                      time vs the MFMA roof of the mode (three 16-bit MFMAs per product: 2500/3 TF; f32: 157.3
-                      TF); traffic = HBM bytes per launch from the PMC passes under profiles/ (null until the
-                      pass for THIS kernel has been collected)
+                      time vs the MFMA roof of the mode; traffic = HBM bytes per launch from the PMC passes under
+                      profiles/ (null until the pass for THIS kernel has been collected)
   roofline_wgrad      the weight-gradient GEMM of the same layer, same way
   roofline_exact_f32  the exact-fp32 forward kernel on the same launch, for the record
   roofline_bf16_c8    the same layer as the bf16 configs run it (single-term bf16 MFMA, channel-blocked bf16
                       input / residual / output) against the 2500 TF bf16 roof and the 8 TB/s HBM roof
-  step_flop_frac      whole step: algorithmic FLOPs per mel-frame (SURVEY.md 8d) x frames / step time vs the
-                      same MFMA roof
   value_exact_f32     the same step with every GEMM on the exact fp32 MFMA chain (5 steps)
-  launch_mode /       how the timed step was issued: "eager_two_streams", or "graph" with graph_form "segments" (a chain
-  graph_form          of segment hipGraphs, the weight-gradient branch replayed on a real second stream) or "single";
-                      probed per configuration (both timed, the faster kept; ties go to eager)
   configs             BASELINE.json configs[2..4] from the same process: nyanko_ljspeech bf16, deepvoice3_vctk bf16
                       (n_gpus = this run's), synthesis RTF (64 utterances); plus dv3lj_b16 (the preset's own batch),
-                      dv3lj_b64_ragged / dv3lj_b16_ragged (LJSpeech-like length spread instead of full-length rows)
-                      and ddp_world1 (the headline step with a one-rank RCCL group armed: what the bucketed
-                      all-reduce path costs on one GPU, eager and replayed)
+                      dv3lj_b64_ragged / dv3lj_b16_ragged (LJSpeech-like length spread instead of full-length rows),
+                      ragged epochs (eager, and replayed over a lattice of shapes), ddp_standin (the step beside a
+                      stand-in for an 8-rank ring) and ddp_world1 (the headline step with a one-rank RCCL group
+                      armed: what the bucketed all-reduce path costs on one GPU, eager and replayed)
   input_pipeline      the same step fed by data.Prefetcher (rank-sharded length-bucketed sampler, pinned
                       staging, H2D + device-side collate on a side stream) instead of a resident batch
   host_buffers        the step rate if the boundary is handed pinned host tensors synchronously (never `value`)
   cpu_baseline        the reference's own train.train() on the host cores when DV3_REFERENCE_ROOT names a reference
                       tree (kind "reference"), else the CPU oracle port of the same step (kind "port"); bounded sample
-  dump_outputs        --dump-outputs DIR: the files written (dump_outputs() says what they hold)
 """
 import argparse
 import json
@@ -1251,10 +1262,14 @@ def main():
     ap.add_argument("--graph", action="store_true", help="replay the whole step as one hipGraph")
     ap.add_argument("--settle", type=float, default=1.0,
                     help="seconds of untimed steps before --warmup (clock governor settle time; 0 = none)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the eager step, input pipeline, host buffers, "
+                         "value_exact_f32, configs, rooflines, CPU baseline (default: the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the rooflines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip value_exact_f32 / configs / input_pipeline (headline + rooflines only)")
+                    help="with --full: skip eager / input_pipeline / host_buffers / value_exact_f32 / configs "
+                         "(headline + rooflines + CPU baseline only)")
     ap.add_argument("--mode", default="train", choices=["train", "conv", "conv-ab", "synth"])
     ap.add_argument("--gl-iters", type=int, default=60, help="Griffin-Lim iterations (synth mode)")
     ap.add_argument("--force-group", action="store_true",
@@ -1332,8 +1347,10 @@ def main():
     m = run.measure(args.steps, args.warmup, settle_s=args.settle, on_last=on_last)
     if dumped:
         dumped.update(hipgraph=bool(run.use_graph), graph_form=run.graph_form())
+    # a plain run measures nothing more: what follows beyond the headline's line runs only under --full
+    extras = args.full and not args.no_extras
     m_eager = None
-    if run.use_graph and not args.no_extras:
+    if run.use_graph and extras:
         # the same step launched eagerly: host enqueue time and the all-reduce time left exposed are only observable there
         run.use_graph = False
         try:
@@ -1382,7 +1399,6 @@ def main():
                                 launch_bound=bool(m_eager["host_enqueue_ms_per_step"] > 0.97 * m_eager["ms_per_step"]),
                                 allreduce_exposed_ms=m_eager["allreduce_exposed_ms"],
                                 note="the same step with per-kernel launches through Python + ctypes (--no-graph)")
-    extras = not args.no_extras
     # ---- the same step fed through the input pipeline (sampler -> pinned staging -> side-stream H2D + device collate)
     if extras:
         try:
@@ -1407,7 +1423,7 @@ def main():
         except Exception as e:
             if rank == 0:
                 out["input_pipeline"] = dict(error="%s: %s" % (type(e).__name__, e))
-    if rank == 0:
+    if rank == 0 and extras:
         # the boundary can also be handed host buffers (train.py:655-663 copies 8 tensors per step): time the
         # H2D of one pinned batch and report the rate with that copy serialised in front of every step
         bt, spk = run.bt, run.spk
@@ -1505,7 +1521,7 @@ def main():
     if rank != 0:
         _shutdown(pg)
         return
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         rmode = "f16x3" if gemm == "bf16" else gemm
         out["roofline"] = conv_roofline(dev, mode=rmode)
         out["roofline_wgrad"] = wgrad_roofline(dev, mode=rmode)
@@ -1519,7 +1535,7 @@ def main():
             out["roofline_bf16_c8"] = {k: rc[k] for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic",
                                                            "us_per_launch", "alg_flops", "alg_bytes", "hbm_gbs",
                                                            "hbm_frac", "variant")}
-    if not args.no_cpu_baseline and world == 1 and args.preset == "deepvoice3_ljspeech":
+    if args.full and not args.no_cpu_baseline and world == 1 and args.preset == "deepvoice3_ljspeech":
         out["cpu_baseline"] = cpu_baseline(args.batch, args.text_len, args.frames)
     _flush_native_stdout()      # the result line is the last line of stdout
     print(json.dumps(out), flush=True)
