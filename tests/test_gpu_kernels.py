@@ -13,7 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import dv3_oracle as O
-from tests.util import rel_err
+from tests.util import assert_close_elementwise, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -332,7 +332,7 @@ def test_speaker_bias_paths(dev):
 
 
 @pytest.mark.parametrize("Tq,Tk,E", [(50, 37, 32), (203, 150, 64), (1, 29, 48)])
-def test_attention_core(dev, Tq, Tk, E):
+def test_attention_core(dev, gemm_mode, Tq, Tk, E):
     """q^T k -> mask -> softmax -> dropout(off) -> context * sqrt(Tk), forward and backward."""
     ops = _ops()
     rng = np.random.RandomState(Tq + Tk)
@@ -349,6 +349,19 @@ def test_attention_core(dev, Tq, Tk, E):
     gin = [t.clone().to(dev).requires_grad_(True) for t in (q, k, v)]
     cg, Pg = ops.attention_core(gin[0], gin[1], gin[2], lens.to(dev))
     assert rel_err(Pg.detach().cpu(), P.detach()) < KTOL
+    # element-wise, relative wherever P > 1e-3 (rel_err above is relative to the row's largest P): the score of E
+    # products errs by <= (split + E u) sum_e |q k| (split: 3 * 2^-18 for a bf16 / fp16 hi+lo operand pair, 0 in f32);
+    # P's relative error is that of its own score plus the row's largest, plus s - max (u |s - max|), expf (2u), the
+    # row sum (Tk/64 + 6 levels), 1/sum and the product
+    with torch.no_grad():
+        u = 2.0 ** -24
+        A = torch.bmm(q.double().abs().transpose(1, 2), k.double().abs()).masked_fill(mask[:, None, :], 0)
+        S64 = torch.bmm(q.double().transpose(1, 2), k.double()).masked_fill(mask[:, None, :], -float("inf"))
+        P64 = F.softmax(S64, dim=-1)
+        dS_ = (S64 - S64.max(-1, keepdim=True).values).masked_fill(mask[:, None, :], 0).abs()
+        e_s = (0.0 if gemm_mode == "f32" else 3 * 2.0 ** -18) + E * u
+        eP = e_s * (A + A.max(-1, keepdim=True).values) + u * (dS_ + dS_.max(-1, keepdim=True).values + (Tk + 63) // 64 + 12)
+    assert_close_elementwise(Pg.detach().cpu(), P64, eP, 1e-3 * eP, "attention P (%s)" % gemm_mode)
     assert rel_err(cg.detach().cpu(), ctx.detach()) < KTOL
     w1 = torch.from_numpy(rng.randn(*ctx.shape).astype(np.float32))
     w2 = torch.from_numpy(rng.randn(*P.shape).astype(np.float32))

@@ -36,6 +36,29 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
+def assert_close_elementwise(got, want, rtol, atol, what):
+    """Fail when any element has |got - want| > atol + rtol * |want|; report the worst element (index, both values and
+    its ratio to the bound).  rtol / atol may be arrays broadcastable to `want` (a per-element error bound).  Returns the
+    worst ratio to the bound (<= 1 when the check passes) so a test can report it."""
+    got = np.asarray(got.detach().cpu() if torch.is_tensor(got) else got, dtype=np.float64)
+    want = np.asarray(want.detach().cpu() if torch.is_tensor(want) else want, dtype=np.float64)
+    rtol = np.asarray(rtol.detach().cpu() if torch.is_tensor(rtol) else rtol, dtype=np.float64)
+    atol = np.asarray(atol.detach().cpu() if torch.is_tensor(atol) else atol, dtype=np.float64)
+    assert got.shape == want.shape, "%s: shape %s != %s" % (what, got.shape, want.shape)
+    err = np.abs(got - want)
+    bound = np.broadcast_to(atol + rtol * np.abs(want), want.shape)
+    bad = ~(err <= bound)                       # NaN on either side fails
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(err == 0, 0.0, err / bound)
+    ratio = np.where(np.isnan(err), np.inf, ratio)
+    worst = np.unravel_index(int(np.argmax(ratio)), ratio.shape) if ratio.size else ()
+    r = float(ratio[worst]) if ratio.size else 0.0
+    assert not bad.any(), "%s: %d of %d elements out of bound; worst at %s: got %r want %r (|err| %.3g, bound %.3g, " \
+        "ratio %.3g)" % (what, int(bad.sum()), bad.size, tuple(int(i) for i in worst), float(got[worst]),
+                         float(want[worst]), float(err[worst]), float(bound[worst]), r)
+    return r
+
+
 def synth_state_dict(shapes, stats, seed, keep=None):
     """Deterministic weights for the preset-size goldens: tensor i (keys in sorted order) =
     mean_i + std_i * RandomState(seed + i).standard_normal(shape), float32 -- numpy's legacy generator is
