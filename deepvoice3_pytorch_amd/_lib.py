@@ -13,7 +13,7 @@ import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "dv3hip.h")
-# DV3_LIBPATH: developer scripts load the experiment build (csrc: `make EXP=1` -> libdv3hip_exp.so) instead
+# DV3_LIBPATH: load another build of the library (an A/B copy, for instance) instead of the in-tree one
 _LIBPATH = os.environ.get("DV3_LIBPATH") or os.path.join(_HERE, "libdv3hip.so")
 if not os.path.isabs(_LIBPATH):
     _LIBPATH = os.path.join(_HERE, _LIBPATH)
@@ -157,7 +157,7 @@ def lib():
             raise Dv3LibraryError("struct %s: C sizeof %d != ctypes %d" % (name, n, ctypes.sizeof(cls)))
     _lib = h
     # developer knobs (include/dv3hip.h: dv3_debug_set) from the environment, for A/B runs
-    for what, var in ((1, "DV3_X3_ABLATE"), (2, "DV3_WGRAD_TILE"), (3, "DV3_X3_PINGPONG")):
+    for what, var in ((2, "DV3_WGRAD_TILE"), (3, "DV3_X3_PINGPONG")):
         if os.environ.get(var) is not None and os.environ[var] != "":
             h.dv3_debug_set(what, int(os.environ[var]))
     return h

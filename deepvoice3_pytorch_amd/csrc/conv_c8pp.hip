@@ -57,17 +57,10 @@ __device__ __forceinline__ bf16x8 c8pp_keep8(const bf16x8& v, uint32_t m) {
   return __builtin_bit_cast(bf16x8, d);
 }
 
-// ABL (make EXP=1 only; dv3_debug_set(21, v)): timing-only ablations, results are wrong: 1 no MFMAs, 2 no staging (no
-// global fetches, no LDS stores) in the loop, 3 no tail, 5 no fragment reads in the loop, 6 no barriers in the loop
 // RF (round 5): the twelve fragment reads of a LOAD phase are issued FIRST and the staging (panel / tile stores, the
 // refetches) runs while they land -- the phase is then max(reads, staging) long instead of their sum (the reads of four
 // waves take 200-350 cycles of the 512 a partner's 16 MFMAs last).  Same instructions, same results.
-// RL (round 5): the residual of a Conv1dGLU / HighwayConv1d layer IS its input (modules.py:139,163,224-226: y = f(conv(x))
-// + x): the 128 `a` channels of this tile are four of the 32-channel chunks the main loop stages anyway.  Their units
-// (raw, before the keep-bytes) are stored a second time into a 64 KB strip [16 channel groups][256 columns] behind the
-// tile buffers, and the tail reads the residual from there instead of fetching 33.5 MB (north star) from memory inside
-// the chip-wide tail burst.  Taken when the descriptor's residual tensor is the input tensor itself.
-template <int JT, bool MASK, int ABL = 0, bool RF = false, bool RL = false, int NW = 8>
+template <int JT, bool MASK, bool RF = false, int NW = 8>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_c8pp_kernel(const ConvArgs args) {
   constexpr int NT = C8ppGeo<NW>::NT, WN = C8ppGeo<NW>::WN, BN = C8ppGeo<NW>::BN, AU = C8ppGeo<NW>::AU;
   constexpr bool PP = NW == 8;               // ping-pong halves
@@ -81,7 +74,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_c8pp_kernel(con
   const int BNH = BN + (JT - 1) * dil;
   bf16x8* const As = reinterpret_cast<bf16x8*>(smem_raw);   // [2 buffers][KB][BM]
   bf16x8* const Xs = As + 2 * KB * BM;                      // [2 buffers][XPS]  ([KB][BNH] + padding)
-  bf16x8* const Rs = Xs + 2 * XPS;                          // RL: [BMH / 8 channel groups][BN] residual units
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -175,20 +167,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_c8pp_kernel(con
     rx[i] = c8pp_ldg<bf16x8>(src, xoff[i]);
     if constexpr (MASK) rk[i] = (uint32_t)c8pp_ldg<uint8_t>(xkeep + (int64_t)chunk * KB * T, xoff[i] >> 4);
   };
-  // `chunk`: the 32-channel chunk the item belongs to (RL: chunks [mt * 4, mt * 4 + 4) hold this tile's `a` channels)
-  auto write_X_item = [&](int buf, auto ic, int chunk) {
+  auto write_X_item = [&](int buf, auto ic) {
     constexpr int i = decltype(ic)::value;
     bf16x8 v = rx[i];
-    if constexpr (RL) {
-      const int cr = chunk - mt * (BMH / 32);                        // uniform
-      if (cr >= 0 && cr < BMH / 32) {
-        int t_ = tid;
-        asm volatile("" : "+v"(t_));                                  // (recomputed here, four times per tile: no register held for it)
-        const int idx = t_ + i * NT;
-        const int k8 = idx / BNH, col = idx - k8 * BNH - p.padL;      // unit (k8, q) of the haloed tile; output column q - padL
-        if (idx < n_items && col >= 0 && col < BN) Rs[(cr * KB + k8) * BN + col] = v;
-      }
-    }
     if constexpr (MASK) v = c8pp_keep8(v, rk[i]);
     Xs[buf * XPS + tid + i * NT] = v;
   };
@@ -200,10 +181,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_c8pp_kernel(con
     load_X_item(chunk, U1{});
     if constexpr (XI == 3) load_X_item(chunk, U2{});
   };
-  auto write_X_all = [&](int buf, int chunk) {
-    write_X_item(buf, U0{}, chunk);
-    write_X_item(buf, U1{}, chunk);
-    if constexpr (XI == 3) write_X_item(buf, U2{}, chunk);
+  auto write_X_all = [&](int buf) {
+    write_X_item(buf, U0{});
+    write_X_item(buf, U1{});
+    if constexpr (XI == 3) write_X_item(buf, U2{});
   };
 
   f32x16 acc[MI][2][NI];   // [row sub-tile][a rows | gate rows][column sub-tile]
@@ -223,7 +204,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_c8pp_kernel(con
   load_A(0, 0);
   load_X_all(0);
   write_A(0);
-  write_X_all(0, 0);
+  write_X_all(0);
   __syncthreads();
   {
     // step 1 = (chunk 0, tap 1) for three-tap layers, (chunk 1, tap 0) for 1 x 1 layers; past the end: re-fetch step 0
@@ -241,7 +222,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_c8pp_kernel(con
   // read in the L phases of step s-1 (intervals 2s-2, 2s-1) and first read in L(s+1) (interval 2s+2); the tile of chunk
   // c+1 during the L phases of chunk c into the buffer last read in chunk c-1.  Every interval ends with a barrier.
   const int late = PP ? (wave >> 2) : 0;
-  if (late && ABL != 6) __syncthreads();
+  if (late) __syncthreads();
   if constexpr (!PP) {
     // the two workgroups of a CU start together: the odd one of a pair waits a little so that they do not run the
     // same phase (args.stagger units of 64 cycles; which blocks share a CU is the dispatcher's business -- adjacent
@@ -261,15 +242,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_c8pp_kernel(con
       // ---------------- LOAD ----------------
       bf16x8 fa[2][MI][2], fb[2][NI];
       auto read_frags = [&]() {
-      if (ABL == 5) {                       // fragments from registers that are live anyway: no LDS reads
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) fa[ks][mi][0] = fa[ks][mi][1] = ra[ks];
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) fb[ks][ni] = rx[ni];
-        }
-      } else
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         const int k8 = 2 * ks + lhi;
@@ -285,7 +257,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_c8pp_kernel(con
       }
       };
       auto stage = [&]() {
-      if (ABL != 2) {
+      {
         // the next step's panel: store (fetched in this wave's previous LOAD phase), then fetch the panel after
         int j2 = j + 2, c2 = c;
         if (JT == 1) { j2 = 0; c2 = c + 2; }
@@ -295,12 +267,12 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_c8pp_kernel(con
         load_A(c2, j2);
         // the next chunk's tile: one item per tap phase (three-tap layers) or all of it (1 x 1 layers)
         if constexpr (JT == 1) {
-          write_X_all((c + 1) & 1, c + 1);
+          write_X_all((c + 1) & 1);
           load_X_all(cx);
         } else {
-          if (j == 0) { write_X_item((c + 1) & 1, U0{}, c + 1); load_X_item(cx, U0{}); }
-          if (j == 1) { write_X_item((c + 1) & 1, U1{}, c + 1); load_X_item(cx, U1{}); }
-          if (j == 2) { write_X_item((c + 1) & 1, U2{}, c + 1); load_X_item(cx, U2{}); }
+          if (j == 0) { write_X_item((c + 1) & 1, U0{}); load_X_item(cx, U0{}); }
+          if (j == 1) { write_X_item((c + 1) & 1, U1{}); load_X_item(cx, U1{}); }
+          if (j == 2) { write_X_item((c + 1) & 1, U2{}); load_X_item(cx, U2{}); }
         }
       }
       };
@@ -324,20 +296,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_c8pp_kernel(con
             fb[ks][ni] = ok ? fb[ks][ni] : zero8;
           }
       }
-      if (ABL != 6) __syncthreads();
+      __syncthreads();
       // the MFMAs are register-only: without the fences the compiler sinks them below the second barrier into the next
       // LOAD phase and the ping-pong degenerates into the in-phase loop (conv_gemm_pp2.hip)
       __builtin_amdgcn_sched_barrier(0);
       // ---------------- COMPUTE: 16 MFMAs of one (chunk, tap) step ----------------
-      if (ABL == 1) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) asm volatile("" ::"v"(fa[ks][mi][0]), "v"(fa[ks][mi][1]));
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) asm volatile("" ::"v"(fb[ks][ni]));
-        }
-      } else
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -350,10 +313,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_c8pp_kernel(con
       __builtin_amdgcn_sched_barrier(0);
       // (4-wave form: the barrier after the LOAD phase orders everything: the next LOAD's stores go to buffers whose last
       //  reads are behind it, its reads to buffers whose stores are behind it)
-      if (PP && ABL != 6 && (!(last_chunk && j == JT - 1) || !late)) __syncthreads();
+      if (PP && (!(last_chunk && j == JT - 1) || !late)) __syncthreads();
     }
   }
-  if (ABL == 3 && acc[0][0][0][0] + acc[1][1][1][7] != 1.2345e30f) return;
 
   // ---- fused tail (conv_common.h), one 32-row sub-tile at a time ----
   int n0e = __builtin_amdgcn_readfirstlane(n0);
@@ -379,23 +341,20 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_c8pp_kernel(con
           for (int r = 0; r < 16; ++r) acc[mi][h][ni][r] *= ds;
   }
   if (p.io_bf16 & DV3_IO_OUT_C8) {
-    // RL: the residual units of this lane's columns sit in the strip (every store to it is behind a barrier this wave passed)
-    const unsigned char* rl = RL ? reinterpret_cast<const unsigned char*>(Rs) + (size_t)(wn * (NI * 32) + l31) * 16 : nullptr;
-    conv_epilogue_c8<BM, BMH, NI>(p, acc[0], gated, mt, wm * (MI * 32), lhi, bcol, tcol, okc, rl, BN);
-    conv_epilogue_c8<BM, BMH, NI>(p, acc[1], gated, mt, wm * (MI * 32) + 32, lhi, bcol, tcol, okc, rl, BN);
+    conv_epilogue_c8<BM, BMH, NI>(p, acc[0], gated, mt, wm * (MI * 32), lhi, bcol, tcol, okc);
+    conv_epilogue_c8<BM, BMH, NI>(p, acc[1], gated, mt, wm * (MI * 32) + 32, lhi, bcol, tcol, okc);
   } else {
-    conv_epilogue<BM, BMH, NI, 0, true>(p, acc[0], gated, mt, wm * (MI * 32), lhi, bcol, tcol, okc);
-    conv_epilogue<BM, BMH, NI, 0, true>(p, acc[1], gated, mt, wm * (MI * 32) + 32, lhi, bcol, tcol, okc);
+    conv_epilogue<BM, BMH, NI, true>(p, acc[0], gated, mt, wm * (MI * 32), lhi, bcol, tcol, okc);
+    conv_epilogue<BM, BMH, NI, true>(p, acc[1], gated, mt, wm * (MI * 32) + 32, lhi, bcol, tcol, okc);
   }
 }
 
-template <int JT, bool MASK, int ABL = 0, bool RF = false, bool RL = false, int NW = 8>
+template <int JT, bool MASK, bool RF = false, int NW = 8>
 int launch_c8pp(const ConvArgs& a, size_t lds, hipStream_t st) {
-  constexpr int NT = C8ppGeo<NW>::NT, BN = C8ppGeo<NW>::BN;
-  if (RL) lds += (size_t)(BMH / 8) * BN * 16;      // the residual strip
+  constexpr int NT = C8ppGeo<NW>::NT;
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_c8pp_kernel<JT, MASK, ABL, RF, RL, NW>,
+    hipError_t e = hipFuncSetAttribute((const void*)conv_c8pp_kernel<JT, MASK, RF, NW>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) {
       dv3_set_error("conv_c8pp: hipFuncSetAttribute: %s", hipGetErrorString(e));
@@ -403,7 +362,7 @@ int launch_c8pp(const ConvArgs& a, size_t lds, hipStream_t st) {
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL((conv_c8pp_kernel<JT, MASK, ABL, RF, RL, NW>), dim3(a.n_blocks), dim3(NT), lds, st, a);
+  hipLaunchKernelGGL((conv_c8pp_kernel<JT, MASK, RF, NW>), dim3(a.n_blocks), dim3(NT), lds, st, a);
   return dv3_check_launch("conv_c8pp");
 }
 
@@ -416,8 +375,6 @@ int launch_c8pp(const ConvArgs& a, size_t lds, hipStream_t st) {
 int g_c8pp_rf = 1;
 int g_c8pp_nw4 = 2;            // dv3_debug_set(34, v): two 4-wave workgroups per CU on 256 x 128 tiles (NW = 4): 0 never, 1 always, 2 by the rule in the dispatcher
 int g_c8pp_stagger = 0, g_c8pp_stagger_mask = 1;   // dv3_debug_set(35 / 36, v): start delay (x 64 cycles) of the blocks with (blockIdx & mask) != 0
-int g_c8pp_rl = 0;             // dv3_debug_set(32, v), experiment build: the residual of a gated layer read from LDS (RL instantiations)
-int g_c8pp_abl = 0;            // dv3_debug_set(21, v): timing-only ablations (EXP build)
 int g_c8pp_min_tiles = 128;   // dv3_debug_set(19, v): the 256 x 256 c8 kernel serves eligible shapes whose grid has at
                               // least v tiles (0 = never; 1 = always)
 
@@ -473,47 +430,13 @@ int dv3_conv_c8pp_dispatch(const dv3_conv_desc* d, hipStream_t st) {
     a.stagger = g_c8pp_stagger;
     a.stagger_mask = g_c8pp_stagger_mask;
     g_dv3_last_conv = 9000 + 110 + 1;   // ... 256 x 128 tile, two workgroups per CU
-    if (d->J == 3) return mask ? launch_c8pp<3, true, 0, true, false, 4>(a, lds4, st) : launch_c8pp<3, false, 0, true, false, 4>(a, lds4, st);
-    return mask ? launch_c8pp<1, true, 0, true, false, 4>(a, lds4, st) : launch_c8pp<1, false, 0, true, false, 4>(a, lds4, st);
+    if (d->J == 3) return mask ? launch_c8pp<3, true, true, 4>(a, lds4, st) : launch_c8pp<3, false, true, 4>(a, lds4, st);
+    return mask ? launch_c8pp<1, true, true, 4>(a, lds4, st) : launch_c8pp<1, false, true, 4>(a, lds4, st);
   }
-#ifdef DV3_EXPERIMENTS
-  if (g_c8pp_abl && !mask && d->J == 3) {
-    switch (g_c8pp_abl) {
-      case 1: return launch_c8pp<3, false, 1>(a, lds, st);
-      case 2: return launch_c8pp<3, false, 2>(a, lds, st);
-      case 3: return launch_c8pp<3, false, 3>(a, lds, st);
-      case 5: return launch_c8pp<3, false, 5>(a, lds, st);
-      case 6: return launch_c8pp<3, false, 6>(a, lds, st);
-    }
-  }
-#endif
-#ifdef DV3_EXPERIMENTS
-  // residual from LDS (RL): MEASURED AND RETIRED (round 5, profiles/r05_c8pp_residual_from_lds.txt): bit-identical, but 4-10 %
-  // SLOWER over the presets' shapes (north star eval 61.2 -> 65.6 us) -- the tail is not waiting for the residual fetch,
-  // and the second store of the staged units plus the strip reads cost more than the 33 MB they keep out of the burst.
-  const bool has_res = gated && d->r && (d->mode == DV3_EPI_HIGHWAY || d->residual);
-  const bool rl = g_c8pp_rl && g_c8pp_rf && has_res && (const void*)d->r == (const void*)d->x_planes && d->Cg == d->Cin && (d->io_bf16 & DV3_IO_OUT_C8) &&
-                  lds + (size_t)(BMH / 8) * BN * 16 <= 160 * 1024;
-  if (rl) {
-    if (d->J == 3) return mask ? launch_c8pp<3, true, 0, true, true>(a, lds, st) : launch_c8pp<3, false, 0, true, true>(a, lds, st);
-    return mask ? launch_c8pp<1, true, 0, true, true>(a, lds, st) : launch_c8pp<1, false, 0, true, true>(a, lds, st);
-  }
-#endif
   if (g_c8pp_rf) {
-    if (d->J == 3) return mask ? launch_c8pp<3, true, 0, true>(a, lds, st) : launch_c8pp<3, false, 0, true>(a, lds, st);
-    return mask ? launch_c8pp<1, true, 0, true>(a, lds, st) : launch_c8pp<1, false, 0, true>(a, lds, st);
+    if (d->J == 3) return mask ? launch_c8pp<3, true, true>(a, lds, st) : launch_c8pp<3, false, true>(a, lds, st);
+    return mask ? launch_c8pp<1, true, true>(a, lds, st) : launch_c8pp<1, false, true>(a, lds, st);
   }
   if (d->J == 3) return mask ? launch_c8pp<3, true>(a, lds, st) : launch_c8pp<3, false>(a, lds, st);
   return mask ? launch_c8pp<1, true>(a, lds, st) : launch_c8pp<1, false>(a, lds, st);
-}
-
-int dv3_c8pp_debug_set(int what, int value) {
-  if (what == 19) g_c8pp_min_tiles = value;
-  if (what == 21) g_c8pp_abl = value;
-  if (what == 30) g_c8pp_rf = value;
-  if (what == 32) g_c8pp_rl = value;
-  if (what == 34) g_c8pp_nw4 = value;
-  if (what == 35) g_c8pp_stagger = value;
-  if (what == 36) g_c8pp_stagger_mask = value;
-  return DV3_OK;
 }

@@ -18,9 +18,12 @@ struct ConvArgs {
   int prio = 0;  // ping-pong tap-GEMM: wave priority scheme (dv3_debug_set(14, v); 0 = none)
   int fast_tail = 0;   // 256 x 256 kernel: interior sub-tiles of a gated launch take conv_epilogue_glu_interior (dv3_debug_set(50, v))
   int ks = 0;    // 128 x 64 split tile: 2 = the k-split form (two wave groups per workgroup, halves of the chunk range)
-  int dp = 0;    // 128 x 64 split tile: deep-prefetch form with this compile-time tap count (1 or 3; 0 = the in-phase loop)
+  // Unused.  pad0 / pad1 hold the places of two retired measurement fields: the kernel-argument layout, and with it the
+  // register allocation of the shipped tap-GEMM kernels, depends on them (without them the exact-fp32 and several split
+  // kernels compile to different code).
+  int pad0 = 0;
   // stream-K form of the 256 x 256 kernels: n_blocks = workgroups (one per CU), sk_units = tiles x chunks
-  int sk_units = 0, sk_base = 0, sk_rem = 0, sk_shift = 0, sk_mshift = 0, sk_abl = 0;   // units; per-workgroup share and remainder (groups with the extra tile); log2(chunks per tile)
+  int sk_units = 0, sk_base = 0, sk_rem = 0, sk_shift = 0, sk_mshift = 0, pad1 = 0;   // units; per-workgroup share and remainder (groups with the extra tile); log2(chunks per tile)
   int sk_base2 = 0, sk_rem2 = 0, sk_tg = 0, sk_tr = 0, sk_qshift = 0;                   // ... of the groups without it; tiles per XCD group, groups with one more; log2(workgroups per group)
   float* sk_ws = nullptr;      // [n_blocks][128 accumulator registers][512 threads]
   int* sk_flags = nullptr;     // [n_blocks], zero between launches
@@ -42,7 +45,6 @@ __device__ __forceinline__ void dv3_st(void* base, uint32_t byte_off, float v) {
 // All addressing is uniform base + 32-bit byte offset (the host checks every tensor < 4 GB):
 // the straightforward 64-bit form made this fully unrolled tail ~10k instructions -- more than
 // the instruction cache, i.e. a fixed ~40 us of fetch stalls per launch at the north-star shape.
-// ABL: measurement variants (dv3_debug_set): 7 = no residual load, 8 = no store.
 // bf16 storage (IOB instantiations = the single-term bf16 kernels): activations may be bf16 tensors; loads widen
 // exactly, stores round to nearest even.  The flags are wave-uniform.
 __device__ __forceinline__ float dv3_ld_act(const void* base, uint32_t byte_off, bool bf) {
@@ -186,7 +188,7 @@ __device__ __forceinline__ float dv3_gate_out(float a, float s, float x, float o
   return __builtin_fmaf(s, a, t);
 }
 
-template <int BM, int BMH, int NI, int ABL = 0, bool IOB = false>
+template <int BM, int BMH, int NI, bool IOB = false>
 __device__ __forceinline__ void conv_epilogue(const dv3_conv_desc& p, f32x16 (&acc)[2][NI], bool gated,
                                               int mt, int row0, int lhi, const int (&bcol)[NI],
                                               const int (&tcol)[NI], const bool (&okc)[NI]) {
@@ -235,7 +237,7 @@ __device__ __forceinline__ void conv_epilogue(const dv3_conv_desc& p, f32x16 (&a
       }
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
-        xr[r][ni] = (has_r && ABL != 7) ? dv3_ld_act(p.r, rbc[ni] + chc * r_rs, inb) : 0.f;
+        xr[r][ni] = has_r ? dv3_ld_act(p.r, rbc[ni] + chc * r_rs, inb) : 0.f;
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -255,7 +257,7 @@ __device__ __forceinline__ void conv_epilogue(const dv3_conv_desc& p, f32x16 (&a
         const float s = __builtin_amdgcn_rcpf(1.0f + __expf(-g));
         // GLU: (a*s [+ x]) * (sqrt(.5) | 1)      HIGHWAY: s*a + (1-s)*x
         const float y = dv3_gate_out(a, s, xr[r][ni], oscale, glu);
-        if (ABL != 8 || y == 1.2345e30f) dv3_st_act(p.y, yb[ni] + ch * y_rs, y, outb);
+        dv3_st_act(p.y, yb[ni] + ch * y_rs, y, outb);
       }
     }
     return;
@@ -628,8 +630,7 @@ __device__ __forceinline__ bool dv3_wide_glu_ok(const dv3_conv_desc& p) {
 
 // One 32-row sub-tile of a wave: acc[0][ni] = `a` rows, acc[1][ni] = gate rows (as conv_epilogue); n0w = flat index of
 // the wave's first column (the lane's quad q = (lane & 31) >> 2 owns frames n0w + ni * 32 + 4 q .. + 3).
-// ABL (experiment build): 12 = no residual load, 13 = no stores
-template <int BMH, int NI, int ABL = 0>
+template <int BMH, int NI>
 __device__ __forceinline__ void conv_epilogue_glu_wide(const dv3_conv_desc& p, f32x16 (&acc)[2][NI], int mt, int row0,
                                                        int lane, int n0w, int Ntot) {
   const int l31 = lane & 31, lhi = lane >> 5;
@@ -660,7 +661,7 @@ __device__ __forceinline__ void conv_epilogue_glu_wide(const dv3_conv_desc& p, f
     const uint32_t chc = chw[k] < Cg ? chw[k] : Cg - 1;
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni)
-      xr[k][ni] = (has_r && ABL != 12) ? dv3_ld<f32x4>(p.r, ro[ni] + chc * r_rs) : f32x4{0.f, 0.f, 0.f, 0.f};
+      xr[k][ni] = has_r ? dv3_ld<f32x4>(p.r, ro[ni] + chc * r_rs) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -687,10 +688,8 @@ __device__ __forceinline__ void conv_epilogue_glu_wide(const dv3_conv_desc& p, f
       if (ch >= Cg || !okw[ni]) continue;
       if (p.ab) {
         const uint32_t o = ao[ni] + ch * T * 4u;
-        if (ABL != 13) {
-          *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(p.ab) + o) = f32x4{a[0], a[1], a[2], a[3]};
-          *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(p.ab) + o + Cg * T * 4u) = f32x4{g[0], g[1], g[2], g[3]};
-        }
+        *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(p.ab) + o) = f32x4{a[0], a[1], a[2], a[3]};
+        *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(p.ab) + o + Cg * T * 4u) = f32x4{g[0], g[1], g[2], g[3]};
       }
       f32x4 y4;
 #pragma unroll
@@ -699,7 +698,7 @@ __device__ __forceinline__ void conv_epilogue_glu_wide(const dv3_conv_desc& p, f
         const float x = xr[k][ni][e];
         y4[e] = dv3_gate_out(a[e], s, x, oscale, glu);
       }
-      if (ABL != 13 || y4[0] == 1.2345e30f) *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(p.y) + yo[ni] + ch * y_rs) = y4;
+      *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(p.y) + yo[ni] + ch * y_rs) = y4;
     }
   }
 }
@@ -731,13 +730,10 @@ __device__ __forceinline__ void dv3_st8(void* base, uint32_t byte_off, const uin
   *reinterpret_cast<uint2*>(reinterpret_cast<char*>(base) + byte_off) = v;
 }
 
-// rl (gated forms, optional): the residual's c8 units of this lane's first column in LDS, [channel group of the tile's
-// `a` rows][rl_cols columns] (conv_c8pp.hip, RL); column sub-tile ni is 32 units further.
 template <int BM, int BMH, int NI>
 __device__ __forceinline__ void conv_epilogue_c8(const dv3_conv_desc& p, f32x16 (&acc)[2][NI], bool gated,
                                                  int mt, int row0, int lhi, const int (&bcol)[NI],
-                                                 const int (&tcol)[NI], const bool (&okc)[NI],
-                                                 const unsigned char* rl = nullptr, int rl_cols = 0) {
+                                                 const int (&tcol)[NI], const bool (&okc)[NI]) {
   const uint32_t T = (uint32_t)p.Tout, M = (uint32_t)p.M, Cg = (uint32_t)p.Cg;
   const uint32_t Cout = gated ? Cg : M;
   const uint32_t c8y = (Cout + 31u) / 32u * 4u;        // 8-channel groups per batch item of y / r / r2
@@ -769,10 +765,7 @@ __device__ __forceinline__ void conv_epilogue_c8(const dv3_conv_desc& p, f32x16 
       g8v[k] = (uint32_t)(mt * BMH + row0) / 8u + (uint32_t)k;
       const uint32_t g8c = g8v[k] * 8u < Cg ? g8v[k] : 0u;
 #pragma unroll
-      for (int ni = 0; ni < NI; ++ni) {
-        if (rl) xr[k][ni] = *reinterpret_cast<const uint2*>(rl + ((size_t)((row0 >> 3) + k) * rl_cols + ni * 32) * 16 + half);
-        else xr[k][ni] = has_r ? dv3_ld<uint2>(p.r, ubc[ni] + g8c * gsz) : uint2{0u, 0u};
-      }
+      for (int ni = 0; ni < NI; ++ni) xr[k][ni] = has_r ? dv3_ld<uint2>(p.r, ubc[ni] + g8c * gsz) : uint2{0u, 0u};
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {

@@ -72,17 +72,6 @@ __device__ __forceinline__ T ldg_off(const void* base, uint32_t byte_off) {
   return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
 }
 
-// ABL 10 (dv3_debug_set(1, 10), 128x256 ping-pong tile): per-wave phase timestamps of ONE workgroup,
-// [wave][slot][0 = s_memrealtime (100 MHz), 1 = s_memtime]; read back with dv3_debug_read(1, ...)
-constexpr int STAMP_SLOTS = 192;
-__device__ unsigned long long g_x3_stamps[8 * STAMP_SLOTS * 2];
-
-// DPJ (round 5, "deep prefetch"): 0 = the loops below; 1 / 3 = the tap count is this compile-time constant and the
-// global fetches run DA steps (weight panels) / DX chunks (activation tiles) ahead through register rings (see the
-// DPJ main loop).  For grids that leave a CU with one or two workgroups -- the decoder's T = 200 layers, every layer at
-// the preset's own batch 16 -- a step of the in-phase loop costs one exposed L2 / HBM round trip (its panel is fetched
-// at the top of the step that stores it); with the rings the round trip is paid once per tile.
-//
 // KS (round 5, "k-split"): 1 = one group of WM x WN waves; 2 = TWO such groups in one workgroup, each with its own LDS
 // buffers, staging the first / second half of the input-channel chunks of the SAME output tile; the second group's
 // accumulators go through LDS to the first, which adds them (first half + second half: a fixed order, a function of the
@@ -91,27 +80,21 @@ __device__ unsigned long long g_x3_stamps[8 * STAMP_SLOTS * 2];
 // second group is the second wave per SIMD that overlaps them, on a k-range half as long.
 // FG (round 6): an input-gradient launch whose tail also runs the gate backward of the layer that PRODUCED this layer's
 // input (dv3_conv_desc.pg; conv_common.h) -- separate instantiations (bf16 pair, no dropout) that contain that tail only.
-template <int WM, int WN, int NI, bool MASK, int ABL = 0, int TERMS = 3, int MI = 1, bool PP = false, bool F16 = false, int DPJ = 0, int KS = 1, bool FG = false>
+template <int WM, int WN, int NI, bool MASK, int TERMS = 3, int MI = 1, bool PP = false, bool F16 = false, int KS = 1, bool FG = false>
 __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(const ConvArgs args) {
-  static_assert(!FG || (!MASK && !F16 && TERMS == 3 && ABL == 0 && DPJ == 0), "fused gate backward: the unmasked bf16-pair forms");
+  static_assert(!FG || (!MASK && !F16 && TERMS == 3), "fused gate backward: the unmasked bf16-pair forms");
   static_assert(!F16 || TERMS == 3, "the fp16 form is the three-term split");
-  static_assert(KS == 1 || (KS == 2 && !PP && DPJ == 0 && ABL == 0), "k-split: two groups on the in-phase loop");
-  static_assert(DPJ == 0 || (DPJ == 1 || DPJ == 3), "deep prefetch: 1 or 3 taps");
-  static_assert(DPJ == 0 || (!PP && MI == 1 && ABL == 0 && TERMS == 3), "deep prefetch: the in-phase three-term tiles");
-  // rings: weight panels in flight (steps) / activation tiles in flight (chunks).  One step of the 1-tap form issues
-  // 4 + 8 loads (+ 8 keep-bit words when masked): the masked ring is one step shorter to stay under the 63 loads vmcnt counts
-  constexpr int DA = DPJ == 0 ? 1 : (DPJ == 1 ? (MASK ? 3 : 4) : 3);
-  constexpr int DX = DPJ == 0 ? 1 : (DPJ == 1 ? (MASK ? 3 : 4) : 2);
-  static_assert(!PP || (WM * WN == 8 && MI == 1 && (ABL == 0 || ABL >= 10)), "ping-pong: 8 waves, one row sub-tile per wave");
+  static_assert(KS == 1 || (KS == 2 && !PP), "k-split: two groups on the in-phase loop");
+  static_assert(!PP || (WM * WN == 8 && MI == 1), "ping-pong: 8 waves, one row sub-tile per wave");
   constexpr int BM = WM * MI * 64, BMH = WM * MI * 32, BN = WN * NI * 32;
   constexpr int NT = WM * WN * 64;
   constexpr int AU = KB * BM / NT;                          // A units per plane per thread per step
-  constexpr int XI = (KB * (BN + (DPJ == 1 ? 0 : HALO_MAX)) + NT - 1) / NT;  // X items per thread per chunk
+  constexpr int XI = (KB * (BN + HALO_MAX) + NT - 1) / NT;  // X items per thread per chunk
   static_assert(KB * BM % NT == 0, "A panel must split evenly");
   const dv3_conv_desc& p = args.d;
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const int J = DPJ ? DPJ : p.J, dil = p.dil;   // (the dispatcher launches a DPJ form only for that tap count)
+  const int J = p.J, dil = p.dil;
   const int BNH = BN + (J - 1) * dil;
   const int xbuf = 2 * KB * BNH;  // units per X buffer (hi + lo)
   // k-split: group index, and thread / wave index INSIDE the group (all staging and tile indexing below is per group)
@@ -212,34 +195,34 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
   }
 
   // ---- register staging ----
-  bf16x8 ra[DA][2][AU];
-  float rx[DX][XI][8];
-  uint32_t rm[MASK ? DX : 1][MASK ? XI : 1][8];
+  bf16x8 ra[2][AU];
+  float rx[XI][8];
+  uint32_t rm[MASK ? XI : 1][8];
 
   const int nchunks_all = (Cin + BKC - 1) / BKC;
   const int nch_first = KS > 1 ? (nchunks_all + 1) / 2 : nchunks_all;      // k-split: the first group's share
   const int c_base = grp * nch_first;                                      // this group's first chunk
   const int nchunks = grp == 0 ? nch_first : nchunks_all - nch_first;      // ... and its number of chunks (local indices below)
 
-  auto load_A = [&](int chunk_l, int j, int slot = 0) {
+  auto load_A = [&](int chunk_l, int j) {
     const int chunk = chunk_l + c_base;
     const bf16x8* srch = Wh + (int64_t)(j * k8_total + chunk * KB) * lda;  // uniform
     const bf16x8* srcl = srch + plane;
 #pragma unroll
     for (int u = 0; u < AU; ++u) {
-      ra[slot][0][u] = ldg_off<bf16x8>(srch, aoff[u]);
-      if (TERMS == 3) ra[slot][1][u] = ldg_off<bf16x8>(srcl, aoff[u]);
+      ra[0][u] = ldg_off<bf16x8>(srch, aoff[u]);
+      if (TERMS == 3) ra[1][u] = ldg_off<bf16x8>(srcl, aoff[u]);
     }
   };
-  auto write_A = [&](int buf, int slot = 0) {
+  auto write_A = [&](int buf) {
     bf16x8* dst = As + buf * (2 * KB * BM);
 #pragma unroll
     for (int u = 0; u < AU; ++u) {
-      dst[tid + u * NT] = ra[slot][0][u];
-      if (TERMS == 3) dst[KB * BM + tid + u * NT] = ra[slot][1][u];
+      dst[tid + u * NT] = ra[0][u];
+      if (TERMS == 3) dst[KB * BM + tid + u * NT] = ra[1][u];
     }
   };
-  auto load_X = [&](int chunk_l, int slot = 0) {
+  auto load_X = [&](int chunk_l) {
     const int c0 = (chunk_l + c_base) * BKC;
     if (c0 + BKC <= Cin) {
       // whole chunk in range (uniform): 8 uniform row bases + one loop-invariant per-thread offset
@@ -251,8 +234,8 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
         for (int e = 0; e < 8; ++e) {
 #pragma unroll
           for (int i = 0; i < XI; ++i) {
-            rx[slot][i][e] = __uint_as_float((uint32_t)ldg_off<uint16_t>(xb + (int64_t)e * x_rsb, xoff[i]) << 16);
-            if (MASK) rm[slot][i][e] = ldg_off<uint32_t>(mb + (int64_t)e * m_rsb, xmo[i]);
+            rx[i][e] = __uint_as_float((uint32_t)ldg_off<uint16_t>(xb + (int64_t)e * x_rsb, xoff[i]) << 16);
+            if (MASK) rm[i][e] = ldg_off<uint32_t>(mb + (int64_t)e * m_rsb, xmo[i]);
           }
         }
       } else {
@@ -260,8 +243,8 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
         for (int e = 0; e < 8; ++e) {
 #pragma unroll
           for (int i = 0; i < XI; ++i) {
-            rx[slot][i][e] = ldg_off<float>(xb + (int64_t)e * x_rsb, xoff[i]);
-            if (MASK) rm[slot][i][e] = ldg_off<uint32_t>(mb + (int64_t)e * m_rsb, xmo[i]);
+            rx[i][e] = ldg_off<float>(xb + (int64_t)e * x_rsb, xoff[i]);
+            if (MASK) rm[i][e] = ldg_off<uint32_t>(mb + (int64_t)e * m_rsb, xmo[i]);
           }
         }
       }
@@ -274,14 +257,14 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
         for (int e = 0; e < 8; ++e) {
           // row relative to this item's k8 block (mod 2^32: may be "negative" when Cin < k8*8)
           const uint32_t dc = (uint32_t)(min(c0 + xk8[i] + e, Cin - 1) - xk8[i]);
-          rx[slot][i][e] = xbf ? __uint_as_float((uint32_t)ldg_off<uint16_t>(p.x, xoff[i] + dc * x_rsb) << 16)
+          rx[i][e] = xbf ? __uint_as_float((uint32_t)ldg_off<uint16_t>(p.x, xoff[i] + dc * x_rsb) << 16)
                          : ldg_off<float>(p.x, xoff[i] + dc * x_rsb);
-          if (MASK) rm[slot][i][e] = ldg_off<uint32_t>(xmask, xmo[MASK ? i : 0] + dc * m_rsb);
+          if (MASK) rm[i][e] = ldg_off<uint32_t>(xmask, xmo[MASK ? i : 0] + dc * m_rsb);
         }
       }
     }
   };
-  auto write_X = [&](int buf, int slot = 0) {
+  auto write_X = [&](int buf) {
     bf16x8* dst = Xs + buf * xbuf;
 #pragma unroll
     for (int i = 0; i < XI; ++i) {
@@ -290,8 +273,8 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          v[e] = rx[slot][i][e];
-          if (MASK) v[e] *= ((rm[slot][i][e] >> xsh[i]) & 1u) ? dscale : 0.f;
+          v[e] = rx[i][e];
+          if (MASK) v[e] *= ((rm[i][e] >> xsh[i]) & 1u) ? dscale : 0.f;
           else if (F16) v[e] *= xscale;
         }
         bf16x8 hi, lo;
@@ -300,7 +283,7 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
           if (xpw) {      // pair words (dv3_conv_desc.x_pair, wave-uniform): the pair is already there
             uint32_t w[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) w[e] = __float_as_uint(rx[slot][i][e]);
+            for (int e = 0; e < 8; ++e) w[e] = __float_as_uint(rx[i][e]);
             dv3_pair_units(w, hi, lo);
           } else split8(v, hi, lo);
         } else split8(v, hi, lo);
@@ -320,31 +303,16 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[mi][h][ni][r] = 0.f;
 
-  const int nsteps = (ABL == 5 || ABL == 9) ? 0 : nchunks * J;
+  const int nsteps = nchunks * J;
   const int a_off = wm * (MI * 32) + l31;
   const int x_off = wn * (NI * 32) + l31;
 
-  if constexpr (DPJ == 0) {
-    load_A(0, 0);
-    load_X(0);
-    write_A(0);
-    write_X(0);
-    __syncthreads();
-  }
+  load_A(0, 0);
+  load_X(0);
+  write_A(0);
+  write_X(0);
+  __syncthreads();
 
-  int n_stamp = 0;
-  auto stamp = [&]() {
-    if constexpr (ABL == 10) {
-      if (blockIdx.x == gridDim.x / 2 && n_stamp < STAMP_SLOTS) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime(), t1 = __builtin_readcyclecounter();
-        if (lane == 0) {
-          g_x3_stamps[(wave * STAMP_SLOTS + n_stamp) * 2] = t0;
-          g_x3_stamps[(wave * STAMP_SLOTS + n_stamp) * 2 + 1] = t1;
-        }
-      }
-      ++n_stamp;
-    }
-  };
   int c = 0, j = 0;
   if constexpr (PP) {
     // ---- ping-pong main loop (8-wave tiles, one workgroup per CU) ----
@@ -366,7 +334,6 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
     const int late = wave >> 2;
     load_A((1 < nsteps && J == 1) ? 1 : 0, (1 < nsteps && J > 1) ? 1 : 0);
     if (1 < nchunks) load_X(1);
-    stamp();                       // slot 0: prologue done
     // wave priority scheme (measurement knob, dv3_debug_set(14, v)): 1 = LOAD phases at priority 3, 2 = COMPUTE
     // phases at priority 3, 3 / 4 = the late / early half at static priority 1
     const int prio = args.prio;
@@ -379,7 +346,6 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
       if (jn == J) { jn = 0; cn = c + 1; }
       const bool has_next = step + 1 < nsteps;
       const bool new_chunk = has_next && jn == 0;
-      stamp();                     // slot 1 + 6*step: LOAD begins
       if (prio == 1) __builtin_amdgcn_s_setprio(3);
       // ---------------- LOAD ----------------
       bf16x8 ah[2][2], al[2][2], bh[2][NI], bl[2][NI];
@@ -422,9 +388,7 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
       // steps re-fetch the current panel and store into the buffer nobody reads any more): a
       // conditional pair makes the compiler guard the fetch's registers with a vmcnt(0) that
       // would then sit behind the activation fetch issued just above.
-      stamp();                     // fragments in registers
       write_A(cur ^ 1);
-      stamp();                     // panel stored
       if (new_chunk) {
         write_X((c + 1) & 1);
         if (cn + 1 < nchunks) load_X(cn + 1);
@@ -435,9 +399,7 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
         const bool more = step + 2 < nsteps;
         load_A(more ? c2 : c, more ? j2 : j);
       }
-      stamp();                     // LOAD issued (the SMEM read waits for the LDS queue)
       __syncthreads();
-      stamp();                     // COMPUTE begins
       if (prio == 1) __builtin_amdgcn_s_setprio(0);
       if (prio == 2) __builtin_amdgcn_s_setprio(3);
       // ---------------- COMPUTE ----------------
@@ -461,112 +423,10 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
           acc[0][1][ni] = mma16<F16>(ah[s][1], bh[s][ni], acc[0][1][ni]);
         }
       }
-      stamp();                     // MFMAs issued
       if (prio == 2) __builtin_amdgcn_s_setprio(0);
       if (has_next || !late) __syncthreads();
       j = jn;
       c = cn;
-    }
-    stamp();                       // slot 1 + 6*nsteps: main loop left
-  } else if constexpr (DPJ > 0) {
-    // ---- deep-prefetch main loop (in-phase tiles, compile-time tap count) ----
-    // Step s = (chunk s / J, tap s % J).  At its top the panel of step s + DA goes into ring slot s % DA (the panel that
-    // slot held was stored at the end of step s - 1) and, at a chunk's first tap, the activation tile of chunk c + DX into
-    // slot c % DX; at its end the panel of step s + 1 (fetched DA - 1 steps ago) and, at a chunk's last tap, the tile of
-    // chunk c + 1 (fetched (DX - 1) chunks ago) are stored into the other LDS buffer.  U steps are unrolled so that every
-    // ring index is a compile-time constant (U a multiple of DA and of DX * J; U and U / J even: the LDS buffer parities too).
-    // Same fragment images, same MFMA order as the loop below: bit-identical results.
-    //
-    // The loop starts U steps BEFORE step 0: the virtual steps run the same fetches and stores (indices clamped into
-    // the tile, so they re-fetch step 0's panel at worst) and stores, and skip only the fragment reads + MFMAs; so do the
-    // up to U - 1 steps behind the last one (the loop leaves at a round boundary only).  That fills the rings in consumption order with the loop's
-    // own instruction stream -- no separate prologue whose differently-ordered pending fetches the compiler would have
-    // to merge into the loop header's wait counts (a first version with a peeled prologue drained the rings to 11
-    // outstanding loads at the top of every U-th step) -- and every fetch and store is unconditional, so each
-    // s_waitcnt vmcnt(N) is exact.
-    constexpr int U = (DPJ == 1 && DA == 4) ? 4 : 6;
-    static_assert(U % DA == 0 && (U / DPJ) % DX == 0 && U % DPJ == 0 && U % 2 == 0 && (U / DPJ) % 2 == 0,
-                  "ring slots and LDS buffer parities must be compile-time");
-    const int last_step = nsteps - 1, last_chunk = nchunks - 1;
-#pragma unroll
-    for (int a = 0; a < DA; ++a)
-#pragma unroll
-      for (int u = 0; u < AU; ++u) ra[a][0][u] = ra[a][1][u] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int x = 0; x < DX; ++x)
-#pragma unroll
-      for (int i = 0; i < XI; ++i)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          rx[x][i][e] = 0.f;
-          if (MASK) rm[x][i][e] = 0u;
-        }
-    int s_first = -U;
-    asm volatile("" : "+s"(s_first));   // opaque: keeps the compiler from peeling the virtual round into a prologue again
-    for (int s0 = s_first; s0 < nsteps; s0 += U) {
-#pragma unroll
-      for (int dd = 0; dd < U; ++dd) {
-        const int s = s0 + dd;
-        const int jj = dd % DPJ;                 // tap
-        const int cx = dd / DPJ;                 // chunk, relative to s0 / J (a multiple of DX)
-        {
-          const int sa = min(max(s + DA, 0), last_step);
-          load_A(sa / DPJ, sa % DPJ, dd % DA);
-        }
-        if (jj == 0) load_X(min(max(s0 / DPJ + cx + DX, 0), last_chunk), cx % DX);
-        if (s >= 0 && s < nsteps) {   // (no early exit from the round: the compiler funnels every loop exit through one
-                                      //  block with an edge back to the header, whose wait counts then assume the worst exit)
-          const bf16x8* AsH = As + (dd & 1) * (2 * KB * BM);
-          const bf16x8* AsL = AsH + KB * BM;
-          const bf16x8* XsH = Xs + (cx & 1) * xbuf;
-          const bf16x8* XsL = XsH + KB * BNH;
-          const bool fix = (need >> jj) & 1u;
-          const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) {
-            const int k8 = 2 * s2 + lhi;
-            const int ai = k8 * BM + a_off;
-            const bf16x8 ah0 = AsH[ai], ah1 = AsH[ai + BMH], al0 = AsL[ai], al1 = AsL[ai + BMH];
-            bf16x8 bh[NI], bl[NI];
-            const int xi = k8 * BNH + x_off + jj * dil;
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) {
-              bh[ni] = XsH[xi + ni * 32];
-              bl[ni] = XsL[xi + ni * 32];
-            }
-            if (fix) {
-#pragma unroll
-              for (int ni = 0; ni < NI; ++ni) {
-                const bool ok = (vbits >> (jj * NI + ni)) & 1u;
-                bh[ni] = ok ? bh[ni] : zero8;
-                bl[ni] = ok ? bl[ni] : zero8;
-              }
-            }
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) {
-              acc[0][0][ni] = mma16<F16>(al0, bh[ni], acc[0][0][ni]);
-              acc[0][1][ni] = mma16<F16>(al1, bh[ni], acc[0][1][ni]);
-            }
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) {
-              acc[0][0][ni] = mma16<F16>(ah0, bl[ni], acc[0][0][ni]);
-              acc[0][1][ni] = mma16<F16>(ah1, bl[ni], acc[0][1][ni]);
-            }
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) {
-              acc[0][0][ni] = mma16<F16>(ah0, bh[ni], acc[0][0][ni]);
-              acc[0][1][ni] = mma16<F16>(ah1, bh[ni], acc[0][1][ni]);
-            }
-          }
-        }
-        // stores for step s + 1, unconditional like the fetches (a conditional store leaves "maybe still pending" marks
-        // on its ring slot at the join, which reach the loop header).  The last step stores into buffers nobody reads any
-        // more; the virtual steps before -1 store ring slots that are not fetched yet: zeros (see the initialisation
-        // above the loop -- the fp16 range guard must not see register garbage), into buffers overwritten before use.
-        write_A((dd & 1) ^ 1, (dd + 1) % DA);
-        if (jj == DPJ - 1) write_X((cx & 1) ^ 1, (cx + 1) % DX);
-        __syncthreads();
-      }
     }
   } else
   for (int step = 0; step < (KS > 1 ? nch_first * J : nsteps); ++step) {
@@ -579,12 +439,10 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
     if (jn == J) { jn = 0; cn = c + 1; }
     const bool has_next = step + 1 < nsteps;
     const bool new_chunk = has_next && jn == 0;
-    if (ABL != 1 && ABL != 2 && ABL != 3) {
-      if (has_next) load_A(cn, jn);
-      // the activation tile streams from HBM (a weight panel is an L2 hit): fetch chunk c+1 at the
-      // FIRST tap of chunk c, J steps ahead of the write that needs it
-      if (j == 0 && c + 1 < nchunks) load_X(c + 1);
-    }
+    if (has_next) load_A(cn, jn);
+    // the activation tile streams from HBM (a weight panel is an L2 hit): fetch chunk c+1 at the
+    // FIRST tap of chunk c, J steps ahead of the write that needs it
+    if (j == 0 && c + 1 < nchunks) load_X(c + 1);
 
     // ---------------- MFMA: two k16 steps of tap j ----------------
     {
@@ -622,13 +480,6 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
             if (TERMS == 3) bl[ni] = ok ? bl[ni] : zero8;
           }
         }
-        if (ABL == 4) {
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) asm volatile("" ::"v"(ah[mi][0]), "v"(ah[mi][1]), "v"(al[mi][0]), "v"(al[mi][1]));
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni) asm volatile("" ::"v"(bh[ni]), "v"(bl[ni]));
-          continue;
-        }
         // small terms first; each accumulator is touched once per pass (no back-to-back RAW)
         if (TERMS == 3) {
 #pragma unroll
@@ -656,11 +507,9 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
       }
     }
 
-    if (ABL != 2 && ABL != 3) {
-      if (has_next) write_A(cur ^ 1);
-      if (new_chunk) write_X((c + 1) & 1);
-    }
-    if (ABL != 3) __syncthreads();
+    if (has_next) write_A(cur ^ 1);
+    if (new_chunk) write_X((c + 1) & 1);
+    __syncthreads();
     j = jn;
     c = cn;
   }
@@ -692,76 +541,72 @@ __global__ __launch_bounds__(WM* WN * 64 * KS) void conv_gemm_bf16x3_kernel(cons
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[mi][h][ni][r] += mine[(((mi * 2 + h) * NI + ni) * 16 + r) * 64];
   }
-  // ABL 6: skip the epilogue but keep the accumulators live
-  if ((ABL != 6 && ABL != 9) || acc[0][0][0][0] + acc[MI - 1][1][0][0] + acc[0][0][NI - 1][5] + acc[MI - 1][1][NI - 1][7] == 1.2345e30f) {
-    static_assert(MI == 1 || MI == 2, "row sub-tiles per wave");
-    if constexpr (F16) {   // the accumulators carry 2^(weight shift + activation shift) x the result
-      constexpr float kInv = 1.0f / (float)(1 << (DV3_F16_WEIGHT_SHIFT + DV3_F16_ACT_SHIFT));
+  static_assert(MI == 1 || MI == 2, "row sub-tiles per wave");
+  if constexpr (F16) {   // the accumulators carry 2^(weight shift + activation shift) x the result
+    constexpr float kInv = 1.0f / (float)(1 << (DV3_F16_WEIGHT_SHIFT + DV3_F16_ACT_SHIFT));
 #pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
+    for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-        for (int h = 0; h < 2; ++h)
+      for (int h = 0; h < 2; ++h)
 #pragma unroll
-          for (int ni = 0; ni < NI; ++ni)
+        for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mi][h][ni][r] *= kInv;
-    }
-    // (batch, time) of this lane's output columns, recomputed from an opaque copy of the tile origin
-    // instead of being carried through the main loop in registers
-    int n0e = n0;
-    asm volatile("" : "+s"(n0e));
-    int bcol[NI], tcol[NI];
-    bool okc[NI];
+          for (int r = 0; r < 16; ++r) acc[mi][h][ni][r] *= kInv;
+  }
+  // (batch, time) of this lane's output columns, recomputed from an opaque copy of the tile origin
+  // instead of being carried through the main loop in registers
+  int n0e = n0;
+  asm volatile("" : "+s"(n0e));
+  int bcol[NI], tcol[NI];
+  bool okc[NI];
 #pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-      const int n = n0e + wn * (NI * 32) + ni * 32 + l31;
-      okc[ni] = n < Ntot;
-      bcol[ni] = n / T;
-      tcol[ni] = n - bcol[ni] * T;
-    }
-    if constexpr (FG) {
-      const int nw0 = n0e + wn * (NI * 32);
-      bool wide_done = false;
-      if constexpr (NI == 2) {
-        if (dv3_wide_gate_ok(p, args.wide) && (size_t)(WM * WN) * DV3_WIDE_LDS <= (size_t)(2 * 2 * KB * BM + 2 * xbuf) * 16) {
-          float* wl = reinterpret_cast<float*>(smem_raw) + wave * (DV3_WIDE_LDS / 4);
-#pragma unroll
-          for (int mi = 0; mi < MI; ++mi) {
-            const int row0 = wm * (MI * 32) + mi * 32;
-            conv_epilogue_wide_block_gate<BM, BMH>(p, acc[mi][0], mt, row0, 0, lane, nw0, Ntot, wl);
-            conv_epilogue_wide_block_gate<BM, BMH>(p, acc[mi][1], mt, row0, 1, lane, nw0, Ntot, wl);
-          }
-          wide_done = true;
-        }
-      }
-      if (!wide_done) {
-        conv_epilogue_dgrad_gate<BM, BMH, NI>(p, acc[0], mt, wm * (MI * 32), lhi, l31, bcol, tcol, okc, nw0 >> 5);
-        if (MI == 2) conv_epilogue_dgrad_gate<BM, BMH, NI>(p, acc[MI - 1], mt, wm * (MI * 32) + 32, lhi, l31, bcol, tcol, okc, nw0 >> 5);
-      }
-    } else
-    if (TERMS == 1 && (p.io_bf16 & DV3_IO_OUT_C8)) {   // bf16 storage: channel-blocked y / ab / residuals
-      conv_epilogue_c8<BM, BMH, NI>(p, acc[0], gated, mt, wm * (MI * 32), lhi, bcol, tcol, okc);
-      if (MI == 2) conv_epilogue_c8<BM, BMH, NI>(p, acc[MI - 1], gated, mt, wm * (MI * 32) + 32, lhi, bcol, tcol, okc);
-    } else if (NI == 2 && TERMS == 3 && ABL == 0 && dv3_wide_epilogue_ok(p, args.wide) &&
-               (size_t)(WM * WN) * DV3_WIDE_LDS <= (size_t)(2 * 2 * KB * BM + 2 * xbuf) * 16) {
-      // 16-byte epilogue through LDS (conv_common.h): the main loop's last barrier is behind every LDS read
-      if constexpr (NI == 2) {
+  for (int ni = 0; ni < NI; ++ni) {
+    const int n = n0e + wn * (NI * 32) + ni * 32 + l31;
+    okc[ni] = n < Ntot;
+    bcol[ni] = n / T;
+    tcol[ni] = n - bcol[ni] * T;
+  }
+  if constexpr (FG) {
+    const int nw0 = n0e + wn * (NI * 32);
+    bool wide_done = false;
+    if constexpr (NI == 2) {
+      if (dv3_wide_gate_ok(p, args.wide) && (size_t)(WM * WN) * DV3_WIDE_LDS <= (size_t)(2 * 2 * KB * BM + 2 * xbuf) * 16) {
         float* wl = reinterpret_cast<float*>(smem_raw) + wave * (DV3_WIDE_LDS / 4);
-        const int nw0 = n0e + wn * (NI * 32);
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
           const int row0 = wm * (MI * 32) + mi * 32;
-          conv_epilogue_wide_block<BM, BMH>(p, acc[mi][0], mt, row0, 0, lane, nw0, Ntot, wl);
-          conv_epilogue_wide_block<BM, BMH>(p, acc[mi][1], mt, row0, 1, lane, nw0, Ntot, wl);
+          conv_epilogue_wide_block_gate<BM, BMH>(p, acc[mi][0], mt, row0, 0, lane, nw0, Ntot, wl);
+          conv_epilogue_wide_block_gate<BM, BMH>(p, acc[mi][1], mt, row0, 1, lane, nw0, Ntot, wl);
         }
+        wide_done = true;
       }
-    } else {
-      conv_epilogue<BM, BMH, NI, ABL, TERMS == 1>(p, acc[0], gated, mt, wm * (MI * 32), lhi, bcol, tcol, okc);
-      if (MI == 2)
-        conv_epilogue<BM, BMH, NI, ABL, TERMS == 1>(p, acc[MI - 1], gated, mt, wm * (MI * 32) + 32, lhi, bcol, tcol, okc);
     }
+    if (!wide_done) {
+      conv_epilogue_dgrad_gate<BM, BMH, NI>(p, acc[0], mt, wm * (MI * 32), lhi, l31, bcol, tcol, okc, nw0 >> 5);
+      if (MI == 2) conv_epilogue_dgrad_gate<BM, BMH, NI>(p, acc[MI - 1], mt, wm * (MI * 32) + 32, lhi, l31, bcol, tcol, okc, nw0 >> 5);
+    }
+  } else
+  if (TERMS == 1 && (p.io_bf16 & DV3_IO_OUT_C8)) {   // bf16 storage: channel-blocked y / ab / residuals
+    conv_epilogue_c8<BM, BMH, NI>(p, acc[0], gated, mt, wm * (MI * 32), lhi, bcol, tcol, okc);
+    if (MI == 2) conv_epilogue_c8<BM, BMH, NI>(p, acc[MI - 1], gated, mt, wm * (MI * 32) + 32, lhi, bcol, tcol, okc);
+  } else if (NI == 2 && TERMS == 3 && dv3_wide_epilogue_ok(p, args.wide) &&
+             (size_t)(WM * WN) * DV3_WIDE_LDS <= (size_t)(2 * 2 * KB * BM + 2 * xbuf) * 16) {
+    // 16-byte epilogue through LDS (conv_common.h): the main loop's last barrier is behind every LDS read
+    if constexpr (NI == 2) {
+      float* wl = reinterpret_cast<float*>(smem_raw) + wave * (DV3_WIDE_LDS / 4);
+      const int nw0 = n0e + wn * (NI * 32);
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) {
+        const int row0 = wm * (MI * 32) + mi * 32;
+        conv_epilogue_wide_block<BM, BMH>(p, acc[mi][0], mt, row0, 0, lane, nw0, Ntot, wl);
+        conv_epilogue_wide_block<BM, BMH>(p, acc[mi][1], mt, row0, 1, lane, nw0, Ntot, wl);
+      }
+    }
+  } else {
+    conv_epilogue<BM, BMH, NI, TERMS == 1>(p, acc[0], gated, mt, wm * (MI * 32), lhi, bcol, tcol, okc);
+    if (MI == 2)
+      conv_epilogue<BM, BMH, NI, TERMS == 1>(p, acc[MI - 1], gated, mt, wm * (MI * 32) + 32, lhi, bcol, tcol, okc);
   }
-  stamp();                         // last slot: epilogue stores issued
 }
 
 // packed fp32 [J][K][lda] -> split image [plane][j][k8][m][8]
@@ -791,14 +636,14 @@ __global__ __launch_bounds__(256) void split_pack_kernel(const float* __restrict
 #ifndef DV3_X3_ISA_KS
 #define DV3_X3_ISA_KS 1
 #endif
-template __global__ void conv_gemm_bf16x3_kernel<2, 2, 1, DV3_X3_ISA_MASK, 0, 3, 1, false, DV3_X3_ISA_F16, DV3_X3_ISA_DPJ, DV3_X3_ISA_KS>(const ConvArgs);
+template __global__ void conv_gemm_bf16x3_kernel<2, 2, 1, DV3_X3_ISA_MASK, 3, 1, false, DV3_X3_ISA_F16, DV3_X3_ISA_KS>(const ConvArgs);
 }  // namespace
 #else
-template <int WM, int WN, int NI, bool MASK, int TERMS, int MI = 1, bool PP = false, bool F16 = false, int DPJ = 0, int KS = 1, bool FG = false>
+template <int WM, int WN, int NI, bool MASK, int TERMS, int MI = 1, bool PP = false, bool F16 = false, int KS = 1, bool FG = false>
 int launch_x3_m(const ConvArgs& a, size_t lds, hipStream_t st) {
   static bool attr_set = false;  // raise the dynamic-LDS cap once per instantiation
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_gemm_bf16x3_kernel<WM, WN, NI, MASK, 0, TERMS, MI, PP, F16, DPJ, KS, FG>,
+    hipError_t e = hipFuncSetAttribute((const void*)conv_gemm_bf16x3_kernel<WM, WN, NI, MASK, TERMS, MI, PP, F16, KS, FG>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) {
       dv3_set_error("conv_gemm_bf16x3: hipFuncSetAttribute: %s", hipGetErrorString(e));
@@ -807,19 +652,9 @@ int launch_x3_m(const ConvArgs& a, size_t lds, hipStream_t st) {
     attr_set = true;
   }
   dim3 grid(a.n_blocks), block(WM * WN * 64 * KS);
-  hipLaunchKernelGGL((conv_gemm_bf16x3_kernel<WM, WN, NI, MASK, 0, TERMS, MI, PP, F16, DPJ, KS, FG>), grid, block, lds * KS, st, a);
+  hipLaunchKernelGGL((conv_gemm_bf16x3_kernel<WM, WN, NI, MASK, TERMS, MI, PP, F16, KS, FG>), grid, block, lds * KS, st, a);
   return dv3_check_launch("conv_gemm_bf16x3");
 }
-int g_x3_ablate = 0;   // debug: dv3_debug_set(); ablation variants of the 128x128 unmasked tile
-#ifdef DV3_EXPERIMENTS   // timing-only ablations / phase stamps: `make EXP=1` (not in the shipped library)
-template <int ABL>
-int launch_x3_abl(const ConvArgs& a, size_t lds, hipStream_t st) {
-  (void)hipFuncSetAttribute((const void*)conv_gemm_bf16x3_kernel<2, 2, 2, false, ABL>,
-                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipLaunchKernelGGL((conv_gemm_bf16x3_kernel<2, 2, 2, false, ABL>), dim3(a.n_blocks), dim3(256), lds, st, a);
-  return dv3_check_launch("conv_gemm_bf16x3(abl)");
-}
-#endif
 // main loop of the 8-wave tiles, dv3_debug_set(3, v): 0 = in-phase, 1 = ping-pong (default)
 int g_x3_pingpong = 1;
 template <int WM, int WN, int NI, int MI, bool PP>
@@ -832,16 +667,6 @@ int launch_x3_big_pp(const ConvArgs& a, size_t lds, hipStream_t st) {
 }
 template <int WM, int WN, int NI, int MI>
 int launch_x3_big(const ConvArgs& a, size_t lds, hipStream_t st) {
-#ifdef DV3_EXPERIMENTS
-  if constexpr (WM == 2 && WN == 4 && MI == 1) {
-    if (g_x3_ablate == 10 && g_x3_pingpong && !a.d.xmask && (a.d.split_terms == 0 || a.d.split_terms == 3)) {
-      (void)hipFuncSetAttribute((const void*)conv_gemm_bf16x3_kernel<2, 4, 2, false, 10, 3, 1, true>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL((conv_gemm_bf16x3_kernel<2, 4, 2, false, 10, 3, 1, true>), dim3(a.n_blocks), dim3(512), lds, st, a);
-      return dv3_check_launch("conv_gemm_bf16x3(stamps)");
-    }
-  }
-#endif
   if constexpr (WM * WN == 8 && MI == 1) {
     if (g_x3_pingpong) return launch_x3_big_pp<WM, WN, NI, MI, true>(a, lds, st);
   }
@@ -849,43 +674,14 @@ int launch_x3_big(const ConvArgs& a, size_t lds, hipStream_t st) {
 }
 template <int WM, int WN, int NI>
 int launch_x3(const ConvArgs& a, size_t lds, hipStream_t st) {
-#ifdef DV3_EXPERIMENTS
-  if (g_x3_ablate && WM == 2 && WN == 2 && NI == 2 && !a.d.xmask && (a.d.split_terms == 0 || a.d.split_terms == 3)) {
-    switch (g_x3_ablate) {
-      case 1: return launch_x3_abl<1>(a, lds, st);
-      case 2: return launch_x3_abl<2>(a, lds, st);
-      case 3: return launch_x3_abl<3>(a, lds, st);
-      case 4: return launch_x3_abl<4>(a, lds, st);
-      case 5: return launch_x3_abl<5>(a, lds, st);
-      case 6: return launch_x3_abl<6>(a, lds, st);
-      case 7: return launch_x3_abl<7>(a, lds, st);
-      case 8: return launch_x3_abl<8>(a, lds, st);
-      case 9: return launch_x3_abl<9>(a, lds, st);
-    }
-  }
-#endif
   if constexpr (WM == 2 && WN == 2 && NI == 1) {
     // k-split form of the 128 x 64 tile (kernel template KS = 2): chosen by the dispatcher (a.ks)
     if (a.ks == 2 && a.d.split_terms != 1) {
       const bool f16 = a.d.split_terms == DV3_SPLIT_F16X3, m = a.d.xmask != nullptr;
-      if (f16) return m ? launch_x3_m<2, 2, 1, true, 3, 1, false, true, 0, 2>(a, lds, st) : launch_x3_m<2, 2, 1, false, 3, 1, false, true, 0, 2>(a, lds, st);
-      return m ? launch_x3_m<2, 2, 1, true, 3, 1, false, false, 0, 2>(a, lds, st) : launch_x3_m<2, 2, 1, false, 3, 1, false, false, 0, 2>(a, lds, st);
+      if (f16) return m ? launch_x3_m<2, 2, 1, true, 3, 1, false, true, 2>(a, lds, st) : launch_x3_m<2, 2, 1, false, 3, 1, false, true, 2>(a, lds, st);
+      return m ? launch_x3_m<2, 2, 1, true, 3, 1, false, false, 2>(a, lds, st) : launch_x3_m<2, 2, 1, false, 3, 1, false, false, 2>(a, lds, st);
     }
   }
-#ifdef DV3_EXPERIMENTS   // measured and retired (profiles/r05_deep_prefetch_rings.txt): experiment build only
-  if constexpr (WM == 2 && WN == 2 && NI == 1) {
-    // deep-prefetch form of the 128 x 64 tile (kernel template DPJ): chosen by the dispatcher (a.dp = 1 or 3 taps)
-    if (a.dp == 1 || a.dp == 3) {
-      const bool f16 = a.d.split_terms == DV3_SPLIT_F16X3, m = a.d.xmask != nullptr;
-      if (a.dp == 1) {
-        if (f16) return m ? launch_x3_m<2, 2, 1, true, 3, 1, false, true, 1>(a, lds, st) : launch_x3_m<2, 2, 1, false, 3, 1, false, true, 1>(a, lds, st);
-        return m ? launch_x3_m<2, 2, 1, true, 3, 1, false, false, 1>(a, lds, st) : launch_x3_m<2, 2, 1, false, 3, 1, false, false, 1>(a, lds, st);
-      }
-      if (f16) return m ? launch_x3_m<2, 2, 1, true, 3, 1, false, true, 3>(a, lds, st) : launch_x3_m<2, 2, 1, false, 3, 1, false, true, 3>(a, lds, st);
-      return m ? launch_x3_m<2, 2, 1, true, 3, 1, false, false, 3>(a, lds, st) : launch_x3_m<2, 2, 1, false, 3, 1, false, false, 3>(a, lds, st);
-    }
-  }
-#endif
   if (a.d.split_terms == DV3_SPLIT_F16X3)
     return a.d.xmask ? launch_x3_m<WM, WN, NI, true, 3, 1, false, true>(a, lds, st) : launch_x3_m<WM, WN, NI, false, 3, 1, false, true>(a, lds, st);
   if (a.d.split_terms == 1)
@@ -895,7 +691,6 @@ int launch_x3(const ConvArgs& a, size_t lds, hipStream_t st) {
 
 int g_x3_ks = 1;        // dv3_debug_set(44, v): k-split form of the 128 x 64 tile: 0 never, 1 by the rule in the dispatcher, 2 wherever eligible
 int g_x3_ks_max_blocks = 256, g_x3_ks_min_steps = 8;   // dv3_debug_set(45 / 46, v): the rule's bounds
-int g_x3_dp = 0;        // dv3_debug_set(43, v), experiment build: deep-prefetch form of the 128 x 64 tile: 0 never, 1 small grids, 2 always
 int g_x3_rel8 = 86;     // dv3_debug_set(42, v): relative cost (percent) of the 256 x 128 ping-pong tile in the picker below.  Rounds 2-4: 93
                         // (north-star sweep).  Round 5's census of a real step (profiles/r05_conv_census_dv3lj_b64.txt) has it ahead
                         // of the 128 x 256 tile stand-alone wherever the two tie on rounds (the encoder's input gradients, the
@@ -948,7 +743,7 @@ int g_x3_pp2 = 128;  // dv3_debug_set(12, v): the 256 x 256 k16 ping-pong kernel
                      // whose grid has at least v tiles (0 = never).  Measured at B=64 over the presets' conv shapes
                      // (scripts/pp2_sweep.py, profiles/r03_pp2_sweep.txt): 0.73-0.88 of the 128 x 256 / 128 x 64 kernels'
                      // time from 152 tiles up, 1.3-1.9 x at 50-100 tiles (half the chip idle).
-extern int g_pp2_ord, g_pp2_ord_u, g_pp2_ord_m, g_pp2_abl, g_pp2_sk, g_pp2_sk_overhead, g_pp2_sk_gain, g_pp2_sk_abl, g_pp2_fast_tail;
+extern int g_pp2_ord_u, g_pp2_ord_m, g_pp2_sk, g_pp2_sk_overhead, g_pp2_sk_gain, g_pp2_fast_tail;
 int g_x3_pp2_sk_units = 8;   // measured (scripts/pp2_sk_check.py): at 9.5 units per CU (the encoder layers: 152 / 76 tiles) the
                              // stream-K form beats the 128-wide kernels by 6-8 %, at 6.3 (101 tiles x 16) it loses to them
 int dv3_conv_gemm_pp2_dispatch(const dv3_conv_desc* d, hipStream_t st);   // conv_gemm_pp2.hip
@@ -1010,25 +805,18 @@ int dv3_conv_gemm_bf16x3_dispatch(const dv3_conv_desc* d, hipStream_t st) {
   DV3_REQUIRE(nb < (1ll << 31), "conv_gemm: grid too large");
   a.n_blocks = (int)nb;
   a.ks = (ks_ok && best->id == 2 && 2 * lds <= 160 * 1024) ? 2 : 0;
-  // deep-prefetch form (the 128 x 64 tile, 1 or 3 taps, three-term splits): experiment build only, off by default
-  a.dp = 0;
-#ifdef DV3_EXPERIMENTS
-  if (best->id == 2 && d->split_terms != 1 && (d->J == 1 || d->J == 3) && g_x3_dp) {
-    if (g_x3_dp == 2 || nb <= 2 * 256) a.dp = d->J;
-  }
-#endif
   g_dv3_last_conv = (d->split_terms == 1 ? 4000 : d->split_terms == DV3_SPLIT_F16X3 ? 5000 : 3000) + best->id * 10 +
-                    ((best->id >= 8 && g_x3_pingpong) ? 1 : 0) + (a.dp ? 5 : 0) + (a.ks == 2 ? 2 : 0);
+                    ((best->id >= 8 && g_x3_pingpong) ? 1 : 0) + (a.ks == 2 ? 2 : 0);
   if (d->pg) {
     // round 6: the fused gate backward lives in its own instantiations (bf16 pair, no dropout) of four tiles
     if (d->xmask || d->split_terms == DV3_SPLIT_F16X3 || d->split_terms == 1) return 1;
     g_dv3_last_conv += 600;            // 36xx: fused gate backward in the tail
     switch (best->id) {
-      case 1: return launch_x3_m<2, 2, 2, false, 3, 1, false, false, 0, 1, true>(a, lds, st);
-      case 2: return a.ks == 2 ? launch_x3_m<2, 2, 1, false, 3, 1, false, false, 0, 2, true>(a, lds, st)
-                               : launch_x3_m<2, 2, 1, false, 3, 1, false, false, 0, 1, true>(a, lds, st);
-      case 8: return launch_x3_m<4, 2, 2, false, 3, 1, true, false, 0, 1, true>(a, lds, st);
-      case 9: return launch_x3_m<2, 4, 2, false, 3, 1, true, false, 0, 1, true>(a, lds, st);
+      case 1: return launch_x3_m<2, 2, 2, false, 3, 1, false, false, 1, true>(a, lds, st);
+      case 2: return a.ks == 2 ? launch_x3_m<2, 2, 1, false, 3, 1, false, false, 2, true>(a, lds, st)
+                               : launch_x3_m<2, 2, 1, false, 3, 1, false, false, 1, true>(a, lds, st);
+      case 8: return launch_x3_m<4, 2, 2, false, 3, 1, true, false, 1, true>(a, lds, st);
+      case 9: return launch_x3_m<2, 4, 2, false, 3, 1, true, false, 1, true>(a, lds, st);
     }
     return 1;
   }
@@ -1046,86 +834,56 @@ int dv3_conv_gemm_bf16x3_dispatch(const dv3_conv_desc* d, hipStream_t st) {
   return 1;
 }
 
-extern int g_wgrad_tile, g_wgrad_prio, g_wgrad_t2_abl, g_wgrad_taps2_default, g_wgrad_t2_window, g_wgrad_t2_il;   // wgrad_gemm_bf16x3.hip, wgrad_taps2.hip
-extern int g_spk_prefetch;                                                                                 // speaker_bias.hip
-extern int g_gate_c8_fast;                                                                                 // elementwise.hip
-extern int g_loss_fast_log;                                                                                // loss.hip
-extern int g_gate_vec;                                                                                     // elementwise.hip
-extern int g_wn_bwd_vec4;                                                                                  // weight_norm.hip
-extern int g_wgrad_c8_pf2, g_wgrad_c8_il, g_wgrad_c8_tr, g_spk_abl;                                                       // wgrad_c8.hip
+extern int g_wgrad_tile, g_wgrad_prio, g_wgrad_taps2_default, g_wgrad_t2_window, g_wgrad_t2_il;   // wgrad_gemm_bf16x3.hip, wgrad_taps2.hip
+extern int g_wgrad_c8_pf2, g_wgrad_c8_il, g_wgrad_c8_tr;                                      // wgrad_c8.hip
+extern int g_c8pp_min_tiles, g_c8pp_rf, g_c8pp_nw4, g_c8pp_stagger, g_c8pp_stagger_mask;       // conv_c8pp.hip
+extern int g_spk_prefetch;                                                                    // speaker_bias.hip
+extern int g_gate_c8_fast, g_gate_vec;                                                        // elementwise.hip
+extern int g_loss_fast_log;                                                                   // loss.hip
+extern int g_wn_bwd_vec4;                                                                     // weight_norm.hip
 int dv3_planes_debug_set(int what, int value);   // conv_planes.hip
-int dv3_c8pp_debug_set(int what, int value);     // conv_c8pp.hip
 int dv3_conv_census_set(int on);                 // conv_gemm.hip
+// Run-time switches for measurement and bit-identity tests (include/dv3hip.h).  An unknown code is an error: a script
+// that names a retired switch must not time the production kernel believing it timed something else.
 extern "C" int dv3_debug_set(int what, int value) {
-#ifndef DV3_EXPERIMENTS
-  // the timing-only ablation / stamp instantiations are compiled with `make EXP=1` only: say so instead of silently
-  // timing the production kernel
-  DV3_REQUIRE(!(value != 0 && (what == 1 || what == 6 || what == 13 || what == 16 || what == 21 || what == 26 || what == 28 || what == 32 || what == 43)),
-              "debug_set(%d, %d): ablation variants are not in this build (make EXP=1)", what, value);
-#endif
-  if (what >= 4 && what <= 8) return dv3_planes_debug_set(what, value);
+  if (what == 4 || what == 5 || what == 7 || what == 8) return dv3_planes_debug_set(what, value);
   if (what == 40) return dv3_conv_census_set(value);
-  if (what == 19 || what == 21 || what == 30 || what == 32 || (what >= 34 && what <= 36)) return dv3_c8pp_debug_set(what, value);
-  if (what == 20) g_wgrad_c8_pf2 = value;
-  if (what == 49) g_wgrad_c8_il = value;
-  if (what == 9) g_x3_rel2 = value;
-  if (what == 12) g_x3_pp2 = value;
-  if (what == 13) g_pp2_abl = value;
-  if (what == 29 || what == 31) {
-    const bool ship = value == 0 || value == 17 || value == 81;
-#ifndef DV3_EXPERIMENTS
-    DV3_REQUIRE(ship, "debug_set(%d, %d): this LOAD-phase variant is not in this build (make EXP=1)", what, value);
-#endif
-    if (what == 29) { g_pp2_ord_u = ship ? value : 0; g_pp2_ord = ship ? 0 : value; }
-    else g_pp2_ord_m = ship ? value : 0;
+  if (what == 29 || what == 31) {   // ORD of the 256 x 256 kernel's unmasked / masked instantiations: the shipped forms
+    DV3_REQUIRE(value == 0 || value == 17 || value == 81, "debug_set(%d, %d): LOAD-phase order 0, 17 or 81", what, value);
+    (what == 29 ? g_pp2_ord_u : g_pp2_ord_m) = value;
+    return DV3_OK;
   }
-  if (what == 50) g_pp2_fast_tail = value;
-  if (what == 51) g_wn_bwd_vec4 = value;
-  if (what == 52) g_wgrad_c8_tr = value;
-  if (what == 54) g_spk_prefetch = value;
-  if (what == 55) g_gate_vec = value;
-  if (what == 56) g_gate_c8_fast = value;
-  if (what == 57) g_loss_fast_log = value;
-  if (what == 22) g_pp2_sk = value;
-  if (what == 23) g_pp2_sk_overhead = value;
-  if (what == 24) g_pp2_sk_gain = value;
-  if (what == 25) g_x3_pp2_sk_units = value;
-  if (what == 26) g_pp2_sk_abl = value;
-  if (what == 27) g_x3_j1_flat = value;
-  if (what == 43) g_x3_dp = value;
-  if (what == 42) g_x3_rel8 = value;
-  if (what == 44) g_x3_ks = value;
-  if (what == 45) g_x3_ks_max_blocks = value;
-  if (what == 46) g_x3_ks_min_steps = value;
-  if (what == 28) g_spk_abl = value;
-  if (what == 14) g_x3_prio = value;
-  if (what == 18) g_x3_wide = value;
-  if (what == 15) g_wgrad_prio = value;
-  if (what == 16) g_wgrad_t2_abl = value;
-  if (what == 17) g_wgrad_taps2_default = value;
-  if (what == 47) g_wgrad_t2_window = value;
-  if (what == 48) g_wgrad_t2_il = value;
-  if (what == 1) g_x3_ablate = value;
-  if (what == 2) g_wgrad_tile = value;
-  if (what == 3) g_x3_pingpong = value;
-  return DV3_OK;
+  DV3_REQUIRE(what != 52 || (value >= 0 && value <= 4), "debug_set(52, %d): wgrad_c8 form 0..4", value);
+  static const struct {
+    int what;
+    int* var;
+  } kSwitches[] = {
+      {2, &g_wgrad_tile},        {3, &g_x3_pingpong},         {9, &g_x3_rel2},          {12, &g_x3_pp2},
+      {14, &g_x3_prio},          {15, &g_wgrad_prio},         {17, &g_wgrad_taps2_default}, {18, &g_x3_wide},
+      {19, &g_c8pp_min_tiles},   {20, &g_wgrad_c8_pf2},       {22, &g_pp2_sk},          {23, &g_pp2_sk_overhead},
+      {24, &g_pp2_sk_gain},      {25, &g_x3_pp2_sk_units},    {27, &g_x3_j1_flat},      {30, &g_c8pp_rf},
+      {34, &g_c8pp_nw4},         {35, &g_c8pp_stagger},       {36, &g_c8pp_stagger_mask}, {42, &g_x3_rel8},
+      {44, &g_x3_ks},            {45, &g_x3_ks_max_blocks},   {46, &g_x3_ks_min_steps}, {47, &g_wgrad_t2_window},
+      {48, &g_wgrad_t2_il},      {49, &g_wgrad_c8_il},        {50, &g_pp2_fast_tail},   {51, &g_wn_bwd_vec4},
+      {52, &g_wgrad_c8_tr},      {54, &g_spk_prefetch},       {55, &g_gate_vec},        {56, &g_gate_c8_fast},
+      {57, &g_loss_fast_log},
+  };
+  for (const auto& sw : kSwitches)
+    if (sw.what == what) {
+      *sw.var = value;
+      return DV3_OK;
+    }
+  dv3_set_error("debug_set(%d, %d): no such switch", what, value);
+  return DV3_EINVAL;
 }
 
-int dv3_pp2_read_stamps(void* dst, int64_t bytes);   // conv_gemm_pp2.hip
 int dv3_decode_read_stamps(void* dst, int64_t bytes);  // decode_step.hip
 int dv3_conv_census_read(int what, void* dst, int64_t bytes);   // conv_gemm.hip
 extern "C" int dv3_debug_read(int what, void* dst, int64_t bytes) {
   if (what == 40 || what == 41) return dv3_conv_census_read(what, dst, bytes);
-  if (what == 2 && dst) return dv3_pp2_read_stamps(dst, bytes);
   if (what == 3 && dst) return dv3_decode_read_stamps(dst, bytes);
-  DV3_REQUIRE(what == 1 && dst && bytes > 0 && bytes <= (int64_t)sizeof(unsigned long long) * 8 * STAMP_SLOTS * 2,
-              "debug_read: bad arguments");
-  hipError_t e = hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_x3_stamps), (size_t)bytes, 0, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) {
-    dv3_set_error("debug_read: %s", hipGetErrorString(e));
-    return DV3_ELAUNCH;
-  }
-  return DV3_OK;
+  dv3_set_error("debug_read(%d): no such buffer", what);
+  return DV3_EINVAL;
 }
 
 extern "C" int dv3_split_pack_bf16(const float* packed, uint16_t* out, int32_t J, int32_t K,

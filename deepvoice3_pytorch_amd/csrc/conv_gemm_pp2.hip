@@ -70,11 +70,6 @@ __device__ __forceinline__ T pp2_ldg(const void* base, uint32_t byte_off) {
   return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
 }
 
-// ABL 4 (dv3_debug_set(13, 4)): phase timestamps of ONE workgroup, [wave][slot][0 = s_memrealtime (100 MHz),
-// 1 = s_memtime (shader clock)]; read back with dv3_debug_read(2, ...)
-constexpr int PP2_STAMPS = 320;
-__device__ unsigned long long g_pp2_stamps[8 * PP2_STAMPS * 2];
-
 // SK (stream-K form, see the note above dv3_conv_gemm_pp2_dispatch): the grid is one workgroup per CU and a workgroup
 // walks a contiguous range of (tile, 32-channel chunk) units -- at most one leading segment that ends a tile another
 // workgroup began (its accumulators go to the workspace) and then segments that begin a tile (the workgroup that
@@ -96,25 +91,11 @@ __device__ unsigned long long g_pp2_stamps[8 * PP2_STAMPS * 2];
 //      input (dv3_conv_desc.pg; conv_common.h: conv_epilogue_dgrad_gate / conv_epilogue_wide_block_gate).  A separate
 //      instantiation that contains that tail and no other: as a run-time branch of the shared tail it cost every
 //      instantiation of this kernel its spill-free register allocation.
-template <bool MASK, bool F16, int ABL = 0, bool SK = false, int ORD = 0, bool PW = false, bool FG = false>
+template <bool MASK, bool F16, bool SK = false, int ORD = 0, bool PW = false, bool FG = false>
 __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) {
   static_assert(!PW || (!MASK && !F16 && !SK), "pair words: the unmasked bf16-pair tile-per-workgroup form");
   static_assert(!FG || (!MASK && !F16 && !SK), "fused gate backward: the unmasked bf16-pair tile-per-workgroup form");
   const dv3_conv_desc& p = args.d;
-  int n_stamp = 0;
-  auto stamp = [&]() {
-    if constexpr (ABL == 4) {
-      if (blockIdx.x == gridDim.x / 2 + 3 && n_stamp < PP2_STAMPS) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime(), t1 = __builtin_readcyclecounter();
-        if ((threadIdx.x & 63) == 0) {
-          g_pp2_stamps[((threadIdx.x >> 6) * PP2_STAMPS + n_stamp) * 2] = t0;
-          g_pp2_stamps[((threadIdx.x >> 6) * PP2_STAMPS + n_stamp) * 2 + 1] = t1;
-        }
-      }
-      ++n_stamp;
-    }
-  };
-  stamp();                               // slot 0: kernel entry
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   constexpr int J = JT;
   bf16x8* const As = reinterpret_cast<bf16x8*>(smem_raw);   // [2 buffers][hi | lo][KB][BM]
@@ -148,10 +129,6 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
     seg_u = sk_g0 + slot * sk_base + min(slot, sk_rem);
     seg_end = seg_u + sk_base + (slot < sk_rem ? 1 : 0);
   }
-  // weight panels by LDS-DMA (dma_A_unit): the experiment of round 3 (+2 % on the tile-per-workgroup kernel, retired
-  // there) -- and the form the stream-K variants use: it frees the eight staging registers of the panel unit, which is
-  // what keeps their main loop free of scratch reloads
-  constexpr bool DMA_A = ABL == 11;
   constexpr bool WIDE_GLU = (ORD & 32) != 0;   // 16-byte gated tail (quad transpose in registers)
   int tid_ = threadIdx.x;
   const int wave_s = __builtin_amdgcn_readfirstlane(tid_ >> 6);
@@ -293,26 +270,6 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
     bf16x8* dst = As + buf * (2 * KB * BM);
     dst[tid + u * NT] = ra[0];
     dst[KB * BM + tid + u * NT] = ra[1];
-  };
-  // EXPERIMENT (ABL == 11, dv3_debug_set(13, 11); compiled and inspected, NOT yet run on hardware -- round 4's first
-  // measurement): the same unit straight from global memory into its LDS slot with global_load_lds_dwordx4 -- no
-  // register round trip, no ds_write.  The panel image As[buf][plane][k8][BM] is indexed tid + u * NT, i.e. the 64
-  // lanes of a wave own 64 CONSECUTIVE 16-byte units: exactly the layout the LDS-DMA instruction writes (M0 = the
-  // wave's base, lane i lands at base + 16 i).  What the ISA of this first form shows (24 global_load_lds_dwordx4, 24
-  // fewer ds_write_b128 and 7 fewer registers than the shipped loop): the workgroup-scope fence inside __syncthreads()
-  // makes the compiler wait vmcnt(0) before the barrier that ends the issuing phase -- the whole memory latency once per
-  // step.  The form to measure next therefore replaces that one barrier by a raw s_barrier with a COUNTED wait
-  // (the 20 activation loads issued after the DMA may stay in flight: vmcnt is in order), as the uniform load schedule
-  // already allows for the register path.
-  auto dma_A_unit = [&](int buf, int chunk, int j, auto uc) {
-    constexpr int u = decltype(uc)::value;
-    const bf16x8* srch = Wh + (int64_t)(j * k8_total + chunk * KB) * lda;  // uniform
-    const uint32_t ao = aoff_of(u);
-    bf16x8* dst = As + buf * (2 * KB * BM) + u * NT + wave * 64;           // uniform per wave
-    typedef const __attribute__((address_space(1))) void* gptr;
-    typedef __attribute__((address_space(3))) void* lptr;
-    __builtin_amdgcn_global_load_lds((gptr)(reinterpret_cast<const char*>(srch) + ao), (lptr)dst, 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((gptr)(reinterpret_cast<const char*>(srch + plane) + ao), (lptr)(dst + KB * BM), 16, 0, 0);
   };
   // half an item (four of its eight channel rows): one uniform base per chunk + a 32-bit per-thread offset
   auto load_X_half = [&](int chunk, auto ic, auto hc) {
@@ -486,7 +443,7 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
   __syncthreads();
   {
     const int cp = min(c0 + 1, c1 - 1);
-    if (!DMA_A) load_A_unit(c0, 1, U0{});          // unit 0 of step 1's panel: stored by the first LOAD phase
+    load_A_unit(c0, 1, U0{});          // unit 0 of step 1's panel: stored by the first LOAD phase
     load_X_half(cp, U0{}, U0{});
     load_X_half(cp, U0{}, U1{});
     load_X_half(cp, U1{}, U0{}); load_X_half(cp, U1{}, U1{});
@@ -507,7 +464,6 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
   // thread -> (row = tid / 4 of the 128 `a` rows, column segment tid % 4 of 64 columns); two loads per thread
   const bool pf_on = (ORD & 4) != 0 && !SK && gated && p.r != nullptr;
   const int late = wave >> 2;
-  stamp();                               // slot 1: prologue done
   if (late) __syncthreads();
   for (int c = c0; c < c1; ++c) {
     const int cr = c - c0;                           // buffer parities count from the segment's first chunk
@@ -523,7 +479,6 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
       const bf16x8* AsH = As + cur * (2 * KB * BM);
       const bf16x8* AsL = AsH + KB * BM;
       const bool fix = (need >> j) & 1u;
-      stamp();                           // 2 + 5*phase: LOAD begins
       // ---------------- LOAD ----------------
       // Order inside the phase: staging first, fragment reads last (pinned with sched_barrier) -- the twelve fragments
       // (48 registers) are dead until then, which keeps the conversion temporaries of the staging inside the
@@ -568,7 +523,7 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
         read_frags(true, (ORD & 16) == 0);
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (ABL != 2) {
+      {
         // panel unit s of the next step: store (it was fetched in this wave's previous LOAD phase), then fetch the
         // unit the NEXT LOAD phase stores: one unit (8 registers) in flight, two barrier intervals to land (an L2 hit)
         int jn = j + 1, cn = c;
@@ -577,25 +532,15 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
         if (j2 >= JT) { j2 = 0; c2 = cn + 1; }
         if (cn >= c1) { cn = c; jn = j; }               // past the end: re-fetch the current panel
         if (c2 >= c1) { c2 = c; j2 = j; }
-        if constexpr (DMA_A) {
-          // both units of the NEXT step's panel by LDS-DMA in the step's first phase: their buffer (cur ^ 1) was last
-          // read in the previous step and is first read two LOAD phases from now (the buffer of the step after is
-          // still being read during this one, so nothing can be sent there yet)
-          if (s == 0) {
-            dma_A_unit(cur ^ 1, cn, jn, U0{});
-            dma_A_unit(cur ^ 1, cn, jn, U1{});
-          }
-          (void)c2; (void)j2;
-        } else if (s == 0) {
-          if (ABL != 9) write_A_unit(cur ^ 1, U0{});
-          if (ABL != 7) load_A_unit(cn, jn, U1{});       // unit 1 of the next step's panel
+        if (s == 0) {
+          write_A_unit(cur ^ 1, U0{});
+          load_A_unit(cn, jn, U1{});       // unit 1 of the next step's panel
         } else {
-          if (ABL != 9) write_A_unit(cur ^ 1, U1{});
-          if (ABL != 7) load_A_unit(c2, j2, U0{});       // unit 0 of the panel after
+          write_A_unit(cur ^ 1, U1{});
+          load_A_unit(c2, j2, U0{});       // unit 0 of the panel after
         }
         // activation item j of the next chunk: convert + store in the tap's first phase, fetch its halves for the
         // chunk after in the tap's two phases
-        constexpr bool WX = ABL != 8, LX = ABL != 6;      // timing-only ablations: no conversion + store / no fetch
         if constexpr (CVC) {
           // conversion + store of item i in the COMPUTE phase 2 i (below); its halves for the chunk after come in the two
           // LOAD phases that follow it (the second half of item 2 in the next chunk's first phase: cx1 = that chunk's successor)
@@ -607,12 +552,12 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
           if (q == 4) load_X_half(cx, U1{}, U1{});
           if (q == 5) load_X_half(cx, U2{}, U0{});
         } else {
-        if (q == 0) { if (WX) write_X_item((cr + 1) & 1, U0{}); if (LX) load_X_half(cx, U0{}, U0{}); }
-        if (q == 1) { if (LX) load_X_half(cx, U0{}, U1{}); }
-        if (q == 2) { if (WX) write_X_item((cr + 1) & 1, U1{}); if (LX) load_X_half(cx, U1{}, U0{}); }
-        if (q == 3) { if (LX) load_X_half(cx, U1{}, U1{}); }
-        if (q == 4) { if (WX) write_X_item((cr + 1) & 1, U2{}); if (LX) load_X_half(cx, U2{}, U0{}); }
-        if (q == 5) { if (LX) load_X_half(cx, U2{}, U1{}); }
+        if (q == 0) { write_X_item((cr + 1) & 1, U0{}); load_X_half(cx, U0{}, U0{}); }
+        if (q == 1) { load_X_half(cx, U0{}, U1{}); }
+        if (q == 2) { write_X_item((cr + 1) & 1, U1{}); load_X_half(cx, U1{}, U0{}); }
+        if (q == 3) { load_X_half(cx, U1{}, U1{}); }
+        if (q == 4) { write_X_item((cr + 1) & 1, U2{}); load_X_half(cx, U2{}, U0{}); }
+        if (q == 5) { load_X_half(cx, U2{}, U1{}); }
         }
         if constexpr ((ORD & 4) != 0 && !SK) {
           if ((q == 1 || q == 3) && last_chunk && pf_on) {
@@ -633,49 +578,36 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
         }
       }
       __builtin_amdgcn_sched_barrier(0);
-      stamp();                           // +1: staging issued
       if constexpr ((ORD & 1) == 0) read_frags(true, true);
       else if constexpr ((ORD & 16) != 0) read_frags(false, true);
       fix_frags();
-      if constexpr (ABL == 4) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        stamp();                         // +2: fragments landed
-      }
       __syncthreads();
       // The MFMAs are register-only instructions: without the two scheduling fences the compiler sinks them below the
       // second barrier into the next LOAD phase -- legal, but then both waves of a SIMD issue their MFMAs in the same
       // barrier interval and stage in the same interval, i.e. the ping-pong degenerates into the in-phase loop.
-      if (ABL != 5) __builtin_amdgcn_sched_barrier(0);
-      stamp();                           // +3: COMPUTE begins
+      __builtin_amdgcn_sched_barrier(0);
       // ---------------- COMPUTE: 24 MFMAs of one k16 block ----------------
-      if (ABL != 1) {
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
+      for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < NI; ++ni) {
-            acc[mi][0][ni] = pp2_mma<F16>(al[mi][0], bh[ni], acc[mi][0][ni]);
-            acc[mi][1][ni] = pp2_mma<F16>(al[mi][1], bh[ni], acc[mi][1][ni]);
-          }
+        for (int ni = 0; ni < NI; ++ni) {
+          acc[mi][0][ni] = pp2_mma<F16>(al[mi][0], bh[ni], acc[mi][0][ni]);
+          acc[mi][1][ni] = pp2_mma<F16>(al[mi][1], bh[ni], acc[mi][1][ni]);
+        }
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
+      for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < NI; ++ni) {
-            acc[mi][0][ni] = pp2_mma<F16>(ah[mi][0], bl[ni], acc[mi][0][ni]);
-            acc[mi][1][ni] = pp2_mma<F16>(ah[mi][1], bl[ni], acc[mi][1][ni]);
-          }
+        for (int ni = 0; ni < NI; ++ni) {
+          acc[mi][0][ni] = pp2_mma<F16>(ah[mi][0], bl[ni], acc[mi][0][ni]);
+          acc[mi][1][ni] = pp2_mma<F16>(ah[mi][1], bl[ni], acc[mi][1][ni]);
+        }
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
+      for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < NI; ++ni) {
-            acc[mi][0][ni] = pp2_mma<F16>(ah[mi][0], bh[ni], acc[mi][0][ni]);
-            acc[mi][1][ni] = pp2_mma<F16>(ah[mi][1], bh[ni], acc[mi][1][ni]);
-          }
-      } else {
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) asm volatile("" ::"v"(ah[mi][0]), "v"(ah[mi][1]), "v"(al[mi][0]), "v"(al[mi][1]));
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) asm volatile("" ::"v"(bh[ni]), "v"(bl[ni]));
-      }
+        for (int ni = 0; ni < NI; ++ni) {
+          acc[mi][0][ni] = pp2_mma<F16>(ah[mi][0], bh[ni], acc[mi][0][ni]);
+          acc[mi][1][ni] = pp2_mma<F16>(ah[mi][1], bh[ni], acc[mi][1][ni]);
+        }
       if constexpr (CVC) {
         // the conversion + store of activation item q / 2 for the next chunk's tile, spread between the MFMAs: two vector
         // ALU instructions behind each of the first 22, the two stores behind the last two (the matrix pipe takes one
@@ -695,12 +627,10 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
           __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
         }
       }
-      stamp();                           // +4: MFMAs issued
-      if (ABL != 5) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
       if (!(last_chunk && q == 2 * JT - 1) || !late) __syncthreads();
     }
   }
-  stamp();                               // main loop left
   if constexpr (CVC && F16) {
     if (sbad != 0 && lane == 0 && A.range_ctr) atomicAdd(A.range_ctr, sbad);
   }
@@ -708,18 +638,12 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
   bool run_tail = true;
   if constexpr (SK) {
     constexpr int ACC = MI * 2 * NI * 16;            // accumulator registers per thread (128)
-#ifdef DV3_EXPERIMENTS
-    const int sk_abl = A.sk_abl;                     // timing-only ablations (dv3_debug_set(26, bits)): experiment build only
-#else
-    constexpr int sk_abl = 0;
-#endif
     float* const ws = A.sk_ws;
     int* const flags = A.sk_flags;
     if (c0 != 0) {
       // a tile another workgroup began: hand the accumulators over.  Image [32 groups of 4 registers][512 threads][4]:
       // one 16-byte store / load per thread and group, consecutive threads consecutive (layout-agnostic)
       char* dst = reinterpret_cast<char*>(ws) + ((size_t)pid * (ACC * NT) + (size_t)tid * 4) * 4;
-      if (!(sk_abl & 1))
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -749,7 +673,7 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
       for (int w2 = pid + 1; (w2 & qm) != 0; ++w2) {          // (the group's last workgroup ends on a tile boundary)
         const int s2 = sk_g0 + (w2 & qm) * sk_base + min(w2 & qm, sk_rem);
         if (s2 >= (tile + 1) * nchunks) break;
-        if (tid == 0 && !(sk_abl & 4))
+        if (tid == 0)
           while (__hip_atomic_load(flags + w2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) __builtin_amdgcn_s_sleep(8);
         __syncthreads();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -759,7 +683,6 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
         const char* src = reinterpret_cast<const char*>(ws) + ((size_t)w2 * (ACC * NT) + (size_t)tid * 4) * 4;
         typedef const __attribute__((address_space(1))) void* gptr_;
         typedef __attribute__((address_space(3))) void* lptr_;
-        if (!(sk_abl & 2))
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
 #pragma unroll
@@ -792,7 +715,7 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
   // main loop.
   const ConvArgs& AT = *dv3_opaque_args<SK>(&args);
   const dv3_conv_desc& pt = AT.d;
-  if (run_tail && (ABL != 3 || acc[0][0][0][0] + acc[1][1][1][7] == 1.2345e30f)) {
+  if (run_tail) {
     if constexpr (F16) {   // the accumulators carry 2^(weight shift + activation shift) x the result
       constexpr float kInv = 1.0f / (float)(1 << (DV3_F16_WEIGHT_SHIFT + DV3_F16_ACT_SHIFT));
 #pragma unroll
@@ -830,7 +753,7 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
         conv_epilogue_dgrad_gate<BM, BMH, NI>(pt, acc[1], mt, wm * (MI * 32) + 32, lhi, l31, bcol, tcol, okc, nw0 >> 5);
       }
     } else
-    if (ABL != 10 && dv3_wide_epilogue_ok(pt, AT.wide)) {
+    if (dv3_wide_epilogue_ok(pt, AT.wide)) {
       // 16-byte epilogue through LDS (conv_common.h): every LDS read of the main loop is behind the last barrier this
       // wave passed, so the whole allocation is free; each wave transposes in its own 8.5 KB
       float* wl = reinterpret_cast<float*>(smem_raw) + wave * (DV3_WIDE_LDS / 4);
@@ -843,30 +766,27 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
       }
     } else if (WIDE_GLU && dv3_wide_glu_ok(pt)) {
       // 16-byte Conv1dGLU / highway tail through a quad transpose in registers (conv_common.h)
-      constexpr int TA = ABL == 12 ? 12 : ABL == 13 ? 13 : 0;
       const int nw0 = n0e + wn * (NI * 32);
-      conv_epilogue_glu_wide<BMH, NI, TA>(pt, acc[0], mt, wm * (MI * 32), lane, nw0, Ntot);
-      conv_epilogue_glu_wide<BMH, NI, TA>(pt, acc[1], mt, wm * (MI * 32) + 32, lane, nw0, Ntot);
+      conv_epilogue_glu_wide<BMH, NI>(pt, acc[0], mt, wm * (MI * 32), lane, nw0, Ntot);
+      conv_epilogue_glu_wide<BMH, NI>(pt, acc[1], mt, wm * (MI * 32) + 32, lane, nw0, Ntot);
     } else {
-      constexpr int TA = ABL == 12 ? 7 : ABL == 13 ? 8 : 0;     // experiment build: 12 = no residual load, 13 = no stores
       // round 6: a wave whose 64 rows and 64 columns all lie inside the tensor takes the straight-line gated tail
       // (conv_common.h: conv_epilogue_glu_interior; every test below is wave-uniform)
       // (not in the stream-K instantiations: their tail sits inside the segment loop and any addition to it costs the
       //  main loop its registers -- 70 -> 2 500 spills with this one)
       bool interior = false;
       if constexpr (!SK)
-        interior = TA == 0 && AT.fast_tail && gated && !pt.spk && pt.store_mode == DV3_STORE_BCT &&
+        interior = AT.fast_tail && gated && !pt.spk && pt.store_mode == DV3_STORE_BCT &&
                    mt * BMH + wm * (MI * 32) + MI * 32 <= pt.Cg && n0e + wn * (NI * 32) + NI * 32 <= Ntot;
       if (!SK && interior) {
         conv_epilogue_glu_interior<BMH, NI>(pt, acc[0], mt, wm * (MI * 32), lhi, bcol, tcol);
         conv_epilogue_glu_interior<BMH, NI>(pt, acc[1], mt, wm * (MI * 32) + 32, lhi, bcol, tcol);
       } else {
-        conv_epilogue<BM, BMH, NI, TA, false>(pt, acc[0], gated, mt, wm * (MI * 32), lhi, bcol, tcol, okc);
-        conv_epilogue<BM, BMH, NI, TA, false>(pt, acc[1], gated, mt, wm * (MI * 32) + 32, lhi, bcol, tcol, okc);
+        conv_epilogue<BM, BMH, NI, false>(pt, acc[0], gated, mt, wm * (MI * 32), lhi, bcol, tcol, okc);
+        conv_epilogue<BM, BMH, NI, false>(pt, acc[1], gated, mt, wm * (MI * 32) + 32, lhi, bcol, tcol, okc);
       }
     }
   }
-  stamp();                               // tail stores issued
   if constexpr (SK) {
     seg_u += c1 - c0;
     __syncthreads();                     // the next segment's prologue overwrites the LDS the wide tail used
@@ -875,12 +795,12 @@ __global__ __launch_bounds__(NT) void conv_gemm_pp2_kernel(const ConvArgs args) 
 }
 
 #ifndef DV3_PP2_ISA_ONLY   // (developer: compile one instantiation for ISA inspection, scripts/pp2_isa.sh)
-template <bool MASK, bool F16, int ABL = 0, bool SK = false, int ORD = 0, bool PW = false, bool FG = false>
+template <bool MASK, bool F16, bool SK = false, int ORD = 0, bool PW = false, bool FG = false>
 int launch_pp2(const ConvArgs& a, size_t lds, hipStream_t st) {
-  if ((ORD & 4) != 0 && lds + 8 * 256 > 160 * 1024) return launch_pp2<MASK, F16, ABL, SK, (ORD & ~4), PW, FG>(a, lds, st);
+  if ((ORD & 4) != 0 && lds + 8 * 256 > 160 * 1024) return launch_pp2<MASK, F16, SK, (ORD & ~4), PW, FG>(a, lds, st);
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_gemm_pp2_kernel<MASK, F16, ABL, SK, ORD, PW, FG>,
+    hipError_t e = hipFuncSetAttribute((const void*)conv_gemm_pp2_kernel<MASK, F16, SK, ORD, PW, FG>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) {
       dv3_set_error("conv_gemm_pp2: hipFuncSetAttribute: %s", hipGetErrorString(e));
@@ -890,7 +810,7 @@ int launch_pp2(const ConvArgs& a, size_t lds, hipStream_t st) {
   }
   if ((ORD & 4) != 0) lds += 8 * 256;   // the prefetch strip
   else if ((ORD & 64) != 0) lds += 32;   // two spare units behind the activation buffers
-  hipLaunchKernelGGL((conv_gemm_pp2_kernel<MASK, F16, ABL, SK, ORD, PW, FG>), dim3(a.n_blocks), dim3(NT), lds, st, a);
+  hipLaunchKernelGGL((conv_gemm_pp2_kernel<MASK, F16, SK, ORD, PW, FG>), dim3(a.n_blocks), dim3(NT), lds, st, a);
   return dv3_check_launch("conv_gemm_pp2");
 }
 
@@ -898,12 +818,7 @@ int launch_pp2(const ConvArgs& a, size_t lds, hipStream_t st) {
 }  // namespace
 
 #ifndef DV3_PP2_ISA_ONLY
-int dv3_pp2_read_stamps(void* dst, int64_t bytes) {
-  if (bytes <= 0 || bytes > (int64_t)sizeof(unsigned long long) * 8 * PP2_STAMPS * 2) return DV3_EINVAL;
-  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_pp2_stamps), (size_t)bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? DV3_OK : DV3_ELAUNCH;
-}
 extern int g_x3_wide;
-int g_pp2_ord = 0;   // experiment build: dv3_debug_set(29, v) with v outside {0, 17, 81}: further ORD variants of the fp16-pair kernel
 // dv3_debug_set(29 / 31, v): ORD of the unmasked / masked instantiations (0, 17, 81).  Round 5 default 81 (weight
 // fragments first, activation items converted between the MFMAs): bit-identical to ORD 0, measured in one process at the
 // north-star shape (scripts/r5_ship_check.py, profiles/r05_pp2_load_phase.txt): fp16-pair forward 152.3 -> 148.8 us, masked
@@ -911,7 +826,6 @@ int g_pp2_ord = 0;   // experiment build: dv3_debug_set(29, v) with v outside {0
 // (legacy bf16x3 mode) keeps ORD 0: there the compiler contracts the mask multiply differently in the two forms.
 int g_pp2_ord_u = 81, g_pp2_ord_m = 81;
 int g_pp2_fast_tail = 1;   // dv3_debug_set(50, v): interior sub-tiles of a gated launch take the straight-line tail (0 = the guarded tail everywhere)
-int g_pp2_abl = 0;   // dv3_debug_set(13, v): timing-only ablations of the unmasked kernel (1 no MFMAs, 2 no staging, 3 no tail)
 
 // Stream-K (round 4).  A 256 x 256 tile grid rarely divides the 256 CUs: the encoder layers of the benchmark step are 152
 // tiles (41 % of the chip idle for the whole launch), the 512-channel converter layers 808 (3.16 rounds: the last one a
@@ -925,7 +839,6 @@ int g_pp2_sk = 1;            // dv3_debug_set(22, v): 0 never, 1 by the rule abo
                              // 3 by the rule in both directions
 int g_pp2_sk_overhead = 2;   // dv3_debug_set(23, v)
 int g_pp2_sk_gain = 80;      // dv3_debug_set(24, v)
-int g_pp2_sk_abl = 0;        // dv3_debug_set(26, v): timing-only ablations (1 no hand-over stores, 2 no hand-over loads, 4 no wait)
 static int pp2_cu_count() {
   static int n = 0;
   if (!n) {
@@ -969,9 +882,9 @@ int dv3_conv_gemm_pp2_dispatch(const dv3_conv_desc* d, hipStream_t st) {
     // tile per workgroup, the default LOAD-phase structure (ORD 81)
     if (mask || f16) return 1;
     g_dv3_last_conv += (d->x_pair ? 5 : 0) + (d->pg ? 10 : 0);   // ...106 pair-word staging, 111 fused gate backward, 116 both
-    if (d->pg) return d->x_pair ? launch_pp2<false, false, 0, false, 81, true, true>(a, lds, st)
-                                : launch_pp2<false, false, 0, false, 81, false, true>(a, lds, st);
-    return launch_pp2<false, false, 0, false, 81, true>(a, lds, st);
+    if (d->pg) return d->x_pair ? launch_pp2<false, false, false, 81, true, true>(a, lds, st)
+                                : launch_pp2<false, false, false, 81, false, true>(a, lds, st);
+    return launch_pp2<false, false, false, 81, true>(a, lds, st);
   }
   {
     const int P = pp2_cu_count(), S = d->Cin / BKC;
@@ -987,7 +900,6 @@ int dv3_conv_gemm_pp2_dispatch(const dv3_conv_desc* d, hipStream_t st) {
     const int q = P / 8;
     const bool grp_ok = (P % 8) == 0 && q > 0 && (q & (q - 1)) == 0 && nb >= 8;
     if (ws_ok && dir_ok && grp_ok && g_pp2_sk && (S & (S - 1)) == 0 && (a.m_tiles & (a.m_tiles - 1)) == 0 && units >= 2 * P && (g_pp2_sk == 2 || sk * 100 < dp * g_pp2_sk_gain)) {
-      a.sk_abl = g_pp2_sk_abl;
       a.sk_units = (int)units;
       a.sk_tg = (int)(nb / 8);
       a.sk_tr = (int)(nb % 8);
@@ -1004,59 +916,27 @@ int dv3_conv_gemm_pp2_dispatch(const dv3_conv_desc* d, hipStream_t st) {
       a.sk_ws = reinterpret_cast<float*>(reinterpret_cast<char*>(d->sk_ws) + (size_t)P * 64);
       g_dv3_last_conv += 1;                            // ...102: stream-K form
       const size_t lds_sk = lds;
-      if (f16) return mask ? launch_pp2<true, true, 0, true>(a, lds_sk, st) : launch_pp2<false, true, 0, true>(a, lds_sk, st);
-      return mask ? launch_pp2<true, false, 0, true>(a, lds_sk, st) : launch_pp2<false, false, 0, true>(a, lds_sk, st);
+      if (f16) return mask ? launch_pp2<true, true, true>(a, lds_sk, st) : launch_pp2<false, true, true>(a, lds_sk, st);
+      return mask ? launch_pp2<true, false, true>(a, lds_sk, st) : launch_pp2<false, false, true>(a, lds_sk, st);
     }
   }
   {
     // LOAD-phase structure (ORD, see the kernel): measured variants, selectable at run time (dv3_debug_set(29, v) for the
-    // unmasked instantiations, (31, v) for the masked ones); anything else needs the experiment build
+    // unmasked instantiations, (31, v) for the masked ones)
     const int o = mask ? (f16 ? g_pp2_ord_m : 0) : g_pp2_ord_u;
 #define DV3_PP2_ORD_SHIP(oo) \
     if (o == oo) { \
-      if (f16) return mask ? launch_pp2<true, true, 0, false, oo>(a, lds, st) : launch_pp2<false, true, 0, false, oo>(a, lds, st); \
-      return mask ? launch_pp2<true, false, 0, false, oo>(a, lds, st) : launch_pp2<false, false, 0, false, oo>(a, lds, st); \
+      if (f16) return mask ? launch_pp2<true, true, false, oo>(a, lds, st) : launch_pp2<false, true, false, oo>(a, lds, st); \
+      return mask ? launch_pp2<true, false, false, oo>(a, lds, st) : launch_pp2<false, false, false, oo>(a, lds, st); \
     }
     DV3_PP2_ORD_SHIP(17) DV3_PP2_ORD_SHIP(81)
 #undef DV3_PP2_ORD_SHIP
   }
-#ifdef DV3_EXPERIMENTS
-  if (g_pp2_ord && f16) {
-    switch (g_pp2_ord) {
-#define DV3_PP2_ORD_CASE(o) case o: return mask ? launch_pp2<true, true, 0, false, o>(a, lds, st) : launch_pp2<false, true, 0, false, o>(a, lds, st);
-#define DV3_PP2_ORD_CASE_U(o) case o: if (!mask) return launch_pp2<false, true, 0, false, o>(a, lds, st); break;
-      DV3_PP2_ORD_CASE_U(1) DV3_PP2_ORD_CASE_U(2) DV3_PP2_ORD_CASE_U(3) DV3_PP2_ORD_CASE_U(4) DV3_PP2_ORD_CASE_U(5) DV3_PP2_ORD_CASE_U(7)
-      DV3_PP2_ORD_CASE_U(10) DV3_PP2_ORD_CASE_U(11) DV3_PP2_ORD_CASE_U(15)
-      DV3_PP2_ORD_CASE(19) DV3_PP2_ORD_CASE(27) DV3_PP2_ORD_CASE(31) DV3_PP2_ORD_CASE(32) DV3_PP2_ORD_CASE(49) DV3_PP2_ORD_CASE(64) DV3_PP2_ORD_CASE(65)
-#undef DV3_PP2_ORD_CASE_U
-#undef DV3_PP2_ORD_CASE
-    }
-  }
-  if (g_pp2_abl && !mask && f16) {
-    switch (g_pp2_abl) {
-      case 1: return launch_pp2<false, true, 1>(a, lds, st);
-      case 2: return launch_pp2<false, true, 2>(a, lds, st);
-      case 3: return launch_pp2<false, true, 3>(a, lds, st);
-      case 4: return launch_pp2<false, true, 4>(a, lds, st);
-      case 5: return launch_pp2<false, true, 5>(a, lds, st);
-      case 6: return launch_pp2<false, true, 6>(a, lds, st);
-      case 7: return launch_pp2<false, true, 7>(a, lds, st);
-      case 8: return launch_pp2<false, true, 8>(a, lds, st);
-      case 9: return launch_pp2<false, true, 9>(a, lds, st);
-      case 10: return launch_pp2<false, true, 10>(a, lds, st);
-      case 11: return launch_pp2<false, true, 11>(a, lds, st);   // EXPERIMENT: weight panels by LDS-DMA (see dma_A_unit)
-      case 12: return launch_pp2<false, true, 12>(a, lds, st);   // tail without the residual load
-      case 13: return launch_pp2<false, true, 13>(a, lds, st);   // tail without the stores
-      case 14: return launch_pp2<false, true, 12, false, 32>(a, lds, st);   // ... the same two of the 16-byte tail
-      case 15: return launch_pp2<false, true, 13, false, 32>(a, lds, st);
-    }
-  }
-#endif
   if (f16) return mask ? launch_pp2<true, true>(a, lds, st) : launch_pp2<false, true>(a, lds, st);
   return mask ? launch_pp2<true, false>(a, lds, st) : launch_pp2<false, false>(a, lds, st);
 }
 #else
 namespace {
-template __global__ void conv_gemm_pp2_kernel<DV3_PP2_ISA_MASK, true, 0, false, DV3_PP2_ISA_ORD>(const ConvArgs);
+template __global__ void conv_gemm_pp2_kernel<DV3_PP2_ISA_MASK, true, false, DV3_PP2_ISA_ORD>(const ConvArgs);
 }
 #endif  // DV3_PP2_ISA_ONLY

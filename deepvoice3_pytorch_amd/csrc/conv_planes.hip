@@ -71,9 +71,6 @@ struct Frags {
   bf16x8 ah[2], al[2], bh[NI], bl[NI];
 };
 
-// ABL: timing-only ablations (dv3_debug_set(6, v); results are wrong): 1 no LDS stores in the steady state,
-// 2 no fragment reads in the steady state, 3 no MFMAs, 4 no epilogue, 5 no global fetches in the steady state,
-// 6 no barriers in the steady state
 // compile-time loop over the taps of one chunk
 template <int JT, typename F>
 __device__ __forceinline__ void steady_chunk(int, F&& f) {
@@ -107,7 +104,7 @@ __device__ __forceinline__ void interleave() {
 #undef DV3_SGB_SLOT
 }
 
-template <int WM, int WN, int NI, int TERMS, bool F16, int ABL = 0, int JT = 0>
+template <int WM, int WN, int NI, int TERMS, bool F16, int JT = 0>
 __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvArgs args) {
   static_assert(!F16 || TERMS == 3, "the fp16 form is the three-term split");
   constexpr int BM = WM * 64, BMH = WM * 32, BN = WN * NI * 32, NT = WM * WN * 64;
@@ -336,33 +333,27 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvA
         cL = (s_begin + 3) / J; jL = (s_begin + 3) - cL * J;
       }
       for (int s = s_begin; s < s_end; ++s) {
-        if (ABL == 9) {   // keep the accumulators in the AccVGPR half of the register file
-#pragma unroll
-          for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) asm volatile("" : "+a"(acc[h][ni]));
-        }
         if (s >= 0) {
           // ---------------- first half: k16 block 0 of step s ----------------
-          if (ABL != 2 && ABL != 8) read_frags(F1, s & 1, cC, jC, 1);
+          read_frags(F1, s & 1, cC, jC, 1);
           fix_frags(F0, jC);
-          if (ABL != 3) mfma(F0);
-          if (ABL != 6 && ABL != 8) __syncthreads();
+          mfma(F0);
+          __syncthreads();
         }
         // ---------------- second half ----------------
-        if (s + 2 < nsteps && ((ABL != 1 && ABL != 8) || s < 0)) {
+        if (s + 2 < nsteps) {
           write_A((s + 2) & 1);
           if (jW == 0) write_X(cW & 1);
         }
-        if (s + 3 < nsteps && ((ABL != 5 && ABL != 8) || s < 0)) {
+        if (s + 3 < nsteps) {
           load_A(cL, jL);
           if (jL == 0) load_X(cL);
         }
         const bool rd = s + 1 >= 0 && s + 1 < nsteps;
-        if (rd && ((ABL != 2 && ABL != 8) || s < 1)) read_frags(F0, (s + 1) & 1, cR, jR, 0);
+        if (rd) read_frags(F0, (s + 1) & 1, cR, jR, 0);
         if (s >= 0) {
           fix_frags(F1, jC);
-          if (ABL != 3) mfma(F1);
+          mfma(F1);
         }
         if (s < 0) __syncthreads();     // warm-up iterations have no first half
         cC = cR; jC = jR;
@@ -377,7 +368,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvA
     // of being issued as a burst in front of them (eight waves bursting 8 reads each stall every wave's MFMA
     // issue behind its own LDS issue: measured +25 us per launch at the north-star shape).
     int s_done = -2;
-    if constexpr (JT > 0 && ABL == 0) {
+    if constexpr (JT > 0) {
       const int ci_lo = JT == 1 ? 2 : 1, ci_hi = nchunks - 2;       // inclusive
       if (J == JT && ci_hi >= ci_lo) {
         generic_steps(-2, ci_lo * JT - 2);
@@ -450,12 +441,10 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvA
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[h][ni][r] *= ds;
       }
-      if ((ABL != 4 && ABL != 8) || acc[0][0][0] + acc[1][NI - 1][7] == 1.2345e30f) {
-        if (TERMS == 1 && (p.io_bf16 & DV3_IO_OUT_C8))
-          conv_epilogue_c8<BM, BMH, NI>(p, acc, gated, mt, wm * 32, lhi, bcol, tcol, okc);
-        else
-          conv_epilogue<BM, BMH, NI, 0, TERMS == 1>(p, acc, gated, mt, wm * 32, lhi, bcol, tcol, okc);
-      }
+      if (TERMS == 1 && (p.io_bf16 & DV3_IO_OUT_C8))
+        conv_epilogue_c8<BM, BMH, NI>(p, acc, gated, mt, wm * 32, lhi, bcol, tcol, okc);
+      else
+        conv_epilogue<BM, BMH, NI, TERMS == 1>(p, acc, gated, mt, wm * 32, lhi, bcol, tcol, okc);
     }
     if (!has_next) break;
     tile = next;
@@ -549,31 +538,12 @@ int g_planes_tile = 0;      // dv3_debug_set(4, v)
 int g_planes_mid_thr = 1;   // dv3_debug_set(8, v): 128x128 tiles once they number v/2 x the CUs, else 128x64 (measured:
                             // 1 -> nyanko bf16 step 13.12 ms, 2 -> 13.25, 4 -> 13.90; scripts/tile_thr_ab.py)
 int g_planes_stagger = -1;  // dv3_debug_set(5, v)
-int g_planes_abl = 0;       // dv3_debug_set(6, v)
-
-#ifdef DV3_EXPERIMENTS
-template <int WM, int WN, int NI, int ABL>
-int launch_planes_abl(const ConvArgs& a, size_t lds, int grid, hipStream_t st) {
-  (void)hipFuncSetAttribute((const void*)conv_planes_kernel<WM, WN, NI, 3, true, ABL>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipLaunchKernelGGL((conv_planes_kernel<WM, WN, NI, 3, true, ABL>), dim3(grid), dim3(WM * WN * 64), lds, st, a);
-  return dv3_check_launch("conv_planes(abl)");
-}
-
-template <int WM, int WN, int NI, int ABL>
-int launch_planes_abl1(const ConvArgs& a, size_t lds, int grid, hipStream_t st) {    // single-term bf16 (c8) ablations
-  (void)hipFuncSetAttribute((const void*)conv_planes_kernel<WM, WN, NI, 1, false, ABL>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipLaunchKernelGGL((conv_planes_kernel<WM, WN, NI, 1, false, ABL>), dim3(grid), dim3(WM * WN * 64), lds, st, a);
-  return dv3_check_launch("conv_planes(abl)");
-}
-#endif
 
 template <int WM, int WN, int NI, int TERMS, bool F16, int JT>
 int launch_planes_j(const ConvArgs& a, size_t lds, int grid, hipStream_t st) {
   static bool attr_set = false;  // raise the dynamic-LDS cap once per instantiation
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_planes_kernel<WM, WN, NI, TERMS, F16, 0, JT>,
+    hipError_t e = hipFuncSetAttribute((const void*)conv_planes_kernel<WM, WN, NI, TERMS, F16, JT>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) {
       dv3_set_error("conv_planes: hipFuncSetAttribute: %s", hipGetErrorString(e));
@@ -581,7 +551,7 @@ int launch_planes_j(const ConvArgs& a, size_t lds, int grid, hipStream_t st) {
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL((conv_planes_kernel<WM, WN, NI, TERMS, F16, 0, JT>), dim3(grid), dim3(WM * WN * 64), lds, st, a);
+  hipLaunchKernelGGL((conv_planes_kernel<WM, WN, NI, TERMS, F16, JT>), dim3(grid), dim3(WM * WN * 64), lds, st, a);
   return dv3_check_launch("conv_planes");
 }
 // dv3_debug_set(7, v): the unrolled steady state with the issue-order requests: 0 off, 1 on, -1 (default) = on for the
@@ -598,32 +568,6 @@ int launch_planes_t(const ConvArgs& a, size_t lds, int grid, hipStream_t st) {
 }
 template <int WM, int WN, int NI>
 int launch_planes(const ConvArgs& a, size_t lds, int grid, hipStream_t st) {
-#ifdef DV3_EXPERIMENTS
-  if (g_planes_abl && a.d.split_terms == DV3_SPLIT_F16X3 && NI == 2) {
-    switch (g_planes_abl) {
-      case 1: return launch_planes_abl<WM, WN, NI, 1>(a, lds, grid, st);
-      case 2: return launch_planes_abl<WM, WN, NI, 2>(a, lds, grid, st);
-      case 3: return launch_planes_abl<WM, WN, NI, 3>(a, lds, grid, st);
-      case 4: return launch_planes_abl<WM, WN, NI, 4>(a, lds, grid, st);
-      case 5: return launch_planes_abl<WM, WN, NI, 5>(a, lds, grid, st);
-      case 6: return launch_planes_abl<WM, WN, NI, 6>(a, lds, grid, st);
-      case 7: return launch_planes_abl<WM, WN, NI, 7>(a, lds, grid, st);
-      case 8: return launch_planes_abl<WM, WN, NI, 8>(a, lds, grid, st);
-      case 9: return launch_planes_abl<WM, WN, NI, 9>(a, lds, grid, st);
-    }
-  }
-  if (g_planes_abl && a.d.split_terms == 1 && NI == 2) {
-    switch (g_planes_abl) {
-      case 1: return launch_planes_abl1<WM, WN, NI, 1>(a, lds, grid, st);
-      case 2: return launch_planes_abl1<WM, WN, NI, 2>(a, lds, grid, st);
-      case 3: return launch_planes_abl1<WM, WN, NI, 3>(a, lds, grid, st);
-      case 4: return launch_planes_abl1<WM, WN, NI, 4>(a, lds, grid, st);
-      case 5: return launch_planes_abl1<WM, WN, NI, 5>(a, lds, grid, st);
-      case 6: return launch_planes_abl1<WM, WN, NI, 6>(a, lds, grid, st);
-      case 8: return launch_planes_abl1<WM, WN, NI, 8>(a, lds, grid, st);
-    }
-  }
-#endif
   if (a.d.split_terms == DV3_SPLIT_F16X3) return launch_planes_t<WM, WN, NI, 3, true>(a, lds, grid, st);
   if (a.d.split_terms == 1) return launch_planes_t<WM, WN, NI, 1, false>(a, lds, grid, st);
   return launch_planes_t<WM, WN, NI, 3, false>(a, lds, grid, st);
@@ -756,7 +700,6 @@ int dv3_conv_planes_dispatch(const dv3_conv_desc* d, hipStream_t st) {
 int dv3_planes_debug_set(int what, int value) {
   if (what == 4) g_planes_tile = value;
   if (what == 5) g_planes_stagger = value;
-  if (what == 6) g_planes_abl = value;
   if (what == 7) g_planes_steady = value;
   if (what == 8) g_planes_mid_thr = value;
   return DV3_OK;

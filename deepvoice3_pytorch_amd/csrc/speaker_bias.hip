@@ -83,7 +83,6 @@ __global__ __launch_bounds__(NT) void spk_fwd_kernel(const SpkArgs a) {
 // LDS: gp rows 264 floats apart, the embedding as [frame][17] (conflict-free for the access patterns below); the four
 // partial dW tiles go through the gp tile's own storage once it has been consumed: 53 KB, three workgroups per CU.
 constexpr int GPL = NT + 8, EVL = EM + 1;
-template <int ABL>
 __global__ __launch_bounds__(NT) void spk_bwd_kernel(const SpkArgs a, float* __restrict__ part, float* __restrict__ de_l, const int g_prefetch) {
   __shared__ __attribute__((aligned(16))) float Ws[CB * EM];
   __shared__ __attribute__((aligned(16))) float gp[CB * GPL];
@@ -123,13 +122,13 @@ __global__ __launch_bounds__(NT) void spk_bwd_kernel(const SpkArgs a, float* __r
       const int i = wave + r * (NT / 64), c = c0 + i;
       const float* po = L.out + ((int64_t)b * C + c) * T + t0 + f0;
       const float* pd = L.dout + (int64_t)b * L.dout_bs + (int64_t)c * L.dout_rs + t0 + f0;
-      if (i < n && ABL != 3 && t0 + f0 + 3 < T) {
+      if (i < n && t0 + f0 + 3 < T) {
         yv[r] = *reinterpret_cast<const f32x4u*>(po);
         if (!c8) dv_[r] = *reinterpret_cast<const f32x4u*>(pd);
       } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          const bool ok = i < n && ABL != 3 && t0 + f0 + k < T;
+          const bool ok = i < n && t0 + f0 + k < T;
           yv[r][k] = ok ? po[k] : 1.0f;
           if (!c8) dv_[r][k] = ok ? pd[k] : 0.f;
         }
@@ -141,7 +140,7 @@ __global__ __launch_bounds__(NT) void spk_bwd_kernel(const SpkArgs a, float* __r
       const unsigned short* base = reinterpret_cast<const unsigned short*>(L.dout);
 #pragma unroll
       for (int g = 0; g < CB / 8; ++g) {
-        const bool ok = c0 + 8 * g < C && t < T && ABL != 3;
+        const bool ok = c0 + 8 * g < C && t < T;
         raw[g] = ok ? *reinterpret_cast<const u16x8*>(base + (((int64_t)b * L.dout_c8p + (c0 >> 3) + g) * T + t) * 8)
                     : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
       }
@@ -182,44 +181,40 @@ __global__ __launch_bounds__(NT) void spk_bwd_kernel(const SpkArgs a, float* __r
     if (g_prefetch && c0 + CB < C) load_tile(c0 + CB);        // in flight during this tile's products
     __syncthreads();
     // d emb: D[e][frame] += sum_rows W[row][e] * gp[row][frame];  A[i = e][k = row], B[k = row][j = frame]
-    if (ABL != 2) {
 #pragma unroll
-      for (int k0 = 0; k0 < CB; k0 += 2) {
-        const float av = l31 < EM ? Ws[(k0 + lhi) * EM + l31] : 0.f;
+    for (int k0 = 0; k0 < CB; k0 += 2) {
+      const float av = l31 < EM ? Ws[(k0 + lhi) * EM + l31] : 0.f;
 #pragma unroll
-        for (int jb = 0; jb < 2; ++jb) {
-          const float bv = gp[(k0 + lhi) * GPL + wave * 64 + jb * 32 + l31];
-          dacc[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, dacc[jb], 0, 0, 0);
-        }
+      for (int jb = 0; jb < 2; ++jb) {
+        const float bv = gp[(k0 + lhi) * GPL + wave * 64 + jb * 32 + l31];
+        dacc[jb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, dacc[jb], 0, 0, 0);
       }
     }
     // dW (+ db): P[row][col] = sum over this wave's 64 frames of gp[row][frame] * emb[frame][col];  A[i = row][k = frame],
     // B[k = frame][j = col], col 16 = ones
-    if (ABL != 1) {
-      f32x16 wacc;
+    f32x16 wacc;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) wacc[r] = 0.f;
+    for (int r = 0; r < 16; ++r) wacc[r] = 0.f;
 #pragma unroll 8
-      for (int k0 = 0; k0 < 64; k0 += 2) {
-        const int f = wave * 64 + k0 + lhi;
-        const float av = gp[l31 * GPL + f];
-        const float bv = l31 <= EM ? evs[f * EVL + l31] : 0.f;
-        wacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, wacc, 0, 0, 0);
-      }
-      __syncthreads();                       // every wave has read the gp tile for both products
-      float* red = gp;                       // [wave][16 registers][64 lanes] = 16 KB of the tile's 33 KB
+    for (int k0 = 0; k0 < 64; k0 += 2) {
+      const int f = wave * 64 + k0 + lhi;
+      const float av = gp[l31 * GPL + f];
+      const float bv = l31 <= EM ? evs[f * EVL + l31] : 0.f;
+      wacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, wacc, 0, 0, 0);
+    }
+    __syncthreads();                       // every wave has read the gp tile for both products
+    float* red = gp;                       // [wave][16 registers][64 lanes] = 16 KB of the tile's 33 KB
 #pragma unroll
-      for (int r = 0; r < 16; ++r) red[(wave * 16 + r) * 64 + lane] = wacc[r];
-      __syncthreads();
-      // C/D layout: register r of lane (l31, lhi) is P[row = (r & 3) + 8 (r >> 2) + 4 lhi][col = l31]; 32 rows x 17 columns
-      // = 544 sums of the four waves' tiles, in wave order
-      for (int idx = tid; idx < CB * (EM + 1); idx += NT) {
-        const int row = idx / (EM + 1), col = idx - row * (EM + 1);
-        const int r = (row & 3) + 4 * (row >> 3), hi = (row >> 2) & 1;
-        const float* q = red + r * 64 + hi * 32 + col;
-        const float v = ((q[0] + q[16 * 64]) + q[2 * 16 * 64]) + q[3 * 16 * 64];
-        if (row < n) part[(((int64_t)a.row0[l] + c0 + row) * n_blocks + blk) * (EM + 1) + col] = v;
-      }
+    for (int r = 0; r < 16; ++r) red[(wave * 16 + r) * 64 + lane] = wacc[r];
+    __syncthreads();
+    // C/D layout: register r of lane (l31, lhi) is P[row = (r & 3) + 8 (r >> 2) + 4 lhi][col = l31]; 32 rows x 17 columns
+    // = 544 sums of the four waves' tiles, in wave order
+    for (int idx = tid; idx < CB * (EM + 1); idx += NT) {
+      const int row = idx / (EM + 1), col = idx - row * (EM + 1);
+      const int r = (row & 3) + 4 * (row >> 3), hi = (row >> 2) & 1;
+      const float* q = red + r * 64 + hi * 32 + col;
+      const float v = ((q[0] + q[16 * 64]) + q[2 * 16 * 64]) + q[3 * 16 * 64];
+      if (row < n) part[(((int64_t)a.row0[l] + c0 + row) * n_blocks + blk) * (EM + 1) + col] = v;
     }
   }
   // d emb out of the C/D layout: rows = e (registers 0..3 and 4..7 of each half: e = (r & 3) + 8 (r >> 2) + 4 lhi < 16)
@@ -306,7 +301,6 @@ int fill_args(SpkArgs& a, const dv3_spk_desc* d, const dv3_spk_layer* layers, bo
 }  // namespace
 
 int g_spk_prefetch = 1;   // dv3_debug_set(54, v): the backward's tile loads one tile ahead (0 = at the top of the tile)
-int g_spk_abl = 0;   // dv3_debug_set(28, v): timing-only ablations of the backward (1 no dW, 2 no d emb, 3 no loads); make EXP=1
 
 extern "C" int dv3_speaker_bias_fwd_f32(const dv3_spk_desc* d, const dv3_spk_layer* layers, void* stream) {
   SpkArgs a;
@@ -347,16 +341,7 @@ extern "C" int dv3_speaker_bias_bwd_f32(const dv3_spk_desc* d, const dv3_spk_lay
   float* part = d->scratch;
   float* de_l = d->scratch + rows * d->B * nT * (EM + 1);
   hipStream_t st = (hipStream_t)stream;
-#ifdef DV3_EXPERIMENTS
-  switch (g_spk_abl) {
-    case 1: hipLaunchKernelGGL(spk_bwd_kernel<1>, dim3(nT, d->B, d->n_layers), dim3(NT), 0, st, a, part, de_l, g_spk_prefetch); break;
-    case 2: hipLaunchKernelGGL(spk_bwd_kernel<2>, dim3(nT, d->B, d->n_layers), dim3(NT), 0, st, a, part, de_l, g_spk_prefetch); break;
-    case 3: hipLaunchKernelGGL(spk_bwd_kernel<3>, dim3(nT, d->B, d->n_layers), dim3(NT), 0, st, a, part, de_l, g_spk_prefetch); break;
-    default: hipLaunchKernelGGL(spk_bwd_kernel<0>, dim3(nT, d->B, d->n_layers), dim3(NT), 0, st, a, part, de_l, g_spk_prefetch);
-  }
-#else
-  hipLaunchKernelGGL(spk_bwd_kernel<0>, dim3(nT, d->B, d->n_layers), dim3(NT), 0, st, a, part, de_l, g_spk_prefetch);
-#endif
+  hipLaunchKernelGGL(spk_bwd_kernel, dim3(nT, d->B, d->n_layers), dim3(NT), 0, st, a, part, de_l, g_spk_prefetch);
   int rc2 = dv3_check_launch("speaker_bias_bwd");
   if (rc2 != DV3_OK) return rc2;
   hipLaunchKernelGGL(spk_finish_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a, (const float*)part, d->B * nT);

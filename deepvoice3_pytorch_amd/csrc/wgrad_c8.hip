@@ -335,7 +335,7 @@ __device__ __forceinline__ bf16x8 lds_tr8(const unsigned char* base, int byte_of
   return __builtin_bit_cast(bf16x8, v);
 }
 
-template <int JT, bool MASK, int NXU, bool IL = false, int ABL = 0, bool PAIR = false>
+template <int JT, bool MASK, int NXU, bool IL = false, bool PAIR = false>
 __global__ __launch_bounds__(512) void wgrad_c8_tr_kernel(const WgradC8TrArgs args) {
   static_assert(!IL || JT == 3, "interleaved staging: the three-tap form");
   static_assert(NXU >= 1 && NXU <= 3, "x units a thread stages: 16 * window <= 512 NXU");
@@ -476,9 +476,9 @@ __global__ __launch_bounds__(512) void wgrad_c8_tr_kernel(const WgradC8TrArgs ar
     __syncthreads();
     auto step = [&](int st, auto set_c) __attribute__((always_inline)) {
       if constexpr (!IL) {
-        if constexpr (ABL != 1) mfma_step(st & BMSK);
-        if constexpr (ABL != 2) write_step(st + DST, (st + DST) & BMSK, set_c);     // past the end: a re-fetched tile into a buffer nobody reads
-        if constexpr (ABL != 3) load_step(st + 2 + DST, set_c);
+        mfma_step(st & BMSK);
+        write_step(st + DST, (st + DST) & BMSK, set_c);     // past the end: a re-fetched tile into a buffer nobody reads
+        load_step(st + 2 + DST, set_c);
       } else {
         // the step as six fenced segments, [two MFMAs of one (k16 block, tap)] [the fragment reads of the next segment]
         // [a piece of the next tile's staging], as wgrad_c8_kernel's IL form; per accumulator the k16 blocks are added in
@@ -561,27 +561,26 @@ __global__ __launch_bounds__(512) void wgrad_c8_tr_kernel(const WgradC8TrArgs ar
   }
 }
 
-template <int JT, bool MASK, int NXU, bool IL = false, int ABL = 0, bool PAIR = false>
+template <int JT, bool MASK, int NXU, bool IL = false, bool PAIR = false>
 int launch_c8_tr(const WgradC8TrArgs& a, int64_t nb, hipStream_t st) {
   const size_t lds = (size_t)(PAIR ? 4 : 2) * (16 * 36 + 16 * a.twx) * 16 + 256 * 16;   // the buffers, keep table
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)wgrad_c8_tr_kernel<JT, MASK, NXU, IL, ABL, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute((const void*)wgrad_c8_tr_kernel<JT, MASK, NXU, IL, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) {
       dv3_set_error("wgrad_c8: hipFuncSetAttribute: %s", hipGetErrorString(e));
       return DV3_ELAUNCH;
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL((wgrad_c8_tr_kernel<JT, MASK, NXU, IL, ABL, PAIR>), dim3((unsigned)nb), dim3(512), lds, st, a);
+  hipLaunchKernelGGL((wgrad_c8_tr_kernel<JT, MASK, NXU, IL, PAIR>), dim3((unsigned)nb), dim3(512), lds, st, a);
   return dv3_check_launch("wgrad_c8_tr");
 }
 
 }  // namespace
 
 // dv3_debug_set(52, v): operand fragments by ds_read_b64_tr_b16 from the untransposed tile -- 0 = the register-transposing
-// forms, 1 = plain, 2 = staging between the MFMAs, 3 = one barrier per two K steps, 4 = both (default; one tap: as 3),
-// 11..13 = timing ablations (no MFMAs / no LDS writes / no global loads)
+// forms, 1 = plain, 2 = staging between the MFMAs, 3 = one barrier per two K steps, 4 = both (default; one tap: as 3)
 int g_wgrad_c8_tr = 4;
 int g_wgrad_c8_il = 1;    // dv3_debug_set(49, v): the three-tap form stages the next tile between the MFMAs (0 = after them)
 int g_wgrad_c8_pf2 = 1;   // dv3_debug_set(20, v): 1 = operands fetched two steps ahead (default), 0 = the round-2 one-step form
@@ -609,24 +608,19 @@ int dv3_wgrad_c8_dispatch(const dv3_wgrad_desc* d, hipStream_t st) {
     for (t.twx = wx; (t.twx & 15) != 4 && (t.twx & 15) != 12; ++t.twx) {}
     g_dv3_last_wgrad = 5100 + d->J;       // 5101 / 5103: fragments by the transposing LDS read
     const bool wide = 16 * wx > 1024;     // a third x unit per thread (dilation 27)
-    if (d->J == 3 && d->xmask_c8 && !wide && g_wgrad_c8_tr >= 11 && g_wgrad_c8_tr <= 13) {     // ablations (timing only)
-      if (g_wgrad_c8_tr == 11) return launch_c8_tr<3, true, 2, false, 1>(t, nb, st);
-      if (g_wgrad_c8_tr == 12) return launch_c8_tr<3, true, 2, false, 2>(t, nb, st);
-      return launch_c8_tr<3, true, 2, false, 3>(t, nb, st);
-    }
     if (d->J == 3 && (g_wgrad_c8_tr == 3 || g_wgrad_c8_tr == 4)) {
       const bool il = g_wgrad_c8_tr == 4;
       g_dv3_last_wgrad += il ? 240 : 200;             // 5303 / 5343: one barrier per two K steps
       if (wide) {
-        if (il) return d->xmask_c8 ? launch_c8_tr<3, true, 3, true, 0, true>(t, nb, st) : launch_c8_tr<3, false, 3, true, 0, true>(t, nb, st);
-        return d->xmask_c8 ? launch_c8_tr<3, true, 3, false, 0, true>(t, nb, st) : launch_c8_tr<3, false, 3, false, 0, true>(t, nb, st);
+        if (il) return d->xmask_c8 ? launch_c8_tr<3, true, 3, true, true>(t, nb, st) : launch_c8_tr<3, false, 3, true, true>(t, nb, st);
+        return d->xmask_c8 ? launch_c8_tr<3, true, 3, false, true>(t, nb, st) : launch_c8_tr<3, false, 3, false, true>(t, nb, st);
       }
-      if (il) return d->xmask_c8 ? launch_c8_tr<3, true, 2, true, 0, true>(t, nb, st) : launch_c8_tr<3, false, 2, true, 0, true>(t, nb, st);
-      return d->xmask_c8 ? launch_c8_tr<3, true, 2, false, 0, true>(t, nb, st) : launch_c8_tr<3, false, 2, false, 0, true>(t, nb, st);
+      if (il) return d->xmask_c8 ? launch_c8_tr<3, true, 2, true, true>(t, nb, st) : launch_c8_tr<3, false, 2, true, true>(t, nb, st);
+      return d->xmask_c8 ? launch_c8_tr<3, true, 2, false, true>(t, nb, st) : launch_c8_tr<3, false, 2, false, true>(t, nb, st);
     }
     if (d->J == 1 && (g_wgrad_c8_tr == 3 || g_wgrad_c8_tr == 4)) {
       g_dv3_last_wgrad += 200;
-      return d->xmask_c8 ? launch_c8_tr<1, true, 1, false, 0, true>(t, nb, st) : launch_c8_tr<1, false, 1, false, 0, true>(t, nb, st);
+      return d->xmask_c8 ? launch_c8_tr<1, true, 1, false, true>(t, nb, st) : launch_c8_tr<1, false, 1, false, true>(t, nb, st);
     }
     if (d->J == 3 && g_wgrad_c8_tr == 2) {
       g_dv3_last_wgrad += 40;             // 5143: staging between the MFMAs

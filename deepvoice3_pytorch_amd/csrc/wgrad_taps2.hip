@@ -125,10 +125,10 @@ __device__ __forceinline__ uint32_t wt2_valid_n(int t, int len, int n) {
 // ~246 and spilled).  The rare paths that branch (re-alignment at the tensor's two ends, the validity mask of a g unit
 // in a row tail) run BEFORE the interleaved region -- a branch would cut the scheduling region -- and the x window's
 // validity / keep mask is applied unconditionally (it is two instructions per element).  Same values: bit-identical slabs.
-template <bool MASK, int ABL = 0, bool GP = false, int DIL = 0, bool IL = false>
+template <bool MASK, bool GP = false, int DIL = 0, bool IL = false>
 __global__ __launch_bounds__(NT) void wgrad_taps2_kernel(const WgradT2Args args) {
   static_assert(DIL == 0 || DIL == 1 || DIL == 3, "window form: d = 1 or 3");
-  static_assert(!IL || (DIL > 0 && ABL == 0), "interleaved staging: the window forms");
+  static_assert(!IL || DIL > 0, "interleaved staging: the window forms");
   constexpr int WLEN = 8 + 2 * DIL;                 // elements of the window of one unit
   constexpr int NW4 = (WLEN + 3) / 4;               // 16-byte loads per window
   constexpr int WL = DIL > 0 ? 4 * NW4 : 1;
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(NT) void wgrad_taps2_kernel(const WgradT2Args args)
     const bf16x8* GsL = GsH + KB * LDM;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      if (ks == 1 && ABL != 6) __builtin_amdgcn_sched_barrier(0);   // one k16 block's ten fragments live at a time
+      if (ks == 1) __builtin_amdgcn_sched_barrier(0);   // one k16 block's ten fragments live at a time
       const int k8 = 2 * ks + lhi;
       const int ai = k8 * LDM + wm * 64 + l31;
       const bf16x8 ah0 = GsH[ai], ah1 = GsH[ai + 32];
@@ -518,11 +518,9 @@ __global__ __launch_bounds__(NT) void wgrad_taps2_kernel(const WgradT2Args args)
 
     // steps in pairs so the register-set index is static: step st + 1 is staged from set (st + 1) & 1
     auto step = [&](int st, auto set_c) __attribute__((always_inline)) {
-      if (ABL != 1) mfma_step(st & 1);
-      if (ABL != 2) {
-        write_step(st + 1, (st + 1) & 1, set_c);      // past the end: a re-fetched tile into the buffer nobody reads
-        load_step(st + 3, set_c);
-      }
+      mfma_step(st & 1);
+      write_step(st + 1, (st + 1) & 1, set_c);      // past the end: a re-fetched tile into the buffer nobody reads
+      load_step(st + 3, set_c);
       __syncthreads();
     };
     for (int st = 0; st < nsteps; st += 2) {
@@ -548,12 +546,12 @@ __global__ __launch_bounds__(NT) void wgrad_taps2_kernel(const WgradT2Args args)
   }
 }
 
-template <bool MASK, int ABL = 0, bool GP = false, int DIL = 0, bool IL = false>
+template <bool MASK, bool GP = false, int DIL = 0, bool IL = false>
 int launch_wgrad_taps2(const WgradT2Args& a, int64_t nb, hipStream_t st) {
   constexpr size_t lds = (size_t)2 * BUF * 16;
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)wgrad_taps2_kernel<MASK, ABL, GP, DIL, IL>,
+    hipError_t e = hipFuncSetAttribute((const void*)wgrad_taps2_kernel<MASK, GP, DIL, IL>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) {
       dv3_set_error("wgrad_taps2: hipFuncSetAttribute: %s", hipGetErrorString(e));
@@ -561,7 +559,7 @@ int launch_wgrad_taps2(const WgradT2Args& a, int64_t nb, hipStream_t st) {
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL((wgrad_taps2_kernel<MASK, ABL, GP, DIL, IL>), dim3((unsigned)nb), dim3(NT), lds, st, a);
+  hipLaunchKernelGGL((wgrad_taps2_kernel<MASK, GP, DIL, IL>), dim3((unsigned)nb), dim3(NT), lds, st, a);
   return dv3_check_launch("wgrad_taps2");
 }
 
@@ -569,7 +567,6 @@ int launch_wgrad_taps2(const WgradT2Args& a, int64_t nb, hipStream_t st) {
 
 int g_wgrad_t2_il = 1;       // dv3_debug_set(48, v): the window forms stage the next tile between the MFMAs (0 = after them)
 int g_wgrad_t2_window = 1;   // dv3_debug_set(47, v): the one-window-for-three-taps form of d = 1 / 3 launches (0 = the per-tap form)
-int g_wgrad_t2_abl = 0;   // dv3_debug_set(16, v): timing-only ablations (1 no MFMAs, 2 no staging, 6 k16 blocks not pinned apart)
 
 // three taps, three-term split, K split over contiguous ranges (called by dv3_wgrad_gemm_bf16x3_dispatch)
 int dv3_wgrad_taps2_dispatch(const dv3_wgrad_desc* d, hipStream_t st) {
@@ -580,24 +577,15 @@ int dv3_wgrad_taps2_dispatch(const dv3_wgrad_desc* d, hipStream_t st) {
   const int64_t nb = (int64_t)a.m_tiles * a.c_tiles * d->n_slabs;
   DV3_REQUIRE(nb < (1ll << 31), "wgrad_gemm: grid too large");
   g_dv3_last_wgrad = 3000 + 40;
-#ifdef DV3_EXPERIMENTS
-  if (g_wgrad_t2_abl && !d->xmask) {
-    switch (g_wgrad_t2_abl) {
-      case 1: return launch_wgrad_taps2<false, 1>(a, nb, st);
-      case 2: return launch_wgrad_taps2<false, 2>(a, nb, st);
-      case 6: return launch_wgrad_taps2<false, 6>(a, nb, st);
-    }
-  }
-#endif
   // window form (kernel template DIL): d = 1 or 3, a tensor long enough for the window's loads
   const int win = (g_wgrad_t2_window && (d->dil == 1 || d->dil == 3) &&
                    (int64_t)(d->B - 1) * d->x_bs + (int64_t)(d->Cin - 1) * d->x_rs + d->Tin >= 16) ? d->dil : 0;
   const bool il = win && g_wgrad_t2_il;
   g_dv3_last_wgrad += (d->g_pair ? 1 : 0) + (win ? 2 : 0) + (il ? 4 : 0);   // ...41 pair-word g, 42 window form, 43 both; +4 interleaved staging
 #define DV3_T2(M, G) \
-  (win == 1 ? (il ? launch_wgrad_taps2<M, 0, G, 1, true>(a, nb, st) : launch_wgrad_taps2<M, 0, G, 1>(a, nb, st)) \
-   : win == 3 ? (il ? launch_wgrad_taps2<M, 0, G, 3, true>(a, nb, st) : launch_wgrad_taps2<M, 0, G, 3>(a, nb, st)) \
-   : launch_wgrad_taps2<M, 0, G, 0>(a, nb, st))
+  (win == 1 ? (il ? launch_wgrad_taps2<M, G, 1, true>(a, nb, st) : launch_wgrad_taps2<M, G, 1>(a, nb, st)) \
+   : win == 3 ? (il ? launch_wgrad_taps2<M, G, 3, true>(a, nb, st) : launch_wgrad_taps2<M, G, 3>(a, nb, st)) \
+   : launch_wgrad_taps2<M, G, 0>(a, nb, st))
   if (d->g_pair) return d->xmask ? DV3_T2(true, true) : DV3_T2(false, true);
   return d->xmask ? DV3_T2(true, false) : DV3_T2(false, false);
 #undef DV3_T2

@@ -1,5 +1,6 @@
 # effective shader clock (GRBM_GUI_ACTIVE / kernel duration) and SQ busy/wait split of the planes tap-GEMM variants:
-# full, MFMAs only, no MFMAs -- is the sum-like behaviour a clock (power) effect?
+# (the timing-only ablations this script also ran -- MFMAs only, no MFMAs -- were retired from the library; git history
+# keeps them)
 R=$PWD; mkdir -p $R/gpurun_out; cd /tmp; export TMPDIR=/tmp; export R
 cat > /tmp/pmc_run.py <<'PY'
 import sys, os
@@ -13,11 +14,9 @@ y = torch.empty(B, C, T, device=dev)
 xp = ops.split_planes(x, f16=True)
 kw = dict(B=B, Cin=C, Tin=T, M=2 * C, Tout=T, J=k, dil=1, padL=1, mode=ops.EPI_GLU, Cg=C, bias=bias, r=x, residual=1, a_split=pk.fwd_s, y=y, x_planes=xp)
 lib.dv3_debug_set(4, 9); lib.dv3_debug_set(7, 0)
-for abl in (0, 8, 3):
-    lib.dv3_debug_set(6, abl)
-    for _ in range(60):
-        ops.conv_gemm(x, None, pk.lda, pk.a_half, **kw)
-    torch.cuda.synchronize()
+for _ in range(60):
+    ops.conv_gemm(x, None, pk.lda, pk.a_half, **kw)
+torch.cuda.synchronize()
 PY
 timeout 200 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS --kernel-trace --output-format csv -d $R/gpurun_out/pmc_clock -- python /tmp/pmc_run.py > $R/gpurun_out/pmc_clock.log 2>&1; echo rc=$?
 cd $R; python - <<'PY'

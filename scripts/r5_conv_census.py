@@ -114,34 +114,6 @@ if len(sys.argv) > 4 and sys.argv[4] == "sweep":
             k[0], k[2], k[3], k[4], k[5], k[6], k[7], k[12], c, us, " ".join("%d:%.1f" % (h, t) for h, t in sorted(res.items())),
             best, res[best] / us))
     print("sum over the step of (picked - best forced): %.2f ms" % (gain / 1e3))
-# deep-prefetch form of the 128 x 64 tile (argv[4] == "dp"; dv3_debug_set(43, 0 | 2)): every split-kernel launch as picked,
-# on the 128 x 64 tile in-phase (hint 22), and on the 128 x 64 tile with the register rings
-if len(sys.argv) > 4 and sys.argv[4] == "dp":
-    print("---- deep prefetch: us per launch ----")
-    tot0 = tot1 = 0.0
-    for (k, c, us, mf, hb) in sorted(rows, key=lambda r: -r[1] * r[2]):
-        if k[12] // 1000 not in (3, 5) or k[5] not in (1, 3):
-            continue
-        d = descs[groups[k][0]]
-
-        def fn(d=d):
-            return L.dv3_conv_gemm_f32(ctypes.byref(d), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        res = {}
-        for (hint, dp) in ((0, 0), (22, 0), (22, 2)):
-            d.tile_hint = hint
-            L.dv3_debug_set(43, dp)
-            if fn() != 0:
-                continue
-            res[(hint, dp)] = graph_time(fn, per_graph=20, replays=3)
-        d.tile_hint = 0
-        L.dv3_debug_set(43, 0)
-        best = min(res.values())
-        tot0 += c * res[(0, 0)]
-        tot1 += c * best
-        print("%-7s Cin %4d M %4d T %4d J %d dil %2d m %d var %d x%d: picked %.1f | 128x64 %.1f | 128x64 rings %.1f (%.2f of picked)" % (
-            k[0], k[2], k[3], k[4], k[5], k[6], k[7], k[12], c, res[(0, 0)], res.get((22, 0), -1), res.get((22, 2), -1),
-            res.get((22, 2), 0) / res[(0, 0)]))
-    print("sum over the step: picked %.2f ms, best of the three %.2f ms" % (tot0 / 1e3, tot1 / 1e3))
 # c8 path (argv[4] == "c8"): every single-term c8 launch as picked, forced onto the 8-wave 256 x 256 form (hint 40) and
 # onto two 4-wave workgroups per CU on 256 x 128 tiles (hint 41)
 if len(sys.argv) > 4 and sys.argv[4] == "c8":

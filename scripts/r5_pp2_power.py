@@ -73,13 +73,3 @@ for name in ("randn", "zeros"):
               residual=1, a_split=z, y=y, tile_hint=30)
     t, f = timeit(lambda: ops.conv_gemm(x, None, pk.lda, pk.a_half, **kw))
     print("x = %-10s zero weight image: %.1f us   avg sclk %.0f MHz" % (name, t, f), flush=True)
-if os.environ.get("DV3_LIBPATH", "").endswith("_exp.so"):
-    for name in ("randn", "zeros"):
-        x = xs[name]
-        kw = dict(B=B, Cin=C, Tin=T, M=2 * C, Tout=T, J=k, dil=1, padL=1, mode=ops.EPI_GLU, Cg=C, bias=bias, r=x,
-                  residual=1, a_split=(pk.fwd_s if name == "randn" else z), y=y, tile_hint=30)
-        for abl, an in ((0, "full"), (1, "no MFMAs"), (2, "no staging"), (3, "no tail")):
-            L.dv3_debug_set(13, abl)
-            t, f = timeit(lambda: ops.conv_gemm(x, None, pk.lda, pk.a_half, **kw))
-            print("x = %-6s (w %s) ablation %-12s: %.1f us   avg sclk %.0f MHz" % (name, "randn" if name == "randn" else "zero", an, t, f), flush=True)
-        L.dv3_debug_set(13, 0)

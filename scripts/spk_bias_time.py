@@ -1,6 +1,5 @@
 # coding: utf-8
-"""Time of the fused speaker-bias block kernels (csrc/speaker_bias.hip) at the block shapes of deepvoice3_vctk (B = 64),
-with timing-only ablations of the backward's first pass (dv3_debug_set(28, v): 1 no dW, 2 no d emb, 3 no loads)."""
+"""Time of the fused speaker-bias block kernels (csrc/speaker_bias.hip) at the block shapes of deepvoice3_vctk (B = 64)."""
 import os
 import sys
 import torch
@@ -35,10 +34,6 @@ for (T, Cs) in [(201, (256,) * 10), (150, (512,) * 7), (804, (256,) * 6)]:
     douts = [torch.randn(B, C, T, device=dev) for C in Cs]
     tf = timeit(lambda: ops.speaker_bias_block(e.detach(), layers))
     outs = ops.speaker_bias_block(e, layers)
-    res = []
-    for abl in (0, 1, 2, 3):
-        L.dv3_debug_set(28, abl)
-        res.append("abl %d: %.1f" % (abl, timeit(lambda: torch.autograd.backward(outs, douts, retain_graph=True))))
-    L.dv3_debug_set(28, 0)
+    tb = timeit(lambda: torch.autograd.backward(outs, douts, retain_graph=True))
     mb = sum(B * C * T * 4 for C in Cs) / 1e6
-    print("T=%d layers=%d C=%d (%.0f MB of biases): forward %.1f us | backward (3 launches) %s" % (T, len(Cs), Cs[0], mb, tf, "  ".join(res)), flush=True)
+    print("T=%d layers=%d C=%d (%.0f MB of biases): forward %.1f us | backward (3 launches) %.1f us" % (T, len(Cs), Cs[0], mb, tf, tb), flush=True)

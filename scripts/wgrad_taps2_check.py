@@ -75,9 +75,4 @@ for dil in (1, 27):
                                                split_bf16=True, k_split=True, out=out_t))
             print("dil %2d tile %d (%d slabs): masked %.1f us   unmasked %.1f us" % (dil, tile, S, tm, tu))
 L.dv3_debug_set(2, 4)
-for abl, name in ((0, "full"), (1, "no MFMAs"), (2, "no staging"), (6, "k16 blocks not pinned apart")):
-    L.dv3_debug_set(16, abl)
-    print("ablation %-20s: %.1f us" % (name, timeit(lambda: ops.wgrad_gemm(gm, x, B=B, M=2 * C, Cin=C, T=T, Tin=T, J=k, dil=1, padL=1,
-                                                                            n_slabs=S, split_bf16=True, k_split=True, out=out_t))))
-L.dv3_debug_set(16, 0)
 L.dv3_debug_set(2, 0)

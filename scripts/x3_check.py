@@ -129,11 +129,6 @@ if __name__ == "__main__":
             except RuntimeError as e:
                 print('skip', shape, hint, str(e)[-60:])
     from deepvoice3_pytorch_amd import _lib
-    for abl in ():
-        _lib.call("dv3_debug_set", 1, abl)
-        print("ablation", abl, end=": ")
-        timeit(21, 1)
-    _lib.call("dv3_debug_set", 1, 0)
     for hint in (0, 21, 29, 21, 29):
         for dil in (1, 27):
             timeit(hint, dil)

@@ -43,7 +43,6 @@ def dev():
 
 
 KS_DEFAULT = 1      # dv3_debug_set(44, v): the k-split form of the 128 x 64 tile (conv_gemm_bf16x3.hip): 0 off / 1 by rule / 2 wherever eligible
-DP_DEFAULT = 0      # dv3_debug_set(43, v): the deep-prefetch form of the 128 x 64 tile is off (conv_gemm_bf16x3.hip, experiment build)
 
 
 def _ops():
@@ -672,74 +671,6 @@ def test_256x256_k16_pingpong_tap_gemm_equals_the_128_wide_kernels(dev, gemm_mod
 
 @pytest.mark.parametrize("B,C,T,k,d,causal,masked", [(3, 64, 75, 3, 2, False, True), (2, 256, 150, 3, 27, False, False),
                                                      (2, 128, 100, 3, 1, True, True), (5, 96, 61, 3, 9, False, True),
-                                                     (7, 32, 33, 3, 1, False, False), (4, 160, 201, 1, 1, False, False),
-                                                     (3, 24, 37, 1, 1, False, True), (2, 512, 150, 3, 3, False, True),
-                                                     (16, 256, 201, 1, 1, False, True), (1, 40, 17, 3, 27, True, False)])
-def test_deep_prefetch_form_of_the_128x64_tile_is_bit_identical(dev, gemm_mode, B, C, T, k, d, causal, masked):
-    """conv_gemm_bf16x3.hip, template DPJ (round 5; experiment build, dv3_debug_set(43, 0 | 1 | 2)): the 128 x 64 split tile with its
-    global fetches 3-4 steps ahead through register rings -- same fragment images, same MFMA order, so forward
-    (Conv1dGLU with the pre-gate save and keep-bits, modules.py:145-164), plain 1 x 1 / Linear and the input-gradient
-    form must agree BIT FOR BIT with the in-phase loop; covers 1 and 3 taps, partial chunks (C % 32 != 0), tiles shorter
-    than the rings (C = 24, 32, 40: one or two steps), columns across batch items, and the fp16 range guard staying
-    silent on the rings' virtual steps."""
-    if gemm_mode == "f32":
-        pytest.skip("split-operand kernel test")
-    from deepvoice3_pytorch_amd import ops, _lib
-    L = _lib.lib()
-    if L.dv3_debug_set(43, 2) != 0:
-        pytest.skip("the deep-prefetch form was measured and retired (profiles/r05_deep_prefetch_rings.txt): it is compiled "
-                    "into the experiment build only (make EXP=1, DV3_LIBPATH=.../libdv3hip_exp.so)")
-    L.dv3_debug_set(43, 0)
-    L.dv3_debug_set(44, 0)          # (the rule would give these small grids to the k-split form)
-    torch.manual_seed(C + T)
-    x = torch.randn(B, C, T, device=dev)
-    v = torch.randn(2 * C, C, k, device=dev) * math.sqrt(4.0 * 0.95 / (k * C))
-    g = v.reshape(2 * C, -1).norm(dim=1).view(-1, 1, 1).clone()
-    bias = torch.randn(2 * C, device=dev) * 0.1
-    pk = ops.pack_weights(v, g, glu_cg=C, need_bwd=True)
-    bits = rs = None
-    if masked:
-        ops.dropout_state.manual_seed(3)
-        bits, rs = ops.dropout_bits(B * C, T, 0.05, dev)
-    padL = (k - 1) * d if causal else (k - 1) // 2 * d
-    kw = dict(B=B, Cin=C, Tin=T, M=2 * C, Tout=T, J=k, dil=d, padL=padL, mode=ops.EPI_GLU, Cg=C, bias=bias, r=x,
-              residual=1, a_split=pk.fwd_s, xmask=bits, xmask_rs=rs or 0, drop_scale=1 / 0.95 if masked else 1.0,
-              tile_hint=22)
-    gm = torch.randn(B, 2 * C, T, device=dev)
-    dres = torch.randn(B, C, T, device=dev)
-    dkw = dict(B=B, Cin=2 * C, Tin=T, M=C, Tout=T, J=k, dil=d, padL=(k - 1) * d - padL, mode=ops.EPI_DGRAD,
-               r=dres, ymask=bits, ymask_rs=rs or 0, drop_scale=1 / 0.95 if masked else 1.0, a_split=pk.bwd_s, tile_hint=22)
-    lkw = dict(B=B, Cin=C, Tin=T, M=2 * C, Tout=T, J=k, dil=d, padL=padL, mode=ops.EPI_RELU, bias=bias, a_split=pk.fwd_s,
-               tile_hint=22)
-    ev0 = ops.f16_range_events() if hasattr(ops, "f16_range_events") else None
-    outs = []
-    try:
-        for dp in (0, 2):
-            L.dv3_debug_set(43, dp)
-            y = torch.empty(B, C, T, device=dev)
-            ab = torch.empty(B, 2 * C, T, device=dev)
-            dx = torch.empty(B, C, T, device=dev)
-            z = torch.empty(B, 2 * C, T, device=dev)
-            ops.conv_gemm(x, None, pk.lda, pk.a_half, y=y, ab=ab, **kw)
-            v0 = L.dv3_debug_get(10)
-            ops.conv_gemm(gm, None, pk.ldb, 0, y=dx, **dkw)
-            v1 = L.dv3_debug_get(10)
-            ops.conv_gemm(x, None, pk.lda, pk.lda, y=z, **lkw)
-            v2 = L.dv3_debug_get(10)
-            assert (v0 % 10, v1 % 10, v2 % 10) == ((5, 5, 5) if dp else (0, 0, 0)), (dp, v0, v1, v2)
-            assert v0 % 1000 // 10 == 2 and v1 % 1000 // 10 == 2
-            outs.append((y, ab, dx, z))
-    finally:
-        L.dv3_debug_set(43, DP_DEFAULT)
-        L.dv3_debug_set(44, KS_DEFAULT)
-    for a, b, name in zip(outs[0], outs[1], ("y", "pre-gate", "dx", "relu")):
-        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (name, float((a - b).abs().max()))
-    if ev0 is not None:
-        assert ops.f16_range_events() == ev0
-
-
-@pytest.mark.parametrize("B,C,T,k,d,causal,masked", [(3, 64, 75, 3, 2, False, True), (2, 256, 150, 3, 27, False, False),
-                                                     (2, 128, 100, 3, 1, True, True), (5, 96, 61, 3, 9, False, True),
                                                      (4, 160, 201, 1, 1, False, False), (3, 40, 37, 1, 1, False, True),
                                                      (2, 512, 150, 3, 3, False, True), (16, 256, 201, 1, 1, False, True),
                                                      (1, 72, 17, 3, 27, True, False), (3, 24, 50, 3, 1, False, False)])
@@ -1026,3 +957,21 @@ def test_memset_is_a_fill_kernel_with_exact_extent(dev):
     assert torch.equal(buf, want)
     t = ops._c8_empty(3, 513, 77, dev)
     assert t.shape == (3, 68, 77, 8) and float(t[:, 64:].float().abs().max()) == 0.0
+
+
+def test_debug_set_refuses_retired_and_unknown_switches(dev):
+    """dv3_debug_set (include/dv3hip.h) is an error for a code it does not handle -- the timing-only ablations and retired
+    experiment switches among them -- and for values outside a switch's shipped forms, so that a stale script cannot
+    time the production kernel believing it timed something else; the shipped switches the tests use still take their
+    values (each set to its default)."""
+    from deepvoice3_pytorch_amd import _lib
+    L = _lib.lib()
+    for what, value, why in ((999, 0, b"no such switch"), (1, 1, b"no such switch"), (13, 1, b"no such switch"),
+                             (52, 11, b"wgrad_c8 form 0..4"), (29, 5, b"LOAD-phase order 0, 17 or 81")):
+        assert L.dv3_debug_set(what, value) != 0, (what, value)
+        msg = L.dv3_last_error()
+        assert msg and msg.startswith(b"debug_set(%d, " % what) and why in msg, (what, value, msg)
+    defaults = ((2, 0), (3, 1), (19, 128), (20, 1), (22, 1), (29, 81), (30, 1), (31, 81), (34, 2), (44, KS_DEFAULT),
+                (47, 1), (48, 1), (49, 1), (51, 1), (52, 4), (55, 1), (57, 1))
+    for what, value in defaults:
+        assert L.dv3_debug_set(what, value) == 0, (what, value, L.dv3_last_error())
