@@ -1,7 +1,8 @@
 # coding: utf-8
 """Spectrogram -> waveform on the GPU: the device-side counterpart of the reference's
 audio.inv_spectrogram (audio.py:37-43) and its helpers (audio.py:26-28,84-93), and the forward analysis
-audio.spectrogram / audio.melspectrogram (audio.py:31-35,46-51).
+audio.spectrogram / audio.melspectrogram (audio.py:31-35,46-51), with the waveform preparation of the multi-speaker
+corpora in front of it: resampling (audio.py:12-13, librosa.load) and silence trimming (vctk.py:52-67).
 
 The reference hands framing and phase reconstruction to the third-party `lws` package on the host
 (audio.py:40-42,54-55); here they run on hand-written HIP FFT kernels (csrc/audio.hip), batched over utterances, so
@@ -419,3 +420,190 @@ def features_from_arrays(wavs, cfg=None, device="cuda:0", **kw):
     """features_items for a list of 1-D host waveforms: one pinned staging buffer, one host-to-device copy."""
     flat, lengths = pack_waveforms(wavs)
     return features_items(flat.to(device, non_blocking=True), lengths, cfg, **kw)
+
+
+# ---------------------------------------------------------------------------------------------
+# waveform preparation for multi-speaker corpora (ABI 46): librosa.load(sr=...) (audio.py:12-13) and
+# librosa.effects.trim (vctk.py:52-67) as ragged launches, in front of features_items
+# ---------------------------------------------------------------------------------------------
+RESAMPLE_ZEROS = 64                        # the published design of resampy's "kaiser_best" filter
+RESAMPLE_ROLLOFF = 0.9475937167399596
+RESAMPLE_BETA = 14.769656459379492
+TRIM_FRAME, TRIM_HOP = 2048, 512           # librosa.effects.trim's defaults
+
+
+def resample_ratio(source_rate, target_rate):
+    """-> (up, down) in lowest terms with target = source * up / down (48000 -> 22050: 147 / 320)"""
+    import math
+    source_rate, target_rate = int(source_rate), int(target_rate)
+    if source_rate < 1 or target_rate < 1:
+        raise ValueError("resample_ratio: rates must be positive integers")
+    g = math.gcd(source_rate, target_rate)
+    return target_rate // g, source_rate // g
+
+
+def resample_half_width(up, down):
+    """H: taps reach H samples below and H + 1 above floor(position): ceil(64 / min(1, up / down))"""
+    return RESAMPLE_ZEROS if up >= down else -(-RESAMPLE_ZEROS * down // up)
+
+
+def resample_table_np(up, down):
+    """float64 [2H + 2][up]: table[j][r] = h(H - j + ((r down) mod up) / up) of include/dv3hip.h
+    (dv3_resample_items_f32): the windowed sinc, evaluated in closed form"""
+    s = min(1.0, up / down)
+    H = resample_half_width(up, down)
+    frac = ((np.arange(up, dtype=np.int64) * down) % up).astype(np.float64) / up
+    t = (H - np.arange(2 * H + 2, dtype=np.float64))[:, None] + frac[None, :]
+    u = np.abs(t) * s / RESAMPLE_ZEROS
+    w = np.where(u < 1.0, np.i0(RESAMPLE_BETA * np.sqrt(np.clip(1.0 - u * u, 0.0, 1.0))) / np.i0(RESAMPLE_BETA), 0.0)
+    return s * RESAMPLE_ROLLOFF * np.sinc(RESAMPLE_ROLLOFF * s * t) * w
+
+
+_RESAMPLE_CACHE = {}
+
+
+def resample_table(device, up, down):
+    """the coefficient table as a float32 device tensor (computed in fp64, rounded once; cached per device and ratio)"""
+    key = (str(device), int(up), int(down))
+    if key not in _RESAMPLE_CACHE:
+        _RESAMPLE_CACHE[key] = torch.from_numpy(resample_table_np(up, down).astype(np.float32)).to(device)
+    return _RESAMPLE_CACHE[key]
+
+
+def _item_lengths(lengths, total, what):
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if lengths.size == 0 or int(lengths.min()) < 0 or int(lengths.sum()) != total:
+        raise ValueError("%s: %d samples do not split into items of lengths %s" % (what, total, lengths.tolist()))
+    return lengths
+
+
+def resample_items(wav_flat, lengths, up, down):
+    """Band-limited resampling of B utterances packed back to back (item b = the next lengths[b] samples of the 1-D
+    float32 device tensor) by up / down -> (flat, lengths): item b becomes ceil(lengths[b] * up / down) samples, the
+    length librosa.resample gives.  The filter is resampy's kaiser_best design in closed form (include/dv3hip.h:
+    dv3_resample_items_f32 states it and its roundings); each output is a function of its own item only.  up == down
+    returns the input without a launch (the filter itself is NOT the identity at ratio 1: its roll-off low-passes)."""
+    import math
+    wav_flat = _c(_chk(wav_flat, "wav_flat"))
+    if wav_flat.dim() != 1:
+        raise ValueError("resample_items: wav_flat must be 1-D (the items back to back)")
+    lengths = _item_lengths(lengths, wav_flat.numel(), "resample_items")
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise ValueError("resample_items: up and down must be positive")
+    g = math.gcd(up, down)
+    up, down = up // g, down // g
+    if up == down:
+        return wav_flat, lengths
+    tile = _lib.lib().dv3_resample_tile(up, down)
+    if tile <= 0:
+        raise ValueError("resample_items: the ratio %d / %d is not supported (terms up to 4096, a bounded window)"
+                         % (up, down))
+    out_len = -(-lengths * up // down)
+    tiles = -(-out_len // tile)
+    if int(tiles.sum()) >= 2 ** 31:
+        raise ValueError("resample_items: batch too large for one launch")
+    dev = wav_flat.device
+    y = torch.empty(int(out_len.sum()), dtype=torch.float32, device=dev)
+    if int(tiles.sum()) == 0:
+        return y, out_len
+    ioff = _sample_offsets(lengths, dev)
+    ooff = _sample_offsets(out_len, dev)
+    toff = torch.from_numpy(np.concatenate([[0], np.cumsum(tiles)]).astype(np.int32)).to(dev, non_blocking=True)
+    table = resample_table(dev, up, down)
+    _lib.call("dv3_resample_items_f32", wav_flat.data_ptr(), ioff.data_ptr(), ooff.data_ptr(), toff.data_ptr(),
+              lengths.size, int(tiles.sum()), up, down, table.data_ptr(), y.data_ptr(), _stream())
+    return y, out_len
+
+
+def trim_num_frames(length):
+    """frames librosa.effects.trim looks at: 1 + length // 512; 0 for a span too short to reflect-pad (< 1025)"""
+    return 1 + int(length) // TRIM_HOP if length > TRIM_FRAME // 2 else 0
+
+
+def _spans(wav_flat, starts, lengths, what):
+    starts = np.asarray(starts, dtype=np.int64).reshape(-1)
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if starts.size == 0 or starts.size != lengths.size or int(lengths.min()) < 0 or int(starts.min()) < 0 or \
+            int((starts + lengths).max()) > wav_flat.numel():
+        raise ValueError("%s: spans must lie inside the %d samples of wav_flat" % (what, wav_flat.numel()))
+    return starts, lengths
+
+
+def trim_items(wav_flat, starts, lengths, top_db=15.0):
+    """librosa.effects.trim(y, top_db) at its defaults for B spans of a flat float32 device tensor: span b =
+    wav_flat[starts[b] : starts[b] + lengths[b]] (host integers -- the frame counts size the launch).  top_db: one number
+    or one per span.  -> (starts, lengths) of the trimmed spans as int64 DEVICE tensors, starts absolute in wav_flat.
+    A span shorter than 1025 samples can not be reflect-padded and is returned unchanged.  See include/dv3hip.h
+    (dv3_trim_items_f32) for the definition."""
+    wav_flat = _c(_chk(wav_flat, "wav_flat"))
+    starts, lengths = _spans(wav_flat, starts, lengths, "trim_items")
+    B = starts.size
+    top = np.broadcast_to(np.asarray(top_db, dtype=np.float32), (B,)).copy()
+    frames = np.array([trim_num_frames(n) for n in lengths], dtype=np.int64)
+    nf = int(frames.sum())
+    if nf >= 2 ** 31:
+        raise ValueError("trim_items: batch too large for one launch")
+    dev = wav_flat.device
+    # one upload: starts | lengths as int64, then the frame offsets and the thresholds
+    sl = torch.from_numpy(np.concatenate([starts, lengths])).to(dev, non_blocking=True)
+    foff = torch.from_numpy(np.concatenate([[0], np.cumsum(frames)]).astype(np.int32)).to(dev, non_blocking=True)
+    top_d = torch.from_numpy(top).to(dev, non_blocking=True)
+    mse = torch.empty(max(nf, 1), dtype=torch.float32, device=dev)
+    out = torch.empty((2, B), dtype=torch.int64, device=dev)
+    _lib.call("dv3_trim_items_f32", wav_flat.data_ptr(), sl[:B].data_ptr(), sl[B:].data_ptr(), foff.data_ptr(), B, nf,
+              top_d.data_ptr(), mse.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), _stream())
+    return out[0], out[1]
+
+
+def gather_spans(wav_flat, starts, lengths):
+    """the spans wav_flat[starts[b] : starts[b] + lengths[b]] copied back to back -> (flat, lengths int64[B] on the
+    host).  starts / lengths: int64 device tensors (trim_items' result) or host integers.  The lengths are read back to
+    the host here when they live on the device (they size the output)."""
+    wav_flat = _c(_chk(wav_flat, "wav_flat"))
+    dev = wav_flat.device
+    if torch.is_tensor(starts) and torch.is_tensor(lengths) and starts.is_cuda:
+        host = torch.stack([starts.to(torch.int64), lengths.to(torch.int64)]).cpu().numpy()       # the one host read
+        starts_h, lengths_h = _spans(wav_flat, host[0], host[1], "gather_spans")
+        starts_d, lengths_d = _c(starts.to(torch.int64)), _c(lengths.to(torch.int64))
+    else:
+        starts_h, lengths_h = _spans(wav_flat, starts, lengths, "gather_spans")
+        sl = torch.from_numpy(np.concatenate([starts_h, lengths_h])).to(dev, non_blocking=True)
+        starts_d, lengths_d = sl[:starts_h.size], sl[starts_h.size:]
+    B = starts_h.size
+    if B > 65535:
+        raise ValueError("gather_spans: at most 65535 spans per call")
+    y = torch.empty(int(lengths_h.sum()), dtype=torch.float32, device=dev)
+    if y.numel():
+        ooff = _sample_offsets(lengths_h, dev)
+        _lib.call("dv3_gather_spans_f32", wav_flat.data_ptr(), starts_d.data_ptr(), lengths_d.data_ptr(),
+                  ooff.data_ptr(), B, int(lengths_h.max()), y.data_ptr(), _stream())
+    return y, lengths_h.copy()
+
+
+def prepare_items(wavs, source_rate, cfg=None, spans=None, top_db=15.0, device="cuda:0"):
+    """The reference's multi-speaker waveform preparation (vctk.py:52-67 after audio.load_wav) for a list of 1-D host
+    waveforms recorded at source_rate: resample to cfg.sample_rate, cut item b to spans[b] = (begin, end) in resampled
+    samples where given (None / no entry: the whole item; the HTS label cut), trim silence at top_db (a number or one
+    per item), and pack the results back to back -> (wav_flat on `device`, lengths int64[B] on the host), what
+    features_items takes.  An item trimmed to nothing has length 0 (features_items wants those dropped from `lengths`;
+    they occupy no samples).  One host-to-device copy, one host read (the trimmed spans: the frame counts size the
+    feature buffers)."""
+    cfg = cfg or AudioConfig()
+    flat, lengths = pack_waveforms(wavs)
+    up, down = resample_ratio(source_rate, cfg.sample_rate)
+    res, rlen = resample_items(flat.to(device, non_blocking=True), lengths, up, down)
+    starts = np.concatenate([[0], np.cumsum(rlen)[:-1]]).astype(np.int64)
+    lens = rlen.copy()
+    if spans is not None:
+        if len(spans) != len(wavs):
+            raise ValueError("prepare_items: one span (or None) per waveform expected")
+        for b, sp in enumerate(spans):
+            if sp is None:
+                continue
+            lo = min(max(int(sp[0]), 0), int(rlen[b]))
+            hi = min(max(int(sp[1]), lo), int(rlen[b]))
+            starts[b] += lo
+            lens[b] = hi - lo
+    t_starts, t_lens = trim_items(res, starts, lens, top_db)
+    return gather_spans(res, t_starts, t_lens)

@@ -30,7 +30,7 @@ extern "C" {
 #define DV3_ELAUNCH (-2)  /* hipLaunch / runtime error        */
 
 /* ABI version, bumped on any struct change; checked by the Python loader. */
-#define DV3_ABI_VERSION 45
+#define DV3_ABI_VERSION 46
 int dv3_abi_version(void);
 const char* dv3_last_error(void);
 /* Fills name (<=255 chars) of device `dev`, number of CUs; returns 0/err. */
@@ -915,6 +915,56 @@ int dv3_analysis_items_f32(const float* x, const int64_t* soff, const int32_t* f
  * m_b = max |x[i]| over item b's samples; gain[b] = 1 when m_b = 0.  The reference scales as (x / m_b) * rescaling_max;
  * here x * gain[b] (dv3_analysis_items_f32), which differs from it by at most an ulp or two per sample. */
 int dv3_item_gain_f32(const float* x, const int64_t* soff, int32_t B, float rescaling_max, float* gain, void* stream);
+
+/* ABI 46 (waveform preparation for multi-speaker corpora): what the reference's VCTK preprocessing does on the host before
+ * the features -- librosa.load(path, sr=hparams.sample_rate) (audio.py:12-13) and librosa.effects.trim (vctk.py:52-67) --
+ * as ragged launches over B utterances packed back to back.  Every output value is a function of its own item alone: not
+ * of B, the order, the neighbours or the grid.
+ *
+ * dv3_resample_items_f32: band-limited resampling by the rational ratio up / down (lowest terms, each <= 4096, up != down;
+ * 48 kHz -> 22.05 kHz is 147 / 320).
+ *   x      flat fp32 samples; item b is x[ioff[b] .. ioff[b+1]), L_b samples          ioff: device int64[B+1]
+ *   y      item b's output is y[ooff[b] .. ooff[b+1]); the caller sizes it ceil(L_b up / down) as librosa.resample does
+ *   toff   device int32[B+1]: item b owns workgroups toff[b] .. toff[b+1) = ceil(outputs_b / dv3_resample_tile(up, down)),
+ *          n_tiles = toff[B]
+ *   table  device float[2H + 2][up], H = ceil(64 / s), s = min(1, up / down): table[j][r] = fp32_rn(h(H - j + frac)) with
+ *          frac = ((r down) mod up) / up, evaluated in fp64 on the host, where
+ *            h(t) = s rho sinc(rho s t) w(|t| s / 64),  sinc(u) = sin(pi u) / (pi u),  rho = 0.9475937167399596,
+ *            w(u) = I0(beta sqrt(1 - u^2)) / I0(beta) for u < 1, else 0,                beta = 14.769656459379492
+ *          (the published design parameters of resampy's "kaiser_best" filter -- 64 zero crossings, that roll-off, that
+ *          Kaiser beta --, which librosa.load used in the reference's era; in closed form, not its interpolated table).
+ * Output n sits at input position n down / up: i0 = (n down) div up, r = n mod up, and
+ *   y[n] = sum over j = 0 .. 2H + 1 of table[j][r] * x[i0 - H + j],   x = 0 outside [0, L_b),
+ * accumulated in fp32 as ONE chain acc = fmaf(table[j][r], x[.], acc) from acc = 0 with j ascending (k ascending): the
+ * roundings are the table's (one fp32 rounding per coefficient) and one per fmaf, so
+ * |y - exact| <= (2H + 4) 2^-24 sum_j |h_j x_j|.  dv3_resample_tile -> outputs per workgroup for this ratio, or
+ * DV3_EINVAL for a ratio the kernel does not take (a term above 4096, or a tile window above 64 KiB of LDS). */
+int dv3_resample_tile(int32_t up, int32_t down);
+int dv3_resample_items_f32(const float* x, const int64_t* ioff, const int64_t* ooff, const int32_t* toff, int32_t B,
+                           int32_t n_tiles, int32_t up, int32_t down, const float* table, float* y, void* stream);
+/* dv3_trim_items_f32: librosa.effects.trim(y, top_db) at its defaults (frame_length 2048, hop_length 512, centred frames,
+ * ref = max), applied to spans: span b is x[start[b] .. start[b] + len[b]) (device int64[B] each).
+ *   foff   device int32[B+1]: span b's frames are rows foff[b] .. foff[b+1) of mse, 1 + len[b] div 512 of them for
+ *          len[b] >= 1025 and NONE for a shorter span; n_frames = foff[B]; mse: device float[n_frames] scratch (on return
+ *          the frame powers)
+ *   top_db device float[B] (vctk.py: 25 after a label cut, 15 otherwise)
+ * Frame f covers span samples [512 f - 1024, 512 f + 1024), reflected at both ends as numpy.pad(mode="reflect") does
+ * (librosa <= 0.9).  mse[f] = (sum of squares) / 2048 in fp32: lane t of 256 adds v^2 of samples t, t + 256, ... by fmaf,
+ * the 256 partial sums are added in a fixed binary tree.  db[f] = 10 log10f(max(1e-10, mse[f])) - 10 log10f(max(1e-10,
+ * max_f mse[f])); frame f is non-silent iff db[f] > -top_db[b].  With first / last the non-silent frames' extremes,
+ *   out_start[b] = start[b] + 512 first,  out_len[b] = min(len[b], 512 (last + 1)) - 512 first
+ * (device int64[B]); (start[b], 0) when no frame is non-silent (top_db <= 0 only: the loudest frame is at 0 dB).  A span
+ * shorter than 1025 samples can not be reflect-padded (numpy raises): it is returned unchanged.  Two launches: the frame
+ * powers, then one workgroup per span for the maximum and the two extremes. */
+int dv3_trim_items_f32(const float* x, const int64_t* start, const int64_t* len, const int32_t* foff, int32_t B,
+                       int32_t n_frames, const float* top_db, float* mse, int64_t* out_start, int64_t* out_len,
+                       void* stream);
+/* dv3_gather_spans_f32: y[ooff[b] + i] = x[start[b] + i], i < len[b] (device int64[B] / int64[B] / int64[B+1]; B <= 65535;
+ * max_len >= every len[b] sizes the grid): the trimmed spans back to back, so that dv3_item_gain_f32 and
+ * dv3_analysis_items_f32 run on them unchanged.  A copy: no rounding.  16 bytes per lane wherever the destination is
+ * 16-byte aligned (per span: a head of <= 3 floats, the aligned body, a tail of <= 3). */
+int dv3_gather_spans_f32(const float* x, const int64_t* start, const int64_t* len, const int64_t* ooff, int32_t B,
+                         int64_t max_len, float* y, void* stream);
 
 #ifdef __cplusplus
 }
