@@ -13,8 +13,30 @@ import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "dv3hip.h")
+
+
+# The package's DV3_* switches are read through these three, once each, at import or in a constructor -- never on a
+# per-step path.  INTEGRATION.md ("Environment switches") lists every one of them; tests/test_cpu_env_switches.py keeps
+# that list and the code in step.
+def _env_str(name, default=""):
+    """the variable's text; `default` when it is unset"""
+    return os.environ.get(name, default)
+
+
+def _env_flag(name, default):
+    """an on / off switch: unset -> `default`; "0" and the empty string -> off; anything else -> on"""
+    v = os.environ.get(name)
+    return bool(default) if v is None else v not in ("0", "")
+
+
+def _env_int(name, default):
+    """an integer switch: unset or empty -> `default`"""
+    v = os.environ.get(name)
+    return int(default) if v in (None, "") else int(v)
+
+
 # DV3_LIBPATH: load another build of the library (an A/B copy, for instance) instead of the in-tree one
-_LIBPATH = os.environ.get("DV3_LIBPATH") or os.path.join(_HERE, "libdv3hip.so")
+_LIBPATH = _env_str("DV3_LIBPATH") or os.path.join(_HERE, "libdv3hip.so")
 if not os.path.isabs(_LIBPATH):
     _LIBPATH = os.path.join(_HERE, _LIBPATH)
 
@@ -156,10 +178,6 @@ def lib():
         if n != ctypes.sizeof(cls):
             raise Dv3LibraryError("struct %s: C sizeof %d != ctypes %d" % (name, n, ctypes.sizeof(cls)))
     _lib = h
-    # developer knobs (include/dv3hip.h: dv3_debug_set) from the environment, for A/B runs
-    for what, var in ((2, "DV3_WGRAD_TILE"), (3, "DV3_X3_PINGPONG")):
-        if os.environ.get(var) is not None and os.environ[var] != "":
-            h.dv3_debug_set(what, int(os.environ[var]))
     return h
 
 

@@ -9,12 +9,17 @@ the whole utterance (dv3_decode_program_run: the loop, the ring buffers, the sto
 hand-over all stay on the device; opt-in, see StepProgram.decode).  `StepProgram` owns the buffers the descriptors point at.
 """
 import ctypes
-import os
 
 import torch
 
 from . import ops
-from ._lib import STRUCTS
+from ._lib import STRUCTS, _env_flag, _env_int, _env_str
+
+# which loop DecodeProgram.decode runs when its caller does not say (see its docstring)
+persistent_default = _env_flag("DV3_DECODE_PERSISTENT", False)
+launched_default = _env_str("DV3_DECODE_LAUNCHED", "1") != "0"      # (only "0" turns it off)
+# developer knob of the persistent program: timing ablations of its barriers (scripts/decode_time.py sets the attribute)
+ablate = _env_int("DV3_DECODE_ABLATE", 0)
 
 
 def item_stops(done_rows, t0, min_steps, max_steps, stops):
@@ -187,8 +192,7 @@ class StepProgram(object):
         if free_running:
             p.done_seq, p.done_ts = dones_seq.data_ptr(), dones_seq.stride(0)
         p.min_steps, p.max_steps = min_steps, max_steps
-        p.reserved = int(os.environ.get("DV3_DECODE_ABLATE", "0"))      # developer knob: timing ablations of the barriers
-        p.wg_per_group = int(os.environ.get("DV3_DECODE_WG", "0"))
+        p.reserved = ablate
         p.sync, p.steps_out = sync.data_ptr(), steps_out.data_ptr()
         ops._lib.call("dv3_decode_program_run", ctypes.byref(p), ops._stream())
         t = int(steps_out.item())
@@ -250,14 +254,14 @@ class StepProgram(object):
         if self.per_item and stops is None:
             raise RuntimeError("decode program: per-utterance attention entries need the per-item stop rule (stops=)")
         if persistent is None:
-            persistent = os.environ.get("DV3_DECODE_PERSISTENT", "0") == "1"
+            persistent = persistent_default
         if persistent:
             if stops is not None:
                 raise RuntimeError("decode program: the persistent program does not take per-utterance decoding "
                                    "(its stop rule is one flag per batch); use the launched or Python-driven loop")
             return self.decode_persistent(cur_in, test_inputs, dones_seq, min_steps, max_steps)
         if launched is None:
-            launched = os.environ.get("DV3_DECODE_LAUNCHED", "1") != "0"
+            launched = launched_default
         if launched:
             return self.decode_launched(cur_in, test_inputs, dones_seq, min_steps, max_steps, stops=stops)
         free_running = test_inputs is None

@@ -16,7 +16,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import CONSTS, STRUCTS
+from ._lib import CONSTS, STRUCTS, _env_flag, _env_int, _env_str
 
 EPI_LINEAR = CONSTS["DV3_EPI_LINEAR"]
 EPI_RELU = CONSTS["DV3_EPI_RELU"]
@@ -30,7 +30,6 @@ STORE_INTERLEAVE2 = CONSTS["DV3_STORE_INTERLEAVE2"]
 
 _conv_desc = STRUCTS["dv3_conv_desc"]
 _wgrad_desc = STRUCTS["dv3_wgrad_desc"]
-_planes_desc = STRUCTS["dv3_planes_desc"]
 _wn_desc = STRUCTS["dv3_wn_desc"]
 _wn_bwd_desc = STRUCTS["dv3_wn_bwd_desc"]
 _gate_bwd_desc = STRUCTS["dv3_gate_bwd_desc"]
@@ -52,10 +51,8 @@ _spec_loss_desc = STRUCTS["dv3_spec_loss_desc"]
 #   "bf16"   operands rounded to bf16 at the matrix-core inputs (hi planes only, one MFMA per
 #            product, fp32 accumulate, fp32 master weights) -- BASELINE.json's bf16 configs.
 # ----------------------------------------------------------------------------------------------
-import os as _os
-
 _GEMM_MODES = ("f16x3", "bf16x3", "f32", "bf16")
-_gemm_mode = _os.environ.get("DV3_GEMM", "f16x3")
+_gemm_mode = _env_str("DV3_GEMM", "f16x3")
 if _gemm_mode not in _GEMM_MODES:
     raise RuntimeError("DV3_GEMM must be one of %s" % (_GEMM_MODES,))
 
@@ -101,6 +98,8 @@ def _stream():
 
 
 reserved_stream_handles = set()      # raw handles new_stream() must not hand out again (capture streams)
+strict_streams = _env_flag("DV3_STRICT_STREAMS", False)     # concurrent_stream: no stream beside the others is an error
+stream_probe = _env_flag("DV3_STREAM_PROBE", True)          # concurrent_stream: 0 = take any stream, unprobed
 stream_probe_log = []      # one record per concurrent_stream() call: bench.py prints them as `stream_queues`
 _hip_rt = None
 
@@ -152,10 +151,10 @@ def concurrent_stream(avoid, tries=12, role="side", strict=None, priority="norma
     if not avoid:
         return new_stream(priority)
     if strict is None:
-        strict = _os.environ.get("DV3_STRICT_STREAMS", "") == "1"
+        strict = strict_streams
     dev = avoid[0].device
     with torch.cuda.device(dev):
-        if _os.environ.get("DV3_STREAM_PROBE", "1") in ("0", "") or torch.cuda.is_current_stream_capturing():
+        if not stream_probe or torch.cuda.is_current_stream_capturing():
             return new_stream(priority)
         cycles = 200000
 
@@ -179,7 +178,6 @@ def concurrent_stream(avoid, tries=12, role="side", strict=None, priority="norma
         except Exception:      # no spin kernel in this build: take any stream
             return new_stream(priority)
         rec["probed"] = True
-        want_shared = _os.environ.get("DV3_SIDE_STREAM_SAME_QUEUE", "") == "1"      # experiment: the opposite choice
         best, best_worst = None, None
         for _ in range(tries):
             s = new_stream(priority)
@@ -188,14 +186,13 @@ def concurrent_stream(avoid, tries=12, role="side", strict=None, priority="norma
             worst = max(ratios)
             if best is None or worst < best_worst:
                 best, best_worst = s, worst
-            beside = worst < 1.5
-            if beside != want_shared:
-                rec["found"] = not want_shared
+            if worst < 1.5:
+                rec["found"] = True
                 return s
         rec["found"] = False
         msg = ("no HIP stream runs beside all %d streams of the step (%s stream; ratios %s): hardware queues are shared, the "
                "overlap this stream is for is lost (GPU_MAX_HW_QUEUES=%s)" % (len(avoid), role, rec["candidates"],
-                                                                           _os.environ.get("GPU_MAX_HW_QUEUES", "default 4")))
+                                                                           _env_str("GPU_MAX_HW_QUEUES", "default 4")))
         if strict:
             raise RuntimeError(msg)
         warnings.warn(msg)
@@ -462,40 +459,7 @@ class Prepack(object):
 
 
 prepacked = None      # set by the trainer for the duration of a training forward
-fused_attention = _os.environ.get("DV3_FUSED_ATTN", "1") not in ("0", "")   # one launch for the attention forward
-
-
-# ----------------------------------------------------------------------------------------------
-# operand planes of an activation tensor (include/dv3hip.h, dv3_split_planes_f32)
-# ----------------------------------------------------------------------------------------------
-# DV3_PLANES=1: every eligible conv layer splits its input once (one HBM pass) and runs the persistent planes
-# tap-GEMM; the default (0) keeps the kernels that split while staging.  (Chained layers get their planes from
-# the producing epilogue instead -- see ConvLayerFn.)
-use_planes = _os.environ.get("DV3_PLANES", "0") not in ("0", "")
-
-
-def split_planes(x, bits=None, bits_rs=0, scale=1.0, f16=False, B=None, C=None, T=None, x_bs=None, x_rs=None):
-    """x fp32 (B, C, T) -> int16 tensor [2][B][C8p][T][8] tagged with its operand type; dropout keep-bits and
-    their 1/(1-p) are applied here, once, for the consuming tap-GEMM."""
-    if B is None:
-        B, C, T = x.shape
-    c8p = _round_up(C, 32) // 8
-    out = torch.empty(2 * B * c8p * T * 8, dtype=torch.int16, device=x.device)
-    d = _planes_desc()
-    d.x = x.data_ptr()
-    d.x_bs = x_bs if x_bs is not None else x.stride(0)
-    d.x_rs = x_rs if x_rs is not None else x.stride(1)
-    d.mask, d.mask_rs, d.scale = _ptr(bits), bits_rs, scale
-    d.out = out.data_ptr()
-    d.B, d.C, d.T, d.dtype = B, C, T, SPLIT_F16 if f16 else SPLIT_BF16
-    _lib.call("dv3_split_planes_f32", ctypes.byref(d), _stream())
-    out._dv3_f16, out._dv3_c8p = bool(f16), c8p
-    return out
-
-
-def planes_eligible(J, dil, Tin, Tout):
-    """the shapes dv3_conv_planes_dispatch takes (the planes carry the dropout mask: no silent fallback)"""
-    return _gemm_mode != "f32" and Tin == Tout and (J - 1) * dil <= 64 and J <= 16
+fused_attention = _env_flag("DV3_FUSED_ATTN", True)   # one launch for the attention forward
 
 
 # ----------------------------------------------------------------------------------------------
@@ -505,7 +469,7 @@ def planes_eligible(J, dil, Tin, Tout):
 # this layout -- every tap-GEMM stages it with plain 16-byte copies and every epilogue writes whole 8-byte halves
 # of units.  DV3_BF16_STORAGE=0 keeps fp32 (B, C, T) activations in the bf16 GEMM mode.
 # ----------------------------------------------------------------------------------------------
-bf16_storage = _os.environ.get("DV3_BF16_STORAGE", "1") not in ("0", "")
+bf16_storage = _env_flag("DV3_BF16_STORAGE", True)
 
 
 def zero_(t):
@@ -528,9 +492,6 @@ def is_c8(t):
     return t is not None and t.dim() == 4 and t.dtype == torch.bfloat16 and t.shape[-1] == 8
 
 
-partial_c8_fill = _os.environ.get("DV3_C8_PARTIAL_FILL", "1") not in ("0", "")
-
-
 def _c8_empty(B, C, T, device):
     """uninitialised c8 tensor; zero-filled when C leaves padding channels / groups (the kernels write whole valid
     groups only; padding must read as zero)"""
@@ -539,11 +500,8 @@ def _c8_empty(B, C, T, device):
     if C % 32:
         # only the groups from the first one with a padding channel on (513 channels: 4 of 68 groups; the whole tensor used to
         # be filled: 56 MB = 9.5 us, eleven times per nyanko step) -- one strided fill kernel
-        if partial_c8_fill:
-            G, g0 = c8_groups(C), C // 8
-            _lib.call("dv3_memset_rows_b8", t.data_ptr() + g0 * T * 16, 0, B, (G - g0) * T * 16, G * T * 16, _stream())
-        else:
-            zero_(t)
+        G, g0 = c8_groups(C), C // 8
+        _lib.call("dv3_memset_rows_b8", t.data_ptr() + g0 * T * 16, 0, B, (G - g0) * T * 16, G * T * 16, _stream())
     t._dv3_C = C
     return t
 
@@ -612,7 +570,7 @@ class MaskPlan(object):
     their masks from it: the same bits the single launches write (tests/test_gpu_model.py).  A call that does not match
     the list falls back to its own launch (same site number), and a step whose list differs from the previous one
     switches the plan off until two steps agree again (ragged eager epochs never plan)."""
-    enabled = bool(int(_os.environ.get("DV3_MASK_PLAN", "1")))
+    enabled = _env_flag("DV3_MASK_PLAN", True)
 
     def __init__(self):
         self.plan = None         # tuple of (site offset, kind, B, C, T, p) two consecutive steps agreed on
@@ -765,10 +723,9 @@ def conv_gemm(x, a, lda, a_half, *, B, Cin, Tin, M, Tout, J=1, dil=1, padL=0, mo
               Cg=0, bias=None, spk=None, spk_strides=(0, 0, 0), r=None, r2=None, residual=0,
               y=None, y_rs=None, ab=None, xmask=None, xmask_rs=0, ymask=None, ymask_rs=0,
               drop_scale=1.0, a_bs=0, store_mode=STORE_BCT, x_bs=None, x_rs=None, tile_hint=0,
-              a_split=None, x_planes=None, r_scale=0.0, out_dtype=torch.float32, x_c8=None, out_c8=False,
+              a_split=None, r_scale=0.0, out_dtype=torch.float32, x_c8=None, out_c8=False,
               xmask_c8=None, ymask_c8=None, gate=None, x_pair=False):
-    """dv3_conv_gemm_f32.  x: [B][Cin][Tin] (strides overridable); returns y.  x_planes: the input already
-    split into operand planes (split_planes; x may then be None).  bf16 storage: x_c8 = the input as a c8 tensor
+    """dv3_conv_gemm_f32.  x: [B][Cin][Tin] (strides overridable); returns y.  bf16 storage: x_c8 = the input as a c8 tensor
     (with its keep-bytes xmask_c8), out_c8 = y / ab written and r / r2 read in c8 (ymask_c8 for DGRAD).
     gate (a GateFuse, DGRAD launches of the split kernels): the tail also runs the gate backward of the layer that
     produced this layer's input and fills gate.dab / .dres / .part; x_pair: x holds pair words (include/dv3hip.h)."""
@@ -794,21 +751,16 @@ def conv_gemm(x, a, lda, a_half, *, B, Cin, Tin, M, Tout, J=1, dil=1, padL=0, mo
     if ab is not None and out_bf16 and not ab_bf16:
         raise RuntimeError("conv_gemm: a bf16 output needs a bf16 pre-gate save")
     if y is None:
-        y = torch.empty((B, Cout, To), dtype=out_dtype, device=(x if x is not None else x_planes).device)
+        y = torch.empty((B, Cout, To), dtype=out_dtype, device=x.device)
         y_bs, y_rs_ = Cout * To, To
     else:
         y_rs_ = y_rs if y_rs is not None else y.stride(1)
         y_bs = y.stride(0)
     d = _conv_desc()
-    d.x = _ptr(x)
+    d.x = x.data_ptr()
     d.a = _ptr(a)
-    if x is not None:
-        d.x_bs = x_bs if x_bs is not None else x.stride(0)
-        d.x_rs = x_rs if x_rs is not None else x.stride(1)
-    if x_planes is not None:
-        if a_split is None or getattr(a_split, "_dv3_f16", False) != x_planes._dv3_f16:
-            raise RuntimeError("x_planes and the split weight image must have the same operand type")
-        d.x_planes, d.x_c8p = x_planes.data_ptr(), x_planes._dv3_c8p
+    d.x_bs = x_bs if x_bs is not None else x.stride(0)
+    d.x_rs = x_rs if x_rs is not None else x.stride(1)
     d.a_bs, d.lda, d.a_half = a_bs, lda, a_half
     d.bias = _ptr(bias)
     d.spk = _ptr(spk)
@@ -857,7 +809,7 @@ def conv_gemm(x, a, lda, a_half, *, B, Cin, Tin, M, Tout, J=1, dil=1, padL=0, mo
 # capture whose stream has no workspace yet therefore gets none (tile-per-workgroup form) unless its owner prepared one
 # first: train_step.GraphedTrainer calls prepare_streamk_ws(device, capture stream) before it begins to capture.
 # DV3_STREAMK=0 turns the form off.
-streamk = _os.environ.get("DV3_STREAMK", "1") not in ("0", "")     # "force": also with a forced tile (scripts)
+streamk = _env_flag("DV3_STREAMK", True)     # "force": also with a forced tile (scripts)
 _sk_ws = {}
 
 
@@ -1118,18 +1070,15 @@ def axpby(a, b, alpha):
     return out
 
 
-# K steps a weight-gradient workgroup gets at least.  0 = the measured rule: 8 for short reductions (B=16: more slabs
+# K steps a weight-gradient workgroup gets at least, by the measured rule: 8 for short reductions (B=16: more slabs
 # fill the chip), rising with the reduction length to 32 (fp32-storage kernels) / 28 (channel-blocked bf16 kernel) for the
 # B=64 ones, where fewer, longer workgroups write fewer partial slabs for the weight-norm backward to read
 # (profiles/r06_ksplit_min_steps_ab.txt: -1.3 % / -1.5 % / -0.8 % on the B=64 / B=32 / vctk-bf16 steps; 20 forced at B=16
 # costs +1.8 %, 56 at B=64 +7 %; the bf16 kernel's cap was 20 while it transposed in registers -- 32 cost +2 % then -- and
 # moved to 28 with the transposing-read kernel, whose K steps are a quarter shorter: 14 costs +1.6 %, 40 +0.3 %).
-ksplit_min_steps = int(_os.environ.get("DV3_KSPLIT_MIN_STEPS", "0"))
-
-
 def _ksplit_count(total_steps, tiles, slots=512, min_steps=None, c8=False):
     if min_steps is None:
-        min_steps = ksplit_min_steps or (max(8, min(28, total_steps // 12)) if c8 else max(8, min(32, total_steps // 14)))
+        min_steps = max(8, min(28, total_steps // 12)) if c8 else max(8, min(32, total_steps // 14))
     return _ksplit_count_c(total_steps, tiles, slots, min_steps)
 
 
@@ -1185,7 +1134,7 @@ def _pad_left(k, dil, causal):
 
 # K-split partial sums of the weight gradient as [J][M][S][Cin] (wgrad_gemm(rows_of_slabs=True)); DV3_SLAB_ROWS=0 = the
 # round-3 layout [S][J][M][Cin], for A/B runs
-slab_rows_default = _os.environ.get("DV3_SLAB_ROWS", "1") not in ("0", "")
+slab_rows_default = _env_flag("DV3_SLAB_ROWS", True)
 
 # called as hook(v, g, bias) (entries may be None) once a conv layer's in-place gradients (see ConvLayerFn.backward)
 # are final for this step: one call per layer
@@ -1223,17 +1172,6 @@ class SideStream(object):
             SideStream._release_point()
             return False
 
-    class _MainSection(object):
-        """a fork point whose weight gradient stays on the step stream (DV3_SIDE_MAIN: balance of the two queues)"""
-
-        def __enter__(self):
-            pass
-
-        def __exit__(self, *exc):
-            SideStream._release_point()
-            return False
-
-    main_rule, _main_spec = (frozenset(), 0), ""       # (set of fork numbers, every-k) from DV3_SIDE_MAIN
     forks_last = 0         # ... of the step before
     forks = 0              # fork points since the last join (GraphedTrainer sizes its segments from a warm-up step's count)
 
@@ -1241,10 +1179,6 @@ class SideStream(object):
     def fork(cls, *tensors):
         # the section's inputs are complete on the step stream: the side stream waits for exactly that point
         cls.forks += 1
-        spec = _os.environ.get("DV3_SIDE_MAIN", "")
-        if spec != cls._main_spec:
-            cls._main_spec, cls.main_rule = spec, _parse_side_main(spec)
-        on_main = cls.forks in cls.main_rule[0] or (cls.main_rule[1] and cls.forks % cls.main_rule[1] == 0)
         if cls.split_capture:
             # two separate captures: nothing ties them here; GraphedTrainer closes both every few fork points and the
             # replay orders step-stream segment j before side segment j with an ordinary event
@@ -1253,7 +1187,7 @@ class SideStream(object):
         else:
             _lib.call("dv3_stream_fork", cls.main.cuda_stream, cls.stream.cuda_stream)
         cls.keep.append([None, [tensors]])
-        return cls._main_section if on_main else cls._section
+        return cls._section
 
     @classmethod
     def retain(cls, *tensors):
@@ -1308,33 +1242,20 @@ class SideStream(object):
 
 
 SideStream._section = SideStream._Section()
-SideStream._main_section = SideStream._MainSection()
-
-
-def _parse_side_main(spec):
-    """DV3_SIDE_MAIN = "3,7,11" (fork numbers of a step, 1-based) and / or "every:k": those weight gradients are issued on
-    the step stream instead of the second one"""
-    nums, every = set(), 0
-    for tok in spec.replace(" ", "").split(","):
-        if tok.startswith("every:"):
-            every = int(tok[6:])
-        elif tok:
-            nums.add(int(tok))
-    return nums, every
 
 
 # Round 6: the gate backward of a gated layer runs in the tail of its consumer's input-gradient launch (GateFuse) when the
 # caller marked the layer's output as having no other consumer (`y._dv3_sole = True`: the stack runners of deepvoice3.py /
 # nyanko.py do).  DV3_FUSE_GATE=0 restores the stand-alone dv3_gate_bwd_f32 launches (A/B runs).
-fuse_gate_bwd = _os.environ.get("DV3_FUSE_GATE", "1") not in ("0", "")
+fuse_gate_bwd = _env_flag("DV3_FUSE_GATE", True)
 # ... where it pays.  Measured per launch (scripts/r6_gate_fuse_kernels.py, profiles/r06_gate_fuse_kernels.txt): the tail
 # costs what the stand-alone kernel costs once that kernel is bandwidth-bound (B = 64: 59 us stand-alone at 5.6 TB/s
 # against +73 us of tail at the north-star shape; break-even at 64 x 512 x 150), and half of it where the stand-alone
 # launch is latency-bound (B = 16, 256 x 804: 12.3 us against +6.4 us).  Elements (B * C * T) up to which a producer offers
 # its gate backward to its consumer (DV3_FUSE_GATE_MAX; 0 = never, a huge value = always):
-fuse_gate_max_elems = int(_os.environ.get("DV3_FUSE_GATE_MAX", str(4 << 20)))
+fuse_gate_max_elems = _env_int("DV3_FUSE_GATE_MAX", 4 << 20)
 # the pre-gate gradient as pair words for the layer's own gradient GEMMs (DV3_PAIR_WORDS=0: fp32, A/B runs)
-pair_words = _os.environ.get("DV3_PAIR_WORDS", "1") not in ("0", "")
+pair_words = _env_flag("DV3_PAIR_WORDS", True)
 gate_fuse_stats = {"fused": 0, "standalone": 0}     # gated-layer backwards served either way (tests, bench)
 
 
@@ -1362,6 +1283,85 @@ def mark_sole_consumer(y):
     if fuse_gate_bwd and getattr(y, "_dv3_tok", None) is not None:
         y._dv3_sole = True
     return y
+
+
+# ----------------------------------------------------------------------------------------------
+# what ConvLayerFn, ConvLayerC8Fn and SpeakerBiasBlockFn share
+# ----------------------------------------------------------------------------------------------
+def _spk_strides(spk):
+    """(batch, channel, time) strides of the additive speaker term: (B, Cg) is constant over time, (B, Cg, T) per frame"""
+    if spk is None:
+        return 0, 0, 0
+    if spk.dim() == 2:
+        return spk.stride(0), 1, 0
+    return spk.stride(0), spk.stride(1), 1
+
+
+def _grads_in_place(leaves):
+    """parameters whose .grad lives in the trainer's flat arena take their gradient in place (no AccumulateGrad add
+    kernel per parameter)"""
+    return all(getattr(t, "_dv3_grad_inplace", False) and t.grad is not None and t.requires_grad for t in leaves)
+
+
+def _grad_inplace_arm(ctx, v, g, bias):
+    """forward: decide whether this layer's parameter gradients go straight into .grad, and count the use of v so the
+    "gradient final" notification fires once, after the last of its uses"""
+    leaves = [t for t in (v, g, bias) if t is not None]
+    ctx.inplace = bool(leaves) and _grads_in_place(leaves)
+    ctx.leaves = (v, g, bias) if ctx.inplace else None
+    if ctx.inplace:
+        v._dv3_pending = getattr(v, "_dv3_pending", 0) + 1
+
+
+def _grad_inplace_finish(ctx):
+    """backward, once the in-place gradients of this use are queued: the last use of v fires grad_ready_hooks"""
+    pv, pg, pb = ctx.leaves
+    pv._dv3_pending -= 1
+    if pv._dv3_pending == 0:
+        for hook in grad_ready_hooks:
+            hook(pv, pg, pb)
+
+
+def _strip_residual_scalings(ctx, dy, scaled):
+    """non-gated layers, y = ((act(pre) + r) * s + r2) * s with s = sqrt(.5): -> (dr, dr2, alpha), alpha = what is left to
+    scale the gradient of `pre` by.  scaled(dy, a) = a * dy in the caller's own storage (fp32: axpby, c8: a torch multiply)"""
+    rs2 = math.sqrt(0.5)
+    dr = dr2 = None
+    alpha = 1.0
+    if ctx.has_r2:
+        dr2 = scaled(dy, rs2)
+        alpha *= rs2
+    if ctx.has_r:
+        dr = scaled(dy, alpha * rs2)
+        alpha *= rs2
+    if ctx.cfg.mode in (EPI_RELU, EPI_SIGMOID, EPI_SOFTSIGN) and (ctx.has_r or ctx.has_r2):
+        raise RuntimeError("activation + fused residual is not used by any layer")
+    return dr, dr2, alpha
+
+
+def _wgrad_tail(ctx, wgrad, S, slab_rows, v, g, Cin, part, *, n_part, part_t, transposed, fork):
+    """The weight-gradient tail of a conv layer's backward -> (dv, dg, dbias), all None with in-place gradients.
+    wgrad() launches the weight-gradient GEMM -> (slabs, tensors it made for the launch).  With in-place gradients and a
+    trainer's second stream the tail runs there (SideStream): `fork` = the tensors it reads, which -- like the slabs and
+    what wgrad() made -- stay referenced until the side stream is known to be past them."""
+    pk = ctx.pk
+    v3 = v if v.dim() == 3 else v.unsqueeze(-1)
+    on_side = ctx.inplace and SideStream.stream is not None
+    into = None
+    if ctx.inplace:
+        pv, pg, pb = ctx.leaves
+        into = (pv.grad, pg.grad if pg is not None else None, pb.grad if pb is not None else None)
+    with SideStream.fork(*fork) if on_side else contextlib.nullcontext():
+        slabs, made = wgrad()
+        dv, dg, dbias = weight_norm_bwd(slabs, S, Cin, _c(v3), _c(g) if g is not None else None, pk.scale, part, n_part,
+                                        pk.O, pk.I, pk.J, transposed, want_bias=ctx.has_bias, into=into,
+                                        rows_of_slabs=slab_rows, part_t=part_t)
+        if not ctx.inplace:
+            return dv.view_as(v), dg, dbias
+        if on_side:
+            SideStream.retain(slabs, *made)
+        _grad_inplace_finish(ctx)
+    return None, None, None
 
 
 class ConvLayerFn(torch.autograd.Function):
@@ -1397,7 +1397,6 @@ class ConvLayerFn(torch.autograd.Function):
             pk = pack_weights(v, g, glu_cg=Cg, transposed=cfg.transposed, need_bwd=need_grad, split_only=split_only)
         bits, bits_rs, dscale, keep8 = None, 0, 1.0, None
         if cfg.training and cfg.p > 0:
-            J_ = 1 if cfg.transposed else (v.shape[2] if v.dim() == 3 else 1)
             if not cfg.transposed and pp2_wants_keep_bytes(Cin, J_, cfg.dil, T, cfg.t_out if cfg.t_out is not None else T):
                 bits, bits_rs, keep8 = dropout_bits_keep(B, Cin, T, cfg.p, x.device, cfg.site)
             else:
@@ -1413,36 +1412,19 @@ class ConvLayerFn(torch.autograd.Function):
         # training forward writes and the operands are rounded to bf16 anyway; fp32 in the fp32-class modes
         ab_dtype = torch.bfloat16 if (_gemm_mode == "bf16" and pk.fwd_s is not None and split_only) else torch.float32
         ab = torch.empty((B, M, T), dtype=ab_dtype, device=x.device) if (gated and need_grad) else None
-        spk_strides = (0, 0, 0)
         if spk is not None:
             spk = _c(spk)
-            if spk.dim() == 2:      # (B, Cg): constant over time
-                spk_strides = (spk.stride(0), 1, 0)
-            else:                   # (B, Cg, T)
-                spk_strides = (spk.stride(0), spk.stride(1), 1)
         res_in = x if gated else (_c(r) if r is not None else None)
         r2c = _c(r2) if r2 is not None else None
-        xp = None
-        if use_planes and pk.fwd_s is not None and planes_eligible(1 if cfg.transposed else J, cfg.dil, T, Tout):
-            xp = split_planes(x, bits, bits_rs, dscale, f16=pk.fwd_f16)
         y = conv_gemm(x, pk.fwd, pk.lda, pk.a_half, B=B, Cin=Cin, Tin=T, M=M, Tout=Tout,
-                      J=(1 if cfg.transposed else J), dil=cfg.dil, padL=padL, mode=mode, Cg=Cg,
-                      bias=bias, spk=spk, spk_strides=spk_strides,
+                      J=J_, dil=cfg.dil, padL=padL, mode=mode, Cg=Cg,
+                      bias=bias, spk=spk, spk_strides=_spk_strides(spk),
                       r=res_in if (mode == EPI_HIGHWAY or cfg.residual or not gated) else None,
-                      r2=r2c, residual=int(cfg.residual), ab=ab, xmask=bits if xp is None else None,
-                      xmask_rs=bits_rs if xp is None else 0, x_planes=xp, xmask_c8=keep8 if xp is None else None,
+                      r2=r2c, residual=int(cfg.residual), ab=ab, xmask=bits, xmask_rs=bits_rs, xmask_c8=keep8,
                       drop_scale=dscale, a_split=pk.fwd_s if _gemm_mode != "f32" else None,
                       store_mode=STORE_INTERLEAVE2 if cfg.transposed else STORE_BCT)
         if need_grad:
-            # parameters whose .grad lives in the trainer's flat arena take their gradient in place
-            # (no AccumulateGrad add kernel per parameter); count the uses so the "gradient final"
-            # notification fires once, after the last of them
-            leaves = [t for t in (v, g, bias) if t is not None]
-            ctx.inplace = bool(leaves) and all(getattr(t, "_dv3_grad_inplace", False) and t.grad is not None and
-                                               t.requires_grad for t in leaves)
-            ctx.leaves = (v, g, bias) if ctx.inplace else None
-            if ctx.inplace:
-                v._dv3_pending = getattr(v, "_dv3_pending", 0) + 1
+            _grad_inplace_arm(ctx, v, g, bias)
             ctx.cfg, ctx.pk, ctx.dims = cfg, pk, (B, Cin, T, Tout, M, Cg, J, padL)
             ctx.bits, ctx.bits_rs, ctx.dscale = bits, bits_rs, dscale
             ctx.spk_dim = spk.dim() if spk is not None else 0
@@ -1456,11 +1438,10 @@ class ConvLayerFn(torch.autograd.Function):
             # pair words (include/dv3hip.h): this layer's pre-gate gradient can go to its two gradient GEMMs as the bf16
             # hi / lo pairs they would otherwise build while staging (both on the three-term split kernels, no per-frame
             # speaker-bias gradient reading the tensor as fp32)
-            ctx.pair_ok = bool(gated and pair_words and split_modes and not use_planes and pk.bwd_s is not None and
+            ctx.pair_ok = bool(gated and pair_words and split_modes and pk.bwd_s is not None and
                                split_only and ab.dtype == torch.float32 and (spk is None or spk.dim() == 2) and
                                not (M <= 64 and Cin <= 64))
-            if fuse_gate_bwd and split_modes and not use_planes and pk.bwd_s is not None:
-                Jd = 1 if cfg.transposed else J
+            if fuse_gate_bwd and split_modes and pk.bwd_s is not None:
                 if gated and ab.dtype == torch.float32 and spk is None and split_only and \
                         B * Cg * T <= fuse_gate_max_elems:
                     ctx.tok = _GateToken(ab, mode, int(cfg.residual), x if mode == EPI_HIGHWAY else None, Cg,
@@ -1468,7 +1449,7 @@ class ConvLayerFn(torch.autograd.Function):
                     y._dv3_tok = ctx.tok
                 prod = getattr(x_in, "_dv3_tok", None) if (x_in is x and getattr(x_in, "_dv3_sole", False)) else None
                 if prod is not None and prod.C == Cin and ctx.needs_input_grad[0] and Tout == T and \
-                        (Jd - 1) * cfg.dil <= 64 and Jd <= 16:
+                        (J_ - 1) * cfg.dil <= 64 and J_ <= 16:
                     ctx.prod = prod
         return y
 
@@ -1515,17 +1496,9 @@ class ConvLayerFn(torch.autograd.Function):
             _lib.call("dv3_deinterleave2_f32", dy.data_ptr(), gmat.data_ptr(), B, O, T, _stream())
             dres, Tg = None, T
         else:
-            # non-gated: y = ((act(pre) + r)*s + r2)*s ; strip the residual scalings first
-            alpha = 1.0
-            if ctx.has_r2:
-                dr2 = axpby(dy, None, rs2)
-                alpha *= rs2
-            if ctx.has_r:
-                dr = axpby(dy, None, alpha * rs2)
-                alpha *= rs2
+            # non-gated: strip the residual scalings first
+            dr, dr2, alpha = _strip_residual_scalings(ctx, dy, lambda d, a: axpby(d, None, a))
             need_y = mode in (EPI_RELU, EPI_SIGMOID, EPI_SOFTSIGN)
-            if need_y and (ctx.has_r or ctx.has_r2):
-                raise RuntimeError("activation + fused residual is not used by any layer")
             if mode == EPI_LINEAR and alpha == 1.0:
                 _, _, part = gate_bwd(dy, None, None, B=B, C=M, T=Tout, mode=EPI_LINEAR, want_dpre=False)
                 gmat = dy
@@ -1535,68 +1508,45 @@ class ConvLayerFn(torch.autograd.Function):
             dres, Tg = None, Tout
         dx = dv = dg = dbias = None
         Mg = gmat.shape[1]
+        Jd = 1 if cfg.transposed else J
         if ctx.needs_input_grad[0]:
             # input gradient: transposed, tap-reversed weights; dropout mask on the output side
-            Jd = 1 if cfg.transposed else J
-            gp = None
-            if use_planes and pk.bwd_s is not None and planes_eligible(Jd, cfg.dil, Tg, T):
-                gp = split_planes(gmat, f16=False)
             gate = None
-            if ctx.prod is not None and gp is None:
+            if ctx.prod is not None:
                 t_ = ctx.prod
                 gate = GateFuse(t_.ab, t_.mode, t_.residual, t_.x, pair=t_.pair)
-            dx = conv_gemm(gmat, pk.bwd, pk.ldb, 0, B=B, Cin=Mg, Tin=Tg, M=Cin, Tout=T, J=Jd, x_planes=gp,
+            dx = conv_gemm(gmat, pk.bwd, pk.ldb, 0, B=B, Cin=Mg, Tin=Tg, M=Cin, Tout=T, J=Jd,
                            dil=cfg.dil, padL=(Jd - 1) * cfg.dil - padL, mode=EPI_DGRAD, r=dres, r_scale=r_scale,
                            ymask=ctx.bits, ymask_rs=ctx.bits_rs, drop_scale=ctx.dscale,
                            a_split=pk.bwd_s if _gemm_mode != "f32" else None, gate=gate, x_pair=g_pair)
             if gate is not None:
                 dx._dv3_gate = _GateResult(ctx.prod, gate, dx._version)
         if ctx.needs_input_grad[1]:
-            Jd = 1 if cfg.transposed else J
             tiles = ((Mg + 127) // 128) * ((Cin + 127) // 128) * Jd
             x3 = _gemm_mode != "f32" and not (Mg <= 64 and Cin <= 64)
-            if x3 and Jd == 3 and _os.environ.get("DV3_WGRAD_TILE", "0") in ("0", "3"):
+            if x3 and Jd == 3:
                 # one 8-wave workgroup per (tile, slab) serves the three taps: one workgroup per CU
                 S = _ksplit_count(B * ((Tg + 31) // 32), tiles // 3, slots=256)
             elif x3:   # split-K over contiguous (batch, chunk) ranges: size the grid to 2 workgroups per CU
                 S = _ksplit_count(B * ((Tg + 31) // 32), tiles)
             else:
                 S = _slab_count(B, tiles)
-            v3 = v if v.dim() == 3 else v.unsqueeze(-1)
             slab_rows = slab_rows_default and S > 1
-            side = SideStream.fork(gmat, x, ctx.bits, part, dy) if (ctx.inplace and SideStream.stream is not None) \
-                else contextlib.nullcontext()
-            with side:
-                slabs = wgrad_gemm(gmat, x, B=B, M=Mg, Cin=Cin, T=Tg, Tin=T, J=Jd, dil=cfg.dil, padL=padL,
-                                   n_slabs=S, xmask=ctx.bits, xmask_rs=ctx.bits_rs, drop_scale=ctx.dscale,
-                                   split_bf16=x3, k_split=x3, rows_of_slabs=slab_rows, g_pair=g_pair)
-                if ctx.inplace:
-                    pv, pg, pb = ctx.leaves
-                    weight_norm_bwd(slabs, S, Cin, _c(v3), _c(g) if g is not None else None, pk.scale, part, n_part,
-                                    pk.O, pk.I, pk.J, cfg.transposed, want_bias=ctx.has_bias,
-                                    into=(pv.grad, pg.grad if pg is not None else None,
-                                          pb.grad if pb is not None else None), rows_of_slabs=slab_rows,
-                                    part_t=part_t)
-                    if SideStream.stream is not None:
-                        SideStream.retain(slabs)
-                    pv._dv3_pending -= 1
-                    if pv._dv3_pending == 0:
-                        for hook in grad_ready_hooks:
-                            hook(pv, pg, pb)
-            if ctx.inplace:
-                dv = dg = dbias = None
-            else:
-                dv, dg, dbias = weight_norm_bwd(slabs, S, Cin, _c(v3), _c(g) if g is not None else None,
-                                                pk.scale, part, n_part, pk.O, pk.I, pk.J, cfg.transposed,
-                                                want_bias=ctx.has_bias, rows_of_slabs=slab_rows, part_t=part_t)
-                dv = dv.view_as(v)
+
+            def wgrad():
+                return wgrad_gemm(gmat, x, B=B, M=Mg, Cin=Cin, T=Tg, Tin=T, J=Jd, dil=cfg.dil, padL=padL,
+                                  n_slabs=S, xmask=ctx.bits, xmask_rs=ctx.bits_rs, drop_scale=ctx.dscale,
+                                  split_bf16=x3, k_split=x3, rows_of_slabs=slab_rows, g_pair=g_pair), ()
+
+            dv, dg, dbias = _wgrad_tail(ctx, wgrad, S, slab_rows, v, g, Cin, part, n_part=n_part, part_t=part_t,
+                                        transposed=cfg.transposed, fork=(gmat, x, ctx.bits, part, dy))
         return dx, dv, dg, dbias, dspk, dr, dr2, None, None
 
 
 # ----------------------------------------------------------------------------------------------
 # per-frame speaker biases of a block of Conv1dGLU layers (include/dv3hip.h: dv3_speaker_bias_fwd_f32 / _bwd_f32)
 # ----------------------------------------------------------------------------------------------
-fused_speaker_bias = _os.environ.get("DV3_FUSED_SPK", "1") not in ("0", "")
+fused_speaker_bias = _env_flag("DV3_FUSED_SPK", True)
 _spk_layer_t, _spk_desc_t = STRUCTS["dv3_spk_layer"], STRUCTS["dv3_spk_desc"]
 SPK_MAX_LAYERS = CONSTS["DV3_SPK_MAX_LAYERS"]
 
@@ -1639,8 +1589,7 @@ class SpeakerBiasBlockFn(torch.autograd.Function):
         saved = ctx.saved_tensors
         e, params, outs = saved[0], saved[1:1 + 3 * L], saved[1 + 3 * L:]
         B, E, T = e.shape
-        leaves = [p for p in params if p is not None]
-        inplace = all(getattr(p, "_dv3_grad_inplace", False) and p.grad is not None and p.requires_grad for p in leaves)
+        inplace = _grads_in_place([p for p in params if p is not None])
         layers = (_spk_layer_t * L)()
         keep, grads = [], []
         for l in range(L):
@@ -1763,26 +1712,19 @@ class ConvLayerC8Fn(torch.autograd.Function):
                 bits, bits_rs = dropout_bits(B * Cin, T, cfg.p, x.device, cfg.site)
         padL = cfg.pad_left if cfg.pad_left is not None else _pad_left(J, cfg.dil, cfg.causal)
         ab = _c8_empty(B, M, T, x.device) if (gated and need_grad) else None
-        spk_strides = (0, 0, 0)
         if spk is not None:
             spk = _c(spk)
-            spk_strides = (spk.stride(0), 1, 0) if spk.dim() == 2 else (spk.stride(0), spk.stride(1), 1)
         if gated:
             res_in = x if (mode == EPI_HIGHWAY or cfg.residual) else None
         else:
             res_in = _c(r) if r is not None else None
         r2c = _c(r2) if r2 is not None else None
         y = conv_gemm(None if x8 else x, None, pk.lda, pk.a_half, B=B, Cin=Cin, Tin=T, M=M, Tout=T, J=J, dil=cfg.dil,
-                      padL=padL, mode=mode, Cg=Cg, bias=bias, spk=spk, spk_strides=spk_strides, r=res_in, r2=r2c,
+                      padL=padL, mode=mode, Cg=Cg, bias=bias, spk=spk, spk_strides=_spk_strides(spk), r=res_in, r2=r2c,
                       residual=int(cfg.residual), ab=ab, xmask=None if x8 else bits, xmask_rs=0 if x8 else bits_rs,
                       drop_scale=dscale, a_split=pk.fwd_s, x_c8=x if x8 else None, out_c8=out8, xmask_c8=keep8)
         if need_grad:
-            leaves = [t for t in (v, g, bias) if t is not None]
-            ctx.inplace = bool(leaves) and all(getattr(t, "_dv3_grad_inplace", False) and t.grad is not None and
-                                               t.requires_grad for t in leaves)
-            ctx.leaves = (v, g, bias) if ctx.inplace else None
-            if ctx.inplace:
-                v._dv3_pending = getattr(v, "_dv3_pending", 0) + 1
+            _grad_inplace_arm(ctx, v, g, bias)
             ctx.cfg, ctx.pk, ctx.dims = cfg, pk, (B, Cin, T, M, Cg, J, padL)
             ctx.bits, ctx.bits_rs, ctx.dscale, ctx.keep8 = bits, bits_rs, dscale, keep8
             ctx.x8, ctx.out8 = x8, out8
@@ -1821,16 +1763,8 @@ class ConvLayerC8Fn(torch.autograd.Function):
                           _stream())
             g8 = gmat
         else:
-            alpha = 1.0
-            if ctx.has_r2:
-                dr2 = dy * rs2
-                alpha *= rs2
-            if ctx.has_r:
-                dr = dy * (alpha * rs2)
-                alpha *= rs2
+            dr, dr2, alpha = _strip_residual_scalings(ctx, dy, lambda d, a: d * a)
             need_y = mode in (EPI_RELU, EPI_SIGMOID, EPI_SOFTSIGN)
-            if need_y and (ctx.has_r or ctx.has_r2):
-                raise RuntimeError("activation + fused residual is not used by any layer")
             if ctx.out8:
                 plain = mode == EPI_LINEAR and alpha == 1.0
                 gm, _, part = gate_bwd_c8(dy, saved if need_y else None, None, B=B, C=M, T=T, mode=mode, alpha=alpha,
@@ -1856,36 +1790,20 @@ class ConvLayerC8Fn(torch.autograd.Function):
                                a_split=pk.bwd_s, x_c8=g8, out_c8=False)
         if ctx.needs_input_grad[1]:
             tiles = ((M + 127) // 128) * ((Cin + 127) // 128)
-            v3 = v if v.dim() == 3 else v.unsqueeze(-1)
             S = _ksplit_count(B * ((T + 31) // 32), tiles, slots=256, c8=True)
             slab_rows = slab_rows_default and S > 1
-            side = SideStream.fork(g8, x, ctx.bits, ctx.keep8, part, dy) if (ctx.inplace and SideStream.stream is not None) \
-                else contextlib.nullcontext()
-            with side:
+
+            def wgrad():
                 if ctx.x8:
                     x8t, keep8 = x, ctx.keep8
                 else:
                     x8t = _ToC8Fn.apply(x)
                     keep8 = mask_bits_to_c8(ctx.bits, ctx.bits_rs, B, Cin, T) if ctx.bits is not None else None
-                slabs = wgrad_gemm_c8(g8, x8t, B=B, M=M, Cin=Cin, T=T, J=J, dil=cfg.dil, padL=padL, n_slabs=S,
-                                      xmask_c8=keep8, drop_scale=ctx.dscale, rows_of_slabs=slab_rows)
-                if ctx.inplace:
-                    pv, pg, pb = ctx.leaves
-                    weight_norm_bwd(slabs, S, Cin, _c(v3), _c(g) if g is not None else None, pk.scale, part, B,
-                                    pk.O, pk.I, pk.J, False, want_bias=ctx.has_bias,
-                                    into=(pv.grad, pg.grad if pg is not None else None,
-                                          pb.grad if pb is not None else None), rows_of_slabs=slab_rows)
-                    if SideStream.stream is not None:
-                        SideStream.retain(slabs, x8t, keep8)
-                    pv._dv3_pending -= 1
-                    if pv._dv3_pending == 0:
-                        for hook in grad_ready_hooks:
-                            hook(pv, pg, pb)
-            if not ctx.inplace:
-                dv, dg, dbias = weight_norm_bwd(slabs, S, Cin, _c(v3), _c(g) if g is not None else None,
-                                                pk.scale, part, B, pk.O, pk.I, pk.J, False, want_bias=ctx.has_bias,
-                                                rows_of_slabs=slab_rows)
-                dv = dv.view_as(v)
+                return wgrad_gemm_c8(g8, x8t, B=B, M=M, Cin=Cin, T=T, J=J, dil=cfg.dil, padL=padL, n_slabs=S,
+                                     xmask_c8=keep8, drop_scale=ctx.dscale, rows_of_slabs=slab_rows), (x8t, keep8)
+
+            dv, dg, dbias = _wgrad_tail(ctx, wgrad, S, slab_rows, v, g, Cin, part, n_part=B, part_t=False,
+                                        transposed=False, fork=(g8, x, ctx.bits, ctx.keep8, part, dy))
         return dx, dv, dg, dbias, dspk, dr, dr2, None, None
 
 

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._lib import _env_flag, _env_int, _env_str
 
 
 class TrainConfig(object):
@@ -141,7 +142,7 @@ class FlatArena(object):
             self.flat[o:o + n].copy_(p.data.reshape(-1))
             p.data = self.flat[o:o + n].view(p.shape)
             p.grad = self.grad[o:o + n].view(p.shape)
-            p._dv3_grad_inplace = not os.environ.get("DV3_NO_INPLACE_GRAD")   # ops.ConvLayerFn accumulates straight into p.grad
+            p._dv3_grad_inplace = True   # ops.ConvLayerFn accumulates straight into p.grad
 
     def rebind(self):
         """Every parameter's .grad must BE its slice of the gradient arena (clip/Adam and the all-reduce
@@ -216,16 +217,14 @@ class Trainer(object):
         # weight-norm backward of 8 layers per launch (ops.WnBwdBatch): opt-in (DV3_WN_BWD_BATCH=1).  Bit-identical, but
         # measured 2 % SLOWER in the step (15.62 vs 15.29 ms, nyanko bf16 11.79 vs 11.53): the per-layer launches
         # already overlap with the input-gradient chain on the side stream, a fat launch every 8 layers competes with it
-        self.batch_wn_bwd = os.environ.get("DV3_WN_BWD_BATCH", "0") == "1"
+        self.batch_wn_bwd = _env_flag("DV3_WN_BWD_BATCH", False)
         # second stream for the weight-gradient branch of backward (ops.SideStream); DV3_WGRAD_STREAM=0 keeps one stream
         # (a stream that shares no hardware queue with the step stream: ops.concurrent_stream)
         self.side_stream = None
         self.side_stream_beside = False
-        if dev.type == "cuda" and os.environ.get("DV3_WGRAD_STREAM", "1") not in ("0", ""):
+        if dev.type == "cuda" and _env_flag("DV3_WGRAD_STREAM", True):
             with torch.cuda.device(dev):
-                # DV3_SIDE_PRIORITY=low: the weight-gradient stream at the device's least stream priority (ops.new_stream)
-                self.side_stream = ops.concurrent_stream([torch.cuda.current_stream()], role="weight-gradient",
-                                                         priority=os.environ.get("DV3_SIDE_PRIORITY", "normal"))
+                self.side_stream = ops.concurrent_stream([torch.cuda.current_stream()], role="weight-gradient")
                 # did the probe SEE this stream run beside the step stream?  (GraphedTrainer.flag_sync needs that: a wait
                 # kernel on a queue it shares with its signal would sit out its time-out)
                 rec = ops.stream_probe_log[-1] if ops.stream_probe_log else {}
@@ -243,9 +242,9 @@ class Trainer(object):
             isolate = [i for i, p in enumerate(self.arena.params) if id(p) in shared]
             group_start = len(self.arena.params) - len(self.late_group) if self.late_group else None
             # the all-reduces are issued (asynchronously) from the weight-gradient stream itself: no collective stream of
-            # the trainer's own to share a hardware queue with (dist.BucketedAllReduce); DV3_COLLECTIVE_STREAM=own: the
-            # round-4 form (a probed fourth stream), kept for A/B runs
-            own = os.environ.get("DV3_COLLECTIVE_STREAM", "") == "own" or self.side_stream is None
+            # the trainer's own to share a hardware queue with (dist.BucketedAllReduce); without a weight-gradient stream:
+            # the round-4 form (a probed stream of the collectives' own)
+            own = self.side_stream is None
             self.comm = _dist.BucketedAllReduce(self.arena, process_group, bucket_mb, last_bucket_mb, isolate=isolate, boundaries=() if group_start is None else (group_start,),
                                                 beside=[st for st in (torch.cuda.current_stream() if dev.type == "cuda" else None,
                                                                       self.side_stream) if st is not None],
@@ -618,12 +617,10 @@ class GraphedTrainer(object):
         trainer.check_lengths(static_batch)
         dev = trainer.device
         if split_streams is None:
-            split_streams = trainer.side_stream is not None and os.environ.get("DV3_SPLIT_GRAPH", "1") not in ("0", "")
+            split_streams = trainer.side_stream is not None and _env_flag("DV3_SPLIT_GRAPH", True)
         self.split = bool(split_streams) and trainer.side_stream is not None
-        self.chunk = int(chunk or os.environ.get("DV3_SPLIT_CHUNK", "0"))      # 0: chosen after the warm-up steps
-        self.cut_on_bucket = os.environ.get("DV3_CUT_ON_BUCKET", "1") not in ("0", "")
-        self.tail_fine = int(os.environ.get("DV3_SPLIT_TAIL", "6"))     # the last N fork points end a segment each (0 = off)
-        self.head_fine = int(os.environ.get("DV3_SPLIT_HEAD", "0"))     # ... and the first N (0 = off)
+        self.chunk = int(chunk or _env_int("DV3_SPLIT_CHUNK", 0))      # 0: chosen after the warm-up steps
+        self.tail_fine = _env_int("DV3_SPLIT_TAIL", 6)     # the last N fork points end a segment each (0 = off)
         self.n_forks = 0
         # ABI 43 (round 6, last part): backward as ONE graph per stream, its fork points ordered by a device flag
         # (include/dv3hip.h: dv3_flag_signal / dv3_flag_wait) instead of segment boundaries.  Not under a process group:
@@ -637,17 +634,14 @@ class GraphedTrainer(object):
         # queues dynamically, and one bench process showed a replay of this form at 11 ms against 6.2 ms -- two graphs whose
         # streams share a queue run one after the other, where the segments only lose their overlap.  bench.py probes it per
         # configuration (like eager against the replay) and keeps it where it is the faster form in that process.
-        fs = os.environ.get("DV3_FLAG_SYNC", "0")
+        fs = _env_str("DV3_FLAG_SYNC", "0")
         small = int(static_batch.mel.size(0)) < 48
         self.flag_sync = (self.split and trainer.comm is None and
                           (fs == "1" or (fs not in ("0", "") and small and not ops.storage_c8() and
                                          getattr(trainer, "side_stream_beside", False))))
         self._flag = torch.zeros(4, dtype=torch.int64, device=dev) if self.flag_sync else None   # flag, epochs, err
         self._flag_checked = False
-        self.flag_lag = int(os.environ.get("DV3_FLAG_LAG", "0"))
-        # a signal kernel at every k-th fork point only (profiles/r06i_flag_sync.txt: k = 2 brings the bf16 presets to parity
-        # and B = 64 to -0.5 %, at -1.3 % instead of -1.8 % for B = 16, which is what the rule serves: k = 1)
-        self.flag_every = int(os.environ.get("DV3_FLAG_EVERY", "1"))
+        self._flag_timeout_ms = _env_int("DV3_FLAG_TIMEOUT_MS", 2000)
         self.seed_offset = torch.zeros(1, dtype=torch.int64, device=dev)
         self._prev_offset = ops.dropout_state.dev_offset        # restored by close()
         ops.dropout_state.dev_offset = self.seed_offset
@@ -697,8 +691,7 @@ class GraphedTrainer(object):
             # HBM-bound one) -- into buffers of this object, which the captured layers read
             self._mask_tables, self._mask_event, self.mask_offset = None, None, None
             mp = ops.mask_plan
-            if mp.enabled and mp.plan and ops.dropout_state.record is None and \
-                    os.environ.get("DV3_MASK_PREDRAW", "1") not in ("0", ""):
+            if mp.enabled and mp.plan and ops.dropout_state.record is None and _env_flag("DV3_MASK_PREDRAW", True):
                 mp.static, self._mask_tables = mp.build(dev, site0)
                 self._mask_buffers = mp.static            # (this object keeps the buffers alive: the replays read them)
                 self._mask_seed = ops.dropout_state.seed  # the seed the captured single-site launches carry too
@@ -742,7 +735,7 @@ class GraphedTrainer(object):
             self.seg_buckets.append(t.comm.take_completed() if t.comm is not None else [])
 
         flag = self._flag
-        timeout_ms = int(os.environ.get("DV3_FLAG_TIMEOUT_MS", "2000"))
+        timeout_ms = self._flag_timeout_ms
 
         def on_fork_flag():
             # the first fork point ends the graph of zero_grad + forward + losses (the replay orders the side graph after
@@ -756,21 +749,11 @@ class GraphedTrainer(object):
             if j >= 4096:
                 raise RuntimeError("GraphedTrainer(flag_sync): more than 4095 fork points in a step")
             p = flag.data_ptr()
-            k = self.flag_every
-            if k > 1 and self.n_forks >= j:
-                # a signal at every k-th fork point only (and at the first and the last): fewer one-thread kernels on the
-                # critical queue; a weight gradient then waits for the next signal at or after its own fork point
-                if j == 1 or j % k == 0 or j == self.n_forks:
-                    _lib.call("dv3_flag_signal", p, p + 8, j, int(j == 1), SS.main.cuda_stream)
-                jw = j if j == 1 else min(-(-j // k) * k, self.n_forks)
-                _lib.call("dv3_flag_wait", p, p + 16, jw, int(j == 1), p + 24, timeout_ms, side_raw)
-                return
+            # a signal at every fork point, and the weight gradient of fork point j waits for exactly that one (a signal at
+            # every k-th fork point only, or a wait that lags some fork points behind, measured no better where this form
+            # is used: profiles/r06i_flag_sync.txt)
             _lib.call("dv3_flag_signal", p, p + 8, j, int(j == 1), SS.main.cuda_stream)
-            # the weight gradient of fork point j starts when the step stream has reached fork point j + lag: the
-            # input-gradient chain is the critical path, and weight gradients that start the moment their operands exist
-            # take compute units from it (the segments' lag of one segment, without their boundaries)
-            jw = min(j + self.flag_lag, self.n_forks) if self.n_forks >= j else j
-            _lib.call("dv3_flag_wait", p, p + 16, jw, int(j == 1), p + 24, timeout_ms, side_raw)
+            _lib.call("dv3_flag_wait", p, p + 16, j, int(j == 1), p + 24, timeout_ms, side_raw)
 
         def on_fork():
             st["forks"] += 1
@@ -778,18 +761,15 @@ class GraphedTrainer(object):
             # issued from the host right after the segment it closes, not `chunk` layers later (nyanko's encoder, 49 MB in
             # five buckets, used to be final only with the last segment: 0.66 ms of exposed wait beside a ring stand-in,
             # profiles/r06_collective_standin.txt)
-            bucket_done = t.comm is not None and bool(t.comm._completed) and self.cut_on_bucket
+            bucket_done = t.comm is not None and bool(t.comm._completed)
             # the LAST forks one per segment (round 6): side segment j starts when step segment j has run to its end, so the
             # weight-gradient branch of the last segment has nothing left to run beside -- the step stream sat idle for
             # 0.46 ms before clip + Adam while the last four layers' weight gradients ran (profiles/r06a timeline); with
             # one-layer segments at the end only the last layer's is exposed
             tail = self.n_forks > 0 and self.n_forks - st["forks"] < self.tail_fine
-            # ... and the FIRST forks one per segment (round 6): segment 0 holds the whole forward, and side segment 0 starts
-            # when it ends -- with `chunk` layers of backward inside it the weight gradients of the model's LAST layers (the
-            # converter's: the largest of the step) waited for those layers' input-gradient chain to finish, 1.3-1.5 ms in
-            # which the step stream ran alone (profiles/r06_split_head.txt)
-            head = st["forks"] <= self.head_fine
-            if st["forks"] % self.chunk == 0 or bucket_done or tail or head:
+            # (the FIRST forks one per segment too, to start the weight-gradient queue 1.3-1.5 ms earlier, made every step
+            # slower: DESIGN.md section 5)
+            if st["forks"] % self.chunk == 0 or bucket_done or tail:
                 end_seg()
                 begin_seg()
 

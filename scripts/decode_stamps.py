@@ -10,7 +10,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from deepvoice3_pytorch_amd import builder, _lib  # noqa: E402
+from deepvoice3_pytorch_amd import builder, decode_program, _lib  # noqa: E402
 
 dev = torch.device("cuda:0")
 preset, B = "deepvoice3_ljspeech", int(sys.argv[1]) if len(sys.argv) > 1 else 64
@@ -27,7 +27,7 @@ with torch.no_grad():
 dec.min_decoder_steps = dec.max_decoder_steps = 30
 dec.persistent_decode = True
 for abl in (64, 64 + 1, 64 + 7):
-    os.environ["DV3_DECODE_ABLATE"] = str(abl)
+    decode_program.ablate = abl
     with torch.no_grad():
         for _ in range(2):
             dec.incremental_forward(enc, tpos)

@@ -11,7 +11,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from deepvoice3_pytorch_amd import builder  # noqa: E402
+from deepvoice3_pytorch_amd import builder, decode_program  # noqa: E402
 
 dev = torch.device("cuda:0")
 preset = sys.argv[1] if len(sys.argv) > 1 else "deepvoice3_ljspeech"
@@ -50,7 +50,7 @@ for label, persistent, graph, abl in (("library-launched chunks", "launched", Fa
                                       ("persistent, no fences", True, False, "1"),
                                       ("persistent, no barriers", True, False, "7"),
                                       ("launches, step graph", False, True, "0"), ("launches, eager", False, False, "0")):
-    os.environ["DV3_DECODE_ABLATE"] = abl
+    decode_program.ablate = int(abl)
     dec.persistent_decode, dec.use_step_graph = persistent is True, graph
     dec.launched_decode = persistent == "launched"
     a, b = run(40), run(200)

@@ -10,12 +10,10 @@ import tests.test_gpu_preset_scale as TS
 dev = torch.device("cuda:0")
 
 
-def run(label, mode, offset, fused=True, wtile=0, os_env=None):
+def run(label, mode, offset, fused=True, wtile=0):
     prev = ops.set_gemm_precision(mode)
     ops.fused_attention = fused
     _lib.call("dv3_debug_set", 2, wtile)
-    if os_env is not None:
-        os.environ["DV3_WGRAD_TILE"] = os_env
     ops.dropout_state.dev_offset = None if offset is None else torch.tensor([offset], dtype=torch.int64, device=dev)
     try:
         TS.test_preset_train_step_matches_oracle(dev, "nyanko_ljspeech", mode)
@@ -26,7 +24,6 @@ def run(label, mode, offset, fused=True, wtile=0, os_env=None):
         ops.set_gemm_precision(prev)
         ops.fused_attention = True
         _lib.call("dv3_debug_set", 2, 0)
-        os.environ.pop("DV3_WGRAD_TILE", None)
         ops.dropout_state.dev_offset = None
 
 
@@ -35,5 +32,5 @@ run("f16x3 offset 0", "f16x3", 0)
 run("f16x3 offset 3", "f16x3", 3)
 run("f32 offset 3", "f32", 3)
 run("f16x3 offset 3 unfused attention", "f16x3", 3, fused=False)
-run("f16x3 offset 3 per-tap wgrad", "f16x3", 3, wtile=1, os_env="1")
+run("f16x3 offset 3 per-tap wgrad", "f16x3", 3, wtile=1)
 run("f16x3 offset 5", "f16x3", 5)

@@ -1,7 +1,7 @@
 # coding: utf-8
 """Round 5: the three presets' step under a world-size-1 RCCL group (bench.ddp_world1_config) against the same step
-without a group, in one process: `collectives issued from the weight-gradient stream (async)` (default) and, with
-DV3_COLLECTIVE_STREAM=own, round 4's own collective stream.  Prints the `stream_queues` records."""
+without a group, in one process, the collectives issued from the weight-gradient stream (async).  Prints the
+`stream_queues` records.  (Round 4's own collective stream, which this script also timed, went with its switch.)"""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -26,5 +26,5 @@ for item in a.presets.split(","):
     out[preset + "_" + gemm] = r
     print(preset, gemm, "no group %.3f ms" % m["ms_per_step"],
           {k: (r[k].get("ms_per_step"), r[k].get("vs_no_group")) for k in ("eager", "hipgraph") if k in r}, flush=True)
-print(json.dumps(dict(collective_stream=os.environ.get("DV3_COLLECTIVE_STREAM", "issue from the weight-gradient stream"),
+print(json.dumps(dict(collective_stream="issue from the weight-gradient stream",
                       GPU_MAX_HW_QUEUES=os.environ.get("GPU_MAX_HW_QUEUES"), results=out)))
