@@ -1110,6 +1110,22 @@ def _slab_count(B, tiles):
     return max(s, 1)
 
 
+def wgrad_plan(B, Mg, Cin, Tg, Jd):
+    """-> (x3, S): does the weight gradient of a (Mg x Cin, Jd taps) layer over B items of Tg frames run on the split
+    kernels in the current GEMM mode (split_bf16 = k_split = x3), and into how many slabs is its sum cut.  The choice of
+    ConvLayerFn.backward; tests that mean "the automatic form" call this."""
+    tiles = ((Mg + 127) // 128) * ((Cin + 127) // 128) * Jd
+    x3 = _gemm_mode != "f32" and not (Mg <= 64 and Cin <= 64)
+    if x3 and Jd == 3:
+        # one 8-wave workgroup per (tile, slab) serves the three taps: one workgroup per CU
+        S = _ksplit_count(B * ((Tg + 31) // 32), tiles // 3, slots=256)
+    elif x3:   # split-K over contiguous (batch, chunk) ranges: size the grid to 2 workgroups per CU
+        S = _ksplit_count(B * ((Tg + 31) // 32), tiles)
+    else:
+        S = _slab_count(B, tiles)
+    return x3, S
+
+
 # ----------------------------------------------------------------------------------------------
 # autograd: one conv-like layer (Conv1dGLU / HighwayConv1d / 1x1 Conv1d(+act) / Linear /
 # ConvTranspose1d) = pack -> tap-GEMM(+fused tail); backward = gate_bwd -> DGRAD tap-GEMM ->
@@ -1522,15 +1538,7 @@ class ConvLayerFn(torch.autograd.Function):
             if gate is not None:
                 dx._dv3_gate = _GateResult(ctx.prod, gate, dx._version)
         if ctx.needs_input_grad[1]:
-            tiles = ((Mg + 127) // 128) * ((Cin + 127) // 128) * Jd
-            x3 = _gemm_mode != "f32" and not (Mg <= 64 and Cin <= 64)
-            if x3 and Jd == 3:
-                # one 8-wave workgroup per (tile, slab) serves the three taps: one workgroup per CU
-                S = _ksplit_count(B * ((Tg + 31) // 32), tiles // 3, slots=256)
-            elif x3:   # split-K over contiguous (batch, chunk) ranges: size the grid to 2 workgroups per CU
-                S = _ksplit_count(B * ((Tg + 31) // 32), tiles)
-            else:
-                S = _slab_count(B, tiles)
+            x3, S = wgrad_plan(B, Mg, Cin, Tg, Jd)
             slab_rows = slab_rows_default and S > 1
 
             def wgrad():

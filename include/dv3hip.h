@@ -220,11 +220,12 @@ int dv3_mask_bits_to_c8(const uint32_t* bits, int32_t bits_rs, uint8_t* out, int
 /*
  * Split-bf16 ("bf16x3") operand form.  The fp32 matrix cores run at 1/16 of the bf16 rate on
  * gfx950, so the GEMM kernels can instead write every fp32 operand as hi + lo with
- *   hi = bf16_rn(v), lo = bf16_rn(v - hi)        (|v - hi - lo| <= 2^-18 |v|)
+ *   hi = bf16_rn(v), lo = bf16_rn(v - hi)        (|v - hi - lo| <= 2^-17 |v|: half an ulp of lo, and reached)
  * and accumulate  A_lo*B_hi + A_hi*B_lo + A_hi*B_hi  in fp32 on v_mfma_f32_32x32x16_bf16:
- * three bf16 MFMAs per product block = 16/3 x the fp32-MFMA rate; the dropped terms bound the
- * relative error of a dot product by ~3*2^-18 of sum|a||b| -- inside the 1e-4 relative parity
- * bar of the reference comparison (tests/ measure it against fp64).
+ * three bf16 MFMAs per product block = 16/3 x the fp32-MFMA rate.  Per product the operand error is at most
+ * 2 * 2^-17 |a||b| and the dropped lo*lo term at most 2^-16 |a||b| (|lo| <= 2^-8 |v|): 2^-15 of sum|a||b| in the worst
+ * case, a few 2^-18 typically -- inside the 1e-4 relative parity bar of the reference comparison
+ * (tests/test_gpu_gemm_operands.py holds every element to the bound derived from these statements, against fp64).
  *
  * dv3_split_pack_bf16 converts a packed fp32 weight image [J][K][lda] (dv3_weight_norm_pack_f32's
  * fwd_pack / bwd_pack) into the layout the bf16x3 tap-GEMM stages with straight 16-byte copies:
@@ -234,11 +235,14 @@ int dv3_mask_bits_to_c8(const uint32_t* bits, int32_t bits_rs, uint8_t* out, int
  *
  * Scaled split-fp16 ("f16x3", dtype = DV3_SPLIT_DTYPE_F16): the same images with
  *   a = v * 2^s, hi = fp16_rn(clamp(a, +-65504)), lo = fp16_rn(a - hi)      (|a - hi - lo| <= 2^-23 |a|
- *   while |a| >= 2^-3; below that the error is absolute, <= 2^-25 in a-units)
+ *   while |a| >= 2^-2, where the residual is a normal fp16 value; below that the error is absolute, <= 2^-25 in
+ *   a-units: everywhere |a - hi - lo| <= max(2^-23 |a|, 2^-25).  fp16 SUBNORMALS ARE KEPT on gfx950, by the
+ *   fp32 -> fp16 conversion of dv3_split8_f16 and at the A / B inputs of the fp16 MFMA alike: measured -- operands
+ *   a = m 2^-16, w' = n 2^-10 give the exact integers in every kernel form, tests/test_gpu_gemm_operands.py family E2)
  * s = DV3_F16_WEIGHT_SHIFT (8) for weights, DV3_F16_ACT_SHIFT (4) for activations (fixed powers of two:
  * exact, no amax pass; weight-normed |w| <= |g| and O(1..100) activations sit far inside the range);
  * the accumulators carry 2^12 x the result and the epilogue multiplies by 2^-12 (exact).  The forward
- * tap-GEMM uses this form: at the preset model sizes the bf16 split's 2^-17 operands, amplified ~100x by
+ * tap-GEMM uses this form: at the preset model sizes the bf16 split's 2^-17-class operands, amplified ~100x by
  * the depth of the network, exceed the 1e-4 parity bar (tests/test_gpu_preset_scale.py measures both);
  * the gradient GEMMs keep the bf16 split, whose exponent range covers gradients without a scale search.
  */
