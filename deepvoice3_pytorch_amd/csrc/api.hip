@@ -1,4 +1,4 @@
-// Error plumbing + library identity for libdv3hip.so.
+// Error plumbing, library identity and the run-time debug switches of libdv3hip.so.
 #include "common.h"
 #include <atomic>
 #include <mutex>
@@ -170,6 +170,61 @@ extern "C" int dv3_debug_get(int what) {
   return 0;
 }
 
+// Run-time switches for measurement and bit-identity tests (include/dv3hip.h), each an int defined beside the host code
+// that reads it.  An unknown code is an error: a script that names a retired switch must not time the production kernel
+// believing it timed something else.
+extern int g_x3_pingpong, g_x3_rel2, g_x3_pp2, g_x3_prio, g_x3_wide, g_x3_pp2_sk_units, g_x3_j1_flat, g_x3_rel8;   // conv_gemm_bf16x3.hip
+extern int g_x3_ks, g_x3_ks_max_blocks, g_x3_ks_min_steps;                                       // conv_gemm_bf16x3.hip
+extern int g_pp2_ord_u, g_pp2_ord_m, g_pp2_sk, g_pp2_sk_overhead, g_pp2_sk_gain, g_pp2_fast_tail;   // conv_gemm_pp2.hip
+extern int g_planes_tile;                                                                        // conv_planes.hip
+extern int g_c8pp_min_tiles, g_c8pp_rf, g_c8pp_nw4, g_c8pp_stagger, g_c8pp_stagger_mask;          // conv_c8pp.hip
+extern int g_wgrad_tile, g_wgrad_prio, g_wgrad_taps2_default, g_wgrad_t2_window, g_wgrad_t2_il;   // wgrad_gemm_bf16x3.hip, wgrad_taps2.hip
+extern int g_wgrad_c8_pf2, g_wgrad_c8_il, g_wgrad_c8_tr;                                         // wgrad_c8.hip
+extern int g_spk_prefetch;                                                                       // speaker_bias.hip
+extern int g_gate_c8_fast, g_gate_vec;                                                           // elementwise.hip
+extern int g_loss_fast_log;                                                                      // loss.hip
+extern int g_wn_bwd_vec4;                                                                        // weight_norm.hip
+int dv3_conv_census_set(int on);                 // conv_gemm.hip
+extern "C" int dv3_debug_set(int what, int value) {
+  if (what == 40) return dv3_conv_census_set(value);
+  if (what == 29 || what == 31) {   // ORD of the 256 x 256 kernel's unmasked / masked instantiations: the shipped forms
+    DV3_REQUIRE(value == 0 || value == 17 || value == 81, "debug_set(%d, %d): LOAD-phase order 0, 17 or 81", what, value);
+    (what == 29 ? g_pp2_ord_u : g_pp2_ord_m) = value;
+    return DV3_OK;
+  }
+  DV3_REQUIRE(what != 52 || (value >= 0 && value <= 4), "debug_set(52, %d): wgrad_c8 form 0..4", value);
+  static const struct {
+    int what;
+    int* var;
+  } kSwitches[] = {
+      {2, &g_wgrad_tile},        {3, &g_x3_pingpong},         {4, &g_planes_tile},      {9, &g_x3_rel2},
+      {12, &g_x3_pp2},           {14, &g_x3_prio},            {15, &g_wgrad_prio},      {17, &g_wgrad_taps2_default},
+      {18, &g_x3_wide},          {19, &g_c8pp_min_tiles},     {20, &g_wgrad_c8_pf2},    {22, &g_pp2_sk},
+      {23, &g_pp2_sk_overhead},  {24, &g_pp2_sk_gain},        {25, &g_x3_pp2_sk_units}, {27, &g_x3_j1_flat},
+      {30, &g_c8pp_rf},          {34, &g_c8pp_nw4},           {35, &g_c8pp_stagger},    {36, &g_c8pp_stagger_mask},
+      {42, &g_x3_rel8},          {44, &g_x3_ks},              {45, &g_x3_ks_max_blocks}, {46, &g_x3_ks_min_steps},
+      {47, &g_wgrad_t2_window},  {48, &g_wgrad_t2_il},        {49, &g_wgrad_c8_il},     {50, &g_pp2_fast_tail},
+      {51, &g_wn_bwd_vec4},      {52, &g_wgrad_c8_tr},        {54, &g_spk_prefetch},    {55, &g_gate_vec},
+      {56, &g_gate_c8_fast},     {57, &g_loss_fast_log},
+  };
+  for (const auto& sw : kSwitches)
+    if (sw.what == what) {
+      *sw.var = value;
+      return DV3_OK;
+    }
+  dv3_set_error("debug_set(%d, %d): no such switch", what, value);
+  return DV3_EINVAL;
+}
+
+int dv3_decode_read_stamps(void* dst, int64_t bytes);  // decode_step.hip
+int dv3_conv_census_read(int what, void* dst, int64_t bytes);   // conv_gemm.hip
+extern "C" int dv3_debug_read(int what, void* dst, int64_t bytes) {
+  if (what == 40 || what == 41) return dv3_conv_census_read(what, dst, bytes);
+  if (what == 3 && dst) return dv3_decode_read_stamps(dst, bytes);
+  dv3_set_error("debug_read(%d): no such buffer", what);
+  return DV3_EINVAL;
+}
+
 extern "C" const char* dv3_last_error(void) { return g_err; }
 extern "C" int dv3_abi_version(void) { return DV3_ABI_VERSION; }
 
@@ -199,7 +254,6 @@ extern "C" int dv3_sizeof(const char* name) {
   DV3_SZ(dv3_softmax_desc);
   DV3_SZ(dv3_softmax_bwd_desc);
   DV3_SZ(dv3_spec_loss_desc);
-  DV3_SZ(dv3_planes_desc);
   DV3_SZ(dv3_wn_multi_entry);
   DV3_SZ(dv3_conv_step_desc);
   DV3_SZ(dv3_attn_step_desc);

@@ -99,7 +99,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_c8pp_kernel(con
   const int k8_total = args.kp >> 3;                        // == p.x_c8p
   const int nchunks = args.kp >> 5;
   const bf16x8* __restrict__ Wh = reinterpret_cast<const bf16x8*>(p.a_split);
-  const bf16x8* __restrict__ XP = reinterpret_cast<const bf16x8*>(p.x_planes);
+  const bf16x8* __restrict__ XP = reinterpret_cast<const bf16x8*>(p.x_c8);
   const uint8_t* __restrict__ const xkeep = p.xmask_c8;
   const int n_items = KB * BNH;
 
@@ -381,7 +381,7 @@ int g_c8pp_min_tiles = 128;   // dv3_debug_set(19, v): the 256 x 256 c8 kernel s
 // Called by dv3_conv_planes_dispatch (conv_planes.hip) for single-term bf16 layers on c8 input.  Returns 1 when the
 // shape is not eligible (the caller continues with the 128-row planes kernel), else a DV3_* code.
 int dv3_conv_c8pp_dispatch(const dv3_conv_desc* d, hipStream_t st) {
-  if (g_c8pp_min_tiles <= 0 || d->split_terms != 1 || !d->a_split || !d->x_planes) return 1;
+  if (g_c8pp_min_tiles <= 0 || d->split_terms != 1 || !d->a_split || !d->x_c8) return 1;
   if ((d->J != 1 && d->J != 3) || (d->J - 1) * d->dil > HALO_MAX) return 1;
   if (d->a_bs != 0 || (d->lda & 3) || d->Tin != d->Tout) return 1;
   const bool gated = d->mode == DV3_EPI_GLU || d->mode == DV3_EPI_HIGHWAY;

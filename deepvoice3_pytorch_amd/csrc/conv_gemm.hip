@@ -346,9 +346,10 @@ extern "C" int dv3_conv_gemm_f32(const dv3_conv_desc* d, void* stream) {
   return rc;
 }
 static int conv_gemm_dispatch(const dv3_conv_desc* d, void* stream) {
-  DV3_REQUIRE(d && (d->x || d->x_planes) && (d->a || d->a_split) && d->y, "conv_gemm: null pointer");
+  DV3_REQUIRE(d && (d->x || d->x_c8) && (d->a || d->a_split) && d->y, "conv_gemm: null pointer");
   DV3_REQUIRE(d->B > 0 && d->Cin > 0 && d->Tin > 0 && d->M > 0 && d->Tout > 0, "conv_gemm: bad dims");
   DV3_REQUIRE(d->J >= 1 && d->J <= 16 && d->dil >= 1, "conv_gemm: bad taps J=%d dil=%d", d->J, d->dil);
+  DV3_REQUIRE(!d->x_c8 || d->split_terms == 1, "conv_gemm: a c8 input is read by the single-term bf16 kernels (split_terms == 1)");
   const bool a_scalar = (d->lda & 3) || (d->a_half & 3) || (d->a_bs & 3) || ((uintptr_t)d->a & 15);
   const bool gated = d->mode == DV3_EPI_GLU || d->mode == DV3_EPI_HIGHWAY;
   if (gated) {
@@ -383,14 +384,14 @@ static int conv_gemm_dispatch(const dv3_conv_desc* d, void* stream) {
     DV3_REQUIRE(!d->ymask_c8, "conv_gemm: ymask_c8 belongs to a c8 DGRAD output");
   }
   DV3_REQUIRE(!d->ymask_c8 || d->mode == DV3_EPI_DGRAD, "conv_gemm: ymask_c8 is a DGRAD input");
-  // keep-bytes mask a c8 input (x_planes, split_terms == 1), or accompany the keep-bits of an fp32 input (the
+  // keep-bytes mask a c8 input (x_c8), or accompany the keep-bits of an fp32 input (the
   // 256 x 256 split kernel stages the byte form, the others the bit form: both must describe the same decisions)
   DV3_REQUIRE(!d->xmask_c8 || d->mode != DV3_EPI_DGRAD, "conv_gemm: xmask_c8 masks the input of a forward layer");
-  DV3_REQUIRE(!d->xmask_c8 || (d->x_planes && d->split_terms == 1) || (!d->x_planes && d->xmask && d->a_split),
+  DV3_REQUIRE(!d->xmask_c8 || d->x_c8 || (d->xmask && d->a_split),
               "conv_gemm: xmask_c8 needs a c8 input, or an fp32 input with its keep-bits and a split weight image");
   // round 6: the producer's gate backward in the input-gradient tail / pair-word input (include/dv3hip.h)
   if (d->pg) {
-    DV3_REQUIRE(d->mode == DV3_EPI_DGRAD && d->store_mode == DV3_STORE_BCT && d->io_bf16 == 0 && !d->x_planes,
+    DV3_REQUIRE(d->mode == DV3_EPI_DGRAD && d->store_mode == DV3_STORE_BCT && d->io_bf16 == 0 && !d->x_c8,
                 "conv_gemm: pg rides on an fp32 (B, C, T) input-gradient launch");
     DV3_REQUIRE(d->a_split && d->split_terms != 1 && (d->tile_hint == 0 || d->tile_hint > 20),
                 "conv_gemm: pg is served by the three-term split kernels");
@@ -402,15 +403,15 @@ static int conv_gemm_dispatch(const dv3_conv_desc* d, void* stream) {
                 "conv_gemm: the producer's pre-gate pair exceeds the 4 GB the epilogue can address");
   }
   if (d->x_pair)
-    DV3_REQUIRE(d->a_split && (d->split_terms == 0 || d->split_terms == 3) && !d->xmask && !d->xmask_c8 && !d->x_planes &&
+    DV3_REQUIRE(d->a_split && (d->split_terms == 0 || d->split_terms == 3) && !d->xmask && !d->xmask_c8 && !d->x_c8 &&
                 d->io_bf16 == 0 && (d->tile_hint == 0 || d->tile_hint > 20),
                 "conv_gemm: pair-word input is read by the bf16-pair split kernels, without dropout");
-  // both operands pre-split: the persistent planes kernel.  No silent fallback: the planes carry the dropout
-  // mask of the consuming layer, which the other kernels would have to be handed separately.
-  if (d->x_planes) {
-    DV3_REQUIRE(!d->xmask, "conv_gemm: x_planes already carry the dropout mask (xmask must be NULL)");
+  // a c8 bf16 input: the 256 x 256 conv_c8pp kernel or the persistent planes kernel (conv_planes.hip), single-term
+  // bf16 both.  No fallback: the other kernels read an fp32 (B, C, T) input.
+  if (d->x_c8) {
+    DV3_REQUIRE(!d->xmask, "conv_gemm: the dropout mask of a c8 input is xmask_c8 (xmask must be NULL)");
     const int rc = dv3_conv_planes_dispatch(d, (hipStream_t)stream);
-    DV3_REQUIRE(rc != 1, "conv_gemm: shape not eligible for the planes kernel (needs a_split, Tin == Tout, "
+    DV3_REQUIRE(rc != 1, "conv_gemm: shape not eligible for the c8 kernels (needs a_split, Tin == Tout, "
                          "(J-1)*dil <= 64, x_c8p == round_up(Cin,32)/8)");
     return rc;
   }

@@ -37,6 +37,19 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
+// Run-time switches of this file's launchers and tile picker (set through dv3_debug_set, api.hip)
+// main loop of the 8-wave tiles, dv3_debug_set(3, v): 0 = in-phase, 1 = ping-pong (default)
+int g_x3_pingpong = 1;
+int g_x3_ks = 1;        // dv3_debug_set(44, v): k-split form of the 128 x 64 tile: 0 never, 1 by the rule in the dispatcher, 2 wherever eligible
+int g_x3_ks_max_blocks = 256, g_x3_ks_min_steps = 8;   // dv3_debug_set(45 / 46, v): the rule's bounds
+int g_x3_rel8 = 86;     // dv3_debug_set(42, v): relative cost (percent) of the 256 x 128 ping-pong tile in the tile picker (pick_tile_x3).  Rounds 2-4: 93
+                        // (north-star sweep).  Round 5's census of a real step (profiles/r05_conv_census_dv3lj_b64.txt) has it ahead
+                        // of the 128 x 256 tile stand-alone wherever the two tie on rounds (the encoder's input gradients, the
+                        // 1 x 1 layers at T = 804); whole steps at 86: 15.56 -> 15.45 ms at B = 64, 7.75 -> 7.71 at B = 16
+                        // (profiles/r05_rel8_step_ab.txt)
+int g_x3_j1_flat = 1;   // dv3_debug_set(27, v)
+int g_x3_rel2 = 112;   // dv3_debug_set(9, v): relative cost (percent) of the 128x64 tile in the tile picker (pick_tile_x3)
+
 namespace {
 
 constexpr int BKC = 32;        // channels per K chunk
@@ -655,8 +668,6 @@ int launch_x3_m(const ConvArgs& a, size_t lds, hipStream_t st) {
   hipLaunchKernelGGL((conv_gemm_bf16x3_kernel<WM, WN, NI, MASK, TERMS, MI, PP, F16, KS, FG>), grid, block, lds * KS, st, a);
   return dv3_check_launch("conv_gemm_bf16x3");
 }
-// main loop of the 8-wave tiles, dv3_debug_set(3, v): 0 = in-phase, 1 = ping-pong (default)
-int g_x3_pingpong = 1;
 template <int WM, int WN, int NI, int MI, bool PP>
 int launch_x3_big_pp(const ConvArgs& a, size_t lds, hipStream_t st) {
   if (a.d.split_terms == DV3_SPLIT_F16X3)
@@ -689,15 +700,6 @@ int launch_x3(const ConvArgs& a, size_t lds, hipStream_t st) {
   return a.d.xmask ? launch_x3_m<WM, WN, NI, true, 3>(a, lds, st) : launch_x3_m<WM, WN, NI, false, 3>(a, lds, st);
 }
 
-int g_x3_ks = 1;        // dv3_debug_set(44, v): k-split form of the 128 x 64 tile: 0 never, 1 by the rule in the dispatcher, 2 wherever eligible
-int g_x3_ks_max_blocks = 256, g_x3_ks_min_steps = 8;   // dv3_debug_set(45 / 46, v): the rule's bounds
-int g_x3_rel8 = 86;     // dv3_debug_set(42, v): relative cost (percent) of the 256 x 128 ping-pong tile in the picker below.  Rounds 2-4: 93
-                        // (north-star sweep).  Round 5's census of a real step (profiles/r05_conv_census_dv3lj_b64.txt) has it ahead
-                        // of the 128 x 256 tile stand-alone wherever the two tie on rounds (the encoder's input gradients, the
-                        // 1 x 1 layers at T = 804); whole steps at 86: 15.56 -> 15.45 ms at B = 64, 7.75 -> 7.71 at B = 16
-                        // (profiles/r05_rel8_step_ab.txt)
-int g_x3_j1_flat = 1;   // dv3_debug_set(27, v)
-int g_x3_rel2 = 112;   // dv3_debug_set(9, v): relative cost (percent) of the 128x64 tile in the picker below
 // bf16x3 tile choice: padded work over the FLAT column axis, weight-panel traffic penalised
 // (a block re-reads its A panel every K step, so narrow column tiles starve the matrix pipe).
 const TileCfg* pick_tile_x3(const dv3_conv_desc* d, bool gated, int want_tile) {
@@ -761,8 +763,7 @@ int dv3_conv_gemm_bf16x3_dispatch(const dv3_conv_desc* d, hipStream_t st) {
   if (d->xmask && (int64_t)d->B * d->Cin * d->xmask_rs >= (1ll << 30)) return 1;
   if ((int64_t)d->J * ((d->Cin + 31) / 32 * 4) * d->lda >= (1ll << 27)) return 1;
   // 256 x 256 tile, k16 ping-pong (conv_gemm_pp2.hip): tile_hint 30 forces it, dv3_debug_set(12, 1) prefers it
-  const bool gated0 = d->mode == DV3_EPI_GLU || d->mode == DV3_EPI_HIGHWAY;
-  const int64_t pp2_tiles = (int64_t)(gated0 ? dv3_cdiv(d->Cg, 128) : dv3_cdiv(d->M, 256)) * dv3_cdiv64((int64_t)d->B * d->Tout, 256);
+  const int64_t pp2_tiles = (int64_t)(gated ? dv3_cdiv(d->Cg, 128) : dv3_cdiv(d->M, 256)) * dv3_cdiv64((int64_t)d->B * d->Tout, 256);
   // with a stream-K workspace the 256 x 256 kernel no longer needs a grid that fills the chip: enough (tile, chunk)
   // units for every CU instead (g_x3_pp2_sk_units per CU, dv3_debug_set(25, v))
   const bool sk_fill = d->sk_ws && g_pp2_sk && (d->mode != DV3_EPI_DGRAD || g_pp2_sk >= 2) && g_x3_pp2 > 0 && pp2_tiles * (d->Cin / 32) >= (int64_t)g_x3_pp2_sk_units * 256;
@@ -832,58 +833,6 @@ int dv3_conv_gemm_bf16x3_dispatch(const dv3_conv_desc* d, hipStream_t st) {
     case 9: return launch_x3_big<2, 4, 2, 1>(a, lds, st);
   }
   return 1;
-}
-
-extern int g_wgrad_tile, g_wgrad_prio, g_wgrad_taps2_default, g_wgrad_t2_window, g_wgrad_t2_il;   // wgrad_gemm_bf16x3.hip, wgrad_taps2.hip
-extern int g_wgrad_c8_pf2, g_wgrad_c8_il, g_wgrad_c8_tr;                                      // wgrad_c8.hip
-extern int g_c8pp_min_tiles, g_c8pp_rf, g_c8pp_nw4, g_c8pp_stagger, g_c8pp_stagger_mask;       // conv_c8pp.hip
-extern int g_spk_prefetch;                                                                    // speaker_bias.hip
-extern int g_gate_c8_fast, g_gate_vec;                                                        // elementwise.hip
-extern int g_loss_fast_log;                                                                   // loss.hip
-extern int g_wn_bwd_vec4;                                                                     // weight_norm.hip
-int dv3_planes_debug_set(int what, int value);   // conv_planes.hip
-int dv3_conv_census_set(int on);                 // conv_gemm.hip
-// Run-time switches for measurement and bit-identity tests (include/dv3hip.h).  An unknown code is an error: a script
-// that names a retired switch must not time the production kernel believing it timed something else.
-extern "C" int dv3_debug_set(int what, int value) {
-  if (what == 4 || what == 5 || what == 7 || what == 8) return dv3_planes_debug_set(what, value);
-  if (what == 40) return dv3_conv_census_set(value);
-  if (what == 29 || what == 31) {   // ORD of the 256 x 256 kernel's unmasked / masked instantiations: the shipped forms
-    DV3_REQUIRE(value == 0 || value == 17 || value == 81, "debug_set(%d, %d): LOAD-phase order 0, 17 or 81", what, value);
-    (what == 29 ? g_pp2_ord_u : g_pp2_ord_m) = value;
-    return DV3_OK;
-  }
-  DV3_REQUIRE(what != 52 || (value >= 0 && value <= 4), "debug_set(52, %d): wgrad_c8 form 0..4", value);
-  static const struct {
-    int what;
-    int* var;
-  } kSwitches[] = {
-      {2, &g_wgrad_tile},        {3, &g_x3_pingpong},         {9, &g_x3_rel2},          {12, &g_x3_pp2},
-      {14, &g_x3_prio},          {15, &g_wgrad_prio},         {17, &g_wgrad_taps2_default}, {18, &g_x3_wide},
-      {19, &g_c8pp_min_tiles},   {20, &g_wgrad_c8_pf2},       {22, &g_pp2_sk},          {23, &g_pp2_sk_overhead},
-      {24, &g_pp2_sk_gain},      {25, &g_x3_pp2_sk_units},    {27, &g_x3_j1_flat},      {30, &g_c8pp_rf},
-      {34, &g_c8pp_nw4},         {35, &g_c8pp_stagger},       {36, &g_c8pp_stagger_mask}, {42, &g_x3_rel8},
-      {44, &g_x3_ks},            {45, &g_x3_ks_max_blocks},   {46, &g_x3_ks_min_steps}, {47, &g_wgrad_t2_window},
-      {48, &g_wgrad_t2_il},      {49, &g_wgrad_c8_il},        {50, &g_pp2_fast_tail},   {51, &g_wn_bwd_vec4},
-      {52, &g_wgrad_c8_tr},      {54, &g_spk_prefetch},       {55, &g_gate_vec},        {56, &g_gate_c8_fast},
-      {57, &g_loss_fast_log},
-  };
-  for (const auto& sw : kSwitches)
-    if (sw.what == what) {
-      *sw.var = value;
-      return DV3_OK;
-    }
-  dv3_set_error("debug_set(%d, %d): no such switch", what, value);
-  return DV3_EINVAL;
-}
-
-int dv3_decode_read_stamps(void* dst, int64_t bytes);  // decode_step.hip
-int dv3_conv_census_read(int what, void* dst, int64_t bytes);   // conv_gemm.hip
-extern "C" int dv3_debug_read(int what, void* dst, int64_t bytes) {
-  if (what == 40 || what == 41) return dv3_conv_census_read(what, dst, bytes);
-  if (what == 3 && dst) return dv3_decode_read_stamps(dst, bytes);
-  dv3_set_error("debug_read(%d): no such buffer", what);
-  return DV3_EINVAL;
 }
 
 extern "C" int dv3_split_pack_bf16(const float* packed, uint16_t* out, int32_t J, int32_t K,

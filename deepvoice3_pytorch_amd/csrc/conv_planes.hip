@@ -1,9 +1,14 @@
-// Persistent "planes" tap-GEMM: the dilated 1-D convolution + fused Conv1dGLU / HighwayConv1d / DGRAD tail of
-// conv_gemm_bf16x3.hip (reference semantics: deepvoice3_pytorch/modules.py:145-164, 205-226, and its autograd),
-// for the case where BOTH operands arrive already split into 16-bit operand planes:
-//   weights      dv3_split_pack_bf16 / dv3_weight_norm_split_pack_bf16 image  [plane][j][k8][m][8]
-//   activations  dv3_split_planes_f32 layout (or a producing epilogue)        [plane][b][c8][t][8]
-// so staging is plain 16-byte copies (no conversion, no dropout work: the producer applied the keep-bits).
+// Persistent single-term bf16 tap-GEMM on c8 tensors, and the home of the c8 layout converters.
+//
+// The dilated 1-D convolution + fused Conv1dGLU / HighwayConv1d / DGRAD tail of conv_gemm_bf16x3.hip (reference
+// semantics: deepvoice3_pytorch/modules.py:145-164, 205-226, and its autograd) for the bf16 GEMM mode, where both
+// operands arrive as bf16 in the layouts the MFMA fragments are cut from:
+//   weights      the hi plane of a dv3_split_pack_bf16 / dv3_weight_norm_split_pack_bf16 image  [j][k8][m][8]
+//   activations  a c8 tensor (dv3_to_c8_f32 or a c8 epilogue), dv3_conv_desc.x_c8                [b][c8][t][8]
+// so staging is plain 16-byte copies; dropout, where the layer has one, is a keep-byte per unit (xmask_c8) applied
+// while staging.  One bf16 MFMA per product (split_terms == 1): variant family 8 of dv3_debug_get(10).  It serves the
+// shapes below the 256 x 256 conv_c8pp kernel's grid threshold.  (Round 1 wrote this kernel with three-term hi/lo forms
+// on fp32 inputs split by a pass of their own; they gave no gain and were removed at ABI 47: DESIGN.md 3.3.)
 //
 // What differs from the ping-pong kernel, and why:
 //   * persistent workgroups: the grid is sized to the chip (two 4-wave workgroups per CU for the 128-column
@@ -12,8 +17,8 @@
 //     (residual reads, y / pre-gate stores) overlaps them instead of a cold prologue after a fresh dispatch.
 //   * the second co-resident workgroup of a CU starts half a tile late (args.stagger), so one workgroup's tail
 //     runs beside the other's main loop instead of both idling the matrix pipes together.
-//   * fragments are double-buffered in REGISTERS at half-step (k16) granularity: while the 12 MFMAs of one k16
-//     block issue, the 8 fragment reads of the next block are in flight, across step boundaries.  LDS tiles are
+//   * fragments are double-buffered in REGISTERS at half-step (k16) granularity: while the 2 NI MFMAs of one k16
+//     block issue, the 2 + NI fragment reads of the next block are in flight, across step boundaries.  LDS tiles are
 //     double-buffered (weights per step, activations per chunk); with every LDS write placed in the second half
 //     of a step one barrier per step (in its middle) orders all reads and writes:
 //        step s, first half : read frags (s, q=1) | MFMA (s, q=0)                          | barrier
@@ -30,8 +35,6 @@
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 int dv3_conv_c8pp_dispatch(const dv3_conv_desc* d, hipStream_t st);   // conv_c8pp.hip
@@ -41,12 +44,8 @@ namespace {
 constexpr int KB = 4;          // k8 blocks per 32-channel chunk
 constexpr int HALO_MAX = 64;   // (J-1)*dil supported by the register staging (model max: 2*27)
 
-template <bool F16>
 __device__ __forceinline__ f32x16 mma16(const bf16x8& a, const bf16x8& b, const f32x16& c) {
-  if constexpr (F16)
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 template <typename T>
 __device__ __forceinline__ T ldg_off(const void* base, uint32_t byte_off) {
@@ -68,7 +67,7 @@ __device__ __forceinline__ bf16x8 keep8(const bf16x8& v, uint32_t m) {
 
 template <int NI>
 struct Frags {
-  bf16x8 ah[2], al[2], bh[NI], bl[NI];
+  bf16x8 ah[2], bh[NI];
 };
 
 // compile-time loop over the taps of one chunk
@@ -104,25 +103,22 @@ __device__ __forceinline__ void interleave() {
 #undef DV3_SGB_SLOT
 }
 
-template <int WM, int WN, int NI, int TERMS, bool F16, int JT = 0>
+template <int WM, int WN, int NI, int JT>
 __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvArgs args) {
-  static_assert(!F16 || TERMS == 3, "the fp16 form is the three-term split");
   constexpr int BM = WM * 64, BMH = WM * 32, BN = WN * NI * 32, NT = WM * WN * 64;
-  constexpr int PL = TERMS == 3 ? 2 : 1;                    // operand planes in use
-  constexpr int AU = KB * BM / NT;                          // A units per plane per thread per step
-  constexpr int XI = (KB * (BN + HALO_MAX) + NT - 1) / NT;  // X units per plane per thread per chunk
+  constexpr int AU = KB * BM / NT;                          // A units per thread per step
+  constexpr int XI = (KB * (BN + HALO_MAX) + NT - 1) / NT;  // X units per thread per chunk
   static_assert(KB * BM % NT == 0, "A panel must split evenly");
   const dv3_conv_desc& p = args.d;
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int J = p.J, dil = p.dil;
   const int BNH = BN + (J - 1) * dil;
-  bf16x8* const As = reinterpret_cast<bf16x8*>(smem_raw);   // [2 buffers][PL][KB][BM]
-  // [2 buffers][PL][XPS]: a plane holds [KB][BNH] units and is padded to XPS = XI * NT, so that every thread
+  bf16x8* const As = reinterpret_cast<bf16x8*>(smem_raw);   // [2 buffers][KB][BM]
+  // [2 buffers][XPS]: a buffer holds [KB][BNH] units and is padded to XPS = XI * NT, so that every thread
   // stores all of its XI staged units unconditionally (no exec-masked branch in the steady-state block)
   constexpr int XPS = XI * NT;
-  bf16x8* const Xs = As + 2 * PL * KB * BM;
-  constexpr int xbuf = PL * XPS;
+  bf16x8* const Xs = As + 2 * KB * BM;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -137,9 +133,13 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvA
   const int nchunks = args.kp >> 5;
   const int nsteps = nchunks * J;
   const bf16x8* __restrict__ Wh = reinterpret_cast<const bf16x8*>(p.a_split);
-  const int64_t wplane = (int64_t)J * k8_total * lda;       // 16-byte units per weight plane
-  const bf16x8* __restrict__ XP = reinterpret_cast<const bf16x8*>(p.x_planes);
-  const int64_t xplane = (int64_t)B * k8_total * T;         // 16-byte units per activation plane
+  const bf16x8* __restrict__ XP = reinterpret_cast<const bf16x8*>(p.x_c8);
+  // Code-generation anchors, not data: the sizes of one weight / activation image, which the three-term form used as
+  // plane strides.  They enter the fetch addresses below times zero.  Without them the compiler allocates registers
+  // and schedules all nine instantiations differently (1-2 % other code sizes); with them the device code is
+  // instruction for instruction what was measured and tested since round 2, so they stay until a re-measurement.
+  const int64_t wimage = (int64_t)J * k8_total * lda;
+  const int64_t ximage = (int64_t)B * k8_total * T;
   const int n_items = KB * BNH;
   const int a_off = wm * 32 + l31;
   const int x_off = wn * (NI * 32) + l31;
@@ -150,12 +150,12 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvA
     for (int i = 0; i < args.stagger; ++i) __builtin_amdgcn_s_sleep(127);
   }
 
-  uint32_t xoff[XI];   // byte offset of unit (b, k8, t) inside a plane, chunk 0
+  uint32_t xoff[XI];   // byte offset of unit (b, k8, t) inside the tensor, chunk 0
   uint32_t aoff[AU];   // byte offset of this thread's weight units inside a (tap, chunk) panel row
-  bf16x8 ra[PL][AU], rx[PL][XI];
-  // bf16 storage (single-term kernel): the c8 input may carry dropout keep-bytes, one per unit (uniform pointer)
-  const uint8_t* __restrict__ const xkeep = TERMS == 1 ? p.xmask_c8 : nullptr;
-  uint32_t rk[TERMS == 1 ? XI : 1];
+  bf16x8 ra[AU], rx[XI];
+  // the c8 input may carry dropout keep-bytes, one per unit (uniform pointer)
+  const uint8_t* __restrict__ const xkeep = p.xmask_c8;
+  uint32_t rk[XI];
 
   auto tile_offsets = [&](int mt, int n0) {
     int h0b, h1b;
@@ -186,59 +186,44 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvA
   auto load_A = [&](int c, int j) {
     const bf16x8* src = Wh + (int64_t)(j * k8_total + c * KB) * lda;  // uniform
 #pragma unroll
-    for (int pl = 0; pl < PL; ++pl)
-#pragma unroll
-      for (int u = 0; u < AU; ++u) ra[pl][u] = ldg_off<bf16x8>(src + pl * wplane, aoff[u]);
+    for (int u = 0; u < AU; ++u) ra[u] = ldg_off<bf16x8>(src + 0 * wimage, aoff[u]);
   };
   auto write_A = [&](int buf) {
-    bf16x8* dst = As + buf * (PL * KB * BM);
+    bf16x8* dst = As + buf * (KB * BM);
 #pragma unroll
-    for (int pl = 0; pl < PL; ++pl)
-#pragma unroll
-      for (int u = 0; u < AU; ++u) dst[pl * KB * BM + tid + u * NT] = ra[pl][u];
+    for (int u = 0; u < AU; ++u) dst[tid + u * NT] = ra[u];
   };
   auto load_X = [&](int c) {
     const bf16x8* src = XP + (int64_t)c * KB * T;                     // uniform: chunk c = 4 k8 blocks further
 #pragma unroll
-    for (int pl = 0; pl < PL; ++pl)
-#pragma unroll
-      for (int i = 0; i < XI; ++i) rx[pl][i] = ldg_off<bf16x8>(src + pl * xplane, xoff[i]);
-    if (TERMS == 1 && xkeep) {
+    for (int i = 0; i < XI; ++i) rx[i] = ldg_off<bf16x8>(src + 0 * ximage, xoff[i]);
+    if (xkeep) {
       const uint8_t* mk = xkeep + (int64_t)c * KB * T;
 #pragma unroll
-      for (int i = 0; i < XI; ++i) rk[TERMS == 1 ? i : 0] = ldg_off<uint8_t>(mk, xoff[i] >> 4);
+      for (int i = 0; i < XI; ++i) rk[i] = ldg_off<uint8_t>(mk, xoff[i] >> 4);
     }
   };
   auto write_X = [&](int buf) {
-    bf16x8* dst = Xs + buf * xbuf;
-    if (TERMS == 1 && xkeep) {
+    bf16x8* dst = Xs + buf * XPS;
+    if (xkeep) {
 #pragma unroll
-      for (int i = 0; i < XI; ++i) rx[0][i] = keep8(rx[0][i], rk[TERMS == 1 ? i : 0]);
+      for (int i = 0; i < XI; ++i) rx[i] = keep8(rx[i], rk[i]);
     }
 #pragma unroll
-    for (int i = 0; i < XI; ++i)
-#pragma unroll
-      for (int pl = 0; pl < PL; ++pl) dst[pl * XPS + tid + i * NT] = rx[pl][i];
+    for (int i = 0; i < XI; ++i) dst[tid + i * NT] = rx[i];
   };
 
   uint32_t vbits = 0, need = 0;
   auto read_frags = [&](Frags<NI>& f, int abuf, int c, int j, int q) {
-    const bf16x8* AsH = As + abuf * (PL * KB * BM);
-    const bf16x8* XsH = Xs + (c & 1) * xbuf;
+    const bf16x8* AsH = As + abuf * (KB * BM);
+    const bf16x8* XsH = Xs + (c & 1) * XPS;
     const int k8 = 2 * q + lhi;
     const int ai = k8 * BM + a_off;
     f.ah[0] = AsH[ai];
     f.ah[1] = AsH[ai + BMH];
-    if (TERMS == 3) {
-      f.al[0] = AsH[KB * BM + ai];
-      f.al[1] = AsH[KB * BM + ai + BMH];
-    }
     const int xi = k8 * BNH + x_off + j * dil;
 #pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-      f.bh[ni] = XsH[xi + ni * 32];
-      if (TERMS == 3) f.bl[ni] = XsH[XPS + xi + ni * 32];
-    }
+    for (int ni = 0; ni < NI; ++ni) f.bh[ni] = XsH[xi + ni * 32];
   };
   // the conv's zero padding at sequence edges: columns whose tap-j input lies outside their own batch item
   auto fix_frags = [&](Frags<NI>& f, int j) {
@@ -248,7 +233,6 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvA
       for (int ni = 0; ni < NI; ++ni) {
         const bool ok = (vbits >> (j * NI + ni)) & 1u;
         f.bh[ni] = ok ? f.bh[ni] : zero8;
-        if (TERMS == 3) f.bl[ni] = ok ? f.bl[ni] : zero8;
       }
     }
   };
@@ -259,27 +243,14 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvA
     for (int ni = 0; ni < NI; ++ni) {
       const bool ok = (vbits >> (j * NI + ni)) & 1u;
       f.bh[ni] = ok ? f.bh[ni] : zero8;
-      if (TERMS == 3) f.bl[ni] = ok ? f.bl[ni] : zero8;
     }
   };
   f32x16 acc[2][NI];
   auto mfma = [&](const Frags<NI>& f) {
-    if (TERMS == 3) {
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) {
-        acc[0][ni] = mma16<F16>(f.al[0], f.bh[ni], acc[0][ni]);
-        acc[1][ni] = mma16<F16>(f.al[1], f.bh[ni], acc[1][ni]);
-      }
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) {
-        acc[0][ni] = mma16<F16>(f.ah[0], f.bl[ni], acc[0][ni]);
-        acc[1][ni] = mma16<F16>(f.ah[1], f.bl[ni], acc[1][ni]);
-      }
-    }
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
-      acc[0][ni] = mma16<F16>(f.ah[0], f.bh[ni], acc[0][ni]);
-      acc[1][ni] = mma16<F16>(f.ah[1], f.bh[ni], acc[1][ni]);
+      acc[0][ni] = mma16(f.ah[0], f.bh[ni], acc[0][ni]);
+      acc[1][ni] = mma16(f.ah[1], f.bh[ni], acc[1][ni]);
     }
   };
 
@@ -386,7 +357,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvA
             read_frags(F1, sp & 1, cC, jC, 1);
             fix_frags_nb(F0, jC);
             mfma(F0);
-            interleave<TERMS * 2 * NI, 0, 0, (2 + NI) * PL>();
+            interleave<2 * NI, 0, 0, 2 + NI>();
             __syncthreads();
             // ---- second half ----
             write_A(sp & 1);
@@ -396,8 +367,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvA
             read_frags(F0, (sp - 1) & 1, cR, jR, 0);
             fix_frags_nb(F1, jC);
             mfma(F1);
-            interleave<TERMS * 2 * NI, AU * PL + (jj == 0 ? XI * PL : 0), AU * PL + (jL == 0 ? XI * PL : 0),
-                       (2 + NI) * PL>();
+            interleave<2 * NI, AU + (jj == 0 ? XI : 0), AU + (jL == 0 ? XI : 0), 2 + NI>();
           });
         }
         s_done = (ci_hi + 1) * JT - 2;
@@ -413,15 +383,6 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvA
       load_A(0, 0);
       load_X(0);
     }
-    if constexpr (F16) {   // the accumulators carry 2^(weight shift + activation shift) x the result
-      constexpr float kInv = 1.0f / (float)(1 << (DV3_F16_WEIGHT_SHIFT + DV3_F16_ACT_SHIFT));
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[h][ni][r] *= kInv;
-    }
     {
       int bcol[NI], tcol[NI];
       bool okc[NI];
@@ -432,7 +393,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvA
         bcol[ni] = n / T;
         tcol[ni] = n - bcol[ni] * T;
       }
-      if (TERMS == 1 && xkeep) {      // x * keep / (1-p): the 1/(1-p) of a masked c8 input, exact on the accumulators
+      if (xkeep) {      // x * keep / (1-p): the 1/(1-p) of a masked c8 input, exact on the accumulators
         const float ds = p.drop_scale;
 #pragma unroll
         for (int h = 0; h < 2; ++h)
@@ -441,54 +402,14 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void conv_planes_kernel(const ConvA
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[h][ni][r] *= ds;
       }
-      if (TERMS == 1 && (p.io_bf16 & DV3_IO_OUT_C8))
+      if (p.io_bf16 & DV3_IO_OUT_C8)
         conv_epilogue_c8<BM, BMH, NI>(p, acc, gated, mt, wm * 32, lhi, bcol, tcol, okc);
       else
-        conv_epilogue<BM, BMH, NI, TERMS == 1>(p, acc, gated, mt, wm * 32, lhi, bcol, tcol, okc);
+        conv_epilogue<BM, BMH, NI, true>(p, acc, gated, mt, wm * 32, lhi, bcol, tcol, okc);
     }
     if (!has_next) break;
     tile = next;
   }
-}
-
-// ---- activation planes from an fp32 BCT tensor (+ dropout keep-bits) ----
-__device__ __forceinline__ void split8_bf16(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int i = 0; i < 8; i += 2) {
-    const f32x2 f = {v[i], v[i + 1]};
-    const bf16x2 h = __builtin_convertvector(f, bf16x2);
-    const f32x2 r = f - __builtin_convertvector(h, f32x2);
-    const bf16x2 l = __builtin_convertvector(r, bf16x2);
-    hi[i] = h[0]; hi[i + 1] = h[1];
-    lo[i] = l[0]; lo[i + 1] = l[1];
-  }
-}
-// one thread per 16-byte unit (b, c8, t); t fastest: the 8 channel reads are row-coalesced, the two unit stores
-// are 16-byte coalesced
-__global__ __launch_bounds__(256) void split_planes_kernel(const dv3_planes_desc p, int c8p, uint32_t* range_ctr) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  const int c8 = blockIdx.y, b = blockIdx.z;
-  if (t >= p.T) return;
-  const float scale = p.scale * (p.dtype == DV3_SPLIT_DTYPE_F16 ? (float)(1 << DV3_F16_ACT_SHIFT) : 1.0f);
-  float v[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int ch = c8 * 8 + e;
-    float x = 0.f;
-    if (ch < p.C) {
-      x = p.x[(int64_t)b * p.x_bs + (int64_t)ch * p.x_rs + t];
-      bool keep = true;
-      if (p.mask) keep = (p.mask[((int64_t)b * p.C + ch) * p.mask_rs + (t >> 5)] >> (t & 31)) & 1u;
-      x = keep ? x * scale : 0.f;
-    }
-    v[e] = x;
-  }
-  bf16x8 hi, lo;
-  if (p.dtype == DV3_SPLIT_DTYPE_F16) dv3_note_range(range_ctr, dv3_split8_f16(v, hi, lo)); else split8_bf16(v, hi, lo);
-  bf16x8* out = reinterpret_cast<bf16x8*>(p.out);
-  const int64_t u = ((int64_t)b * c8p + c8) * p.T + t;
-  out[u] = hi;
-  out[(int64_t)p.B * c8p * p.T + u] = lo;
 }
 
 // ---- fp32 (B,C,T) <-> c8 (bf16 [B][C8][T][8]) and keep-bits -> keep-bytes: one thread per unit (b, group, t), t fastest
@@ -534,16 +455,11 @@ __global__ __launch_bounds__(256) void mask_bits_to_c8_kernel(const uint32_t* __
   out[((int64_t)b * c8p + g) * T + t] = (uint8_t)m;
 }
 
-int g_planes_tile = 0;      // dv3_debug_set(4, v)
-int g_planes_mid_thr = 1;   // dv3_debug_set(8, v): 128x128 tiles once they number v/2 x the CUs, else 128x64 (measured:
-                            // 1 -> nyanko bf16 step 13.12 ms, 2 -> 13.25, 4 -> 13.90; scripts/tile_thr_ab.py)
-int g_planes_stagger = -1;  // dv3_debug_set(5, v)
-
-template <int WM, int WN, int NI, int TERMS, bool F16, int JT>
+template <int WM, int WN, int NI, int JT>
 int launch_planes_j(const ConvArgs& a, size_t lds, int grid, hipStream_t st) {
   static bool attr_set = false;  // raise the dynamic-LDS cap once per instantiation
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_planes_kernel<WM, WN, NI, TERMS, F16, JT>,
+    hipError_t e = hipFuncSetAttribute((const void*)conv_planes_kernel<WM, WN, NI, JT>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) {
       dv3_set_error("conv_planes: hipFuncSetAttribute: %s", hipGetErrorString(e));
@@ -551,26 +467,17 @@ int launch_planes_j(const ConvArgs& a, size_t lds, int grid, hipStream_t st) {
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL((conv_planes_kernel<WM, WN, NI, TERMS, F16, JT>), dim3(grid), dim3(WM * WN * 64), lds, st, a);
+  hipLaunchKernelGGL((conv_planes_kernel<WM, WN, NI, JT>), dim3(grid), dim3(WM * WN * 64), lds, st, a);
   return dv3_check_launch("conv_planes");
 }
-// dv3_debug_set(7, v): the unrolled steady state with the issue-order requests: 0 off, 1 on, -1 (default) = on for the
-// single-term kernel only.  Three-term kernels: measured slower (reads land late behind 24 MFMAs).  Single-term: its
-// 8 MFMAs per step do not cover the generic loop's scalar bookkeeping -- 3-8 % faster unrolled, bit-identical
-// (scripts/planes_steady_c8.py: 80.4 -> 74.8 us eval, 92.3 -> 87.7 us training forward at the north-star shape).
-int g_planes_steady = -1;
-template <int WM, int WN, int NI, int TERMS, bool F16>
-int launch_planes_t(const ConvArgs& a, size_t lds, int grid, hipStream_t st) {
-  const bool steady = g_planes_steady < 0 ? TERMS == 1 : g_planes_steady != 0;
-  if (steady && a.d.J == 3) return launch_planes_j<WM, WN, NI, TERMS, F16, 3>(a, lds, grid, st);
-  if (steady && a.d.J == 1) return launch_planes_j<WM, WN, NI, TERMS, F16, 1>(a, lds, grid, st);
-  return launch_planes_j<WM, WN, NI, TERMS, F16, 0>(a, lds, grid, st);
-}
+// The tap counts the models use run the unrolled steady state with the issue-order requests (JT = J): the kernel's 8
+// MFMAs per step do not cover the generic loop's scalar bookkeeping -- 3-8 % faster unrolled, bit-identical (80.4 ->
+// 74.8 us eval, 92.3 -> 87.7 us training forward at the north-star shape; profiles/r02y_planes_single_term_ablation.md).
 template <int WM, int WN, int NI>
 int launch_planes(const ConvArgs& a, size_t lds, int grid, hipStream_t st) {
-  if (a.d.split_terms == DV3_SPLIT_F16X3) return launch_planes_t<WM, WN, NI, 3, true>(a, lds, grid, st);
-  if (a.d.split_terms == 1) return launch_planes_t<WM, WN, NI, 1, false>(a, lds, grid, st);
-  return launch_planes_t<WM, WN, NI, 3, false>(a, lds, grid, st);
+  if (a.d.J == 3) return launch_planes_j<WM, WN, NI, 3>(a, lds, grid, st);
+  if (a.d.J == 1) return launch_planes_j<WM, WN, NI, 1>(a, lds, grid, st);
+  return launch_planes_j<WM, WN, NI, 0>(a, lds, grid, st);
 }
 
 int dv3_num_cus() {
@@ -587,18 +494,6 @@ int dv3_num_cus() {
 }
 
 }  // namespace
-
-extern "C" int dv3_split_planes_f32(const dv3_planes_desc* d, void* stream) {
-  DV3_REQUIRE(d && d->x && d->out, "split_planes: null pointer");
-  DV3_REQUIRE(d->B > 0 && d->C > 0 && d->T > 0, "split_planes: bad dims");
-  DV3_REQUIRE(d->dtype == DV3_SPLIT_DTYPE_BF16 || d->dtype == DV3_SPLIT_DTYPE_F16, "split_planes: bad dtype");
-  DV3_REQUIRE(((uintptr_t)d->out & 15) == 0, "split_planes: out must be 16-byte aligned");
-  if (d->mask) DV3_REQUIRE(d->mask_rs * 32 >= d->T, "split_planes: mask row stride too small");
-  const int c8p = (d->C + 31) / 32 * 4;
-  DV3_REQUIRE(c8p <= 65535 && d->B <= 65535, "split_planes: grid too large");
-  hipLaunchKernelGGL(split_planes_kernel, dim3(dv3_cdiv(d->T, 256), c8p, d->B), dim3(256), 0, (hipStream_t)stream, *d, c8p, dv3_range_ctr());
-  return dv3_check_launch("split_planes");
-}
 
 extern "C" int dv3_to_c8_f32(const float* x, int64_t x_bs, int64_t x_rs, uint16_t* out, int32_t B, int32_t C,
                              int32_t T, void* stream) {
@@ -635,22 +530,24 @@ extern "C" int dv3_mask_bits_to_c8(const uint32_t* bits, int32_t bits_rs, uint8_
   return dv3_check_launch("mask_bits_to_c8");
 }
 
-// called by dv3_conv_gemm_f32 (conv_gemm.hip) when d->x_planes != NULL; returns 1 when the shape is not
-// eligible (caller falls back to the other kernels when it can), else a DV3_* code.
+int g_planes_tile = 0;   // dv3_debug_set(4, v): 1 / 2 / 9 force that tile of this kernel (and keep conv_c8pp out), 0 = auto
+
+// called by dv3_conv_gemm_f32 (conv_gemm.hip) when d->x_c8 != NULL, which has required split_terms == 1 by then;
+// returns 1 when the shape is not eligible (the caller reports it), else a DV3_* code.
 int dv3_conv_planes_dispatch(const dv3_conv_desc* d, hipStream_t st) {
   const bool gated = d->mode == DV3_EPI_GLU || d->mode == DV3_EPI_HIGHWAY;
   if (!d->a_split || d->a_bs != 0 || (d->lda & 3) || d->Tin != d->Tout) return 1;
   if ((d->J - 1) * d->dil > HALO_MAX || d->J * 2 > 32) return 1;
   const int kp = (d->Cin + 31) / 32 * 32;
   if (d->x_c8p != kp / 8) return 1;
-  if (((uintptr_t)d->x_planes & 15) != 0) return 1;
-  if ((int64_t)d->B * d->x_c8p * d->Tout >= (1ll << 28)) return 1;          // 32-bit byte offsets per plane
+  if (((uintptr_t)d->x_c8 & 15) != 0) return 1;
+  if ((int64_t)d->B * d->x_c8p * d->Tout >= (1ll << 28)) return 1;          // 32-bit byte offsets
   if ((int64_t)d->J * (kp / 8) * d->lda >= (1ll << 27)) return 1;
   const int64_t ntot = (int64_t)d->B * d->Tout;
   if (ntot >= (1ll << 30)) return 1;
-  // single-term bf16 on c8 input: the 256 x 256 k32 ping-pong kernel (conv_c8pp.hip) where its grid fills the chip
+  // the 256 x 256 k32 ping-pong kernel (conv_c8pp.hip) where its grid fills the chip
   // (tile_hint 40 forces it, dv3_debug_set(19, v) moves the threshold)
-  if (d->split_terms == 1 && (d->tile_hint == 40 || (d->tile_hint == 0 && g_planes_tile == 0))) {
+  if ((d->tile_hint == 40 || (d->tile_hint == 0 && g_planes_tile == 0))) {
     const int rc = dv3_conv_c8pp_dispatch(d, st);
     if (rc != 1) return rc;
     if (d->tile_hint == 40) return 1;
@@ -660,17 +557,16 @@ int dv3_conv_planes_dispatch(const dv3_conv_desc* d, hipStream_t st) {
   if (id != 1 && id != 2 && id != 9) {
     const int64_t mt = gated ? dv3_cdiv(d->Cg, 64) : dv3_cdiv(d->M, 128);
     // measured at the north-star shape (profiles/r02c_planes_kernel_ablation.md): the 8-wave 128x256 tile is the
-    // fastest where it fills the chip; two co-resident 128x128 workgroups otherwise; 128x64 for small problems
+    // fastest where it fills the chip; two co-resident 128x128 workgroups once they number half the CUs (whole bf16
+    // nyanko steps with that threshold at 1/2, 1, 2 x the CUs: 13.12, 13.25, 13.90 ms); 128x64 for small problems
     const int64_t cols128 = dv3_cdiv64(ntot, 128);
     id = (mt * dv3_cdiv64(ntot, 256) >= (int64_t)dv3_num_cus()) ? 9
-         : (2 * mt * cols128 >= g_planes_mid_thr * (int64_t)dv3_num_cus()) ? 1 : 2;
+         : (2 * mt * cols128 >= (int64_t)dv3_num_cus()) ? 1 : 2;
   }
   const int BM = 128, BMH = 64, BN = id == 1 ? 128 : id == 2 ? 64 : 256;
   const int NT = id == 9 ? 512 : 256;
-  const int PL = d->split_terms == 1 ? 1 : 2;
-  const int BNH = BN + (d->J - 1) * d->dil;
   const int XI = (KB * (BN + HALO_MAX) + NT - 1) / NT;
-  const size_t lds = (size_t)(2 * PL * KB * BM + 2 * PL * XI * NT) * 16;   // X planes padded to XI * NT units
+  const size_t lds = (size_t)(2 * KB * BM + 2 * XI * NT) * 16;   // X buffers padded to XI * NT units
   if (lds > 160 * 1024) return 1;
   ConvArgs a;
   a.d = *d;
@@ -681,26 +577,21 @@ int dv3_conv_planes_dispatch(const dv3_conv_desc* d, hipStream_t st) {
   DV3_REQUIRE(nb < (1ll << 31), "conv_planes: grid too large");
   a.n_blocks = (int)nb;
   const int cus = dv3_num_cus();
-  a.a_scalar = cus;                       // (re-used field) number of CUs, for the stagger parity
+  // ConvArgs has no field of its own for this and its layout is not to change (conv_common.h): this kernel stages no
+  // fp32 operand, so it reads a_scalar as the number of CUs, for the stagger parity of co-resident workgroups
+  a.a_scalar = cus;
   const int per_cu = (NT == 256 && 2 * lds <= 160 * 1024) ? 2 : 1;
   const int grid = (int)(nb < (int64_t)cus * per_cu ? nb : (int64_t)cus * per_cu);
   const int nsteps = (kp / 32) * d->J;
-  // half a tile's main loop: nsteps x 24 MFMAs x 32 cycles x 2 waves per SIMD / 2, in s_sleep(127) units (~8.1k cycles)
+  // start-up delay of the second co-resident workgroup in s_sleep(127) units (~8.1k cycles): nsteps x 24 MFMAs x 32
+  // cycles x 2 waves per SIMD / 2 -- sized in round 1 as half a tile's main loop of the three-term form, kept as measured
   a.stagger = 0;
-  if (per_cu == 2 && grid > cus) a.stagger = g_planes_stagger >= 0 ? g_planes_stagger : (nsteps * 768 + 4000) / 8128;
-  g_dv3_last_conv = (d->split_terms == DV3_SPLIT_F16X3 ? 6000 : d->split_terms == 1 ? 8000 : 7000) + id * 10;
+  if (per_cu == 2 && grid > cus) a.stagger = (nsteps * 768 + 4000) / 8128;
+  g_dv3_last_conv = 8000 + id * 10;
   switch (id) {
     case 1: return launch_planes<2, 2, 2>(a, lds, grid, st);
     case 2: return launch_planes<2, 2, 1>(a, lds, grid, st);
     case 9: return launch_planes<2, 4, 2>(a, lds, grid, st);
   }
   return 1;
-}
-
-int dv3_planes_debug_set(int what, int value) {
-  if (what == 4) g_planes_tile = value;
-  if (what == 5) g_planes_stagger = value;
-  if (what == 7) g_planes_steady = value;
-  if (what == 8) g_planes_mid_thr = value;
-  return DV3_OK;
 }

@@ -857,7 +857,7 @@ def _conv_gemm_c8(x, a, lda, a_half, *, B, Cin, Tin, M, Tout, J, dil, padL, mode
     if x_c8 is not None:
         if x_c8.shape[1] != c8_groups(Cin) or x_c8.shape[2] != Tin or not x_c8.is_contiguous():
             raise RuntimeError("conv_gemm: c8 input shape %s does not match Cin=%d Tin=%d" % (tuple(x_c8.shape), Cin, Tin))
-        d.x_planes, d.x_c8p = x_c8.data_ptr(), x_c8.shape[1]
+        d.x_c8, d.x_c8p = x_c8.data_ptr(), x_c8.shape[1]
         d.xmask_c8 = _ptr(xmask_c8)
     else:
         d.x, d.x_bs, d.x_rs = x.data_ptr(), x.stride(0), x.stride(1)

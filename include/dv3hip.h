@@ -30,7 +30,7 @@ extern "C" {
 #define DV3_ELAUNCH (-2)  /* hipLaunch / runtime error        */
 
 /* ABI version, bumped on any struct change; checked by the Python loader. */
-#define DV3_ABI_VERSION 46
+#define DV3_ABI_VERSION 47
 int dv3_abi_version(void);
 const char* dv3_last_error(void);
 /* Fills name (<=255 chars) of device `dev`, number of CUs; returns 0/err. */
@@ -39,8 +39,9 @@ int dv3_device_info(int dev, char* name, int name_len, int* n_cu);
 int dv3_sizeof(const char* name);
 /* Developer knobs for measurements (what = 2: bf16x3 wgrad tile, 0 auto / 1 = 128x128 / 2 = 256x128; what = 3: 8-wave bf16x3
  * tap-GEMM tiles on the in-phase (0) or ping-pong (1, default) main loop; what = 4: tile of the planes
- * tap-GEMM, 0 auto / 1 = 128x128 (4 waves, two workgroups per CU) / 2 = 128x64 / 9 = 128x256 (8 waves);
- * what = 5: start-up stagger of the second co-resident workgroup, -1 auto / n = n sleeps of ~4 us;
+ * tap-GEMM (c8 input), 0 auto, conv_c8pp where its grid fills the chip / 1 = 128x128 (4 waves, two workgroups per CU) /
+ * 2 = 128x64 / 9 = 128x256 (8 waves): the only way to force a planes tile; what = 5, 7, 8 (its stagger, steady state
+ * and mid-tile threshold) are retired;
  * what = 34: conv_c8pp form, 0 = 8 waves on 256x256 only / 1 = two 4-wave workgroups per CU on 256x128 / 2 = by rule;
  * what = 40: launch census of dv3_conv_gemm_f32, 1 = clear and record / 0 = stop; what = 42: relative cost (percent)
  * of the 256x128 ping-pong tile in the split kernels' tile picker; what = 44: k-split form of the 128x64 split tile,
@@ -135,12 +136,13 @@ typedef struct dv3_conv_desc {
                                                 is a SCALED FP16 hi/lo image (below), the activations are
                                                 split the same way while staging: three fp16 MFMAs per
                                                 product, 2^-22-class operands = fp32-class results      */
-  const uint16_t* x_planes;                  /* the input ALREADY split into operand planes (dv3_split_planes_f32
-                                                layout, dtype matching split_terms; dropout already applied) or
-                                                NULL.  Non-NULL (with a_split) selects the persistent planes
-                                                kernel: both operands are staged with plain 16-byte copies.
+  const uint16_t* x_c8;                      /* the input as a c8 bf16 tensor [B][x_c8p][Tin][8] (below), written by
+                                                dv3_to_c8_f32 or a c8 epilogue, or NULL.  Non-NULL requires a_split
+                                                and split_terms == 1 (anything else is DV3_EINVAL) and selects the
+                                                single-term bf16 kernels on c8 tensors (conv_c8pp, conv_planes):
+                                                both operands are staged with plain 16-byte copies.
                                                 `x` may then be NULL unless the epilogue reads it as `r`.     */
-  int32_t x_c8p;                             /* 8-channel blocks per batch item in x_planes (= round_up(Cin,32)/8) */
+  int32_t x_c8p;                             /* 8-channel blocks per batch item in x_c8 (= round_up(Cin,32)/8) */
   float r_scale;                             /* DGRAD: y = acc * dropmask + r_scale * r (0 means 1).  The gradient
                                                 that reaches a residual Conv1dGLU's input through the skip path is
                                                 sqrt(.5) * dy: the epilogue reads dy itself instead of a scaled copy */
@@ -148,7 +150,7 @@ typedef struct dv3_conv_desc {
                                                 single-term bf16 kernels (split_terms == 1) only: DV3_IO_IN_BF16 = x, r
                                                 and r2 are bf16 tensors (same element strides), DV3_IO_OUT_BF16 = y and
                                                 ab are written as bf16 (round to nearest even).  0 = fp32 everywhere.  */
-  const uint8_t* xmask_c8;                   /* c8 input (x_planes, split_terms == 1): dropout keep-BYTES [B][x_c8p][Tin],
+  const uint8_t* xmask_c8;                   /* c8 input (x_c8): dropout keep-BYTES [B][x_c8p][Tin],
                                                 bit e of byte (b, g, t) = keep channel 8g+e at frame t
                                                 (dv3_mask_bits_to_c8); applied while staging, 1/(1-p) = drop_scale in
                                                 the epilogue.  NULL = no dropout.                                     */
@@ -192,13 +194,13 @@ typedef struct dv3_conv_desc {
 /*
  * Channel-blocked bf16 activation storage ("c8", BASELINE configs 3/4: bf16 activations in HBM, fp32 accumulate):
  * a (B, C, T) activation is held as  bf16 [B][C8][T][8],  C8 = round_up(C,32)/8 -- channel c of frame t is element
- * c%8 of the 16-byte unit (b, c/8, t); channels >= C are zero.  This IS plane 0 of dv3_split_planes_f32's layout: a
- * tensor written by one layer's epilogue is the next layer's `x_planes` (split_terms == 1) with no conversion, the
+ * c%8 of the 16-byte unit (b, c/8, t); channels >= C are zero.  One unit is one MFMA B-fragment lane: a
+ * tensor written by one layer's epilogue is the next layer's `x_c8` (split_terms == 1) with no conversion, the
  * tap-GEMM stages it with plain 16-byte copies, and the epilogue's accumulator tile maps to whole 8-byte halves of
  * units (csrc/conv_common.h).  Any C: the kernels write whole valid groups and keep the padding channels zero;
  * gated layers need Cg % 8 == 0 (the a and gate halves of the saved pre-gate pair start on group boundaries).
  *   DV3_IO_OUT_C8   y (and ab) are written in c8; r / r2 (and the DGRAD addend) are READ in c8
- * (the tensors on the two sides of an epilogue share one layout; x is c8 exactly when x_planes is given).
+ * (the tensors on the two sides of an epilogue share one layout; x is c8 exactly when x_c8 is given).
  */
 #define DV3_IO_OUT_C8 16
 int dv3_conv_gemm_f32(const dv3_conv_desc* d, void* stream);
@@ -308,24 +310,6 @@ int dv3_flag_wait(const uint64_t* flag, uint64_t* epoch, int32_t j, int32_t bump
 #define DV3_F16_ACT_SHIFT 4
 int dv3_split_pack_bf16(const float* packed, uint16_t* out, int32_t J, int32_t K, int32_t lda,
                         int32_t dtype, void* stream);
-
-/*
- * Operand planes of an activation tensor: what the tap-GEMM's B operand looks like after the split, written
- * ONCE by whoever produces the tensor instead of being re-derived by every consuming workgroup.
- *   out[plane][b][c8][t][8]  plane 0 = hi, 1 = lo; c8 < C8p = round_up(C,32)/8 (zero units beyond C);
- *   one 16-byte unit = 8 consecutive channels of one (b, t) column = one MFMA B-fragment lane.
- *   value = x * keep(mask bit) * scale, then  dtype BF16: hi = bf16_rn(v), lo = bf16_rn(v - hi)
- *                                             dtype F16:  a = clamp(v * 2^DV3_F16_ACT_SHIFT), hi/lo = fp16 split
- * `out` holds 2*B*C8p*T*8 uint16.  mask: dropout keep-bits [B*C rows][mask_rs words] or NULL.
- */
-typedef struct dv3_planes_desc {
-  const float* x; int64_t x_bs, x_rs;        /* [B][C][T]                                   */
-  const uint32_t* mask; int32_t mask_rs;
-  float scale;                               /* 1/(1-p) of the consuming layer's dropout, or 1 */
-  uint16_t* out;
-  int32_t B, C, T, dtype;
-} dv3_planes_desc;
-int dv3_split_planes_f32(const dv3_planes_desc* d, void* stream);
 
 /*
  * dv3_wgrad_gemm_f32 -- weight-gradient GEMM (autograd of F.conv1d w.r.t. weight; also

@@ -1,6 +1,6 @@
 # coding: utf-8
-"""The north-star shape's operands (Conv1dGLU fwd, B=64 x 256 x 1024, k=3) and the event timer that bf16_stage1.py,
-planes_steady_c8.py and wgrad_ab.py import.  The A/B this file was written for -- the tap-GEMM that splits while staging
+"""The north-star shape's operands (Conv1dGLU fwd, B=64 x 256 x 1024, k=3) and the event timer that bf16_stage1.py
+and wgrad_ab.py import.  The A/B this file was written for -- the tap-GEMM that splits while staging
 against the persistent planes kernel on fp32 inputs split by a pass of their own (the opt-in route of DESIGN.md 3.3) --
 went with that route (DESIGN.md 3.3 keeps its result; git history keeps the script)."""
 import math, sys, os

@@ -129,6 +129,54 @@ def test_c8_gated_layers_forward_backward(dev, modes, kind, C, k, d, causal, T, 
         assert rel_err(dp8[n].cpu(), dpr[n].cpu()) < TOL_GRAD, n
 
 
+def test_c8_input_is_refused_unless_single_term(dev, modes):
+    """dv3_conv_desc.x_c8 is read by the single-term bf16 kernels only (include/dv3hip.h): the forward descriptor of the
+    first GATED case, as the library itself recorded it (launch census), re-issued with split_terms = 0, 3 and
+    DV3_SPLIT_F16X3 is DV3_EINVAL with the message below -- a host-side refusal before any launch (the output tensor and
+    the last-kernel code stay as they were), never another kernel; unchanged it is served as before."""
+    import ctypes
+    ops = modes
+    from deepvoice3_pytorch_amd import modules, _lib
+    L = _lib.lib()
+    kind, C, k, d, causal, T, B = GATED[0]
+    torch.manual_seed(0)
+    layer = modules.Conv1dGLU(1, 16, C, C, k, dropout=0.2, dilation=d, causal=causal, residual=True).to(dev).eval()
+    ops.set_gemm_precision("bf16")
+    ops.bf16_storage = True
+    x8 = ops.to_c8(torch.randn(B, C, T, device=dev))
+    L.dv3_debug_set(40, 1)
+    try:
+        with torch.no_grad():
+            y8 = layer(x8)
+    finally:
+        L.dv3_debug_set(40, 0)
+    n = L.dv3_debug_get(40)
+    assert n >= 1 and ops.is_c8(y8)
+    Desc = ops._conv_desc
+    sz = ctypes.sizeof(Desc)
+    raw = (ctypes.c_char * (n * sz))()
+    assert L.dv3_debug_read(40, raw, n * sz) == 0
+    desc = Desc.from_buffer_copy(bytes(raw[(n - 1) * sz:n * sz]))
+    assert desc.x_c8 == x8.data_ptr() and desc.y == y8.data_ptr() and desc.split_terms == 1
+    assert (desc.B, desc.Cin, desc.Tout, desc.J, desc.dil) == (B, C, T, k, d)
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    served = L.dv3_debug_get(10)
+    assert served // 1000 == 8
+    y8.fill_(3.0)
+    torch.cuda.synchronize()
+    for terms in (0, 3, ops.CONSTS["DV3_SPLIT_F16X3"]):
+        desc.split_terms = terms
+        assert L.dv3_conv_gemm_f32(ctypes.byref(desc), st) != 0, terms
+        assert L.dv3_last_error() == b"conv_gemm: a c8 input is read by the single-term bf16 kernels (split_terms == 1)", terms
+        assert L.dv3_debug_get(10) == served, terms
+    torch.cuda.synchronize()
+    assert bool((y8 == 3.0).all())
+    desc.split_terms = 1
+    assert L.dv3_conv_gemm_f32(ctypes.byref(desc), st) == 0, L.dv3_last_error()
+    torch.cuda.synchronize()
+    assert not bool((y8 == 3.0).all())
+
+
 def test_c8_plain_layers(dev, modes):
     """1x1 Conv1d / Linear forms around the gated layers: c8 -> c8 (+ ReLU, on the forward's own decisions),
     c8 -> fp32 with a channel count that has no c8 form (513 linear bins), fp32 -> c8 with two c8 residuals (the

@@ -967,11 +967,12 @@ def test_debug_set_refuses_retired_and_unknown_switches(dev):
     from deepvoice3_pytorch_amd import _lib
     L = _lib.lib()
     for what, value, why in ((999, 0, b"no such switch"), (1, 1, b"no such switch"), (13, 1, b"no such switch"),
+                             (5, 0, b"no such switch"), (7, 1, b"no such switch"), (8, 2, b"no such switch"),
                              (52, 11, b"wgrad_c8 form 0..4"), (29, 5, b"LOAD-phase order 0, 17 or 81")):
         assert L.dv3_debug_set(what, value) != 0, (what, value)
         msg = L.dv3_last_error()
         assert msg and msg.startswith(b"debug_set(%d, " % what) and why in msg, (what, value, msg)
-    defaults = ((2, 0), (3, 1), (19, 128), (20, 1), (22, 1), (29, 81), (30, 1), (31, 81), (34, 2), (44, KS_DEFAULT),
+    defaults = ((2, 0), (3, 1), (4, 0), (19, 128), (20, 1), (22, 1), (29, 81), (30, 1), (31, 81), (34, 2), (44, KS_DEFAULT),
                 (47, 1), (48, 1), (49, 1), (51, 1), (52, 4), (55, 1), (57, 1))
     for what, value in defaults:
         assert L.dv3_debug_set(what, value) == 0, (what, value, L.dv3_last_error())
