@@ -491,8 +491,12 @@ __global__ __launch_bounds__(256) void decode_program_kernel(const dv3_decode_pr
           __syncthreads();
         }
       } else {
-        const int b = b0 + i;
-        if (i < NB && b < prog.B) attn_step_item(en.attn, t, b, lds, red, redi);
+        // member i reads items i, i + P, ... of its group: with fewer than NB workgroups per group (wg_per_group < 4, or a
+        // batch above 256 items at the default) one workgroup takes several items in turn
+        for (int ii = i; ii < NB && b0 + ii < prog.B; ii += P) {
+          attn_step_item(en.attn, t, b0 + ii, lds, red, redi);
+          __syncthreads();                  // the next item reuses q / the scores in LDS
+        }
       }
       // the next layer's weights (this workgroup's first tile of it) are requested before the barrier is waited on
       {
