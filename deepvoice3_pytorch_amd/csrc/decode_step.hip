@@ -80,13 +80,20 @@ __device__ __forceinline__ void conv_step_prefetch(const dv3_conv_step_desc& p, 
 
 // one (output-channel block, batch block) tile of a layer at step t; all 256 threads of the workgroup take part.
 // loaded: w already holds conv_step_prefetch(p, mblk) (else the tile requests it first).
-template <bool GATED>
+// SLOTS (p.t_off set, include/dv3hip.h "slot mode"): every batch item runs at its own step t - t_off[b].  What was one
+// step index of the workgroup is then one per item ROW of the tile -- NB scalars (the ring slot, the input row), read
+// through a clamped, workgroup-uniform batch index, never a per-lane value in the staging loop -- and a lane of the
+// tail uses the one of its own item.  An item outside [0, t_cap) computes on its clamped rows and stores neither a
+// ring frame nor a stacked row.
+template <bool GATED, bool SLOTS>
 __device__ __forceinline__ void conv_step_tile_t(const dv3_conv_step_desc& p, const int t, const int mblk, const int b0,
                                                  float* lds, f32x4 (&w)[KPF], const bool loaded, unsigned long long* st) {
   typedef StepLane<GATED> LN;
   dec_stamp(st, 0);
   if (!loaded) conv_step_prefetch_t<GATED>(p, mblk, w);
   const int tid = threadIdx.x;
+  int tb[NB], slotb[NB];            // SLOTS: the items' own (clamped) steps and ring slots
+  bool liveb[NB];
   const LN ln;
   const int mq = ln.mq, ks = ln.ks;
   const int Mrows = GATED ? p.Cg : p.M;
@@ -95,7 +102,16 @@ __device__ __forceinline__ void conv_step_tile_t(const dv3_conv_step_desc& p, co
   const int nu = kpad / LN::NKS;
   const int L = p.L;
   const int slot = L > 0 ? t % L : 0;
-  const float* __restrict__ xin = p.x + (int64_t)t * p.x_ts;
+  const float* __restrict__ xin = p.x + (SLOTS ? (int64_t)0 : (int64_t)t * p.x_ts);
+  if (SLOTS) {
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      const int ti = t - p.t_off[min(b0 + nb, B - 1)];
+      liveb[nb] = ti >= 0 && ti < p.t_cap;
+      tb[nb] = min(max(ti, 0), p.t_cap - 1);
+      slotb[nb] = L > 0 ? tb[nb] % L : 0;
+    }
+  }
   float* Xs = lds;                                  // [kpad][NB]
   float* redA = lds + (size_t)kpad * NB;            // [slice][MT][2*NB]
   float* redB = redA + RED_A;                       // [16][MT][2*NB]
@@ -107,16 +123,24 @@ __device__ __forceinline__ void conv_step_tile_t(const dv3_conv_step_desc& p, co
   const bool fok = m < Mrows && fb < B;
   const int mc = min(m, Mrows - 1), fbc = min(fb, B - 1);
   float t_ba = 0.f, t_bg = 0.f, t_spk = 0.f, t_xr = 0.f, t_r = 0.f, t_r2 = 0.f, t_pa = 0.f;
+  int ft = t;                       // the step of this tail lane's item
+  bool flive = true;
+  if (SLOTS) {
+    const int ti = t - p.t_off[fbc];
+    flive = ti >= 0 && ti < p.t_cap;
+    ft = min(max(ti, 0), p.t_cap - 1);
+  }
   if (tid < MT * NB) {
     if (p.bias) {
       t_ba = p.bias[mc];
       if (GATED) t_bg = p.bias[p.Cg + mc];
     }
     if (GATED && p.spk) t_spk = p.spk[(int64_t)fbc * p.spk_bs + mc];
-    if (GATED && (p.mode == DV3_EPI_HIGHWAY || p.residual)) t_xr = xin[(int64_t)fbc * p.x_bs + mc];
+    if (GATED && (p.mode == DV3_EPI_HIGHWAY || p.residual))
+      t_xr = xin[(SLOTS ? (int64_t)ft * p.x_ts : (int64_t)0) + (int64_t)fbc * p.x_bs + mc];
     if (!GATED && p.r) t_r = p.r[(int64_t)fbc * p.r_bs + mc];
     if (p.r2) t_r2 = p.r2[(int64_t)fbc * p.r2_bs + mc];
-    if (p.post_add) t_pa = p.post_add[(int64_t)t * p.post_add_ts + (int64_t)fbc * p.post_add_bs + mc];
+    if (p.post_add) t_pa = p.post_add[(int64_t)ft * p.post_add_ts + (int64_t)fbc * p.post_add_bs + mc];
   }
 
   // ---- stage the window: tap J-1 is the new frame, tap j the frame (J-1-j)*dil steps back ----
@@ -131,6 +155,19 @@ __device__ __forceinline__ void conv_step_tile_t(const dv3_conv_step_desc& p, co
       for (int jj = 0; jj < 4; ++jj) {
         const int j = j0 + jj;
         if (j < J) {                                          // uniform
+          if (SLOTS) {                                        // each item row at its own slot / input row
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) {
+              const int bc = min(b0 + nb, B - 1);
+              if (j == J - 1) {
+                v[jj][nb] = xin[(int64_t)tb[nb] * p.x_ts + (int64_t)bc * p.x_bs + c];
+              } else {
+                int sl = (slotb[nb] - (J - 1 - j) * p.dil) % L;
+                if (sl < 0) sl += L;
+                v[jj][nb] = p.ring[((int64_t)sl * B + bc) * Cin + c];
+              }
+            }
+          } else {
           const float* src;
           int64_t bs;
           if (j == J - 1) {
@@ -144,7 +181,8 @@ __device__ __forceinline__ void conv_step_tile_t(const dv3_conv_step_desc& p, co
           }
 #pragma unroll
           for (int nb = 0; nb < NB; ++nb) v[jj][nb] = src[(int64_t)min(b0 + nb, B - 1) * bs];    // clamped: rows past the
-        }                                                                                       // batch are never stored
+          }                                                                                     // batch are never stored
+        }
       }
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
@@ -155,7 +193,9 @@ __device__ __forceinline__ void conv_step_tile_t(const dv3_conv_step_desc& p, co
           if (ring_owner && j == J - 1) {
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb)
-              if (b0 + nb < B) p.ring[((int64_t)slot * B + b0 + nb) * Cin + c] = v[jj][nb];
+              if (SLOTS) {
+                if (b0 + nb < B && liveb[nb]) p.ring[((int64_t)slotb[nb] * B + b0 + nb) * Cin + c] = v[jj][nb];
+              } else if (b0 + nb < B) p.ring[((int64_t)slot * B + b0 + nb) * Cin + c] = v[jj][nb];
           }
         }
       }
@@ -271,7 +311,7 @@ __device__ __forceinline__ void conv_step_tile_t(const dv3_conv_step_desc& p, co
         o = sigmoidf_(y);
         p.y_act[(int64_t)fb * p.y_act_bs + m] = o;
       }
-      if (p.out_seq) p.out_seq[(int64_t)t * p.out_seq_ts + (int64_t)fb * p.out_seq_bs + m] = o;
+      if (p.out_seq && flive) p.out_seq[(int64_t)ft * p.out_seq_ts + (int64_t)fb * p.out_seq_bs + m] = o;
     }
   }
   dec_stamp(st, 5);
@@ -280,8 +320,8 @@ __device__ __forceinline__ void conv_step_tile_t(const dv3_conv_step_desc& p, co
 __device__ __forceinline__ void conv_step_tile(const dv3_conv_step_desc& p, const int t, const int mblk, const int b0,
                                                float* lds, f32x4 (&w)[KPF], const bool loaded,
                                                unsigned long long* st = nullptr) {
-  if (p.mode == DV3_EPI_GLU || p.mode == DV3_EPI_HIGHWAY) conv_step_tile_t<true>(p, t, mblk, b0, lds, w, loaded, st);
-  else conv_step_tile_t<false>(p, t, mblk, b0, lds, w, loaded, st);
+  if (p.mode == DV3_EPI_GLU || p.mode == DV3_EPI_HIGHWAY) conv_step_tile_t<true, false>(p, t, mblk, b0, lds, w, loaded, st);
+  else conv_step_tile_t<false, false>(p, t, mblk, b0, lds, w, loaded, st);
 }
 
 __global__ __launch_bounds__(256) void conv_step_kernel(const dv3_conv_step_desc p) {
@@ -290,7 +330,19 @@ __global__ __launch_bounds__(256) void conv_step_kernel(const dv3_conv_step_desc
   conv_step_tile(p, p.t ? p.t[0] : p.t_value, blockIdx.x, blockIdx.y * NB, lds, w, false);
 }
 
+// slot mode: its own kernel, so that the shared-counter one above carries none of it
+__global__ __launch_bounds__(256) void conv_step_slots_kernel(const dv3_conv_step_desc p) {
+  extern __shared__ float lds[];
+  f32x4 w[KPF];
+  const int t = p.t ? p.t[0] : p.t_value;
+  if (p.mode == DV3_EPI_GLU || p.mode == DV3_EPI_HIGHWAY)
+    conv_step_tile_t<true, true>(p, t, blockIdx.x, blockIdx.y * NB, lds, w, false, nullptr);
+  else
+    conv_step_tile_t<false, true>(p, t, blockIdx.x, blockIdx.y * NB, lds, w, false, nullptr);
+}
+
 // one attention read of batch item b at step t; all 256 threads of the workgroup take part
+// (slot mode: the caller passes the item's own step; the stacked row and the window's two sides follow from it)
 __device__ __forceinline__ void attn_step_item(const dv3_attn_step_desc& p, const int t, const int b, float* lds,
                                                float* red, int* redi) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -397,6 +449,16 @@ __global__ __launch_bounds__(256) void attn_step_kernel(const dv3_attn_step_desc
   __shared__ float red[4];
   __shared__ int redi[4];
   attn_step_item(p, p.t ? p.t[0] : p.t_value, blockIdx.x, lds, red, redi);
+}
+
+// slot mode: the workgroup's item at its own step; an idle slot (step outside [0, t_cap)) stores nothing
+__global__ __launch_bounds__(256) void attn_step_slots_kernel(const dv3_attn_step_desc p) {
+  extern __shared__ float lds[];
+  __shared__ float red[4];
+  __shared__ int redi[4];
+  const int tb = (p.t ? p.t[0] : p.t_value) - p.t_off[blockIdx.x];
+  if (tb < 0 || tb >= p.t_cap) return;             // workgroup-uniform
+  attn_step_item(p, tb, blockIdx.x, lds, red, redi);
 }
 
 // fwd_pack [Ktot][lda] -> step-tile order, window elements zero-padded to kpad (include/dv3hip.h: dv3_conv_step_pack_f32)
@@ -546,7 +608,8 @@ extern "C" int dv3_conv_step_f32(const dv3_conv_step_desc* d, void* stream) {
   if (rc != DV3_OK) return rc;
   const bool gated = d->mode == DV3_EPI_GLU || d->mode == DV3_EPI_HIGHWAY;
   const int rows = gated ? d->Cg : d->M;
-  hipLaunchKernelGGL(conv_step_kernel, dim3(dv3_cdiv(rows, MT), dv3_cdiv(d->B, NB)), dim3(256), lds, (hipStream_t)stream, *d);
+  hipLaunchKernelGGL(d->t_off ? conv_step_slots_kernel : conv_step_kernel, dim3(dv3_cdiv(rows, MT), dv3_cdiv(d->B, NB)),
+                     dim3(256), lds, (hipStream_t)stream, *d);
   return dv3_check_launch("conv_step");
 }
 
@@ -563,6 +626,7 @@ static int conv_step_check(const dv3_conv_step_desc* d, bool need_t, size_t* lds
   if (d->J > 1) DV3_REQUIRE(d->ring && (d->t || !need_t) && d->L >= (d->J - 1) * d->dil + 1,
                             "conv_step: k > 1 needs ring, t and L >= (k-1)*d+1");
   if (d->post_add || d->out_seq || d->x_ts) DV3_REQUIRE(d->t || !need_t, "conv_step: post_add / out_seq / x_ts need the step counter");
+  if (d->t_off) DV3_REQUIRE(d->t_cap > 0 && (d->t || !need_t), "conv_step: slot mode (t_off) needs t_cap > 0 and the step counter");
   const size_t lds = (size_t)dv3_conv_step_lds_bytes(d->J, d->Cin);
   DV3_REQUIRE(((uintptr_t)d->a & 15) == 0, "conv_step: the step-tile weight image must be 16-byte aligned");
   DV3_REQUIRE(lds <= DV3_CONV_STEP_LDS_MAX, "conv_step: window too large for LDS (%zu bytes)", lds);
@@ -621,6 +685,9 @@ extern "C" int dv3_decode_program_run(const dv3_decode_program* d, void* stream)
     DV3_REQUIRE(en.kind == 0 || !en.attn.key_len,
                 "decode_program: per-utterance attention (key_len) is not taken by the persistent program, whose stop "
                 "rule is one flag per batch; use dv3_decode_program_launch");
+    DV3_REQUIRE(!(en.kind == 0 ? en.conv.t_off : en.attn.t_off),
+                "decode_program: slot mode (t_off) is not taken by the persistent program, whose loop variable is one step "
+                "index and whose stop rule is one flag per batch; use dv3_decode_program_launch");
     DV3_REQUIRE((en.kind == 0 ? en.conv.B : en.attn.B) == d->B, "decode_program: entry %d has another batch size", e);
     if (l > lds_max) lds_max = l;
   }
@@ -660,22 +727,72 @@ extern "C" int dv3_decode_program_launch(const dv3_decode_program* d, void* stre
         c.t = nullptr;
         c.t_value = t;
         const bool gated = c.mode == DV3_EPI_GLU || c.mode == DV3_EPI_HIGHWAY;
-        hipLaunchKernelGGL(conv_step_kernel, dim3(dv3_cdiv(gated ? c.Cg : c.M, MT), dv3_cdiv(c.B, NB)), dim3(256), lds[e], st, c);
+        hipLaunchKernelGGL(c.t_off ? conv_step_slots_kernel : conv_step_kernel,
+                           dim3(dv3_cdiv(gated ? c.Cg : c.M, MT), dv3_cdiv(c.B, NB)), dim3(256), lds[e], st, c);
       } else {
         dv3_attn_step_desc a = en.attn;
         a.t = nullptr;
         a.t_value = t;
-        hipLaunchKernelGGL(attn_step_kernel, dim3(a.B), dim3(256), lds[e], st, a);
+        hipLaunchKernelGGL(a.t_off ? attn_step_slots_kernel : attn_step_kernel, dim3(a.B), dim3(256), lds[e], st, a);
       }
     }
   }
   return dv3_check_launch("decode_program_launch");
 }
 
+// ---- slot mode: a fresh sequence in some batch slots (include/dv3hip.h: dv3_decode_slots_reset) ----
+namespace {
+constexpr int RESET_JOBS = 128;
+struct SlotResetJob { float* ptr; int32_t rows; int32_t cols; int64_t row_stride; int64_t item_stride; };
+struct SlotResetArgs { SlotResetJob job[RESET_JOBS]; };
+// blockIdx.x: job, blockIdx.y: entry of the slot list.  A job is `rows` rows of `cols` 4-byte words per item
+// (a ring: L rows of Cin; a window: 2 rows of 1 int; the decoder input: 1 row)
+__global__ __launch_bounds__(256) void slots_reset_kernel(const SlotResetArgs a, const int32_t* __restrict__ slots, const int B) {
+  const SlotResetJob j = a.job[blockIdx.x];
+  const int s = slots[blockIdx.y];
+  if (s < 0 || s >= B) return;
+  const int64_t n = (int64_t)j.rows * j.cols;
+  for (int64_t i = threadIdx.x; i < n; i += 256)
+    j.ptr[(i / j.cols) * j.row_stride + (int64_t)s * j.item_stride + (i % j.cols)] = 0.f;     // (+0.f and int 0: the same bits)
+}
+}  // namespace
+
+extern "C" int dv3_decode_slots_reset(const dv3_decode_program* d, const int32_t* slots, int32_t n, void* stream) {
+  DV3_REQUIRE(d && d->entries_host && slots, "decode_slots_reset: null pointer");
+  DV3_REQUIRE(d->n_entries > 0 && d->B > 0 && n > 0 && n <= 65535, "decode_slots_reset: bad dims");
+  DV3_REQUIRE(d->entries_host[0].kind == 0, "decode_slots_reset: entry 0 must be the conv entry that reads the decoder input");
+  SlotResetArgs a;
+  int nj = 0;
+  {
+    const dv3_conv_step_desc& c = d->entries_host[0].conv;
+    a.job[nj++] = SlotResetJob{const_cast<float*>(c.x), 1, c.Cin, 0, c.x_bs};
+  }
+  for (int e = 0; e < d->n_entries; ++e) {
+    const dv3_decode_entry& en = d->entries_host[e];
+    DV3_REQUIRE(en.kind == 0 || en.kind == 1, "decode_slots_reset: entry %d has kind %d", e, en.kind);
+    DV3_REQUIRE((en.kind == 0 ? en.conv.B : en.attn.B) == d->B, "decode_slots_reset: entry %d has another batch size", e);
+    DV3_REQUIRE(nj < RESET_JOBS, "decode_slots_reset: more than %d rings and windows", RESET_JOBS - 1);
+    if (en.kind == 0) {
+      const dv3_conv_step_desc& c = en.conv;
+      if (c.ring) {
+        DV3_REQUIRE(c.L > 0 && c.Cin > 0, "decode_slots_reset: entry %d has a ring without dims", e);
+        a.job[nj++] = SlotResetJob{c.ring, c.L, c.Cin, (int64_t)c.B * c.Cin, c.Cin};
+      }
+    } else if (en.attn.last_attended) {
+      DV3_REQUIRE(en.attn.key_len, "decode_slots_reset: entry %d keeps one window for the batch (no key_len)", e);
+      a.job[nj++] = SlotResetJob{reinterpret_cast<float*>(en.attn.last_attended), 2, 1, en.attn.B, 1};
+    }
+  }
+  hipLaunchKernelGGL(slots_reset_kernel, dim3(nj, n), dim3(256), 0, (hipStream_t)stream, a, slots, d->B);
+  return dv3_check_launch("decode_slots_reset");
+}
+
 static int attn_step_check(const dv3_attn_step_desc* d, bool need_t, size_t* lds_out) {
   DV3_REQUIRE(d && d->q && d->k && d->v && d->ctx, "attn_step: null pointer");
   DV3_REQUIRE(d->B > 0 && d->E > 0 && d->Tk > 0, "attn_step: bad dims");
   if (d->last_attended || d->attn_seq) DV3_REQUIRE(d->t || !need_t, "attn_step: the window / stacked output need the step counter");
+  if (d->t_off) DV3_REQUIRE(d->t_cap > 0 && d->key_len && (d->t || !need_t),
+                            "attn_step: slot mode (t_off) needs t_cap > 0, key_len (per-item windows) and the step counter");
   const size_t lds = ((size_t)d->E + d->Tk) * sizeof(float);
   DV3_REQUIRE(lds <= 64 * 1024, "attn_step: E + Tk too large for LDS");
   *lds_out = lds;
@@ -686,6 +803,6 @@ extern "C" int dv3_attn_step_f32(const dv3_attn_step_desc* d, void* stream) {
   size_t lds = 0;
   const int rc = attn_step_check(d, true, &lds);
   if (rc != DV3_OK) return rc;
-  hipLaunchKernelGGL(attn_step_kernel, dim3(d->B), dim3(256), lds, (hipStream_t)stream, *d);
+  hipLaunchKernelGGL(d->t_off ? attn_step_slots_kernel : attn_step_kernel, dim3(d->B), dim3(256), lds, (hipStream_t)stream, *d);
   return dv3_check_launch("attn_step");
 }

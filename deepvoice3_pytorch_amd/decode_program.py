@@ -7,6 +7,11 @@ buffer on a device step counter, k-tap GEMV, the whole layer tail) and one dv3_a
 that the host replays launch by launch (optionally as one hipGraph per step), or that ONE persistent launch walks for
 the whole utterance (dv3_decode_program_run: the loop, the ring buffers, the stop rule and the layer-to-layer
 hand-over all stay on the device; opt-in, see StepProgram.decode).  `StepProgram` owns the buffers the descriptors point at.
+
+Slot mode (StepProgram(B, device, t_cap=...)): the program is built ONCE for B batch slots and lives
+across utterances.  Every slot runs at its own step t - t_off[b] (the kernels' slot mode, include/dv3hip.h), so a slot
+whose utterance has ended is handed to the next one (`admit`) while its neighbours keep decoding; `RollingSchedule` is
+the host-side book of which ticket sits in which slot since which global step.
 """
 import ctypes
 
@@ -50,13 +55,30 @@ def item_results(stops, outputs, alignments, dones, states):
     return outputs, alignments, dones, states, lengths.long()
 
 
+SLOT_IDLE = 2 ** 31 - 1          # t_off of a slot nobody sits in: its step t - t_off is negative for every t >= 0
+
+
 class StepProgram(object):
-    def __init__(self, B, device):
+    def __init__(self, B, device, t_cap=None):
+        """t_cap: slot mode -- the rows every stacked output and step-indexed table holds per slot (the decoder's
+        max_decoder_steps + 1); the program then owns t_off and key_len (int32[B] on the device)"""
         self.B, self.dev = B, device
         self.f32 = dict(dtype=torch.float32, device=device)
         self.t_dev = torch.zeros(1, dtype=torch.int32, device=device)      # the step counter every launch reads
         self.keep, self.prog = [self.t_dev], []
         self.per_item = False         # an attention entry reads per-utterance key lengths (attn_step(key_len=...))
+        self.t_cap = None if t_cap is None else int(t_cap)
+        if self.t_cap is not None:
+            if self.t_cap < 1:
+                raise ValueError("decode program: slot mode needs t_cap >= 1")
+            self.t_off = torch.full((B,), SLOT_IDLE, dtype=torch.int32, device=device)
+            self.key_len = torch.ones(B, dtype=torch.int32, device=device)
+            self.t = 0                # the global step (host): the next launch's t_value
+            self.keep.extend([self.t_off, self.key_len])
+
+    @property
+    def slot_mode(self):
+        return self.t_cap is not None
 
     def buffer(self, *shape):
         t = torch.zeros(*shape, **self.f32)
@@ -104,22 +126,35 @@ class StepProgram(object):
         if out_seq is not None:
             d.out_seq, d.out_seq_ts, d.out_seq_bs = out_seq.data_ptr(), out_seq.stride(0), out_seq.stride(1)
         d.B, d.Cin, d.M = B, Cin, (2 * Cout if gated else Cout)
+        if self.slot_mode:
+            d.t_off, d.t_cap = self.t_off.data_ptr(), self.t_cap
         d.Cg, d.J, d.dil, d.mode, d.residual = (Cout if gated else 0), k, dil, mode, int(residual)
         self.keep.extend([pk, x, y, spk, r, r2, post_add, y_act, y_pre, out_seq])
         self.prog.append(("dv3_conv_step_f32", d))
         return y
 
-    def attn_step(self, q, k, v, window_backward, window_ahead, monotonic, attn_seq=None, key_len=None):
+    def attn_step(self, q, k, v, window_backward, window_ahead, monotonic, attn_seq=None, key_len=None, rows=False):
         """one attention read over (B, E, Tk) keys / values (deepvoice3.py:143-171 at Tq = 1, no padding mask);
-        key_len (device int32[B]): per-utterance mode -- item b reads its own keys n < key_len[b] with its own window"""
+        key_len (device int32[B]): per-utterance mode -- item b reads its own keys n < key_len[b] with its own window.
+        rows: k and v are already the contiguous-row (B, Tk, E) images the kernel reads (slot mode: the slots' rows,
+        rewritten at every admission)"""
         B = self.B
-        E, Tk = k.size(1), k.size(2)
+        if self.slot_mode:
+            if not rows or key_len is not None:
+                raise RuntimeError("decode program: slot mode reads per-slot key / value rows and its own key_len")
+            key_len = self.key_len
+        E, Tk = (k.size(2), k.size(1)) if rows else (k.size(1), k.size(2))
         ctx = torch.empty(B, E, **self.f32)
         la = self.buffer(2 * B if key_len is not None else 2).to(torch.int32) if monotonic else None
         if la is not None:
             self.keep.append(la)
         # one-frame reads want a key / value ROW contiguous: (B, Tk, E), transposed once per utterance batch
-        kt, vt = ops.transpose(k.contiguous()), ops.transpose(v.contiguous())
+        if rows:
+            if not (k.is_contiguous() and v.is_contiguous()):
+                raise RuntimeError("decode program: key / value rows must be contiguous")
+            kt, vt = k, v
+        else:
+            kt, vt = ops.transpose(k.contiguous()), ops.transpose(v.contiguous())
         self.keep.extend([kt, vt])
         a = STRUCTS["dv3_attn_step_desc"]()
         a.q, a.q_bs, a.k, a.v, a.kv_tke = q.data_ptr(), q.stride(0), kt.data_ptr(), vt.data_ptr(), 1
@@ -133,6 +168,8 @@ class StepProgram(object):
             key_len = key_len.to(device=self.dev, dtype=torch.int32).contiguous()
             a.key_len = key_len.data_ptr()
             self.per_item = True
+        if self.slot_mode:
+            a.t_off, a.t_cap = self.t_off.data_ptr(), self.t_cap
         self.keep.extend([q, k, v, ctx, attn_seq, key_len])
         self.prog.append(("dv3_attn_step_f32", a))
         return ctx
@@ -170,6 +207,87 @@ class StepProgram(object):
         if ti is not None and fed == 0:
             raise RuntimeError("decode program: no entry reads the decoder input buffer")
         return arr, ti
+
+    # ---- slot mode -------------------------------------------------------------------------------------------------
+    def seal(self, cur_in, outs, dones_seq, states, aligns, write_operands, align_scale=1.0):
+        """slot mode: the program is complete.  cur_in: the decoder-input buffer (the x of entry 0); outs / dones_seq /
+        states / aligns: the stacked (t_cap, B, .) outputs; write_operands(slot_index int64[n] on the device, memory,
+        text_positions, speaker_embed): the decoder family's writer of the per-slot operands (projected keys and values,
+        position codes, speaker biases) for a group of admitted utterances."""
+        if not self.slot_mode:
+            raise RuntimeError("decode program: seal() is the slot mode's")
+        if not self.prog or self.prog[0][0] != "dv3_conv_step_f32" or self.prog[0][1].x != cur_in.data_ptr():
+            raise RuntimeError("decode program: entry 0 must read the decoder input buffer")
+        self.outs, self.dones_seq, self.states, self.aligns = outs, dones_seq, states, aligns
+        self.align_scale = float(align_scale)
+        self._write_operands = write_operands
+        self._arr, _ = self._entries(cur_in, None)
+        p = STRUCTS["dv3_decode_program"]()
+        p.entries_host = ctypes.addressof(self._arr)
+        p.n_entries, p.B = len(self.prog), self.B
+        p.n_steps = 1
+        self._p = p
+        return self
+
+    def admit(self, slots, memory, text_positions, text_lengths, speaker_embed=None):
+        """hand the batch slots `slots` (a list of n ints) to n new utterances at the current global step: memory = the
+        encoder's (keys, values) (n, Tt, D) of the group, text_positions (n, Tt), text_lengths n ints (item i reads its
+        keys < text_lengths[i]), speaker_embed (n, E) or None.  Writes the per-slot operands, key_len and
+        t_off = the global step, and starts a fresh sequence in those slots (one dv3_decode_slots_reset launch)."""
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        keys = memory[0]
+        tl = torch.as_tensor(text_lengths).reshape(-1).to(torch.int64).cpu()
+        if n == 0 or len(set(slots)) != n or min(slots) < 0 or max(slots) >= self.B:
+            raise ValueError("decode program: admit() takes distinct slot indices in [0, %d), got %s" % (self.B, slots))
+        if keys.size(0) != n or tl.numel() != n or int(tl.min()) < 1 or int(tl.max()) > keys.size(1):
+            raise ValueError("decode program: admit() of %d slots got %d utterances with text lengths %s over %d keys" % (
+                n, keys.size(0), tl.tolist(), keys.size(1)))
+        idx = torch.tensor(slots, dtype=torch.int64).to(self.dev)
+        with torch.no_grad():
+            self._write_operands(idx, memory, text_positions, speaker_embed)
+            self.key_len[idx] = tl.to(torch.int32).to(self.dev)
+            self.t_off[idx] = self.t
+            self._idx32 = idx.to(torch.int32)
+            ops._lib.call("dv3_decode_slots_reset", ctypes.byref(self._p), self._idx32.data_ptr(), n, ops._stream())
+
+    def release(self, slots):
+        """the slots are idle from the next step on (nothing of theirs is stored until they are admitted again)"""
+        if len(slots):
+            self.t_off[torch.tensor([int(s) for s in slots], dtype=torch.int64).to(self.dev)] = SLOT_IDLE
+
+    def run_steps(self, n):
+        """n steps of every slot, one library call (dv3_decode_program_launch); the global step advances by n"""
+        if n > 0:
+            self._p.t0, self._p.n_steps = self.t, int(n)
+            ops._lib.call("dv3_decode_program_launch", ctypes.byref(self._p), ops._stream())
+            self.t += int(n)
+
+    def slot_step(self, slot_t_off):
+        """the step a slot admitted at global step slot_t_off runs next"""
+        return self.t - int(slot_t_off)
+
+    def done_flags(self):
+        """the stacked done flags > 0.5 as host rows [t_b][slot] (one device read per chunk of steps)"""
+        return (self.dones_seq.reshape(self.t_cap, self.B) > 0.5).tolist()
+
+    def read_slot(self, slot, n):
+        """copies of slot's first n stacked rows -> (outputs (n, D), alignments (n, Tk_cap), dones (n,), states (n, Cs))"""
+        ali = self.aligns[:n, slot].clone()
+        if self.align_scale != 1.0:
+            ali = ali * self.align_scale
+        return (self.outs[:n, slot].clone(), ali, self.dones_seq[:n, slot, 0].clone(), self.states[:n, slot].clone())
+
+    def read_slots(self, slots, steps):
+        """the stacked results of several slots as one zero-tailed batch (item_results): slots[i] ran steps[i] steps
+        -> (outputs (n, max steps, D), alignments (n, max steps, Tk_cap), states (n, max steps, Cs))"""
+        idx = torch.tensor([int(s) for s in slots], dtype=torch.int64).to(self.dev)
+        m = max(steps)
+        outputs, alignments, states = (x[:m].index_select(1, idx).transpose(0, 1) for x in (self.outs, self.aligns, self.states))
+        if self.align_scale != 1.0:
+            alignments = alignments * self.align_scale
+        outputs, alignments, _, states, _ = item_results(list(steps), outputs, alignments, [], states)
+        return outputs, alignments, states
 
     def decode_persistent(self, cur_in, test_inputs, dones_seq, min_steps, max_steps):
         """the whole loop as one launch of the persistent program kernel (include/dv3hip.h: dv3_decode_program_run)
@@ -251,6 +369,11 @@ class StepProgram(object):
         it is opt-in.  Per-utterance mode (attention entries with key_len): pass stops = [0] * B; every item stops by
         its own done flag (item_stops), the loop runs until all have, and stops holds each item's step count; the
         persistent program does not take this mode."""
+        if self.slot_mode:
+            if persistent or (persistent is None and persistent_default):
+                raise RuntimeError("decode program: the persistent program does not take slot mode (its loop is one "
+                                   "step index for the batch); slots run through admit() / run_steps()")
+            raise RuntimeError("decode program: a slot-mode program runs through admit() / run_steps(), not decode()")
         if self.per_item and stops is None:
             raise RuntimeError("decode program: per-utterance attention entries need the per-item stop rule (stops=)")
         if persistent is None:
@@ -341,3 +464,103 @@ class StepTrace(object):
     def result(self):
         out, ali, st = (b[:, :self.n] for b in self._bufs)
         return out.contiguous(), ali, self.dones, st.contiguous()
+
+
+class RollingSchedule(object):
+    """The host-side book of rolling admission: which ticket sits in which batch slot since which global step.  A pure
+    host object (no GPU, no model).  One round (RollingSynthesizer.poll) is
+        admit()          queued tickets, first in first out, into the free slots in ascending slot order; each gets
+                         t_off = the current global step;
+        advance(chunk)   every slot runs `chunk` decoder steps (idle ones included: a decode step costs the same at
+                         any occupancy -- that is the point of refilling them);
+        retire(slot)     for every slot whose utterance has stopped within the steps it has run.
+    steps counts the decoder steps executed; log keeps (ticket, slot, t_off, retired_at) per retired ticket."""
+
+    def __init__(self, slots, chunk=8):
+        if slots < 1 or chunk < 1:
+            raise ValueError("RollingSchedule: slots and chunk must be positive")
+        self.n_slots, self.chunk = int(slots), int(chunk)
+        self.t = 0                                   # global step
+        self.steps = 0                               # decoder steps executed
+        self.queue = []                              # tickets waiting, FIFO
+        self.slot_ticket = [None] * self.n_slots
+        self.slot_t_off = [0] * self.n_slots
+        self.log = []
+
+    def submit(self, ticket):
+        self.queue.append(ticket)
+
+    def busy(self):
+        return [s for s in range(self.n_slots) if self.slot_ticket[s] is not None]
+
+    def pending(self):
+        return bool(self.queue) or any(t is not None for t in self.slot_ticket)
+
+    def admit(self):
+        """-> [(ticket, slot)] admitted now"""
+        out = []
+        for s in range(self.n_slots):
+            if not self.queue:
+                break
+            if self.slot_ticket[s] is None:
+                tk = self.queue.pop(0)
+                self.slot_ticket[s], self.slot_t_off[s] = tk, self.t
+                out.append((tk, s))
+        return out
+
+    def advance(self, n=None):
+        n = self.chunk if n is None else int(n)
+        self.t += n
+        self.steps += n
+        return n
+
+    def steps_run(self, slot):
+        """decoder steps the slot's utterance has run"""
+        return self.t - self.slot_t_off[slot]
+
+    def retire(self, slot):
+        tk = self.slot_ticket[slot]
+        if tk is None:
+            raise RuntimeError("RollingSchedule: slot %d is free" % slot)
+        self.slot_ticket[slot] = None
+        self.log.append((tk, slot, self.slot_t_off[slot], self.t))
+        return tk
+
+
+def simulate_rolling(step_counts, slots, chunk=8):
+    """decoder steps rolling admission executes for utterances that need step_counts[i] steps, submitted in that order
+    before the first round -> (steps, the RollingSchedule with its log)"""
+    sch = RollingSchedule(slots, chunk)
+    for i, n in enumerate(step_counts):
+        if n < 1:
+            raise ValueError("simulate_rolling: every utterance needs at least one step")
+        sch.submit(i)
+    while sch.pending():
+        sch.admit()
+        sch.advance()
+        for s in sch.busy():
+            if sch.steps_run(s) >= step_counts[sch.slot_ticket[s]]:
+                sch.retire(s)
+    return sch.steps, sch
+
+
+def simulate_waves(step_counts, slots, chunk=None):
+    """decoder steps rigid waves of `slots` utterances execute: every wave runs until its slowest item has stopped
+    (chunk: rounded up to whole chunks of steps, as a loop that reads the done flags once per chunk runs them;
+    None: the exact maximum, the most favourable count for waves)"""
+    total = 0
+    for i in range(0, len(step_counts), slots):
+        m = max(step_counts[i:i + slots])
+        total += m if chunk is None else -(-m // chunk) * chunk
+    return total
+
+
+def cfg2_step_counts(n, seed, r=4, max_steps=None):
+    """decoder steps of n utterances with LJSpeech-shaped lengths: mel frames ~ N(566, 180) clipped to
+    [120, 870], steps = frames / r (optionally capped at max_steps)"""
+    import numpy as np
+    frames = np.clip(np.random.RandomState(seed).normal(566.0, 180.0, n), 120, 870)
+    steps = np.maximum((frames / r).astype(np.int64), 1)
+    if max_steps is not None:
+        steps = np.minimum(steps, max_steps)
+    return [int(v) for v in steps]

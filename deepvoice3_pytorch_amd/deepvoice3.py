@@ -591,50 +591,11 @@ class Decoder(nn.Module):
             states, aligns = P.buffer(n_max, B, Cs), P.buffer(n_max, B, Tk)
             P.keep.extend([keys_bct, values_bct, proj, pe_all, cur_in, nxt_in])
 
-            def glu_step(f, x, residual, **kw):
-                spk = None
-                if f.speaker_proj is not None:
-                    se = speaker_embed if speaker_embed.dim() == 2 else speaker_embed[:, 0, :]
-                    spk = f.speaker_bias(se).contiguous()
-                return P.conv_step(f.conv, x, ops.EPI_GLU, f.conv.out_channels // 2, k=f.conv.kernel_size[0],
-                                   dil=f.conv.dilation[0], gated=True, residual=residual, spk=spk, **kw)
+            def spk_of(f):
+                se = speaker_embed if speaker_embed.dim() == 2 else speaker_embed[:, 0, :]
+                return f.speaker_bias(se).contiguous()
 
-            # ---- the step program (deepvoice3.py:397-461) ----
-            x = cur_in
-            mods, i = list(self.preattention), 0
-            while i < len(mods):
-                f = mods[i]
-                if isinstance(f, Conv1dGLU):
-                    x = glu_step(f, x, f.residual)
-                elif isinstance(f, _conv.Conv1d):
-                    relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-                    if f.kernel_size[0] != 1:
-                        raise RuntimeError("fast decode: only 1x1 plain convolutions in the pre-attention stack")
-                    x = P.conv_step(f, x, ops.EPI_RELU if relu else ops.EPI_LINEAR, f.out_channels)
-                    i += int(relu)
-                else:
-                    raise RuntimeError("fast decode: unsupported pre-attention module %r" % type(f))
-                i += 1
-            first_att = True
-            n_conv = len(self.convolutions)
-            for idx, (f, attention) in enumerate(zip(self.convolutions, self.attention)):
-                residual = x
-                st = states if idx == n_conv - 1 else None
-                if attention is None:
-                    x = glu_step(f, x, f.residual, r2=residual, out_seq=st)   # (glu + residual) * sqrt(.5)
-                    continue
-                xq = glu_step(f, x, f.residual, post_add=pe_all)              # conv output + the step's position code
-                kp, vp = proj[idx]
-                q = P.conv_step(attention.query_projection, xq, ops.EPI_LINEAR, attention.query_projection.out_features)
-                # ave_alignment = the FIRST layer's alignment * 2^(n-1)/n (the reference's `ave + ave`)
-                ctx = P.attn_step(q, kp, vp, attention.window_backward, attention.window_ahead,
-                                  self.force_monotonic_attention[idx], attn_seq=aligns if first_att else None,
-                                  key_len=key_len)
-                first_att = False
-                x = P.conv_step(attention.out_projection, ctx, ops.EPI_LINEAR, attention.out_projection.out_features,
-                                r=xq, r2=residual, out_seq=st)
-            pre = P.conv_step(self.last_conv, x, ops.EPI_LINEAR, D, y_act=nxt_in, out_seq=outs)
-            P.conv_step(self.fc, pre, ops.EPI_SIGMOID, 1, out_seq=dones_seq)
+            self._step_entries(P, cur_in, nxt_in, pe_all, proj, spk_of, key_len, outs, dones_seq, states, aligns)
             t = P.decode(cur_in, test_inputs, dones_seq, self.min_decoder_steps, self.max_decoder_steps,
                          getattr(self, "use_step_graph", False), getattr(self, "persistent_decode", None),
                          getattr(self, "launched_decode", None), stops=stops)
@@ -646,6 +607,126 @@ class Decoder(nn.Module):
             outputs = outs[:t].transpose(0, 1).contiguous()
             dones = [dones_seq[i].view(B, 1, 1) for i in range(t)]
         return outputs, alignments, dones, decoder_states
+
+    def _step_entries(self, P, cur_in, nxt_in, pe_all, proj, spk_of, key_len, outs, dones_seq, states, aligns, rows=False):
+        """the step program (deepvoice3.py:397-461) appended to P.  proj[idx]: attention layer idx's projected (keys,
+        values) -- (B, E, Tk), or the (B, Tk, E) row images with rows=True; spk_of(f): the (B, C) speaker bias of GLU
+        layer f (called only for layers that have one)"""
+        D = self.in_dim * self.r
+
+        def glu_step(f, x, residual, **kw):
+            spk = spk_of(f) if f.speaker_proj is not None else None
+            return P.conv_step(f.conv, x, ops.EPI_GLU, f.conv.out_channels // 2, k=f.conv.kernel_size[0],
+                               dil=f.conv.dilation[0], gated=True, residual=residual, spk=spk, **kw)
+
+        x = cur_in
+        mods, i = list(self.preattention), 0
+        while i < len(mods):
+            f = mods[i]
+            if isinstance(f, Conv1dGLU):
+                x = glu_step(f, x, f.residual)
+            elif isinstance(f, _conv.Conv1d):
+                relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+                if f.kernel_size[0] != 1:
+                    raise RuntimeError("fast decode: only 1x1 plain convolutions in the pre-attention stack")
+                x = P.conv_step(f, x, ops.EPI_RELU if relu else ops.EPI_LINEAR, f.out_channels)
+                i += int(relu)
+            else:
+                raise RuntimeError("fast decode: unsupported pre-attention module %r" % type(f))
+            i += 1
+        first_att = True
+        n_conv = len(self.convolutions)
+        for idx, (f, attention) in enumerate(zip(self.convolutions, self.attention)):
+            residual = x
+            st = states if idx == n_conv - 1 else None
+            if attention is None:
+                x = glu_step(f, x, f.residual, r2=residual, out_seq=st)   # (glu + residual) * sqrt(.5)
+                continue
+            xq = glu_step(f, x, f.residual, post_add=pe_all)              # conv output + the step's position code
+            kp, vp = proj[idx]
+            q = P.conv_step(attention.query_projection, xq, ops.EPI_LINEAR, attention.query_projection.out_features)
+            # ave_alignment = the FIRST layer's alignment * 2^(n-1)/n (the reference's `ave + ave`)
+            ctx = P.attn_step(q, kp, vp, attention.window_backward, attention.window_ahead,
+                              self.force_monotonic_attention[idx], attn_seq=aligns if first_att else None,
+                              key_len=key_len, rows=rows)
+            first_att = False
+            x = P.conv_step(attention.out_projection, ctx, ops.EPI_LINEAR, attention.out_projection.out_features,
+                            r=xq, r2=residual, out_seq=st)
+        pre = P.conv_step(self.last_conv, x, ops.EPI_LINEAR, D, y_act=nxt_in, out_seq=outs)
+        P.conv_step(self.fc, pre, ops.EPI_SIGMOID, 1, out_seq=dones_seq)
+
+    def slot_program(self, slots, max_text_len):
+        """The step program in slot mode (decode_program.StepProgram), built ONCE for `slots` batch
+        slots and texts of up to max_text_len ids, without an utterance: per-slot key / value rows (B, Tk_cap, E),
+        speaker-bias rows, position-code columns and stacked outputs of max_decoder_steps + 1 rows per slot.
+        P.admit(slot list, memory, text_positions, text_lengths, speaker_embed) hands slots to new utterances,
+        P.run_steps(n) decodes.  Only configurations the fused step kernels take: no module-by-module fallback."""
+        from .decode_program import StepProgram
+        B, Tk = int(slots), int(max_text_len)
+        dev = self.last_conv.bias.device if self.last_conv.bias is not None else next(self.parameters()).device
+        if self.training:
+            raise RuntimeError("slot_program: eval mode only")
+        if dev.type != "cuda" or not getattr(self, "fast_decode", False) or not self._fast_decode_eligible(Tk):
+            raise RuntimeError("slot_program: rolling admission runs on the fused decode-step kernels only, and this "
+                               "decoder (or %d keys) is not eligible for them (_fast_decode_eligible); there is no "
+                               "module-by-module fallback in slot mode" % Tk)
+        D = self.in_dim * self.r
+        t_cap = self.max_decoder_steps + 1
+        if t_cap >= self.embed_query_positions.weight.size(0):
+            raise RuntimeError("slot_program: decoder steps exceed max_positions")
+        multi = self.speaker_proj1 is not None
+        with torch.no_grad():
+            P = StepProgram(B, dev, t_cap=t_cap)
+            cur_in = P.buffer(B, D)
+            n_att = sum(1 for a in self.attention if a is not None)
+            Cs = self.convolutions[-1].conv.out_channels // 2
+            Cq = self.embed_query_positions.weight.size(1)
+            outs, dones_seq = P.buffer(t_cap, B, D), P.buffer(t_cap, B, 1)
+            states, aligns = P.buffer(t_cap, B, Cs), P.buffer(t_cap, B, Tk)
+            pe_all = P.buffer(t_cap, B, Cq)
+            rows = []
+            for att in self.attention:
+                if att is None:
+                    rows.append(None)
+                    continue
+                E = att.query_projection.out_features
+                rows.append((P.buffer(B, Tk, E), P.buffer(B, Tk, E)))
+            spk_rows = {}
+
+            def spk_of(f):
+                spk_rows[id(f)] = (f, P.buffer(B, f.conv.out_channels // 2))
+                return spk_rows[id(f)][1]
+
+            self._step_entries(P, cur_in, cur_in, pe_all, rows, spk_of, None, outs, dones_seq, states, aligns, rows=True)
+            pos = torch.arange(1, t_cap + 1, device=dev, dtype=torch.long)[None]
+
+            def write_operands(idx, memory, text_positions, speaker_embed):
+                keys, values = memory
+                n, Tt = keys.size(0), keys.size(1)
+                if Tt > Tk:
+                    raise ValueError("slot_program: %d keys, the slots hold %d" % (Tt, Tk))
+                if multi and speaker_embed is None:
+                    raise ValueError("slot_program: a multi-speaker decoder needs speaker_embed at admission")
+                w = self._rate(self.key_position_rate, self.speaker_proj1, speaker_embed)
+                keys_bct = self.embed_keys_positions.forward_bct(text_positions, w, base=keys.transpose(1, 2).contiguous())
+                values_bct = values.transpose(1, 2).contiguous()
+                for att, kv in zip(self.attention, rows):
+                    if att is None:
+                        continue
+                    k = att.key_projection.forward_bct(keys_bct) if att.key_projection is not None else keys_bct
+                    v = att.value_projection.forward_bct(values_bct) if att.value_projection is not None else values_bct
+                    kv[0][idx, :Tt] = ops.transpose(k.contiguous())
+                    kv[1][idx, :Tt] = ops.transpose(v.contiguous())
+                wq = self._rate(self.query_position_rate, self.speaker_proj2, speaker_embed)
+                pe = self.embed_query_positions.forward_bct(pos.expand(n, t_cap).contiguous(), wq)      # (n, C, t_cap)
+                pe_all[:, idx] = pe.permute(2, 0, 1)
+                for f, buf in spk_rows.values():
+                    se = speaker_embed if speaker_embed.dim() == 2 else speaker_embed[:, 0, :]
+                    buf[idx] = f.speaker_bias(se)
+
+            scale = float(2 ** (n_att - 1)) / n_att if n_att else 1.0
+            P.seal(cur_in, outs, dones_seq, states, aligns, write_operands, align_scale=scale)
+        return P
 
     @staticmethod
     def _incremental_stack(modules, x, speaker_embed):

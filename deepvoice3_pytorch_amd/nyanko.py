@@ -262,33 +262,7 @@ class Decoder(nn.Module):
             xq = P.buffer(B, D)
             P.keep.extend([k, v, pe_all, cur_in, nxt_in])
 
-            def run(mods, x, last_kw=None):
-                """a Conv1d(+ReLU) / HighwayConv1d stack, one launch per layer; last_kw: extra outputs of the last layer"""
-                mods = list(mods)
-                i = 0
-                while i < len(mods):
-                    f = mods[i]
-                    relu = isinstance(f, _conv.Conv1d) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-                    last = (i + int(relu)) == len(mods) - 1
-                    kw = dict(last_kw) if (last and last_kw) else {}
-                    if isinstance(f, HighwayConv1d):
-                        x = P.conv_step(f.conv, x, ops.EPI_HIGHWAY, f.conv.out_channels // 2, k=f.conv.kernel_size[0],
-                                        dil=f.conv.dilation[0], gated=True, **kw)
-                    else:
-                        x = P.conv_step(f, x, ops.EPI_RELU if relu else ops.EPI_LINEAR, f.out_channels, **kw)
-                        i += int(relu)
-                    i += 1
-                return x
-
-            # audio encoder: Q (into the concat buffer) and Q + position code (the attention query input)
-            run(self.audio_encoder_modules, cur_in, dict(y=xq, post_add=pe_all, y_pre=cat[:, D:]))
-            q = P.conv_step(att.query_projection, xq, ops.EPI_LINEAR, att.query_projection.out_features)
-            ctx = P.attn_step(q, k, v, att.window_backward, att.window_ahead, self.force_monotonic_attention,
-                              attn_seq=aligns, key_len=key_len)
-            P.conv_step(att.out_projection, ctx, ops.EPI_LINEAR, att.out_projection.out_features, r=xq, y=cat[:, :D])
-            x = run(self.audio_decoder_modules, cat, dict(out_seq=states))
-            pre = P.conv_step(self.last_conv, x, ops.EPI_LINEAR, F, y_act=nxt_in, out_seq=outs)
-            P.conv_step(self.fc, pre, ops.EPI_SIGMOID, 1, out_seq=dones_seq)
+            self._step_entries(P, cur_in, nxt_in, pe_all, k, v, key_len, outs, dones_seq, states, aligns, cat, xq)
             t = P.decode(cur_in, test_inputs, dones_seq, self.min_decoder_steps, self.max_decoder_steps,
                          getattr(self, "use_step_graph", False), getattr(self, "persistent_decode", None),
                          getattr(self, "launched_decode", None), stops=stops)
@@ -297,6 +271,90 @@ class Decoder(nn.Module):
             outputs = outs[:t].transpose(0, 1).contiguous()
             dones = [dones_seq[i].view(B, 1, 1) for i in range(t)]
         return outputs, alignments, dones, decoder_states
+
+    def _step_entries(self, P, cur_in, nxt_in, pe_all, k, v, key_len, outs, dones_seq, states, aligns, cat, xq, rows=False):
+        """the step program (nyanko.py:283-321) appended to P; k, v: the projected keys / values (B, E, Tk), or their
+        (B, Tk, E) row images with rows=True; cat (B, 2D) = [R | Q], xq (B, D) = Q + position code"""
+        att = self.attention
+        D = self.last_conv.in_channels
+        F = self.in_dim * self.r
+
+        def run(mods, x, last_kw=None):
+            """a Conv1d(+ReLU) / HighwayConv1d stack, one launch per layer; last_kw: extra outputs of the last layer"""
+            mods = list(mods)
+            i = 0
+            while i < len(mods):
+                f = mods[i]
+                relu = isinstance(f, _conv.Conv1d) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+                last = (i + int(relu)) == len(mods) - 1
+                kw = dict(last_kw) if (last and last_kw) else {}
+                if isinstance(f, HighwayConv1d):
+                    x = P.conv_step(f.conv, x, ops.EPI_HIGHWAY, f.conv.out_channels // 2, k=f.conv.kernel_size[0],
+                                    dil=f.conv.dilation[0], gated=True, **kw)
+                else:
+                    x = P.conv_step(f, x, ops.EPI_RELU if relu else ops.EPI_LINEAR, f.out_channels, **kw)
+                    i += int(relu)
+                i += 1
+            return x
+
+        # audio encoder: Q (into the concat buffer) and Q + position code (the attention query input)
+        run(self.audio_encoder_modules, cur_in, dict(y=xq, post_add=pe_all, y_pre=cat[:, D:]))
+        q = P.conv_step(att.query_projection, xq, ops.EPI_LINEAR, att.query_projection.out_features)
+        ctx = P.attn_step(q, k, v, att.window_backward, att.window_ahead, self.force_monotonic_attention,
+                          attn_seq=aligns, key_len=key_len, rows=rows)
+        P.conv_step(att.out_projection, ctx, ops.EPI_LINEAR, att.out_projection.out_features, r=xq, y=cat[:, :D])
+        x = run(self.audio_decoder_modules, cat, dict(out_seq=states))
+        pre = P.conv_step(self.last_conv, x, ops.EPI_LINEAR, F, y_act=nxt_in, out_seq=outs)
+        P.conv_step(self.fc, pre, ops.EPI_SIGMOID, 1, out_seq=dones_seq)
+
+    def slot_program(self, slots, max_text_len):
+        """The step program in slot mode (decode_program.StepProgram): built once for `slots` batch
+        slots and texts of up to max_text_len ids; see deepvoice3.Decoder.slot_program.  (The position codes are the
+        frozen table for every item: only the keys and values are per slot.)"""
+        from .decode_program import StepProgram
+        B, Tk = int(slots), int(max_text_len)
+        dev = self.embed_query_positions.weight.device
+        if self.training:
+            raise RuntimeError("slot_program: eval mode only")
+        if dev.type != "cuda" or not getattr(self, "fast_decode", True) or not self._fast_decode_eligible(Tk):
+            raise RuntimeError("slot_program: rolling admission runs on the fused decode-step kernels only, and this "
+                               "decoder (or %d keys) is not eligible for them (_fast_decode_eligible); there is no "
+                               "module-by-module fallback in slot mode" % Tk)
+        att = self.attention
+        F, D = self.in_dim * self.r, self.last_conv.in_channels
+        E = att.query_projection.out_features
+        t_cap = self.max_decoder_steps + 1
+        with torch.no_grad():
+            P = StepProgram(B, dev, t_cap=t_cap)
+            pe_all = self.embed_query_positions.weight[1:t_cap + 1].detach().contiguous()      # (t_cap, D)
+            if pe_all.size(0) < t_cap:
+                raise RuntimeError("slot_program: decoder steps exceed max_positions")
+            pe_all = pe_all[:, None, :].expand(t_cap, B, pe_all.size(1))                         # batch stride 0
+            cur_in = P.buffer(B, F)
+            outs, dones_seq = P.buffer(t_cap, B, F), P.buffer(t_cap, B, 1)
+            states, aligns = P.buffer(t_cap, B, D), P.buffer(t_cap, B, Tk)
+            cat, xq = P.buffer(B, 2 * D), P.buffer(B, D)
+            kt, vt = P.buffer(B, Tk, E), P.buffer(B, Tk, E)
+            P.keep.append(pe_all)
+            self._step_entries(P, cur_in, cur_in, pe_all, kt, vt, None, outs, dones_seq, states, aligns, cat, xq, rows=True)
+
+            def write_operands(idx, memory, text_positions, speaker_embed):
+                keys, values = memory
+                Tt = keys.size(1)
+                if Tt > Tk:
+                    raise ValueError("slot_program: %d keys, the slots hold %d" % (Tt, Tk))
+                keys_bct = keys.transpose(1, 2).contiguous()
+                if text_positions is not None:
+                    keys_bct = ops.add_position_encoding(keys_bct, text_positions, self.embed_keys_positions.weight,
+                                                         None, False)
+                values_bct = values.transpose(1, 2).contiguous()
+                k = att.key_projection.forward_bct(keys_bct) if att.key_projection is not None else keys_bct
+                v = att.value_projection.forward_bct(values_bct) if att.value_projection is not None else values_bct
+                kt[idx, :Tt] = ops.transpose(k.contiguous())
+                vt[idx, :Tt] = ops.transpose(v.contiguous())
+
+            P.seal(cur_in, outs, dones_seq, states, aligns, write_operands)
+        return P
 
     def incremental_forward(self, encoder_out, text_positions, initial_input=None, test_inputs=None,
                             text_lengths=None):

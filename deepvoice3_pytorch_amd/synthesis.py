@@ -9,10 +9,22 @@ synthesis.py:42-73, without its text frontend): every utterance comes back as if
 The model part is MultiSpeakerTTSModel.synthesize_batch (per-utterance attention, stop and zero tails on the HIP
 kernels); the waveforms are ONE batched Griffin-Lim call with per-item frame counts (audio.inv_spectrogram_batch(...,
 frame_lengths=)), each item equal to the inverse of its own trimmed spectrogram.
+
+Rolling admission: tts_batch is one rigid wave -- every item starts at step 0 and nothing new starts
+before the slowest item has stopped.  RollingSynthesizer keeps a fixed number of decode SLOTS busy instead: an utterance
+is admitted into a slot as soon as one frees, decodes at its own step index next to neighbours that are further along,
+and retires (post-net + Griffin-Lim) when its own stop rule fires.
+
+    rs = synthesis.RollingSynthesizer(model, slots=64, max_text_len=200)
+    ticket = rs.submit(ids)                      # queued; admitted when a slot frees
+    for ticket, mel, linear, alignment, wav in rs.poll(): ...     # one chunk of decoder steps; what retired in it
+    for ... in rs.drain(): ...                   # until the queue and the slots are empty
+    for index, mel, linear, alignment, wav in synthesis.tts_stream(model, sequences, slots=64): ...   # completion order
 """
 import torch
 
 from . import audio
+from .decode_program import RollingSchedule, item_stops
 
 
 def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None):
@@ -46,3 +58,186 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None):
         out.append((mel[b, :n], linear[b, :n * up], alignments[b, :n // steps_per_frame, :lengths[b]],
                     wavs[b, :int(samples[b])]))
     return out
+
+
+class RollingSynthesizer(object):
+    """Synthesis with rolling admission: `slots` decode slots that are refilled as utterances finish.
+
+    The decoder's step program is built once in slot mode (Decoder.slot_program) and lives across utterances.  Between
+    two chunks of `chunk` decoder steps, queued requests are admitted first in first out into the free slots: the
+    encoder runs on the admitted group under ops.ItemLengths (the per-utterance path of synthesize_batch) and its
+    outputs go into the slot rows.  After a chunk, every busy slot's own done flags are put to the reference's B = 1
+    stop rule (decode_program.item_stops) at the slot's own step index; the slots that stopped are freed, and the
+    retired group goes through the post-net under ItemLengths and ONE Griffin-Lim call with per-item frame counts.
+    Everything runs on the current stream, admission and retirement included.  Inference only; a decoder the fused
+    step kernels do not take is refused (no module-by-module fallback)."""
+
+    def __init__(self, model, slots=64, max_text_len=256, audio_cfg=None, chunk=8):
+        if slots < 1 or max_text_len < 1 or chunk < 1:
+            raise ValueError("RollingSynthesizer: slots, max_text_len and chunk must be positive")
+        model.eval()
+        self.model, self.audio_cfg = model, audio_cfg
+        self.max_text_len = int(max_text_len)
+        self.dec = model.seq2seq.decoder
+        if not hasattr(self.dec, "slot_program"):
+            raise RuntimeError("RollingSynthesizer: %r has no slot-mode step program" % type(self.dec))
+        self.prog = self.dec.slot_program(slots, self.max_text_len)
+        self.schedule = RollingSchedule(slots, chunk)
+        self.min_steps = int(self.dec.min_decoder_steps)
+        self.max_steps = int(self.dec.max_decoder_steps)        # = the program's t_cap - 1
+        self._req = {}
+        self._next = 0
+
+    def submit(self, ids, speaker_id=None, max_decoder_steps=None):
+        """queue one utterance (a sequence of int ids) -> its ticket (0, 1, 2, ... in submission order).
+        max_decoder_steps: this request's own cap (default and upper limit: the decoder's)"""
+        ids = [int(i) for i in ids]
+        if len(ids) < 1:
+            raise ValueError("RollingSynthesizer.submit: empty sequence")
+        if len(ids) > self.max_text_len:
+            raise ValueError("RollingSynthesizer.submit: %d ids, the slots hold max_text_len = %d" % (
+                len(ids), self.max_text_len))
+        cap = self.max_steps if max_decoder_steps is None else int(max_decoder_steps)
+        if cap < 0 or cap > self.max_steps:
+            raise ValueError("RollingSynthesizer.submit: max_decoder_steps %d outside [0, %d] (the decoder's own)" % (
+                cap, self.max_steps))
+        multi = getattr(self.model, "n_speakers", 1) > 1
+        if multi != (speaker_id is not None):
+            raise ValueError("RollingSynthesizer.submit: speaker_id is %s for a model of %d speakers" % (
+                "missing" if multi else "given", getattr(self.model, "n_speakers", 1)))
+        ticket = self._next
+        self._next += 1
+        self._req[ticket] = (ids, speaker_id, cap)
+        self.schedule.submit(ticket)
+        return ticket
+
+    def pending(self):
+        return self.schedule.pending()
+
+    def _speaker_embed(self, tickets, dev):
+        if getattr(self.model, "n_speakers", 1) <= 1:
+            return None
+        spk = torch.tensor([int(self._req[t][1]) for t in tickets], dtype=torch.long).to(dev)
+        return self.model.embed_speakers(spk)
+
+    def _admit(self, admitted):
+        from . import ops
+        model = self.model
+        dev = self.prog.dev
+        tickets = [t for t, _ in admitted]
+        seqs = [self._req[t][0] for t in tickets]
+        lengths = [len(s) for s in seqs]
+        n, Tt = len(seqs), max(lengths)
+        pad = model.seq2seq.encoder.embed_tokens.padding_idx
+        text = torch.full((n, Tt), 0 if pad is None else pad, dtype=torch.long)
+        for b, s in enumerate(seqs):
+            text[b, :len(s)] = torch.as_tensor(s, dtype=torch.long)
+        text = text.to(dev)
+        tl = torch.tensor(lengths, dtype=torch.int64)
+        pos = torch.arange(1, Tt + 1, device=dev)[None, :].expand(n, Tt)
+        text_positions = torch.where(pos <= tl.to(dev)[:, None], pos, torch.zeros_like(pos))
+        prev, ops.valid = ops.valid, ops.ItemLengths(tl, Tt, dev)
+        try:
+            with torch.no_grad():
+                se = self._speaker_embed(tickets, dev)
+                memory = model.seq2seq.encoder(text, lengths=None, speaker_embed=se)
+                self.prog.admit([s for _, s in admitted], memory, text_positions, tl, se)
+        finally:
+            ops.valid = prev
+
+    def _retire(self, retired):
+        """retired: [(ticket, slot, steps)] -> [(ticket, mel, linear, alignment, wav)]"""
+        from . import ops
+        model = self.model
+        dev = self.prog.dev
+        tickets = [t for t, _, _ in retired]
+        steps = [n for _, _, n in retired]
+        lengths = [len(self._req[t][0]) for t in tickets]
+        G, Td = len(retired), max(steps)
+        with torch.no_grad():
+            outputs, alignments, states = self.prog.read_slots([s for _, s, _ in retired], steps)
+            self.prog.release([s for _, s, _ in retired])
+            mel = outputs.reshape(G, -1, model.mel_dim)
+            post_in = states.view(G, mel.size(1), -1) if model.use_decoder_state_for_postnet_input else mel
+            vl = ops.ItemLengths(lengths, max(lengths), dev)
+            vl.set_dec(steps, Td)
+            prev, ops.valid = ops.valid, vl
+            try:
+                linear = model.postnet(post_in, self._speaker_embed(tickets, dev)).contiguous()
+                ops.zero_frames(linear, vl.dec_len, min(steps), linear.size(1) // Td)
+            finally:
+                ops.valid = prev
+            r = mel.size(1) // Td
+            up = linear.size(1) // mel.size(1)
+            frames = torch.tensor(steps, dtype=torch.int64) * r
+            wavs, samples = audio.inv_spectrogram_batch(linear, self.audio_cfg, frame_lengths=frames * up)
+        out = []
+        for b, t in enumerate(tickets):
+            n = int(frames[b])
+            out.append((t, mel[b, :n], linear[b, :n * up], alignments[b, :steps[b], :lengths[b]],
+                        wavs[b, :int(samples[b])]))
+            del self._req[t]
+        return out
+
+    def poll(self):
+        """one round: admit what fits, run one chunk of decoder steps, retire what stopped
+        -> a list of (ticket, mel (T, mel_dim), linear (T * upsampling, linear_dim), alignment (steps, Tt), wav (L,)),
+        each as tts_batch returns an utterance; empty when nothing retired (or nothing is pending)"""
+        sch = self.schedule
+        admitted = sch.admit()
+        if admitted:
+            self._admit(admitted)
+        busy = sch.busy()
+        if not busy:
+            return []
+        n = sch.advance()
+        self.prog.run_steps(n)
+        flags = self.prog.done_flags()
+        retired = []
+        for s in busy:
+            t1 = sch.steps_run(s)
+            t0 = t1 - n
+            rows = [[flags[t][s]] for t in range(t0, min(t1, self.prog.t_cap))]
+            stop = [0]
+            item_stops(rows, t0, self.min_steps, self._req[sch.slot_ticket[s]][2], stop)
+            if stop[0]:
+                retired.append((sch.retire(s), s, stop[0]))
+        return self._retire(retired) if retired else []
+
+    def drain(self):
+        """poll until the queue and the slots are empty"""
+        while self.schedule.pending():
+            for res in self.poll():
+                yield res
+
+
+def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, audio_cfg=None, chunk=8,
+               max_decoder_steps=None):
+    """Rolling-admission counterpart of tts_batch, as a generator: sequences (any iterable of id lists; speaker_ids an
+    iterable alongside, or None; max_decoder_steps None, one cap, or an iterable of per-utterance caps) are submitted
+    in order as slots free -- at most `slots` are queued ahead -- and every utterance is yielded when it retires, in
+    COMPLETION order: (index in `sequences`, mel, linear, alignment, wav), the entries as tts_batch returns them.
+    max_text_len None: the longest sequence (the iterable is then read up front)."""
+    if max_text_len is None:
+        sequences = [list(s) for s in sequences]
+        if not sequences:
+            return
+        max_text_len = max(len(s) for s in sequences)
+    rs = RollingSynthesizer(model, slots=slots, max_text_len=max_text_len, audio_cfg=audio_cfg, chunk=chunk)
+    it = iter(sequences)
+    spk = iter(speaker_ids) if speaker_ids is not None else None
+    caps = None
+    if max_decoder_steps is not None and not isinstance(max_decoder_steps, int):
+        caps = iter(max_decoder_steps)
+    more = True
+    while more or rs.pending():
+        while more and len(rs.schedule.queue) < slots:
+            try:
+                ids = next(it)
+            except StopIteration:
+                more = False
+                break
+            rs.submit(ids, next(spk) if spk is not None else None,
+                      next(caps) if caps is not None else max_decoder_steps)
+        for res in rs.poll():
+            yield res

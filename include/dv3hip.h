@@ -30,7 +30,7 @@ extern "C" {
 #define DV3_ELAUNCH (-2)  /* hipLaunch / runtime error        */
 
 /* ABI version, bumped on any struct change; checked by the Python loader. */
-#define DV3_ABI_VERSION 47
+#define DV3_ABI_VERSION 48
 int dv3_abi_version(void);
 const char* dv3_last_error(void);
 /* Fills name (<=255 chars) of device `dev`, number of CUs; returns 0/err. */
@@ -716,6 +716,16 @@ int dv3_clip_adam_f32(float* p, const float* g, float* m, float* v, int64_t n,
  *   the reference computes for that utterance alone at B = 1.  last_attended is then [2][B] (slot t&1 row read,
  *   slot (t+1)&1 row written) and EVERY item stores its own first-maximum argmax.  Not taken by
  *   dv3_decode_program_run (its device-side stop rule is one flag per batch): refused there.
+ *   ABI 48, slot mode (t_off != NULL, both kernels): item b runs at its OWN step t_b = t - t_off[b] -- its ring slot
+ *   t_b mod L, its position-code row, its teacher-input row, its stacked rows of out_seq / attn_seq and its t_b & 1
+ *   side of last_attended -- so that a batch slot whose utterance has ended can be handed to the next utterance while
+ *   its neighbours keep decoding (rolling admission: t_off[b] = the global step at which slot b was admitted).  A slot
+ *   whose t_b lies outside [0, t_cap) is idle: it reads only its own rows (table rows clamped into [0, t_cap)) and
+ *   stores no ring frame, no stacked row and no last_attended; the attention kernel stores nothing at all for it.
+ *   t_cap > 0 is then required: the rows out_seq, attn_seq, post_add and (with x_ts) x hold.  Slot mode is a separate
+ *   instantiation of the kernels: with t_off == NULL the code is the shared-counter one.  dv3_decode_program_launch
+ *   passes t_off through (the global t travels in t_value); dv3_decode_program_run refuses it (as it refuses key_len:
+ *   its loop and stop rule are one step counter and one flag per batch).
  * ------------------------------------------------------------------------------------ */
 typedef struct dv3_conv_step_desc {
   const float* x; int64_t x_bs;
@@ -736,6 +746,8 @@ typedef struct dv3_conv_step_desc {
   int64_t x_ts;                              /* the new frame of step t is x + t*x_ts (teacher forcing: x = test_inputs,
                                                 deepvoice3.py:411-415); 0 = the same buffer every step               */
   int32_t t_value, reserved;                 /* the step index when `t` is NULL (host-driven loops: dv3_decode_program_launch) */
+  const int32_t* t_off;                      /* [B] device ints: slot mode (ABI 48), item b runs at step t - t_off[b]; or NULL */
+  int32_t t_cap, reserved2;                  /* slot mode: items whose step is outside [0, t_cap) are idle            */
 } dv3_conv_step_desc;
 int dv3_conv_step_f32(const dv3_conv_step_desc* d, void* stream);
 /* fwd_pack ([J*Cin][lda] fp32; gated: `a` rows at column 0, gate rows at column a_half) -> the step-tile image
@@ -763,6 +775,8 @@ typedef struct dv3_attn_step_desc {
   int32_t kv_tke, reserved;                  /* 1: k and v are (B, Tk, E) -- the reference's own layout (deepvoice3.py:
                                                 132-141), a key / value row is contiguous: coalesced for a one-frame read */
   const int32_t* key_len;                    /* [B] device ints: per-utterance mode (ABI 44), or NULL           */
+  const int32_t* t_off;                      /* [B] device ints: slot mode (ABI 48; needs key_len), or NULL     */
+  int32_t t_cap, reserved2;                  /* slot mode: items whose step is outside [0, t_cap) store nothing  */
 } dv3_attn_step_desc;
 int dv3_attn_step_f32(const dv3_attn_step_desc* d, void* stream);
 
@@ -805,6 +819,12 @@ int dv3_decode_program_run(const dv3_decode_program* prog, void* stream);
  * steps, reads the done flags of the chunk, and discards the steps after the stopping one (later steps never change
  * earlier outputs, so the kept prefix is what a step-by-step loop produces). */
 int dv3_decode_program_launch(const dv3_decode_program* prog, void* stream);
+/* Slot mode: start a fresh sequence in `n` batch slots of a program (the reference's start_fresh_sequence plus a zero
+ * initial input, for those items only) in ONE launch.  Walks entries_host and, for every slot index s in `slots`
+ * (DEVICE int32[n], each in [0, B)): zeroes item s's columns of every conv entry's ring (L, B, Cin), both rows of every
+ * attention entry's last_attended ([2][B]: the entries must be per-utterance ones, key_len != NULL) and item s's row of
+ * the decoder input (the x of entry 0, Cin floats).  At most 128 rings + windows per program. */
+int dv3_decode_slots_reset(const dv3_decode_program* prog, const int32_t* slots, int32_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Audio inverse (audio.py:37-43, synthesis.py:64-71): linear spectrogram -> waveform on the
