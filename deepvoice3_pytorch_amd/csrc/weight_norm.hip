@@ -382,6 +382,7 @@ extern "C" int dv3_weight_norm_pack_f32(const dv3_wn_desc* d, void* stream) {
   DV3_REQUIRE(d && d->v && d->scale && d->fwd_pack, "wn_pack: null pointer");
   DV3_REQUIRE(d->O > 0 && d->I > 0 && d->J > 0, "wn_pack: bad dims");
   DV3_REQUIRE((d->lda & 3) == 0, "wn_pack: lda must be a multiple of 4");
+  DV3_REQUIRE(!d->bwd_pack || ((d->ldb & 3) == 0 && d->ldb >= d->I), "wn_pack: bad ldb");
   hipStream_t st = (hipStream_t)stream;
   const dv3_wn_desc p = *d;
   if (!d->transposed) {
@@ -402,13 +403,9 @@ extern "C" int dv3_weight_norm_pack_f32(const dv3_wn_desc* d, void* stream) {
     const size_t lds = (size_t)32 * (32 * d->J + 1) * 4;
     hipLaunchKernelGGL(wn_pack_fwd_kernel, dim3(dv3_cdiv(d->O, 32), dv3_cdiv(d->I, 32)), dim3(256),
                        lds, st, p);
-    if (d->bwd_pack) {
-      DV3_REQUIRE((d->ldb & 3) == 0 && d->ldb >= d->I, "wn_pack: bad ldb");
-      hipLaunchKernelGGL(wn_pack_bwd_kernel, dim3(d->O), dim3(256), 0, st, p);
-    }
+    if (d->bwd_pack) hipLaunchKernelGGL(wn_pack_bwd_kernel, dim3(d->O), dim3(256), 0, st, p);
   } else {
     DV3_REQUIRE(d->lda >= d->J * d->O, "wn_pack(T): lda < J*O");
-    if (d->bwd_pack) DV3_REQUIRE((d->ldb & 3) == 0 && d->ldb >= d->I, "wn_pack(T): bad ldb");
     hipLaunchKernelGGL(wn_inv_norm_kernel, dim3(d->I), dim3(256), 0, st, d->v, d->g, d->scale,
                        d->O * d->J);
     if (d->bwd_pack && d->ldb != d->I) {
@@ -430,10 +427,10 @@ extern "C" int dv3_weight_norm_split_pack_bf16(const dv3_wn_desc* d, uint16_t* f
                                  d->lda >= d->a_half + d->glu_cg), "wn_split_pack: bad GLU layout");
   DV3_REQUIRE(d->glu_cg > 0 || d->lda >= d->O, "wn_split_pack: lda < O");
   DV3_REQUIRE(d->fwd_dtype == DV3_SPLIT_DTYPE_BF16 || d->fwd_dtype == DV3_SPLIT_DTYPE_F16, "wn_split_pack: bad fwd_dtype");
+  const size_t lds = (size_t)32 * (32 * d->J + 1) * 4;
+  DV3_REQUIRE(lds <= 64 * 1024, "wn_split_pack: too many taps");      // before any launch: a refused call writes nothing
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(wn_inv_norm_kernel, dim3(d->O), dim3(256), 0, st, d->v, d->g, d->scale, d->I * d->J);
-  const size_t lds = (size_t)32 * (32 * d->J + 1) * 4;
-  DV3_REQUIRE(lds <= 64 * 1024, "wn_split_pack: too many taps");
   hipLaunchKernelGGL(wn_split_both_kernel, dim3(dv3_cdiv(d->O, 32), dv3_cdiv(d->I, 32)), dim3(256), lds, st,
                      *d, reinterpret_cast<wn_bf16x8*>(fwd_split), reinterpret_cast<wn_bf16x8*>(bwd_split), dv3_range_ctr());
   return dv3_check_launch("weight_norm_split_pack_bf16");
