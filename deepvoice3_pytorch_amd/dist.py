@@ -12,6 +12,8 @@ xGMI is point-to-point (7 links x ~153 GB/s per GPU): a ring all-reduce of S byt
 2*(N-1)/N*S per GPU over one link pair, ~25 MB buckets keep each collective well above the
 latency floor while leaving >= 4 of them to pipeline behind the converter/decoder backward.
 """
+import contextlib
+
 import torch
 import torch.distributed as dist
 
@@ -84,6 +86,7 @@ class BucketedAllReduce(object):
         self.pending = [0] * len(self.buckets)
         self.launched = [False] * len(self.buckets)
         self._armed = False
+        self._muted = False     # collective_free(): arm() does not arm, nothing may be launched
         self._completed = []
         # measurement (bench.py): when a list, finish() appends an (event, event) pair bracketing the point where
         # the step stream joins the collective stream -- their distance is the all-reduce time NOT hidden behind
@@ -162,13 +165,39 @@ class BucketedAllReduce(object):
         return len(self._handles)
 
     def arm(self):
-        """Call right before backward."""
+        """Call right before backward.  Inside collective_free() the bookkeeping is reset and the hooks stay off."""
         for b, (_, _, plist) in enumerate(self.buckets):
             self.pending[b] = len(plist)
             self.launched[b] = False
         self.notified = [False] * len(self.arena.params)
         self._completed = []
-        self._armed = True
+        self._armed = not self._muted
+
+    @contextlib.contextmanager
+    def collective_free(self):
+        """Backward passes that belong to THIS rank alone -- the forward + backward warm-up of a step that is captured for
+        a new padded shape (train_step.GraphedTrainer(dry_warmup=True)), which its peers do not run.  Trainer.forward_backward
+        calls arm() right before backward, so disarm() in front of it would not last: inside this block arm() leaves the
+        gradient-ready hooks off, no bucket is launched or noted, and a launch that is asked for anyway is an error.  On
+        the way out the bookkeeping is that of a communicator that has not seen a backward: nothing pending, launched or
+        noted, no handle in flight.  (The passes do tell which parameters report in place: the autograd hooks of those are
+        dropped on the way out, as finish() drops them after the first armed backward.)"""
+        if self._works or self._sync_issued:
+            raise RuntimeError("BucketedAllReduce.collective_free: all-reduces of an earlier backward are still in flight "
+                               "(finish() or join() first)")
+        prev, self._muted, self._armed = self._muted, True, False
+        try:
+            yield self
+        finally:
+            self._muted, self._armed = prev, False
+            if not self._pruned and self._inplace_seen:
+                # as finish() does after the first armed backward: the capture that follows then sees the notifications
+                # every later backward sees, whether an eager step came before it or not
+                self.prune_hooks()
+            self.pending = [0] * len(self.buckets)
+            self.launched = [False] * len(self.buckets)
+            self.notified = [False] * len(self.arena.params)
+            self._completed = []
 
     def take_completed(self):
         """the buckets that became complete since the last call (segment capture only; see _report)"""
@@ -181,6 +210,8 @@ class BucketedAllReduce(object):
     def launch_after(self, bucket_ids, streams):
         """all-reduce `bucket_ids` on the collective stream once everything enqueued on `streams` so far has run
         (the replay of a segmented step: called between two segment launches, never inside a capture)"""
+        if self._muted:
+            raise RuntimeError("BucketedAllReduce: an all-reduce was asked for inside collective_free()")
         if self.side is None:   # CPU / gloo (tests): synchronous
             for b in bucket_ids:
                 lo, hi, _ = self.buckets[b]
@@ -244,6 +275,8 @@ class BucketedAllReduce(object):
             self.exposed_events.append((e0, e1))
 
     def _launch(self, b):
+        if self._muted:
+            raise RuntimeError("BucketedAllReduce: an all-reduce was asked for inside collective_free()")
         lo, hi, _ = self.buckets[b]
         view = self.arena.grad[lo:hi]
         self.launched[b] = True

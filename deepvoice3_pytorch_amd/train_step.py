@@ -12,6 +12,7 @@ sequence masks, ~12 .item() syncs, per-tensor Adam -- is done here on the device
     global-norm clip + Adam over ONE flat parameter arena (csrc/optim.hip)
 Scalars stay on the device; nothing in step() synchronises with the host.
 """
+import contextlib
 import ctypes
 import math
 import os
@@ -569,6 +570,11 @@ def _capture_stream(device, avoid=()):
     return st
 
 
+def _split_graph_default():
+    """DV3_SPLIT_GRAPH (on): the step is captured as segments with the second stream in hipGraphs of its own"""
+    return _env_flag("DV3_SPLIT_GRAPH", True)
+
+
 class GraphedTrainer(object):
     """Whole-step hipGraph replay: forward + losses + backward + (bucketed all-reduce) + clip/Adam captured once per
     batch shape and replayed -- removes the per-kernel host launch cost (~330 launches/step: 5-16 ms of host time,
@@ -617,7 +623,7 @@ class GraphedTrainer(object):
         trainer.check_lengths(static_batch)
         dev = trainer.device
         if split_streams is None:
-            split_streams = trainer.side_stream is not None and _env_flag("DV3_SPLIT_GRAPH", True)
+            split_streams = trainer.side_stream is not None and _split_graph_default()
         self.split = bool(split_streams) and trainer.side_stream is not None
         self.chunk = int(chunk or _env_int("DV3_SPLIT_CHUNK", 0))      # 0: chosen after the warm-up steps
         self.tail_fine = _env_int("DV3_SPLIT_TAIL", 6)     # the last N fork points end a segment each (0 = off)
@@ -647,7 +653,11 @@ class GraphedTrainer(object):
         ops.dropout_state.dev_offset = self.seed_offset
         s = _capture_stream(dev, avoid=(trainer.side_stream, torch.cuda.current_stream()))   # (the warm-up steps' stream-K launches take their workspace per stream too)
         s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
+        # data parallel: the dry passes belong to this rank alone (its peers meet this shape at another step, or never), so
+        # they must not issue a collective -- the gradient-ready hooks stay off and nothing is left pending or in flight.
+        # The real warm-up steps are the same optimisation steps on every rank: their all-reduces stay.
+        quiet = trainer.comm.collective_free() if (dry_warmup and trainer.comm is not None) else contextlib.nullcontext()
+        with torch.cuda.stream(s), quiet:
             for _ in range(warmup):      # real optimisation steps (lr / bias corrections set first)
                 if dry_warmup:           # ... or forward + backward only (_set_hyper would count an Adam step)
                     trainer._zero_grad()
@@ -922,6 +932,11 @@ class GraphedTrainer(object):
                                    "backward streams do not run side by side here; set DV3_FLAG_SYNC=0" % n)
         return self.scal
 
+    def bucket_order(self):
+        """the bucket ids in the order a replay issues their all-reduces from the host (segmented form under a process
+        group; [] otherwise)"""
+        return [b for bs in self.seg_buckets for b in bs] + list(self.rest_buckets)
+
     def flag_timeouts(self):
         """fork-point waits of the replayed steps that gave up (host sync); 0 in a healthy run"""
         if self._flag is None:
@@ -977,6 +992,20 @@ class LatticeReplay(object):
     afterwards; all of them share one block pool (a step at a time), so the memory is that of the largest shape.
     An LRU bounds the number of live captures.
 
+    Data parallel (`Trainer(process_group=...)`).  Every rank keeps its own captures and meets new shapes at its own
+    steps, so ranks replay steps of different shapes side by side, and one rank captures while its peers replay.  What
+    has to be the same on every rank is the sequence of collectives, and it is:
+      * capturing a shape issues none -- the dry warm-up passes run inside dist.BucketedAllReduce.collective_free(), and
+        the segmented capture only notes which segment completes which bucket;
+      * a replay issues every bucket's all-reduce once, from the host, in ONE order per model: `bucket_order` is that of
+        the first capture, and a later capture whose flattened order differs is refused (RuntimeError) -- the shape may
+        move a bucket to another segment (size rules cut the segments differently), never in front of another bucket;
+      * only the segmented replay is accepted (a trainer without its second stream, or DV3_SPLIT_GRAPH=0, is refused in
+        the constructor): a single graph would carry captured collectives, one graph per shape and per rank;
+      * check_range() takes the same decision on every rank (MAX all-reduce of the event count): call it at the same
+        step on every rank.
+    A dist.RingStandin communicator has no peers and is accepted under the same rules.
+
     step(batch) -> the scalars of the step (device tensors of the captured step that ran; read them before the next
     step of the same shape).  `stats`: captures, replays, capture seconds."""
 
@@ -984,10 +1013,19 @@ class LatticeReplay(object):
         import collections
         self.t = trainer
         self.max_graphs, self.warmup = int(max_graphs), int(warmup)
+        if trainer.comm is not None and (trainer.side_stream is None or not _split_graph_default()):
+            raise RuntimeError(
+                "LatticeReplay under a process group needs the segmented (split-stream) replay, whose all-reduces are "
+                "issued from the host between segment launches: %s.  A single graph per shape and per rank with captured "
+                "collectives is not offered." % ("the trainer has no second stream (DV3_WGRAD_STREAM=0, or not on a GPU)"
+                                                 if trainer.side_stream is None else "DV3_SPLIT_GRAPH=0 switches it off"))
         self.graphs = collections.OrderedDict()
         self.pool = torch.cuda.graph_pool_handle() if trainer.device.type == "cuda" else None
         self.stats = dict(captures=0, replays=0, capture_s=0.0, evictions=0)
         self._n_made = 0
+        self.bucket_order = None          # data parallel: the first capture's issue order, the one every capture must have
+        self.bucket_orders = {}           # key -> the order its capture noted (kept after an eviction: a record)
+        self._offset0, self._offset0_set = None, False      # ops.dropout_state.dev_offset before the first capture
 
     @staticmethod
     def key_of(batch):
@@ -995,6 +1033,54 @@ class LatticeReplay(object):
         if v is None:
             raise RuntimeError("LatticeReplay: the batch carries no valid lengths (data.device_collate(lattice=...))")
         return (v.t_in, v.t_dec, int(batch.text.shape[0]))
+
+    def _release(self, g):
+        """close one capture.  GraphedTrainer.close() hands ops.dropout_state.dev_offset back only when it is still that
+        capture's own; with several live captures that left the global at a closed capture's frozen counter.  Here every
+        capture restores to the value from before this object's first capture, and while captures of this object are
+        still live the global goes to one of theirs (the most recently used)."""
+        st = ops.dropout_state
+        mine = st.dev_offset is g.seed_offset
+        g._prev_offset = self._offset0
+        g.close()
+        if mine and self.graphs:
+            st.dev_offset = next(reversed(self.graphs.values())).seed_offset
+
+    def _capture(self, key, batch):
+        st = ops.dropout_state
+        if not self._offset0_set:
+            self._offset0, self._offset0_set = st.dev_offset, True
+        if st.seed is None:
+            st.manual_seed(torch.initial_seed())
+        seed0 = st.seed
+        # every capture draws from its own Philox stream: its step counter starts at zero like every other's
+        st.seed = (seed0 + 0x9E3779B1 * (self._n_made + 1)) & 0x7FFFFFFFFFFFFFFF
+        comm = self.t.comm
+        try:
+            g = GraphedTrainer(self.t, clone_batch(batch), warmup=self.warmup, dry_warmup=True, pool=self.pool,
+                               split_streams=True if comm is not None else None)
+        finally:
+            st.seed = seed0
+        self._n_made += 1
+        if comm is not None:
+            why = None
+            order = g.bucket_order()
+            if not g.split:
+                why = "the step was not captured in the segmented form"
+            elif comm._works or comm._completed or any(comm.launched):
+                why = "the capture left all-reduces pending or in flight"
+            elif sorted(order) != list(range(len(comm.buckets))):
+                why = "the capture does not issue every bucket exactly once: %r" % (order,)
+            elif self.bucket_order is not None and order != self.bucket_order:
+                why = ("its replay would issue the gradient buckets in the order %r, the captures before it issue %r: ranks "
+                       "that replay different shapes in one step would pair different buckets" % (order, self.bucket_order))
+            if why is not None:
+                self._release(g)
+                raise RuntimeError("LatticeReplay under a process group, shape (t_in, t_dec, B) = %r: %s" % (key, why))
+            if self.bucket_order is None:
+                self.bucket_order = order
+            self.bucket_orders[key] = order
+        return g
 
     def step(self, batch):
         import time
@@ -1004,21 +1090,12 @@ class LatticeReplay(object):
             t0 = time.perf_counter()
             if len(self.graphs) >= self.max_graphs:
                 _, old = self.graphs.popitem(last=False)
-                old.close()
+                self._release(old)
                 self.stats["evictions"] += 1
-            st = ops.dropout_state
-            if st.seed is None:
-                st.manual_seed(torch.initial_seed())
-            seed0 = st.seed
-            # every capture draws from its own Philox stream: its step counter starts at zero like every other's
-            st.seed = (seed0 + 0x9E3779B1 * (self._n_made + 1)) & 0x7FFFFFFFFFFFFFFF
-            try:
-                g = GraphedTrainer(self.t, clone_batch(batch), warmup=self.warmup, dry_warmup=True, pool=self.pool)
-            finally:
-                st.seed = seed0
-            self._n_made += 1
+            g = self._capture(key, batch)
             self.graphs[key] = g
-            torch.cuda.synchronize()
+            if self.t.device.type == "cuda":
+                torch.cuda.synchronize()
             self.stats["captures"] += 1
             self.stats["capture_s"] += time.perf_counter() - t0
         else:
@@ -1028,16 +1105,19 @@ class LatticeReplay(object):
 
     def check_range(self):
         """the f16x3 range guard (GraphedTrainer.check_range): > 0 = the process has moved to bf16x3, every capture of
-        this object packed f16x3 operands and is dropped -- the next step of each shape captures again"""
+        this object packed f16x3 operands and is dropped -- the next step of each shape captures again.
+        Under a process group of more than one rank the event count is all-reduced (MAX, Trainer.check_range) before the
+        decision, so every rank moves to bf16x3 and drops its captures at the same step: this is a collective -- call it
+        at the same step on every rank."""
         n = self.t.check_range()
         if n:
             self.close()
         return n
 
     def close(self):
-        for g in self.graphs.values():
-            g.close()
-        self.graphs.clear()
+        while self.graphs:
+            _, g = self.graphs.popitem(last=False)
+            self._release(g)
 
 
 # ------------------------------------------------------------------------------------------------
