@@ -9,13 +9,18 @@ The reference hands framing and phase reconstruction to the third-party `lws` pa
 synthesis never leaves the device (synthesis.py:64-71 copies the spectrogram to the CPU first).
 
 Conventions (AudioConfig.convention):
-  "lws"    (default) the framing of `lws.lws(1024, hop, mode="speech")` the reference's features are made with and its
-           inverse is framed by: sqrt-symmetric-Hann analysis window, perfect-reconstruction synthesis window, 1024 - hop
-           zeros of padding on both sides -- T frames <-> (T + 1) * hop - 1024 samples (L = 256 k -> k + 3 frames).
+  "lws"    (default) the framing of `lws.lws(fft_size, hop, mode="speech")` the reference's features are made with and
+           its inverse is framed by: sqrt-symmetric-Hann analysis window, perfect-reconstruction synthesis window,
+           fft_size - hop zeros of padding on both sides -- T frames <-> (T + 1) * hop - fft_size samples (1024 / 256:
+           L = 256 k -> k + 3 frames).
            Restated from the package's published source in oracle/audio_oracle.py (lws_windows / lws_stft / lws_istft).
            Phase reconstruction is Griffin-Lim on that framing (north_star), not lws's own run_lws iterations.
   "torch"  torch.stft / torch.istft conventions (periodic Hann, center=True reflect padding, L = hop * (T - 1)): rounds
            1-3's form, kept for A/B runs and for callers that pair it with torch-made features.
+
+Frame size: AudioConfig.fft_size is 512, 1024 (every reference preset) or 2048 -- the sizes the FFT kernels are built for
+(FFT_SIZES); 16 kHz corpora use 512 / 128, 44.1 and 48 kHz voices 2048 / 512.  The functions below that take a hop
+instead of a config take the size as `fft_size=` (default 1024).
 """
 import numpy as np
 import torch
@@ -23,8 +28,24 @@ import torch
 from . import _lib
 from .ops import _stream, _chk, _c
 
-N_FFT = 1024
+N_FFT = 1024                       # the default frame size (every reference preset)
 N_BIN = N_FFT // 2 + 1
+FFT_SIZES = (512, 1024, 2048)      # the sizes csrc/audio.hip instantiates (include/dv3hip.h: the `_n` entry points)
+
+
+def check_fft_size(fft_size):
+    """-> fft_size as an int when the HIP FFT kernels are built for it, else ValueError naming it"""
+    if isinstance(fft_size, bool) or fft_size not in FFT_SIZES or int(fft_size) != fft_size:
+        raise ValueError("fft_size=%r is not supported: the HIP FFT kernels are built for fft_size in %s (4096 would "
+                         "need 96 KB of LDS per workgroup)" % (fft_size, ", ".join(str(n) for n in FFT_SIZES)))
+    return int(fft_size)
+
+
+def check_bins(n_bins, fft_size, what):
+    """a spectrogram's last dimension must be fft_size // 2 + 1 (the kernels read that many bins per frame)"""
+    if int(n_bins) != fft_size // 2 + 1:
+        raise ValueError("%s: the spectrogram has %d bins, but fft_size=%d frames %d (fft_size // 2 + 1)"
+                         % (what, n_bins, fft_size, fft_size // 2 + 1))
 
 
 def resolve_window_scale(window_scale, hop, fft_size=N_FFT):
@@ -44,15 +65,16 @@ class AudioConfig(object):
                  window_scale="hop_normalized"):
         """window_scale (lws framing only): amplitude factor of the analysis window, the one constant of the third-party
         package this repository holds by recollection only (audio).  "hop_normalized" (default since
-        round 6) = sqrt(2 * hop / 1024) (0.7071 at hop 256): `lws.lws(fsize, fshift)` with an integer first argument
+        round 6) = sqrt(2 * hop / fft_size) (0.7071 at 1024 / 256): `lws.lws(fsize, fshift)` with an integer first argument
         builds `awin = sqrt(hann(fsize, symmetric) * 2 * fshift / fsize)` as two independent recollections of lws.pyx
         have it.  1.0 = plain sqrt(hann) (rounds 4-5's default) stays selectable.  The two differ in ONE observable: every
         magnitude by 3.01 dB, i.e. every normalised [0, 1] feature by 0.0301, and an inverted waveform's amplitude by the
         inverse factor (tests/test_audio.py::test_window_scale_is_the_unconfirmed_constant); perfect reconstruction, the
         frame count and Griffin-Lim's fixed points do not depend on it (the synthesis window carries the inverse factor).
         tests/test_audio.py compares with the real package wherever it is importable."""
-        if fft_size != N_FFT:
-            raise ValueError("the HIP FFT kernels are built for fft_size=1024 (every reference preset)")
+        fft_size = check_fft_size(fft_size)
+        if not 0 < hop_size <= fft_size:
+            raise ValueError("hop_size=%r must lie in [1, fft_size=%d]" % (hop_size, fft_size))
         if convention not in ("lws", "torch"):
             raise ValueError("convention must be 'lws' (the reference's framing) or 'torch'")
         window_scale = resolve_window_scale(window_scale, hop_size, fft_size)
@@ -82,12 +104,12 @@ def lws_windows_np(fsize=N_FFT, fshift=256, scale=None):
 _WIN_CACHE = {}
 
 
-def lws_windows(device, hop, scale=None):
-    """the two tables as float32 device tensors (cached per device, hop and window scale)"""
-    scale = resolve_window_scale(scale, hop)
-    key = (str(device), int(hop), float(scale))
+def lws_windows(device, hop, scale=None, fft_size=N_FFT):
+    """the two tables as float32 device tensors (cached per device, frame size, hop and window scale)"""
+    scale = resolve_window_scale(scale, hop, fft_size)
+    key = (str(device), int(fft_size), int(hop), float(scale))
     if key not in _WIN_CACHE:
-        a, s = lws_windows_np(N_FFT, hop, scale)
+        a, s = lws_windows_np(fft_size, hop, scale)
         _WIN_CACHE[key] = (torch.from_numpy(a.astype(np.float32)).to(device), torch.from_numpy(s.astype(np.float32)).to(device))
     return _WIN_CACHE[key]
 
@@ -104,7 +126,7 @@ def lws_num_samples(T, hop, fsize=N_FFT):
 
 
 def magnitudes(linear_outputs, cfg):
-    """(B, T, 513) normalised spectrogram (the model's linear_outputs) -> magnitudes ** power."""
+    """(B, T, fft_size // 2 + 1) normalised spectrogram (the model's linear_outputs) -> magnitudes ** power."""
     x = _c(_chk(linear_outputs, "linear_outputs"))
     mag = torch.empty_like(x)
     _lib.call("dv3_gl_prepare_f32", x.data_ptr(), mag.data_ptr(), x.numel(), float(cfg.min_level_db),
@@ -112,55 +134,71 @@ def magnitudes(linear_outputs, cfg):
     return mag
 
 
-def num_samples(T, hop, convention):
-    """samples the inverse makes of T frames: (T + 1) * hop - 1024 on the lws framing, hop * (T - 1) on the torch one"""
-    return lws_num_samples(T, hop) if convention == "lws" else hop * (T - 1)
+def num_samples(T, hop, convention, fft_size=N_FFT):
+    """samples the inverse makes of T frames: (T + 1) * hop - fft_size on the lws framing, hop * (T - 1) on the torch one"""
+    return lws_num_samples(T, hop, fft_size) if convention == "lws" else hop * (T - 1)
 
 
-def istft(mag, phasor, hop, convention="torch", window_scale=None, tlen=None):
-    """mag (B,T,513), phasor (B,T,513,2) or None -> y (B, hop*(T-1)); lws framing: (B, (T+1)*hop - 1024).
-    tlen (device int32[B]): item b has only its first tlen[b] frames -- its own signal, zeros after it."""
+def min_frames(hop, convention, fft_size=N_FFT):
+    """the fewest frames the inverse takes at this hop: the lws framing needs a positive signal length, the torch one a
+    signal longer than its reflect padding of fft_size // 2 (csrc/audio.hip: items_tlo)"""
+    t = 2
+    while num_samples(t, hop, convention, fft_size) <= (0 if convention == "lws" else fft_size // 2):
+        t += 1
+    return t
+
+
+def istft(mag, phasor, hop, convention="torch", window_scale=None, tlen=None, fft_size=N_FFT):
+    """mag (B,T,F), phasor (B,T,F,2) or None, F = fft_size // 2 + 1 -> y (B, hop*(T-1)); lws framing: (B, (T+1)*hop -
+    fft_size).  tlen (device int32[B]): item b has only its first tlen[b] frames -- its own signal, zeros after it."""
+    fft_size = check_fft_size(fft_size)
     B, T, F = mag.shape
-    assert F == N_BIN
-    frames = torch.empty((B, T, N_FFT), dtype=torch.float32, device=mag.device)
+    check_bins(F, fft_size, "istft")
+    if phasor is not None and tuple(phasor.shape) != (B, T, F, 2):
+        raise ValueError("istft: phasor must be (%d, %d, %d, 2), got %s" % (B, T, F, tuple(phasor.shape)))
+    frames = torch.empty((B, T, fft_size), dtype=torch.float32, device=mag.device)
     if tlen is not None:
         lws = convention == "lws"
-        swin = lws_windows(mag.device, hop, window_scale)[1] if lws else None
-        _lib.call("dv3_gl_istft_items_f32", mag.data_ptr(), phasor.data_ptr() if phasor is not None else None,
-                  swin.data_ptr() if lws else None, frames.data_ptr(), B, T, hop, tlen.data_ptr(), int(lws), _stream())
-        y = torch.empty((B, num_samples(T, hop, convention)), dtype=torch.float32, device=mag.device)
-        _lib.call("dv3_overlap_add_items_f32", frames.data_ptr(), y.data_ptr(), B, T, hop, tlen.data_ptr(), int(lws),
+        swin = lws_windows(mag.device, hop, window_scale, fft_size)[1] if lws else None
+        _lib.call("dv3_gl_istft_items_f32_n", mag.data_ptr(), phasor.data_ptr() if phasor is not None else None,
+                  swin.data_ptr() if lws else None, frames.data_ptr(), B, T, hop, tlen.data_ptr(), int(lws), fft_size,
                   _stream())
+        y = torch.empty((B, num_samples(T, hop, convention, fft_size)), dtype=torch.float32, device=mag.device)
+        _lib.call("dv3_overlap_add_items_f32_n", frames.data_ptr(), y.data_ptr(), B, T, hop, tlen.data_ptr(), int(lws),
+                  fft_size, _stream())
         return y
     if convention == "lws":
-        _, swin = lws_windows(mag.device, hop, window_scale)
-        _lib.call("dv3_lws_istft_frames_f32", mag.data_ptr(), phasor.data_ptr() if phasor is not None else None,
-                  swin.data_ptr(), frames.data_ptr(), B, T, _stream())
-        y = torch.empty((B, lws_num_samples(T, hop)), dtype=torch.float32, device=mag.device)
-        _lib.call("dv3_lws_overlap_add_f32", frames.data_ptr(), y.data_ptr(), B, T, hop, _stream())
+        _, swin = lws_windows(mag.device, hop, window_scale, fft_size)
+        _lib.call("dv3_lws_istft_frames_f32_n", mag.data_ptr(), phasor.data_ptr() if phasor is not None else None,
+                  swin.data_ptr(), frames.data_ptr(), B, T, fft_size, _stream())
+        y = torch.empty((B, lws_num_samples(T, hop, fft_size)), dtype=torch.float32, device=mag.device)
+        _lib.call("dv3_lws_overlap_add_f32_n", frames.data_ptr(), y.data_ptr(), B, T, hop, fft_size, _stream())
         return y
-    _lib.call("dv3_istft_frames_f32", mag.data_ptr(), phasor.data_ptr() if phasor is not None else None,
-              frames.data_ptr(), B, T, _stream())
+    _lib.call("dv3_istft_frames_f32_n", mag.data_ptr(), phasor.data_ptr() if phasor is not None else None,
+              frames.data_ptr(), B, T, fft_size, _stream())
     y = torch.empty((B, hop * (T - 1)), dtype=torch.float32, device=mag.device)
-    _lib.call("dv3_overlap_add_f32", frames.data_ptr(), y.data_ptr(), B, T, hop, _stream())
+    _lib.call("dv3_overlap_add_f32_n", frames.data_ptr(), y.data_ptr(), B, T, hop, fft_size, _stream())
     return y
 
 
-def stft(y, T, hop, want_phasor=True, want_spec=False, convention="torch", window_scale=None):
-    """y (B, hop*(T-1)) -> unit phasors and/or the complex STFT, each (B,T,513,2); lws framing: T = lws_num_frames(L)."""
+def stft(y, T, hop, want_phasor=True, want_spec=False, convention="torch", window_scale=None, fft_size=N_FFT):
+    """y (B, hop*(T-1)) -> unit phasors and/or the complex STFT, each (B,T,fft_size // 2 + 1,2); lws framing: T =
+    lws_num_frames(L, hop, fft_size)."""
+    fft_size = check_fft_size(fft_size)
     y = _c(_chk(y, "y"))
     B = y.shape[0]
-    ph = torch.empty((B, T, N_BIN, 2), dtype=torch.float32, device=y.device) if want_phasor else None
-    sp = torch.empty((B, T, N_BIN, 2), dtype=torch.float32, device=y.device) if want_spec else None
+    n_bin = fft_size // 2 + 1
+    ph = torch.empty((B, T, n_bin, 2), dtype=torch.float32, device=y.device) if want_phasor else None
+    sp = torch.empty((B, T, n_bin, 2), dtype=torch.float32, device=y.device) if want_spec else None
     if convention == "lws":
-        assert T == lws_num_frames(y.shape[1], hop)
-        awin, _ = lws_windows(y.device, hop, window_scale)
-        _lib.call("dv3_lws_stft_f32", y.data_ptr(), awin.data_ptr(), ph.data_ptr() if ph is not None else None,
-                  sp.data_ptr() if sp is not None else None, None, B, T, hop, y.shape[1], _stream())
+        assert T == lws_num_frames(y.shape[1], hop, fft_size)
+        awin, _ = lws_windows(y.device, hop, window_scale, fft_size)
+        _lib.call("dv3_lws_stft_f32_n", y.data_ptr(), awin.data_ptr(), ph.data_ptr() if ph is not None else None,
+                  sp.data_ptr() if sp is not None else None, None, B, T, hop, y.shape[1], fft_size, _stream())
         return ph, sp
     assert y.shape[1] == hop * (T - 1)
-    _lib.call("dv3_stft_phase_f32", y.data_ptr(), ph.data_ptr() if ph is not None else None,
-              sp.data_ptr() if sp is not None else None, None, B, T, hop, _stream())
+    _lib.call("dv3_stft_phase_f32_n", y.data_ptr(), ph.data_ptr() if ph is not None else None,
+              sp.data_ptr() if sp is not None else None, None, B, T, hop, fft_size, _stream())
     return ph, sp
 
 
@@ -169,7 +207,7 @@ def stft(y, T, hop, want_phasor=True, want_spec=False, convention="torch", windo
 # ---------------------------------------------------------------------------------------------
 def mel_basis(sample_rate=22050, n_fft=1024, n_mels=80, fmin=125.0, fmax=7600.0):
     """The Slaney-style triangular filterbank librosa.filters.mel builds by default (htk=False,
-    norm='slaney'), restated: audio.py:70-76 with hparams.py fmin/fmax.  (num_mels, 513) float32."""
+    norm='slaney'), restated: audio.py:70-76 with hparams.py fmin/fmax.  (num_mels, n_fft // 2 + 1) float32."""
     def hz_to_mel(f):
         f = np.asarray(f, dtype=np.float64)
         mel = f / (200.0 / 3)
@@ -194,24 +232,26 @@ def mel_basis(sample_rate=22050, n_fft=1024, n_mels=80, fmin=125.0, fmax=7600.0)
 
 
 def _analysis_mag(wav, cfg):
-    """(B, L) waveform -> |STFT(preemphasis(wav))| as (B, 513, T).  lws framing (default): any L, T = lws_num_frames(L)
-    (L = 256 k -> k + 3 frames, as the reference's preprocessing produces them); torch framing: L = hop * (T - 1)."""
+    """(B, L) waveform -> |STFT(preemphasis(wav))| as (B, fft_size // 2 + 1, T).  lws framing (default): any L, T =
+    lws_num_frames(L) (1024 / 256: L = 256 k -> k + 3 frames, as the reference's preprocessing produces them); torch
+    framing: L = hop * (T - 1)."""
     wav = _c(_chk(wav, "wav"))
     B, L = wav.shape
-    hop = cfg.hop_size
+    hop, n_fft = cfg.hop_size, cfg.fft_size
     pre = torch.empty_like(wav)
     _lib.call("dv3_preemphasis_f32", wav.data_ptr(), pre.data_ptr(), B, L, float(cfg.preemphasis), _stream())
     if cfg.convention == "lws":
-        T = lws_num_frames(L, hop)
-        awin, _ = lws_windows(wav.device, hop, cfg.window_scale)
-        mag = torch.empty((B, N_BIN, T), dtype=torch.float32, device=wav.device)
-        _lib.call("dv3_lws_stft_f32", pre.data_ptr(), awin.data_ptr(), None, None, mag.data_ptr(), B, T, hop, L, _stream())
+        T = lws_num_frames(L, hop, n_fft)
+        awin, _ = lws_windows(wav.device, hop, cfg.window_scale, n_fft)
+        mag = torch.empty((B, n_fft // 2 + 1, T), dtype=torch.float32, device=wav.device)
+        _lib.call("dv3_lws_stft_f32_n", pre.data_ptr(), awin.data_ptr(), None, None, mag.data_ptr(), B, T, hop, L, n_fft,
+                  _stream())
         return mag
     if L % hop:
         raise ValueError("waveform length must be a multiple of hop_size (%d)" % hop)
     T = L // hop + 1
-    mag = torch.empty((B, N_BIN, T), dtype=torch.float32, device=wav.device)
-    _lib.call("dv3_stft_phase_f32", pre.data_ptr(), None, None, mag.data_ptr(), B, T, hop, _stream())
+    mag = torch.empty((B, n_fft // 2 + 1, T), dtype=torch.float32, device=wav.device)
+    _lib.call("dv3_stft_phase_f32_n", pre.data_ptr(), None, None, mag.data_ptr(), B, T, hop, n_fft, _stream())
     return mag
 
 
@@ -223,14 +263,14 @@ def _db_norm(x, cfg):
 
 
 def spectrogram_batch(wav, cfg=None):
-    """audio.spectrogram (audio.py:31-35) for a (B, L) device batch -> (B, 513, T) in [0, 1]."""
+    """audio.spectrogram (audio.py:31-35) for a (B, L) device batch -> (B, fft_size // 2 + 1, T) in [0, 1]."""
     cfg = cfg or AudioConfig()
     return _db_norm(_analysis_mag(wav, cfg), cfg)
 
 
 def melspectrogram_batch(wav, cfg=None, num_mels=80, fmin=125.0, fmax=7600.0):
     """audio.melspectrogram (audio.py:46-51) for a (B, L) device batch -> (B, num_mels, T) in [0, 1]:
-    the filterbank product runs on the tap-GEMM kernel as a 1x1 convolution over the 513 bins."""
+    the filterbank product runs on the tap-GEMM kernel as a 1x1 convolution over the fft_size // 2 + 1 bins."""
     from . import ops
     cfg = cfg or AudioConfig()
     mag = _analysis_mag(wav, cfg)
@@ -241,34 +281,36 @@ def melspectrogram_batch(wav, cfg=None, num_mels=80, fmin=125.0, fmax=7600.0):
     return _db_norm(mel, cfg)
 
 
-def griffin_lim(mag, hop, n_iter, init_phasor=None, convention="torch", window_scale=None, tlen=None):
-    """Griffin & Lim: alternate projections between the given magnitudes and consistent STFTs.  tlen (device int32[B]):
-    per-item frame counts -- item b iterates on its own first tlen[b] frames and signal (see istft)."""
-    y = istft(mag, init_phasor, hop, convention, window_scale, tlen)
+def griffin_lim(mag, hop, n_iter, init_phasor=None, convention="torch", window_scale=None, tlen=None, fft_size=N_FFT):
+    """Griffin & Lim: alternate projections between the given magnitudes (B, T, fft_size // 2 + 1) and consistent STFTs.
+    tlen (device int32[B]): per-item frame counts -- item b iterates on its own first tlen[b] frames and signal (see
+    istft)."""
+    y = istft(mag, init_phasor, hop, convention, window_scale, tlen, fft_size)
     B, T, _ = mag.shape
     if n_iter > 0:
-        frames = torch.empty((B, T, N_FFT), dtype=torch.float32, device=mag.device)
+        frames = torch.empty((B, T, fft_size), dtype=torch.float32, device=mag.device)
         y2 = torch.empty_like(y)
         lws = convention == "lws"
         if lws:
-            awin, swin = lws_windows(mag.device, hop, window_scale)
+            awin, swin = lws_windows(mag.device, hop, window_scale, fft_size)
         for _ in range(n_iter):
             if tlen is not None:
-                _lib.call("dv3_gl_project_items_f32", y.data_ptr(), mag.data_ptr(), awin.data_ptr() if lws else None,
+                _lib.call("dv3_gl_project_items_f32_n", y.data_ptr(), mag.data_ptr(), awin.data_ptr() if lws else None,
                           swin.data_ptr() if lws else None, frames.data_ptr(), B, T, hop, tlen.data_ptr(), int(lws),
-                          _stream())
-                _lib.call("dv3_overlap_add_items_f32", frames.data_ptr(), y2.data_ptr(), B, T, hop, tlen.data_ptr(),
-                          int(lws), _stream())
+                          fft_size, _stream())
+                _lib.call("dv3_overlap_add_items_f32_n", frames.data_ptr(), y2.data_ptr(), B, T, hop, tlen.data_ptr(),
+                          int(lws), fft_size, _stream())
                 y, y2 = y2, y
                 continue
             # stft -> unit phase -> x magnitude -> inverse FFT -> window in one launch (the phasors never reach HBM)
             if lws:
-                _lib.call("dv3_lws_gl_project_f32", y.data_ptr(), mag.data_ptr(), awin.data_ptr(), swin.data_ptr(),
-                          frames.data_ptr(), B, T, hop, _stream())
-                _lib.call("dv3_lws_overlap_add_f32", frames.data_ptr(), y2.data_ptr(), B, T, hop, _stream())
+                _lib.call("dv3_lws_gl_project_f32_n", y.data_ptr(), mag.data_ptr(), awin.data_ptr(), swin.data_ptr(),
+                          frames.data_ptr(), B, T, hop, fft_size, _stream())
+                _lib.call("dv3_lws_overlap_add_f32_n", frames.data_ptr(), y2.data_ptr(), B, T, hop, fft_size, _stream())
             else:
-                _lib.call("dv3_gl_project_f32", y.data_ptr(), mag.data_ptr(), frames.data_ptr(), B, T, hop, _stream())
-                _lib.call("dv3_overlap_add_f32", frames.data_ptr(), y2.data_ptr(), B, T, hop, _stream())
+                _lib.call("dv3_gl_project_f32_n", y.data_ptr(), mag.data_ptr(), frames.data_ptr(), B, T, hop, fft_size,
+                          _stream())
+                _lib.call("dv3_overlap_add_f32_n", frames.data_ptr(), y2.data_ptr(), B, T, hop, fft_size, _stream())
             y, y2 = y2, y
     return y
 
@@ -281,21 +323,26 @@ def inv_preemphasis_(y, coef):
 
 
 def inv_spectrogram_batch(linear_outputs, cfg=None, init_phasor=None, frame_lengths=None):
-    """(B, T, 513) device tensor (model linear_outputs) -> waveforms on the device: (B, (T+1)*hop - 1024) on the lws
-    framing (what the reference's processor.istft returns for T frames), (B, hop*(T-1)) on the torch framing.
+    """(B, T, fft_size // 2 + 1) device tensor (model linear_outputs) -> waveforms on the device: (B, (T+1)*hop -
+    fft_size) on the lws framing (what the reference's processor.istft returns for T frames), (B, hop*(T-1)) on the torch
+    framing.  A spectrogram of another width than cfg.fft_size // 2 + 1 is refused (ValueError).
     frame_lengths (B host ints): a batch of utterances padded to T frames; item b is inverted from its own first
     frame_lengths[b] frames exactly as its B = 1 call on the trimmed spectrogram, its samples past its own length are
     zero.  -> (waveforms, sample lengths (int64[B], host)) in that case."""
     cfg = cfg or AudioConfig()
+    if linear_outputs.dim() != 3:
+        raise ValueError("inv_spectrogram_batch: a (B, T, bins) spectrogram expected, got %s" % (tuple(linear_outputs.shape),))
+    check_bins(linear_outputs.shape[-1], cfg.fft_size, "inv_spectrogram_batch")
     if frame_lengths is not None:
         return _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths)
     mag = magnitudes(linear_outputs, cfg)
-    y = griffin_lim(mag, cfg.hop_size, cfg.griffin_lim_iters, init_phasor, cfg.convention, cfg.window_scale)
+    y = griffin_lim(mag, cfg.hop_size, cfg.griffin_lim_iters, init_phasor, cfg.convention, cfg.window_scale,
+                    fft_size=cfg.fft_size)
     return inv_preemphasis_(y, cfg.preemphasis)
 
 
 def inv_spectrogram(spectrogram, cfg=None, device="cuda:0"):
-    """Drop-in for audio.inv_spectrogram (audio.py:37-43): (513, T) numpy -> waveform numpy."""
+    """Drop-in for audio.inv_spectrogram (audio.py:37-43): (fft_size // 2 + 1, T) numpy -> waveform numpy."""
     s = torch.as_tensor(np.ascontiguousarray(np.asarray(spectrogram, dtype=np.float32).T)).unsqueeze(0)
     y = inv_spectrogram_batch(s.to(device), cfg)
     return y[0].cpu().numpy()
@@ -304,17 +351,15 @@ def inv_spectrogram(spectrogram, cfg=None, device="cuda:0"):
 def _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths):
     B, T = linear_outputs.shape[0], linear_outputs.shape[1]
     fl = torch.as_tensor(frame_lengths).reshape(-1).to(torch.int64).cpu()
-    hop = cfg.hop_size
-    tmin = 2
-    while num_samples(tmin, hop, cfg.convention) <= (0 if cfg.convention == "lws" else N_FFT // 2):
-        tmin += 1
+    hop, n_fft = cfg.hop_size, cfg.fft_size
+    tmin = min_frames(hop, cfg.convention, n_fft)
     if fl.numel() != B or int(fl.min()) < tmin or int(fl.max()) > T:
         raise ValueError("inv_spectrogram_batch: %d frame lengths in [%d, %d] expected, got %s" % (
             B, tmin, T, fl.tolist()))
     tlen = fl.to(torch.int32).to(linear_outputs.device)
     mag = magnitudes(linear_outputs, cfg)
-    y = griffin_lim(mag, hop, cfg.griffin_lim_iters, init_phasor, cfg.convention, cfg.window_scale, tlen)
-    lengths = torch.tensor([num_samples(int(n), hop, cfg.convention) for n in fl], dtype=torch.int64)
+    y = griffin_lim(mag, hop, cfg.griffin_lim_iters, init_phasor, cfg.convention, cfg.window_scale, tlen, n_fft)
+    lengths = torch.tensor([num_samples(int(n), hop, cfg.convention, n_fft) for n in fl], dtype=torch.int64)
     out = torch.empty_like(y)
     _lib.call("dv3_deemphasis_items_f32", y.data_ptr(), out.data_ptr(), B, y.shape[1],
               lengths.to(torch.int32).to(y.device).data_ptr(), float(cfg.preemphasis), _stream())
@@ -328,12 +373,12 @@ def _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths):
 _MEL_CACHE = {}
 
 
-def mel_tables(device, sample_rate=22050, num_mels=80, fmin=125.0, fmax=7600.0):
-    """(basis (num_mels, 513) float32, band int32 (num_mels, 2)) on `device`: band[m] = [first, last + 1) of filter m's
-    nonzero bins (the kernel's dot skips the bins outside it -- exact zeros, so the fp32 sum is the same)"""
-    key = (str(device), int(sample_rate), int(num_mels), float(fmin), float(fmax))
+def mel_tables(device, sample_rate=22050, num_mels=80, fmin=125.0, fmax=7600.0, fft_size=N_FFT):
+    """(basis (num_mels, fft_size // 2 + 1) float32, band int32 (num_mels, 2)) on `device`: band[m] = [first, last + 1) of
+    filter m's nonzero bins (the kernel's dot skips the bins outside it -- exact zeros, so the fp32 sum is the same)"""
+    key = (str(device), int(sample_rate), int(num_mels), float(fmin), float(fmax), int(fft_size))
     if key not in _MEL_CACHE:
-        w = mel_basis(sample_rate, N_FFT, num_mels, fmin, fmax)
+        w = mel_basis(sample_rate, fft_size, num_mels, fmin, fmax)
         band = np.zeros((num_mels, 2), dtype=np.int32)
         for m in range(num_mels):
             nz = np.nonzero(w[m])[0]
@@ -366,8 +411,8 @@ def _sample_offsets(lengths, device):
 
 def features_items(wav_flat, lengths, cfg=None, num_mels=80, fmin=125, fmax=7600, rescaling=None):
     """Linear and mel features of B utterances packed back to back in `wav_flat` (a 1-D float32 device tensor; item b
-    is the next lengths[b] samples) -> (lin (sum T_b, 513), mel (sum T_b, num_mels), frames int64[B] on the host),
-    T_b = lws_num_frames(lengths[b], hop): the rows of PackedBatch.lin / .mel (data.py), item b's at
+    is the next lengths[b] samples) -> (lin (sum T_b, fft_size // 2 + 1), mel (sum T_b, num_mels), frames int64[B] on the
+    host), T_b = lws_num_frames(lengths[b], hop, fft_size): the rows of PackedBatch.lin / .mel (data.py), item b's at
     frames[:b].sum() ... frames[:b + 1].sum().  Each row depends on its own item only: the linear rows are bit for bit
     spectrogram_batch(item[None])[0].T, and the mel rows are a fixed-order sum (see include/dv3hip.h:
     dv3_analysis_items_f32).  rescaling: None / False, or rescaling_max (hparams.rescaling_max) -- item b is analysed
@@ -382,23 +427,23 @@ def features_items(wav_flat, lengths, cfg=None, num_mels=80, fmin=125, fmax=7600
     if B == 0 or int(lengths.min()) < 1 or int(lengths.sum()) != wav_flat.numel():
         raise ValueError("features_items: %d samples do not split into items of lengths %s (each >= 1)"
                          % (wav_flat.numel(), lengths.tolist()))
-    hop = cfg.hop_size
-    frames = np.array([lws_num_frames(int(n), hop) for n in lengths], dtype=np.int64)
+    hop, n_fft = cfg.hop_size, cfg.fft_size
+    frames = np.array([lws_num_frames(int(n), hop, n_fft) for n in lengths], dtype=np.int64)
     nf = int(frames.sum())
-    if nf >= 2 ** 31 or int(lengths.max()) >= 2 ** 31 - N_FFT:
+    if nf >= 2 ** 31 or int(lengths.max()) >= 2 ** 31 - n_fft:
         raise ValueError("features_items: batch too large for one launch (%d frames)" % nf)
     dev = wav_flat.device
     soff = _sample_offsets(lengths, dev)
     foff = torch.from_numpy(np.concatenate([[0], np.cumsum(frames)]).astype(np.int32)).to(dev, non_blocking=True)
-    awin, _ = lws_windows(dev, hop, cfg.window_scale)
-    basis, band = mel_tables(dev, cfg.sample_rate, num_mels, fmin, fmax)
+    awin, _ = lws_windows(dev, hop, cfg.window_scale, n_fft)
+    basis, band = mel_tables(dev, cfg.sample_rate, num_mels, fmin, fmax, n_fft)
     gain = item_gains(wav_flat, lengths, rescaling, soff) if rescaling else None
-    lin = torch.empty((nf, N_BIN), dtype=torch.float32, device=dev)
+    lin = torch.empty((nf, n_fft // 2 + 1), dtype=torch.float32, device=dev)
     mel = torch.empty((nf, num_mels), dtype=torch.float32, device=dev)
-    _lib.call("dv3_analysis_items_f32", wav_flat.data_ptr(), soff.data_ptr(), foff.data_ptr(), B, nf, hop,
+    _lib.call("dv3_analysis_items_f32_n", wav_flat.data_ptr(), soff.data_ptr(), foff.data_ptr(), B, nf, hop,
               float(cfg.preemphasis), awin.data_ptr(), gain.data_ptr() if gain is not None else None, basis.data_ptr(),
               band.data_ptr(), num_mels, float(cfg.min_level_db), float(cfg.ref_level_db), lin.data_ptr(),
-              mel.data_ptr(), _stream())
+              mel.data_ptr(), n_fft, _stream())
     return lin, mel, frames
 
 

@@ -5,20 +5,22 @@
 // The reference delegates phase reconstruction to the third-party `lws` package (not vendored,
 // "parity unpinned"); the north-star asks for Griffin-Lim as FFT + reduction kernels.
 // These kernels implement Griffin-Lim with torch.stft / torch.istft conventions (periodic Hann
-// window of n_fft = 1024, hop 256, center=True with reflect padding, onesided 513 bins, istft
-// normalised by the overlap-added squared window) so the CPU oracle (oracle/audio_oracle.py)
+// window of n_fft points, hop as given, center=True with reflect padding, onesided n_fft/2 + 1 bins,
+// istft normalised by the overlap-added squared window) so the CPU oracle (oracle/audio_oracle.py)
 // can be an independent restatement on torch-CPU FFTs.
 //
-// One workgroup (256 threads) transforms one 1024-point frame in LDS: Stockham auto-sort radix-4,
-// five passes, one butterfly per thread per pass, twiddles from sincospif.  Frames are
-// independent, so the grid is B*T workgroups; the only cross-frame step is the overlap-add, a
-// gather over <= 4 frames per sample (deterministic, no atomics).
+// One workgroup (256 threads) transforms one N-point frame in LDS, N = 512, 1024 or 2048 (a template
+// parameter of every kernel that frames): Stockham auto-sort radix-4 passes, at 512 and 2048 closed
+// by one radix-2 pass (fft_lds), twiddles from sincospif or a table.  Frames are independent, so the
+// grid is B*T workgroups; the only cross-frame step is the overlap-add, a gather over the frames
+// that cover a sample (<= 4 at hop = N/4; deterministic, no atomics).  The preset's size, 1024 / 256,
+// is what the entry points without an n_fft argument run.
 #include "common.h"
+
+#include <type_traits>
 
 namespace {
 
-constexpr int NFFT = 1024;
-constexpr int NBIN = NFFT / 2 + 1;
 constexpr float PI_F = 3.14159265358979323846f;
 
 struct cplx {
@@ -33,9 +35,10 @@ __device__ __forceinline__ cplx csub(cplx a, cplx b) { return {a.x - b.x, a.y - 
 __device__ __forceinline__ int item_frames(const int32_t* tlen, int b, int T, int tlo) {
   return tlen ? min(max(tlen[b], tlo), T) : T;
 }
-template <bool LWS>
+template <int NFFT, bool LWS>
 __device__ __forceinline__ int item_samples(int Tb, int hop) { return LWS ? (Tb + 1) * hop - NFFT : hop * (Tb - 1); }
 
+template <int NFFT>
 __device__ __forceinline__ float hann(int n) { return 0.5f - 0.5f * cospif(2.0f * (float)n / (float)NFFT); }
 
 // ---- forward-analysis steps shared by the batch path (preemphasis_kernel, stft_phase_kernel<true>,
@@ -52,7 +55,7 @@ __device__ __forceinline__ float gain_mul(float x, float g) {
   return x * g;
 }
 // the lws framing of frame t into A: aw[n] * sample(t * hop + n - (NFFT - hop)) inside [0, L), zeros outside
-template <class Sample>
+template <int NFFT, class Sample>
 __device__ __forceinline__ void lws_frame(cplx* A, int t, int hop, int L, const float* aw, int tid, Sample sample) {
   for (int n = tid; n < NFFT; n += 256) {
     const int i = t * hop + n - (NFFT - hop);
@@ -71,8 +74,9 @@ __device__ __forceinline__ float db_norm(float x, float min_level, float min_db,
   return fminf(fmaxf((db - min_db) / (-min_db), 0.f), 1.f);
 }
 
-// W[j] = exp(+2 pi i j / 1024), filled once per workgroup (4 sincospif per thread instead of 3 per butterfly and
+// W[j] = exp(+2 pi i j / NFFT), filled once per workgroup (4 sincospif per thread instead of 3 per butterfly and
 // pass: the transcendental calls were most of a frame's instructions).  hann(n) = 0.5 - 0.5 * Re W[n].
+template <int NFFT>
 __device__ __forceinline__ void fill_twiddles(cplx* W, int tid) {
   for (int j = tid; j < NFFT; j += 256) {
     float s, c;
@@ -82,42 +86,72 @@ __device__ __forceinline__ void fill_twiddles(cplx* W, int tid) {
 }
 __device__ __forceinline__ float hann_t(const cplx* W, int n) { return 0.5f - 0.5f * W[n].x; }
 
-// In-LDS 1024-point complex FFT (SIGN = -1 forward, +1 inverse, unnormalised).  `a` holds the
-// input in natural order; the result ends in `b` (5 passes: a->b->a->b->a->b).  256 threads.
-template <int SIGN>
-__device__ __forceinline__ void fft1024(cplx* a, cplx* b, int tid, const cplx* W = nullptr) {
+// In-LDS N-point complex FFT, N = 512, 1024 or 2048 (SIGN = -1 forward, +1 inverse, unnormalised).  `a` holds the
+// input in natural order; the result ends in `b`.  256 threads.  Stockham auto-sort: radix-4 passes at strides ns = 1,
+// 4, ... while 4 ns <= N (five at 1024 and 2048, four at 512; a->b->a->...), each of the N/4 butterflies of a pass by
+// thread j mod 256: one per thread at 1024, two at 2048, and at 512 only threads 0..127 -- waves 0 and 1 whole, waves 2
+// and 3 idle, so the predicate is wave-uniform.  512 = 2 * 4^4 and 2048 = 2 * 4^5 leave one radix-2 pass, taken LAST
+// (ns = N/2): there butterfly j reads and writes the same two elements j and j + N/2, so it may run in place.  At 2048
+// the radix-4 passes end in `b` and the radix-2 pass stays there; at 512 they end in `a` and it moves the result to `b`.
+// Its twiddle is exp(SIGN 2 pi i j / N) = W[j] itself.  One barrier per pass (in front of it) and one after the last.
+template <int N, int SIGN>
+__device__ __forceinline__ void fft_lds(cplx* a, cplx* b, int tid, const cplx* W = nullptr) {
+  static_assert(N == 512 || N == 1024 || N == 2048, "fft_lds: 512, 1024 or 2048 points");
   cplx* src = a;
   cplx* dst = b;
 #pragma unroll
-  for (int ns = 1; ns < NFFT; ns *= 4) {
+  for (int ns = 1; ns * 4 <= N; ns *= 4) {
     __syncthreads();
-    const int k = tid & (ns - 1);
-    const float ang = (float)SIGN * 2.0f * (float)k / (float)(ns * 4);  // in units of pi
-    cplx v[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      v[r] = src[tid + r * (NFFT / 4)];
-      if (r) {
-        if (W) {       // exp(SIGN * 2 pi i k r / (4 ns)) = W[k r 256/ns] (conjugated for SIGN < 0); k r / (4 ns) < 3/4
-          const cplx w = W[k * r * (NFFT / 4 / ns)];
-          v[r] = cmul(v[r], cplx{w.x, SIGN < 0 ? -w.y : w.y});
-        } else {
-          float s, c;
-          sincospif(ang * (float)r, &s, &c);
-          v[r] = cmul(v[r], cplx{c, s});
+    for (int u = 0; u < (N == 2048 ? 2 : 1); ++u) {
+      const int j = tid + 256 * u;                    // this thread's butterfly
+      if (N == 512 && j >= N / 4) continue;           // 128 butterflies: waves 0 and 1
+      const int k = j & (ns - 1);
+      const float ang = (float)SIGN * 2.0f * (float)k / (float)(ns * 4);  // in units of pi
+      cplx v[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        v[r] = src[j + r * (N / 4)];
+        if (r) {
+          if (W) {       // exp(SIGN * 2 pi i k r / (4 ns)) = W[k r (N/4)/ns] (conjugated for SIGN < 0); k r / (4 ns) < 3/4
+            const cplx w = W[k * r * (N / 4 / ns)];
+            v[r] = cmul(v[r], cplx{w.x, SIGN < 0 ? -w.y : w.y});
+          } else {
+            float s, c;
+            sincospif(ang * (float)r, &s, &c);
+            v[r] = cmul(v[r], cplx{c, s});
+          }
         }
       }
+      // radix-4 DFT, natural order: X[q] = sum_m v[m] * w^(q*m), w = exp(SIGN * i*pi/2)
+      const cplx s02 = cadd(v[0], v[2]), d02 = csub(v[0], v[2]);
+      const cplx s13 = cadd(v[1], v[3]), d13 = csub(v[1], v[3]);
+      const cplx jd13 = (SIGN < 0) ? cplx{d13.y, -d13.x} : cplx{-d13.y, d13.x};  // w * d13
+      const int j0 = ((j - k) << 2) + k;  // (j / ns) * ns * 4 + k
+      dst[j0] = cadd(s02, s13);
+      dst[j0 + ns] = cadd(d02, jd13);
+      dst[j0 + 2 * ns] = csub(s02, s13);
+      dst[j0 + 3 * ns] = csub(d02, jd13);
     }
-    // radix-4 DFT, natural order: X[q] = sum_m v[m] * w^(q*m), w = exp(SIGN * i*pi/2)
-    const cplx s02 = cadd(v[0], v[2]), d02 = csub(v[0], v[2]);
-    const cplx s13 = cadd(v[1], v[3]), d13 = csub(v[1], v[3]);
-    const cplx jd13 = (SIGN < 0) ? cplx{d13.y, -d13.x} : cplx{-d13.y, d13.x};  // w * d13
-    const int j0 = ((tid - k) << 2) + k;  // (tid / ns) * ns * 4 + k
-    dst[j0] = cadd(s02, s13);
-    dst[j0 + ns] = cadd(d02, jd13);
-    dst[j0 + 2 * ns] = csub(s02, s13);
-    dst[j0 + 3 * ns] = csub(d02, jd13);
     cplx* t = src; src = dst; dst = t;
+  }
+  if constexpr (N != 1024) {   // the radix-2 pass at ns = N/2: X[j] = u + w v, X[j + N/2] = u - w v, into `b` (src == b: in place)
+    __syncthreads();
+#pragma unroll
+    for (int j = tid; j < N / 2; j += 256) {
+      const cplx u = src[j];
+      cplx v = src[j + N / 2];
+      if (W) {
+        const cplx w = W[j];
+        v = cmul(v, cplx{w.x, SIGN < 0 ? -w.y : w.y});
+      } else {
+        float s, c;
+        sincospif((float)SIGN * 2.0f * (float)j / (float)N, &s, &c);
+        v = cmul(v, cplx{c, s});
+      }
+      b[j] = cadd(u, v);
+      b[j + N / 2] = csub(u, v);
+    }
   }
   __syncthreads();
 }
@@ -135,13 +169,14 @@ __global__ void gl_prepare_kernel(const float* __restrict__ lin, float* __restri
 }
 
 // frames[b][t][n] = hann[n] * irfft(mag[b][t][:] * phasor[b][t][:])[n]   (phasor NULL: zero phase)
-// LWS: the conventions of lws.lws(1024, hop) (audio.py:54-55; oracle/audio_oracle.py: lws_windows): `sw` = the
+// LWS: the conventions of lws.lws(NFFT, hop) (audio.py:54-55; oracle/audio_oracle.py: lws_windows): `sw` = the
 // perfect-reconstruction synthesis window (the overlap-add normaliser is folded into it)
-template <bool LWS>
+template <int NFFT, bool LWS>
 __global__ __launch_bounds__(256) void istft_frames_kernel(const float* __restrict__ mag,
                                                            const float* __restrict__ phasor,
                                                            float* __restrict__ frames, const float* __restrict__ sw,
                                                            const int32_t* __restrict__ tlen, int T, int tlo) {
+  constexpr int NBIN = NFFT / 2 + 1;
   __shared__ cplx A[NFFT], Bf[NFFT];
   const int tid = threadIdx.x;
   const int64_t fr = blockIdx.x;
@@ -155,22 +190,22 @@ __global__ __launch_bounds__(256) void istft_frames_kernel(const float* __restri
     A[k] = z;
     if (k > 0 && k < NFFT / 2) A[NFFT - k] = cplx{z.x, -z.y};
   }
-  fft1024<+1>(A, Bf, tid);
+  fft_lds<NFFT, +1>(A, Bf, tid);
   float* out = frames + fr * NFFT;
-  for (int n = tid; n < NFFT; n += 256) out[n] = Bf[n].x * (1.0f / NFFT) * (LWS ? sw[n] : hann(n));
+  for (int n = tid; n < NFFT; n += 256) out[n] = Bf[n].x * (1.0f / NFFT) * (LWS ? sw[n] : hann<NFFT>(n));
 }
 
 // y[b][i] = sum_t frames[b][t][p - t*hop] / sum_t hann^2[p - t*hop],  p = i + NFFT/2, i < hop*(T-1)
 // LWS: p = i + (NFFT - hop) (the zero padding lws strips), no division (the synthesis window carries the normaliser)
 // tlen (per item): item b overlap-adds its own Tb frames into its own item_samples(Tb) samples, zeros after them
-template <bool LWS>
+template <int NFFT, bool LWS>
 __global__ void ola_kernel(const float* __restrict__ frames, float* __restrict__ y, int T, int hop,
                            int L, const int32_t* __restrict__ tlen, int tlo) {
   const int b = blockIdx.y;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= L) return;
   const int Tb = item_frames(tlen, b, T, tlo);
-  if (tlen && i >= item_samples<LWS>(Tb, hop)) {
+  if (tlen && i >= item_samples<NFFT, LWS>(Tb, hop)) {
     y[(int64_t)b * L + i] = 0.f;
     return;
   }
@@ -189,7 +224,7 @@ __global__ void ola_kernel(const float* __restrict__ frames, float* __restrict__
     if (n < 0 || n >= NFFT) continue;
     acc += fb[(int64_t)t * NFFT + n];
     if (!interior) {
-      const float w = hann(n);
+      const float w = hann<NFFT>(n);
       wsum += w * w;
     }
   }
@@ -198,29 +233,30 @@ __global__ void ola_kernel(const float* __restrict__ frames, float* __restrict__
 
 // phasor[b][t][k] = Z / max(|Z|, 1e-8), Z = rfft(hann * reflect_pad(y[b])[t*hop : t*hop + NFFT])[k]
 // (spec, optional: Z itself, for tests / spectral convergence)
-// LWS: Z = rfft(aw * zero_pad(y[b], NFFT - hop)[t*hop : t*hop + NFFT]) -- lws.lws(1024, hop).stft (sqrt-Hann analysis window
+// LWS: Z = rfft(aw * zero_pad(y[b], NFFT - hop)[t*hop : t*hop + NFFT]) -- lws.lws(NFFT, hop).stft (sqrt-Hann analysis window
 // `aw`, zeros instead of reflection)
-template <bool LWS>
+template <int NFFT, bool LWS>
 __global__ __launch_bounds__(256) void stft_phase_kernel(const float* __restrict__ y,
                                                          float* __restrict__ phasor,
                                                          float* __restrict__ spec,
                                                          float* __restrict__ mag_bct, int T, int hop, int L,
                                                          const float* __restrict__ aw) {
+  constexpr int NBIN = NFFT / 2 + 1;
   __shared__ cplx A[NFFT], Bf[NFFT];
   const int tid = threadIdx.x;
   const int b = blockIdx.x / T, t = blockIdx.x - b * T;
   const float* yb = y + (int64_t)b * L;
   if constexpr (LWS) {
-    lws_frame(A, t, hop, L, aw, tid, [=](int i) { return yb[i]; });
+    lws_frame<NFFT>(A, t, hop, L, aw, tid, [=](int i) { return yb[i]; });
   } else {
     for (int n = tid; n < NFFT; n += 256) {
       int i = t * hop + n - NFFT / 2;  // index into the un-padded signal
       if (i < 0) i = -i;
       if (i >= L) i = 2 * (L - 1) - i;
-      A[n] = cplx{yb[i] * hann(n), 0.f};
+      A[n] = cplx{yb[i] * hann<NFFT>(n), 0.f};
     }
   }
-  fft1024<-1>(A, Bf, tid);
+  fft_lds<NFFT, -1>(A, Bf, tid);
   const int64_t fr = blockIdx.x;
   for (int k = tid; k <= NFFT / 2; k += 256) {
     const cplx z = Bf[k];
@@ -237,49 +273,19 @@ __global__ __launch_bounds__(256) void stft_phase_kernel(const float* __restrict
   }
 }
 
-// One Griffin-Lim projection per frame without leaving LDS: STFT of the current signal estimate -> unit phase ->
-// times the target magnitude -> inverse FFT -> synthesis window.  Equals stft_phase_kernel followed by
-// istft_frames_kernel (same arithmetic, same order) minus the phasor round trip through HBM (8 KB per frame).
-__global__ __launch_bounds__(256) void gl_project_kernel(const float* __restrict__ y, const float* __restrict__ mag,
-                                                         float* __restrict__ frames, int T, int hop, int L) {
-  __shared__ cplx A[NFFT], Bf[NFFT], W[NFFT];
-  const int tid = threadIdx.x;
-  const int b = blockIdx.x / T, t = blockIdx.x - b * T;
-  const float* yb = y + (int64_t)b * L;
-  fill_twiddles(W, tid);
-  __syncthreads();
-  for (int n = tid; n < NFFT; n += 256) {
-    int i = t * hop + n - NFFT / 2;
-    if (i < 0) i = -i;
-    if (i >= L) i = 2 * (L - 1) - i;
-    A[n] = cplx{yb[i] * hann_t(W, n), 0.f};
-  }
-  fft1024<-1>(A, Bf, tid, W);
-  const int64_t fr = blockIdx.x;
-  const float* m = mag + fr * NBIN;
-  for (int k = tid; k <= NFFT / 2; k += 256) {
-    const cplx z = Bf[k];
-    const float inv = 1.0f / fmaxf(sqrtf(z.x * z.x + z.y * z.y), 1e-8f);
-    const float px = z.x * inv, py = z.y * inv;       // the unit phasor stft_phase_kernel would store
-    cplx w{m[k] * px, m[k] * py};
-    if (k == 0 || k == NFFT / 2) w.y = 0.f;
-    A[k] = w;
-    if (k > 0 && k < NFFT / 2) A[NFFT - k] = cplx{w.x, -w.y};
-  }
-  fft1024<+1>(A, Bf, tid, W);
-  float* out = frames + fr * NFFT;
-  for (int n = tid; n < NFFT; n += 256) out[n] = Bf[n].x * (1.0f / NFFT) * hann_t(W, n);
-}
-
-// The same projection for TWO frames per workgroup: both input frames are real, so they ride one complex FFT as
+// One Griffin-Lim projection without leaving LDS: STFT of the current signal estimate -> unit phase -> times the target
+// magnitude -> inverse FFT -> synthesis window.  Equals stft_phase_kernel followed by istft_frames_kernel (same
+// arithmetic, same order) minus the phasor round trip through HBM (8 KB per frame at 1024), for TWO frames per
+// workgroup: both input frames are real, so they ride one complex FFT as
 // z = x1 + i x2 (X1[k] = (Z[k] + conj Z[N-k]) / 2, X2[k] = (Z[k] - conj Z[N-k]) / 2i), and the two Hermitian target
 // spectra ride one inverse FFT as V = Y1 + i Y2 (y1 = Re v, y2 = Im v): half the FFT passes -- the LDS traffic that
 // bounds this kernel -- per frame.  Frames (2q, 2q+1) of one batch item; an odd last frame pairs with nothing.
-template <bool LWS>
+template <int NFFT, bool LWS>
 __global__ __launch_bounds__(256) void gl_project2_kernel(const float* __restrict__ y, const float* __restrict__ mag,
                                                           float* __restrict__ frames, int T, int hop, int L, int TP,
                                                           const float* __restrict__ aw, const float* __restrict__ sw,
                                                           const int32_t* __restrict__ tlen, int tlo) {
+  constexpr int NBIN = NFFT / 2 + 1;
   __shared__ cplx A[NFFT], Bf[NFFT], W[NFFT];
   const int tid = threadIdx.x;
   const int b = blockIdx.x / TP, t1 = 2 * (blockIdx.x - b * TP);
@@ -287,8 +293,8 @@ __global__ __launch_bounds__(256) void gl_project2_kernel(const float* __restric
   const int Tb = item_frames(tlen, b, T, tlo);
   if (t1 >= Tb) return;                      // a pair past the item's own frames (workgroup-uniform, before any barrier)
   const bool two = t1 + 1 < Tb;
-  L = tlen ? item_samples<LWS>(Tb, hop) : L;
-  fill_twiddles(W, tid);
+  L = tlen ? item_samples<NFFT, LWS>(Tb, hop) : L;
+  fill_twiddles<NFFT>(W, tid);
   __syncthreads();
   for (int n = tid; n < NFFT; n += 256) {
     if constexpr (LWS) {      // lws framing: zeros outside the signal, sqrt-Hann analysis window from the table
@@ -305,7 +311,7 @@ __global__ __launch_bounds__(256) void gl_project2_kernel(const float* __restric
       A[n] = cplx{yb[i1] * h, two ? yb[i2] * h : 0.f};
     }
   }
-  fft1024<-1>(A, Bf, tid, W);
+  fft_lds<NFFT, -1>(A, Bf, tid, W);
   const int64_t fr = (int64_t)b * T + t1;
   const float* m1 = mag + fr * NBIN;
   const float* m2 = m1 + (two ? NBIN : 0);
@@ -324,7 +330,7 @@ __global__ __launch_bounds__(256) void gl_project2_kernel(const float* __restric
     A[k] = cplx{w1.x - w2.y, w1.y + w2.x};
     if (k > 0 && k < NFFT / 2) A[NFFT - k] = cplx{w1.x + w2.y, -w1.y + w2.x};
   }
-  fft1024<+1>(A, Bf, tid, W);
+  fft_lds<NFFT, +1>(A, Bf, tid, W);
   float* out = frames + fr * NFFT;
   for (int n = tid; n < NFFT; n += 256) {
     const float h = (LWS ? sw[n] : hann_t(W, n)) * (1.0f / NFFT);
@@ -411,17 +417,18 @@ __global__ __launch_bounds__(256) void item_gain_kernel(const float* __restrict_
 }
 
 // One workgroup per OUTPUT ROW g of the packed result: frame t = g - foff[b] of item b (foff[b] <= g < foff[b+1]).
-// preemphasis (optionally of gain[b] * x) inline -> lws framing of item b's own samples [0, L_b) -> 1024-point FFT in
+// preemphasis (optionally of gain[b] * x) inline -> lws framing of item b's own samples [0, L_b) -> NFFT-point FFT in
 // LDS -> |X| -> lin row (dB-normalised) and, from the magnitudes left in LDS, the mel row: one lane per filter, a
 // fixed-order fmaf chain over the filter's ascending nonzero bins [band[2m], band[2m+1]).  Nothing of the row depends
 // on another item, on B or on the grid: the row is what item b alone gives.  The linear row takes the same steps, in
 // the same expressions, as preemphasis_kernel -> stft_phase_kernel<true> -> amp_to_db_norm_kernel.
-template <bool GAIN>
+template <int NFFT, bool GAIN>
 __global__ __launch_bounds__(256) void analysis_items_kernel(
     const float* __restrict__ x, const int64_t* __restrict__ soff, const int32_t* __restrict__ foff, int B, int hop,
     float coef, const float* __restrict__ aw, const float* __restrict__ gain, const float* __restrict__ basis,
     const int32_t* __restrict__ band, int n_mels, float min_db, float ref_db, float* __restrict__ lin,
     float* __restrict__ mel) {
+  constexpr int NBIN = NFFT / 2 + 1;
   __shared__ cplx A[NFFT], Bf[NFFT];
   const int tid = threadIdx.x;
   const int g = blockIdx.x;
@@ -435,13 +442,13 @@ __global__ __launch_bounds__(256) void analysis_items_kernel(
   const int L = (int)(soff[b + 1] - soff[b]);
   if constexpr (GAIN) {
     const float gb = gain[b];
-    lws_frame(A, t, hop, L, aw, tid, [=](int i) {
+    lws_frame<NFFT>(A, t, hop, L, aw, tid, [=](int i) {
       return i ? preemph(gain_mul(xb[i], gb), gain_mul(xb[i - 1], gb), coef) : gain_mul(xb[0], gb);
     });
   } else {
-    lws_frame(A, t, hop, L, aw, tid, [=](int i) { return preemph_at(xb, i, coef); });
+    lws_frame<NFFT>(A, t, hop, L, aw, tid, [=](int i) { return preemph_at(xb, i, coef); });
   }
-  fft1024<-1>(A, Bf, tid);                            // ends with a barrier; the spectrum is in Bf, A is free
+  fft_lds<NFFT, -1>(A, Bf, tid);                      // ends with a barrier; the spectrum is in Bf, A is free
   float* Ms = reinterpret_cast<float*>(A);
   const float min_level = db_min_level(min_db);
   for (int k = tid; k < NBIN; k += 256) {
@@ -488,77 +495,171 @@ extern "C" int dv3_gl_prepare_f32(const float* lin, float* mag, int64_t n, float
   return dv3_check_launch("gl_prepare");
 }
 
-extern "C" int dv3_istft_frames_f32(const float* mag, const float* phasor, float* frames, int32_t B,
-                                    int32_t T, void* stream) {
+// ---- the entry points that frame: one host function per entry point, templated on the frame size N.  The entry
+// points of ABI <= 48 (no n_fft argument) are the N = 1024 instantiation; their `_n` siblings (ABI 49) pick the
+// instantiation from n_fft.  3 * N * 8 bytes of static LDS (A, Bf, W) is 48 KB at 2048; 4096 would need 96 KB, past the
+// 64 KB a workgroup may declare, so the siblings take 512, 1024 and 2048 and refuse everything else. ----
+template <class F>
+static int with_fft_size(const char* what, int32_t n_fft, F f) {
+  switch (n_fft) {
+    case 512: return f(std::integral_constant<int, 512>{});
+    case 1024: return f(std::integral_constant<int, 1024>{});
+    case 2048: return f(std::integral_constant<int, 2048>{});
+  }
+  dv3_set_error("%s: n_fft = %d is not supported: the FFT kernels are built for 512, 1024 and 2048", what, (int)n_fft);
+  return DV3_EINVAL;
+}
+
+// lws framing: T frames cover (T + 1) * hop - N samples (a signal padded with N - hop zeros on both sides)
+template <int N>
+static inline int lws_len(int T, int hop) { return (T + 1) * hop - N; }
+// the sample counts above and hop * (T - 1) are ints: T and hop are checked with this before either is formed
+static inline bool samples_fit(int T, int hop) { return (int64_t)(T + 1LL) * hop <= INT32_MAX; }
+
+template <int N>
+static int istft_frames(const float* mag, const float* phasor, float* frames, int32_t B, int32_t T, void* stream) {
   DV3_REQUIRE(mag && frames && B > 0 && T > 0, "istft_frames: bad arguments");
-  hipLaunchKernelGGL(istft_frames_kernel<false>, dim3((unsigned)((int64_t)B * T)), dim3(256), 0,
+  hipLaunchKernelGGL((istft_frames_kernel<N, false>), dim3((unsigned)((int64_t)B * T)), dim3(256), 0,
                      (hipStream_t)stream, mag, phasor, frames, (const float*)nullptr, (const int32_t*)nullptr, (int)T, 1);
   return dv3_check_launch("istft_frames");
 }
-extern "C" int dv3_lws_istft_frames_f32(const float* mag, const float* phasor, const float* swin, float* frames, int32_t B,
-                                        int32_t T, void* stream) {
+template <int N>
+static int lws_istft_frames(const float* mag, const float* phasor, const float* swin, float* frames, int32_t B, int32_t T,
+                            void* stream) {
   DV3_REQUIRE(mag && frames && swin && B > 0 && T > 0, "lws_istft_frames: bad arguments");
-  hipLaunchKernelGGL(istft_frames_kernel<true>, dim3((unsigned)((int64_t)B * T)), dim3(256), 0,
+  hipLaunchKernelGGL((istft_frames_kernel<N, true>), dim3((unsigned)((int64_t)B * T)), dim3(256), 0,
                      (hipStream_t)stream, mag, phasor, frames, swin, (const int32_t*)nullptr, (int)T, 1);
   return dv3_check_launch("lws_istft_frames");
 }
 
-extern "C" int dv3_overlap_add_f32(const float* frames, float* y, int32_t B, int32_t T, int32_t hop,
-                                   void* stream) {
-  DV3_REQUIRE(frames && y && B > 0 && T > 1 && hop > 0 && hop <= 1024, "overlap_add: bad arguments");
+template <int N>
+static int overlap_add(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, void* stream) {
+  DV3_REQUIRE(frames && y && B > 0 && T > 1 && hop > 0 && hop <= N && samples_fit(T, hop), "overlap_add: bad arguments");
   const int L = hop * (T - 1);
-  hipLaunchKernelGGL(ola_kernel<false>, dim3(dv3_cdiv(L, 256), B), dim3(256), 0, (hipStream_t)stream, frames, y,
+  hipLaunchKernelGGL((ola_kernel<N, false>), dim3(dv3_cdiv(L, 256), B), dim3(256), 0, (hipStream_t)stream, frames, y,
                      T, hop, L, (const int32_t*)nullptr, 1);
   return dv3_check_launch("overlap_add");
 }
-
-// lws framing: T frames cover (T + 1) * hop - 1024 samples (a signal padded with 1024 - hop zeros on both sides)
-static inline int lws_len(int T, int hop) { return (T + 1) * hop - NFFT; }
-extern "C" int dv3_lws_overlap_add_f32(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, void* stream) {
-  DV3_REQUIRE(frames && y && B > 0 && T > 1 && hop > 0 && hop <= 1024 && lws_len(T, hop) > 0, "lws_overlap_add: bad arguments");
-  const int L = lws_len(T, hop);
-  hipLaunchKernelGGL(ola_kernel<true>, dim3(dv3_cdiv(L, 256), B), dim3(256), 0, (hipStream_t)stream, frames, y, T, hop, L,
+template <int N>
+static int lws_overlap_add(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, void* stream) {
+  DV3_REQUIRE(frames && y && B > 0 && T > 1 && hop > 0 && hop <= N && samples_fit(T, hop) && lws_len<N>(T, hop) > 0,
+              "lws_overlap_add: bad arguments");
+  const int L = lws_len<N>(T, hop);
+  hipLaunchKernelGGL((ola_kernel<N, true>), dim3(dv3_cdiv(L, 256), B), dim3(256), 0, (hipStream_t)stream, frames, y, T, hop, L,
                      (const int32_t*)nullptr, 1);
   return dv3_check_launch("lws_overlap_add");
 }
-extern "C" int dv3_lws_stft_f32(const float* y, const float* awin, float* phasor, float* spec, float* mag_bct, int32_t B,
-                                int32_t T, int32_t hop, int32_t L, void* stream) {
-  DV3_REQUIRE(y && awin && (phasor || spec || mag_bct) && B > 0 && T > 1 && hop > 0 && hop <= 1024 && L > 0,
-              "lws_stft: bad arguments");
-  DV3_REQUIRE(L <= lws_len(T, hop) && L > lws_len(T - 1, hop), "lws_stft: %d frames do not frame %d samples at hop %d", T, L, hop);
-  hipLaunchKernelGGL(stft_phase_kernel<true>, dim3((unsigned)((int64_t)B * T)), dim3(256), 0, (hipStream_t)stream, y, phasor,
+template <int N>
+static int lws_stft(const float* y, const float* awin, float* phasor, float* spec, float* mag_bct, int32_t B, int32_t T,
+                    int32_t hop, int32_t L, void* stream) {
+  DV3_REQUIRE(y && awin && (phasor || spec || mag_bct) && B > 0 && T > 1 && hop > 0 && hop <= N && L > 0 &&
+              samples_fit(T, hop), "lws_stft: bad arguments");
+  DV3_REQUIRE(L <= lws_len<N>(T, hop) && L > lws_len<N>(T - 1, hop), "lws_stft: %d frames do not frame %d samples at hop %d", T, L, hop);
+  hipLaunchKernelGGL((stft_phase_kernel<N, true>), dim3((unsigned)((int64_t)B * T)), dim3(256), 0, (hipStream_t)stream, y, phasor,
                      spec, mag_bct, T, hop, L, awin);
   return dv3_check_launch("lws_stft");
 }
-extern "C" int dv3_lws_gl_project_f32(const float* y, const float* mag, const float* awin, const float* swin, float* frames,
-                                      int32_t B, int32_t T, int32_t hop, void* stream) {
-  DV3_REQUIRE(y && mag && frames && awin && swin && B > 0 && T > 1 && hop > 0 && hop <= 1024 && lws_len(T, hop) > 0,
-              "lws_gl_project: bad arguments");
+template <int N>
+static int lws_gl_project(const float* y, const float* mag, const float* awin, const float* swin, float* frames, int32_t B,
+                          int32_t T, int32_t hop, void* stream) {
+  DV3_REQUIRE(y && mag && frames && awin && swin && B > 0 && T > 1 && hop > 0 && hop <= N && samples_fit(T, hop) &&
+              lws_len<N>(T, hop) > 0, "lws_gl_project: bad arguments");
   const int TP = (T + 1) / 2;
-  hipLaunchKernelGGL(gl_project2_kernel<true>, dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
-                     frames, T, hop, lws_len(T, hop), TP, awin, swin, (const int32_t*)nullptr, 1);
+  hipLaunchKernelGGL((gl_project2_kernel<N, true>), dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
+                     frames, T, hop, lws_len<N>(T, hop), TP, awin, swin, (const int32_t*)nullptr, 1);
   return dv3_check_launch("lws_gl_project");
 }
 
-extern "C" int dv3_stft_phase_f32(const float* y, float* phasor, float* spec, float* mag_bct, int32_t B,
-                                  int32_t T, int32_t hop, void* stream) {
-  DV3_REQUIRE(y && (phasor || spec || mag_bct) && B > 0 && T > 1 && hop > 0, "stft_phase: bad arguments");
+template <int N>
+static int stft_phase(const float* y, float* phasor, float* spec, float* mag_bct, int32_t B, int32_t T, int32_t hop,
+                      void* stream) {
+  DV3_REQUIRE(y && (phasor || spec || mag_bct) && B > 0 && T > 1 && hop > 0 && samples_fit(T, hop), "stft_phase: bad arguments");
   const int L = hop * (T - 1);
-  DV3_REQUIRE(L > 512, "stft_phase: signal shorter than the reflect padding");
-  hipLaunchKernelGGL(stft_phase_kernel<false>, dim3((unsigned)((int64_t)B * T)), dim3(256), 0,
+  DV3_REQUIRE(L > N / 2, "stft_phase: signal shorter than the reflect padding");
+  hipLaunchKernelGGL((stft_phase_kernel<N, false>), dim3((unsigned)((int64_t)B * T)), dim3(256), 0,
                      (hipStream_t)stream, y, phasor, spec, mag_bct, T, hop, L, (const float*)nullptr);
   return dv3_check_launch("stft_phase");
 }
 
-extern "C" int dv3_gl_project_f32(const float* y, const float* mag, float* frames, int32_t B, int32_t T, int32_t hop,
-                                  void* stream) {
-  DV3_REQUIRE(y && mag && frames && B > 0 && T > 1 && hop > 0, "gl_project: bad arguments");
+template <int N>
+static int gl_project(const float* y, const float* mag, float* frames, int32_t B, int32_t T, int32_t hop, void* stream) {
+  DV3_REQUIRE(y && mag && frames && B > 0 && T > 1 && hop > 0 && samples_fit(T, hop), "gl_project: bad arguments");
   const int L = hop * (T - 1);
-  DV3_REQUIRE(L > 512, "gl_project: signal shorter than the reflect padding");
+  DV3_REQUIRE(L > N / 2, "gl_project: signal shorter than the reflect padding");
   const int TP = (T + 1) / 2;     // two real frames per complex FFT
-  hipLaunchKernelGGL(gl_project2_kernel<false>, dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
+  hipLaunchKernelGGL((gl_project2_kernel<N, false>), dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
                      frames, T, hop, L, TP, (const float*)nullptr, (const float*)nullptr, (const int32_t*)nullptr, 1);
   return dv3_check_launch("gl_project");
+}
+
+extern "C" int dv3_istft_frames_f32(const float* mag, const float* phasor, float* frames, int32_t B,
+                                    int32_t T, void* stream) {
+  return istft_frames<1024>(mag, phasor, frames, B, T, stream);
+}
+extern "C" int dv3_istft_frames_f32_n(const float* mag, const float* phasor, float* frames, int32_t B, int32_t T,
+                                      int32_t n_fft, void* stream) {
+  return with_fft_size("istft_frames", n_fft, [&](auto n) { return istft_frames<decltype(n)::value>(mag, phasor, frames, B, T, stream); });
+}
+extern "C" int dv3_lws_istft_frames_f32(const float* mag, const float* phasor, const float* swin, float* frames, int32_t B,
+                                        int32_t T, void* stream) {
+  return lws_istft_frames<1024>(mag, phasor, swin, frames, B, T, stream);
+}
+extern "C" int dv3_lws_istft_frames_f32_n(const float* mag, const float* phasor, const float* swin, float* frames, int32_t B,
+                                          int32_t T, int32_t n_fft, void* stream) {
+  return with_fft_size("lws_istft_frames", n_fft,
+                       [&](auto n) { return lws_istft_frames<decltype(n)::value>(mag, phasor, swin, frames, B, T, stream); });
+}
+
+extern "C" int dv3_overlap_add_f32(const float* frames, float* y, int32_t B, int32_t T, int32_t hop,
+                                   void* stream) {
+  return overlap_add<1024>(frames, y, B, T, hop, stream);
+}
+extern "C" int dv3_overlap_add_f32_n(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, int32_t n_fft,
+                                     void* stream) {
+  return with_fft_size("overlap_add", n_fft, [&](auto n) { return overlap_add<decltype(n)::value>(frames, y, B, T, hop, stream); });
+}
+extern "C" int dv3_lws_overlap_add_f32(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, void* stream) {
+  return lws_overlap_add<1024>(frames, y, B, T, hop, stream);
+}
+extern "C" int dv3_lws_overlap_add_f32_n(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, int32_t n_fft,
+                                         void* stream) {
+  return with_fft_size("lws_overlap_add", n_fft, [&](auto n) { return lws_overlap_add<decltype(n)::value>(frames, y, B, T, hop, stream); });
+}
+extern "C" int dv3_lws_stft_f32(const float* y, const float* awin, float* phasor, float* spec, float* mag_bct, int32_t B,
+                                int32_t T, int32_t hop, int32_t L, void* stream) {
+  return lws_stft<1024>(y, awin, phasor, spec, mag_bct, B, T, hop, L, stream);
+}
+extern "C" int dv3_lws_stft_f32_n(const float* y, const float* awin, float* phasor, float* spec, float* mag_bct, int32_t B,
+                                  int32_t T, int32_t hop, int32_t L, int32_t n_fft, void* stream) {
+  return with_fft_size("lws_stft", n_fft,
+                       [&](auto n) { return lws_stft<decltype(n)::value>(y, awin, phasor, spec, mag_bct, B, T, hop, L, stream); });
+}
+extern "C" int dv3_lws_gl_project_f32(const float* y, const float* mag, const float* awin, const float* swin, float* frames,
+                                      int32_t B, int32_t T, int32_t hop, void* stream) {
+  return lws_gl_project<1024>(y, mag, awin, swin, frames, B, T, hop, stream);
+}
+extern "C" int dv3_lws_gl_project_f32_n(const float* y, const float* mag, const float* awin, const float* swin, float* frames,
+                                        int32_t B, int32_t T, int32_t hop, int32_t n_fft, void* stream) {
+  return with_fft_size("lws_gl_project", n_fft,
+                       [&](auto n) { return lws_gl_project<decltype(n)::value>(y, mag, awin, swin, frames, B, T, hop, stream); });
+}
+
+extern "C" int dv3_stft_phase_f32(const float* y, float* phasor, float* spec, float* mag_bct, int32_t B,
+                                  int32_t T, int32_t hop, void* stream) {
+  return stft_phase<1024>(y, phasor, spec, mag_bct, B, T, hop, stream);
+}
+extern "C" int dv3_stft_phase_f32_n(const float* y, float* phasor, float* spec, float* mag_bct, int32_t B, int32_t T,
+                                    int32_t hop, int32_t n_fft, void* stream) {
+  return with_fft_size("stft_phase", n_fft, [&](auto n) { return stft_phase<decltype(n)::value>(y, phasor, spec, mag_bct, B, T, hop, stream); });
+}
+
+extern "C" int dv3_gl_project_f32(const float* y, const float* mag, float* frames, int32_t B, int32_t T, int32_t hop,
+                                  void* stream) {
+  return gl_project<1024>(y, mag, frames, B, T, hop, stream);
+}
+extern "C" int dv3_gl_project_f32_n(const float* y, const float* mag, float* frames, int32_t B, int32_t T, int32_t hop,
+                                    int32_t n_fft, void* stream) {
+  return with_fft_size("gl_project", n_fft, [&](auto n) { return gl_project<decltype(n)::value>(y, mag, frames, B, T, hop, stream); });
 }
 
 // The same filter in parallel over the row.  |coef| < 1, so the response to a sample dies off geometrically: a chunk of
@@ -658,49 +759,82 @@ extern "C" int dv3_deemphasis_f32(const float* x, float* y, int32_t B, int32_t L
 // ---- per-item frame counts (ABI 44, include/dv3hip.h: dv3_gl_istft_items_f32 ...): a batch of utterances of different
 // lengths, each item's inverse exactly its B = 1 call on its own trimmed spectrogram ----
 // the fewest frames a framing takes at this hop: lws needs a positive signal length, torch one longer than the reflect pad
+template <int N>
 static int items_tlo(int lws, int hop) {
   int t = 2;
-  while (lws ? lws_len(t, hop) <= 0 : hop * (t - 1) <= NFFT / 2) ++t;
+  while (lws ? lws_len<N>(t, hop) <= 0 : hop * (t - 1) <= N / 2) ++t;
   return t;
+}
+template <int N>
+static int gl_istft_items(const float* mag, const float* phasor, const float* swin, float* frames, int32_t B, int32_t T,
+                          int32_t hop, const int32_t* tlen, int32_t lws, void* stream) {
+  DV3_REQUIRE(mag && frames && tlen && (!lws || swin) && B > 0 && T > 1 && hop > 0 && hop <= N &&
+              samples_fit(T, hop) && T >= items_tlo<N>(lws, hop), "gl_istft_items: bad arguments");
+  if (lws)
+    hipLaunchKernelGGL((istft_frames_kernel<N, true>), dim3((unsigned)((int64_t)B * T)), dim3(256), 0, (hipStream_t)stream, mag,
+                       phasor, frames, swin, tlen, (int)T, items_tlo<N>(lws, hop));
+  else
+    hipLaunchKernelGGL((istft_frames_kernel<N, false>), dim3((unsigned)((int64_t)B * T)), dim3(256), 0, (hipStream_t)stream, mag,
+                       phasor, frames, (const float*)nullptr, tlen, (int)T, items_tlo<N>(lws, hop));
+  return dv3_check_launch("gl_istft_items");
+}
+template <int N>
+static int overlap_add_items(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, const int32_t* tlen,
+                             int32_t lws, void* stream) {
+  DV3_REQUIRE(frames && y && tlen && B > 0 && T > 1 && hop > 0 && hop <= N && samples_fit(T, hop) &&
+              T >= items_tlo<N>(lws, hop), "overlap_add_items: bad arguments");
+  const int L = lws ? lws_len<N>(T, hop) : hop * (T - 1);
+  if (lws)
+    hipLaunchKernelGGL((ola_kernel<N, true>), dim3(dv3_cdiv(L, 256), B), dim3(256), 0, (hipStream_t)stream, frames, y, T, hop, L,
+                       tlen, items_tlo<N>(lws, hop));
+  else
+    hipLaunchKernelGGL((ola_kernel<N, false>), dim3(dv3_cdiv(L, 256), B), dim3(256), 0, (hipStream_t)stream, frames, y, T, hop, L,
+                       tlen, items_tlo<N>(lws, hop));
+  return dv3_check_launch("overlap_add_items");
+}
+template <int N>
+static int gl_project_items(const float* y, const float* mag, const float* awin, const float* swin, float* frames, int32_t B,
+                            int32_t T, int32_t hop, const int32_t* tlen, int32_t lws, void* stream) {
+  DV3_REQUIRE(y && mag && frames && tlen && (!lws || (awin && swin)) && B > 0 && T > 1 && hop > 0 && hop <= N &&
+              samples_fit(T, hop) && T >= items_tlo<N>(lws, hop), "gl_project_items: bad arguments");
+  const int TP = (T + 1) / 2;
+  const int L = lws ? lws_len<N>(T, hop) : hop * (T - 1);
+  if (lws)
+    hipLaunchKernelGGL((gl_project2_kernel<N, true>), dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
+                       frames, T, hop, L, TP, awin, swin, tlen, items_tlo<N>(lws, hop));
+  else
+    hipLaunchKernelGGL((gl_project2_kernel<N, false>), dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
+                       frames, T, hop, L, TP, (const float*)nullptr, (const float*)nullptr, tlen, items_tlo<N>(lws, hop));
+  return dv3_check_launch("gl_project_items");
 }
 extern "C" int dv3_gl_istft_items_f32(const float* mag, const float* phasor, const float* swin, float* frames, int32_t B,
                                       int32_t T, int32_t hop, const int32_t* tlen, int32_t lws, void* stream) {
-  DV3_REQUIRE(mag && frames && tlen && (!lws || swin) && B > 0 && T > 1 && hop > 0 && hop <= 1024 &&
-              T >= items_tlo(lws, hop), "gl_istft_items: bad arguments");
-  if (lws)
-    hipLaunchKernelGGL(istft_frames_kernel<true>, dim3((unsigned)((int64_t)B * T)), dim3(256), 0, (hipStream_t)stream, mag,
-                       phasor, frames, swin, tlen, (int)T, items_tlo(lws, hop));
-  else
-    hipLaunchKernelGGL(istft_frames_kernel<false>, dim3((unsigned)((int64_t)B * T)), dim3(256), 0, (hipStream_t)stream, mag,
-                       phasor, frames, (const float*)nullptr, tlen, (int)T, items_tlo(lws, hop));
-  return dv3_check_launch("gl_istft_items");
+  return gl_istft_items<1024>(mag, phasor, swin, frames, B, T, hop, tlen, lws, stream);
+}
+extern "C" int dv3_gl_istft_items_f32_n(const float* mag, const float* phasor, const float* swin, float* frames, int32_t B,
+                                        int32_t T, int32_t hop, const int32_t* tlen, int32_t lws, int32_t n_fft, void* stream) {
+  return with_fft_size("gl_istft_items", n_fft,
+                       [&](auto n) { return gl_istft_items<decltype(n)::value>(mag, phasor, swin, frames, B, T, hop, tlen, lws, stream); });
 }
 extern "C" int dv3_overlap_add_items_f32(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, const int32_t* tlen,
                                          int32_t lws, void* stream) {
-  DV3_REQUIRE(frames && y && tlen && B > 0 && T > 1 && hop > 0 && hop <= 1024 && T >= items_tlo(lws, hop),
-              "overlap_add_items: bad arguments");
-  const int L = lws ? lws_len(T, hop) : hop * (T - 1);
-  if (lws)
-    hipLaunchKernelGGL(ola_kernel<true>, dim3(dv3_cdiv(L, 256), B), dim3(256), 0, (hipStream_t)stream, frames, y, T, hop, L,
-                       tlen, items_tlo(lws, hop));
-  else
-    hipLaunchKernelGGL(ola_kernel<false>, dim3(dv3_cdiv(L, 256), B), dim3(256), 0, (hipStream_t)stream, frames, y, T, hop, L,
-                       tlen, items_tlo(lws, hop));
-  return dv3_check_launch("overlap_add_items");
+  return overlap_add_items<1024>(frames, y, B, T, hop, tlen, lws, stream);
+}
+extern "C" int dv3_overlap_add_items_f32_n(const float* frames, float* y, int32_t B, int32_t T, int32_t hop,
+                                           const int32_t* tlen, int32_t lws, int32_t n_fft, void* stream) {
+  return with_fft_size("overlap_add_items", n_fft,
+                       [&](auto n) { return overlap_add_items<decltype(n)::value>(frames, y, B, T, hop, tlen, lws, stream); });
 }
 extern "C" int dv3_gl_project_items_f32(const float* y, const float* mag, const float* awin, const float* swin, float* frames,
                                         int32_t B, int32_t T, int32_t hop, const int32_t* tlen, int32_t lws, void* stream) {
-  DV3_REQUIRE(y && mag && frames && tlen && (!lws || (awin && swin)) && B > 0 && T > 1 && hop > 0 && hop <= 1024 &&
-              T >= items_tlo(lws, hop), "gl_project_items: bad arguments");
-  const int TP = (T + 1) / 2;
-  const int L = lws ? lws_len(T, hop) : hop * (T - 1);
-  if (lws)
-    hipLaunchKernelGGL(gl_project2_kernel<true>, dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
-                       frames, T, hop, L, TP, awin, swin, tlen, items_tlo(lws, hop));
-  else
-    hipLaunchKernelGGL(gl_project2_kernel<false>, dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
-                       frames, T, hop, L, TP, (const float*)nullptr, (const float*)nullptr, tlen, items_tlo(lws, hop));
-  return dv3_check_launch("gl_project_items");
+  return gl_project_items<1024>(y, mag, awin, swin, frames, B, T, hop, tlen, lws, stream);
+}
+extern "C" int dv3_gl_project_items_f32_n(const float* y, const float* mag, const float* awin, const float* swin,
+                                          float* frames, int32_t B, int32_t T, int32_t hop, const int32_t* tlen, int32_t lws,
+                                          int32_t n_fft, void* stream) {
+  return with_fft_size("gl_project_items", n_fft, [&](auto n) {
+    return gl_project_items<decltype(n)::value>(y, mag, awin, swin, frames, B, T, hop, tlen, lws, stream);
+  });
 }
 extern "C" int dv3_deemphasis_items_f32(const float* x, float* y, int32_t B, int32_t L, const int32_t* lens, float coef,
                                         void* stream) {
@@ -730,17 +864,35 @@ extern "C" int dv3_item_gain_f32(const float* x, const int64_t* soff, int32_t B,
   return dv3_check_launch("item_gain");
 }
 
+template <int N>
+static int analysis_items(const float* x, const int64_t* soff, const int32_t* foff, int32_t B, int32_t n_frames, int32_t hop,
+                          float preemphasis, const float* awin, const float* gain, const float* mel_basis,
+                          const int32_t* mel_band, int32_t n_mels, float min_level_db, float ref_level_db, float* lin,
+                          float* mel, void* stream) {
+  DV3_REQUIRE(x && soff && foff && awin && B > 0 && n_frames > 0 && hop > 0 && hop <= N && (lin || mel) &&
+              (!mel || (mel_basis && n_mels > 0)) && min_level_db < 0.f, "analysis_items: bad arguments");
+  if (gain)
+    hipLaunchKernelGGL((analysis_items_kernel<N, true>), dim3(n_frames), dim3(256), 0, (hipStream_t)stream, x, soff, foff, B,
+                       hop, preemphasis, awin, gain, mel_basis, mel_band, n_mels, min_level_db, ref_level_db, lin, mel);
+  else
+    hipLaunchKernelGGL((analysis_items_kernel<N, false>), dim3(n_frames), dim3(256), 0, (hipStream_t)stream, x, soff, foff, B,
+                       hop, preemphasis, awin, gain, mel_basis, mel_band, n_mels, min_level_db, ref_level_db, lin, mel);
+  return dv3_check_launch("analysis_items");
+}
 extern "C" int dv3_analysis_items_f32(const float* x, const int64_t* soff, const int32_t* foff, int32_t B,
                                       int32_t n_frames, int32_t hop, float preemphasis, const float* awin,
                                       const float* gain, const float* mel_basis, const int32_t* mel_band, int32_t n_mels,
                                       float min_level_db, float ref_level_db, float* lin, float* mel, void* stream) {
-  DV3_REQUIRE(x && soff && foff && awin && B > 0 && n_frames > 0 && hop > 0 && hop <= 1024 && (lin || mel) &&
-              (!mel || (mel_basis && n_mels > 0)) && min_level_db < 0.f, "analysis_items: bad arguments");
-  if (gain)
-    hipLaunchKernelGGL(analysis_items_kernel<true>, dim3(n_frames), dim3(256), 0, (hipStream_t)stream, x, soff, foff, B,
-                       hop, preemphasis, awin, gain, mel_basis, mel_band, n_mels, min_level_db, ref_level_db, lin, mel);
-  else
-    hipLaunchKernelGGL(analysis_items_kernel<false>, dim3(n_frames), dim3(256), 0, (hipStream_t)stream, x, soff, foff, B,
-                       hop, preemphasis, awin, gain, mel_basis, mel_band, n_mels, min_level_db, ref_level_db, lin, mel);
-  return dv3_check_launch("analysis_items");
+  return analysis_items<1024>(x, soff, foff, B, n_frames, hop, preemphasis, awin, gain, mel_basis, mel_band, n_mels,
+                              min_level_db, ref_level_db, lin, mel, stream);
+}
+extern "C" int dv3_analysis_items_f32_n(const float* x, const int64_t* soff, const int32_t* foff, int32_t B,
+                                        int32_t n_frames, int32_t hop, float preemphasis, const float* awin,
+                                        const float* gain, const float* mel_basis, const int32_t* mel_band, int32_t n_mels,
+                                        float min_level_db, float ref_level_db, float* lin, float* mel, int32_t n_fft,
+                                        void* stream) {
+  return with_fft_size("analysis_items", n_fft, [&](auto n) {
+    return analysis_items<decltype(n)::value>(x, soff, foff, B, n_frames, hop, preemphasis, awin, gain, mel_basis, mel_band, n_mels,
+                               min_level_db, ref_level_db, lin, mel, stream);
+  });
 }

@@ -253,24 +253,28 @@ class WaveformDataset(torch.utils.data.Dataset):
     preprocessed directory.  rows: [(wav path, text[, speaker id])]; items are (text ids, float32 wav[, speaker id]),
     `text_to_sequence` being the caller's text frontend as in PreprocessedDataset.  frame_lengths are the frame counts
     the features will have (audio.lws_num_frames of the sample count in each wav header, read without decoding), so
-    LengthBucketedSampler buckets exactly as it does on the preprocessed train.txt of the same corpus."""
+    LengthBucketedSampler buckets exactly as it does on the preprocessed train.txt of the same corpus.  The framing is
+    hop_size / sample_rate / fft_size, or that of `cfg` (an audio.AudioConfig -- the one waveform_collate is given)."""
 
-    def __init__(self, rows, text_to_sequence, hop_size=256, sample_rate=22050):
+    def __init__(self, rows, text_to_sequence, hop_size=256, sample_rate=22050, fft_size=1024, cfg=None):
         from . import audio, preprocess
+        if cfg is not None:
+            hop_size, sample_rate, fft_size = cfg.hop_size, cfg.sample_rate, cfg.fft_size
+        fft_size = audio.check_fft_size(fft_size)
         self.rows = [tuple(r) for r in rows]
         if not self.rows or len(self.rows[0]) not in (2, 3):
             raise ValueError("WaveformDataset: rows are (wav path, text[, speaker id])")
         self.multi_speaker = len(self.rows[0]) == 3
         self.text_to_sequence, self.sample_rate = text_to_sequence, sample_rate
         self.num_samples = [preprocess.wav_num_samples(r[0]) for r in self.rows]
-        self.frame_lengths = [audio.lws_num_frames(n, hop_size) for n in self.num_samples]
+        self.frame_lengths = [audio.lws_num_frames(n, hop_size, fft_size) for n in self.num_samples]
 
     @classmethod
-    def from_ljspeech(cls, in_dir, text_to_sequence, min_text=20, hop_size=256, sample_rate=22050):
+    def from_ljspeech(cls, in_dir, text_to_sequence, min_text=20, hop_size=256, sample_rate=22050, fft_size=1024, cfg=None):
         """the utterances preprocess.build_from_path would write, in its order (metadata.csv, min_text filter)"""
         from . import preprocess
         return cls([(p, text) for _, p, text in preprocess.read_metadata(in_dir, min_text)], text_to_sequence,
-                   hop_size, sample_rate)
+                   hop_size, sample_rate, fft_size, cfg)
 
     def __len__(self):
         return len(self.rows)

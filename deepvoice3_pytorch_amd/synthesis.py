@@ -27,12 +27,20 @@ from . import audio
 from .decode_program import RollingSchedule, item_stops
 
 
+def check_linear_dim(model, audio_cfg, what):
+    """the model's linear_dim must be the audio config's fft_size // 2 + 1 (513 at 1024, 257 at 512, 1025 at 2048):
+    refused here, once, with both numbers, instead of inside Griffin-Lim after the decode"""
+    cfg = audio_cfg or audio.AudioConfig()
+    audio.check_bins(model.linear_dim, cfg.fft_size, "%s: model.linear_dim = %d" % (what, model.linear_dim))
+
+
 def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None):
     """sequences: a list of int id sequences (one per utterance); speaker_ids: None or one id per utterance.
     -> a list of (mel (T_b, mel_dim), linear (T_b * upsampling, linear_dim), alignment (steps_b, Tt_b), wav (L_b,)),
     device tensors, each trimmed to its own utterance."""
     if len(sequences) == 0:
         return []
+    check_linear_dim(model, audio_cfg, "tts_batch")
     dev = next(model.parameters()).device
     lengths = [len(s) for s in sequences]
     if min(lengths) < 1:
@@ -82,6 +90,7 @@ class RollingSynthesizer(object):
         if not hasattr(self.dec, "slot_program"):
             raise RuntimeError("RollingSynthesizer: %r has no slot-mode step program" % type(self.dec))
         self.prog = self.dec.slot_program(slots, self.max_text_len)
+        check_linear_dim(model, audio_cfg, "RollingSynthesizer")     # retirement ends in Griffin-Lim on audio_cfg's framing
         self.schedule = RollingSchedule(slots, chunk)
         self.min_steps = int(self.dec.min_decoder_steps)
         self.max_steps = int(self.dec.max_decoder_steps)        # = the program's t_cap - 1

@@ -419,18 +419,18 @@ _lib.impl("fused_clip_adam", _fused_clip_adam, "CUDA")
 # ------------------------------------------------------------------------------------------------------------------
 # audio.inv_spectrogram's phase reconstruction (audio.py:37-43; csrc/audio.hip): magnitudes (B, T, n_fft/2+1)
 # ------------------------------------------------------------------------------------------------------------------
-_lib.define("griffin_lim(Tensor mag, int hop, int n_iter) -> Tensor")
-_lib.define("istft(Tensor mag, Tensor phasor, int hop) -> Tensor")
+_lib.define("griffin_lim(Tensor mag, int hop, int n_iter, int n_fft=1024) -> Tensor")
+_lib.define("istft(Tensor mag, Tensor phasor, int hop, int n_fft=1024) -> Tensor")
 
 
-def _griffin_lim(mag, hop, n_iter):
+def _griffin_lim(mag, hop, n_iter, n_fft=1024):
     from . import audio
-    return audio.griffin_lim(mag, hop, n_iter)
+    return audio.griffin_lim(mag, hop, n_iter, fft_size=n_fft)
 
 
-def _istft(mag, phasor, hop):
+def _istft(mag, phasor, hop, n_fft=1024):
     from . import audio
-    return audio.istft(mag, phasor, hop)
+    return audio.istft(mag, phasor, hop, fft_size=n_fft)
 
 
 _lib.impl("griffin_lim", _griffin_lim, "CUDA")

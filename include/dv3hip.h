@@ -30,7 +30,7 @@ extern "C" {
 #define DV3_ELAUNCH (-2)  /* hipLaunch / runtime error        */
 
 /* ABI version, bumped on any struct change; checked by the Python loader. */
-#define DV3_ABI_VERSION 48
+#define DV3_ABI_VERSION 49
 int dv3_abi_version(void);
 const char* dv3_last_error(void);
 /* Fills name (<=255 chars) of device `dev`, number of CUs; returns 0/err. */
@@ -838,21 +838,44 @@ int dv3_decode_slots_reset(const dv3_decode_program* prog, const int32_t* slots,
  *   frames  [B][T][1024]     windowed time-domain frames
  *   y       [B][L]
  * One Griffin-Lim iteration = istft_frames -> overlap_add -> stft_phase, or fused: gl_project -> overlap_add.
+ *
+ * Frame size (ABI 49).  The entry points above and below that take no n_fft frame by 1024 (every reference preset).
+ * Each of them has a sibling named with the suffix `_n` that takes `int32_t n_fft` in front of `stream` and frames
+ * by it: n_fft = 512, 1024 or 2048 (DV3_EINVAL and a message for any other value, before anything is launched; 4096
+ * would need 96 KB of LDS per workgroup and another kernel shape).  A sibling at n_fft = 1024 is its parent, bit for
+ * bit.  Every "1024" of the parent's description reads n_fft and every "513" reads n_fft/2 + 1:
+ *   mag [B][T][n_fft/2 + 1], phasor [B][T][n_fft/2 + 1][2], frames [B][T][n_fft], awin / swin [n_fft],
+ *   hop <= n_fft, L = hop * (T - 1) > n_fft/2 on the torch framing (the reflect padding),
+ *   L = (T + 1) * hop - n_fft > 0 samples on the lws framing, frame t starting at sample t * hop - (n_fft - hop).
+ * The transform is an in-LDS Stockham FFT of 256 threads per frame: radix-4 passes, closed at 512 = 2 * 4^4 and
+ * 2048 = 2 * 4^5 by one radix-2 pass.
  * ------------------------------------------------------------------------------------ */
 /* mag = (10^((clip(x,0,1)*(-min_db) + min_db + ref_db)/20))^power   audio.py:39-41,84-93 */
 int dv3_gl_prepare_f32(const float* lin, float* mag, int64_t n, float min_level_db,
                        float ref_level_db, float power, void* stream);
 int dv3_istft_frames_f32(const float* mag, const float* phasor /* NULL: zero phase */,
                          float* frames, int32_t B, int32_t T, void* stream);
+/* mag [B][T][n_fft/2 + 1], phasor [B][T][n_fft/2 + 1][2], frames [B][T][n_fft] */
+int dv3_istft_frames_f32_n(const float* mag, const float* phasor /* NULL: zero phase */,
+                           float* frames, int32_t B, int32_t T, int32_t n_fft, void* stream);
 int dv3_overlap_add_f32(const float* frames, float* y, int32_t B, int32_t T, int32_t hop,
                         void* stream);
+/* frames [B][T][n_fft] -> y [B][hop * (T - 1)], hop <= n_fft */
+int dv3_overlap_add_f32_n(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, int32_t n_fft,
+                          void* stream);
 /* one Griffin-Lim projection, fused: frames = istft_frames(mag, phase(stft(y))) without storing the phasors */
 int dv3_gl_project_f32(const float* y, const float* mag, float* frames, int32_t B, int32_t T, int32_t hop,
                        void* stream);
+/* y [B][hop * (T - 1)] (longer than n_fft/2), mag [B][T][n_fft/2 + 1] -> frames [B][T][n_fft] */
+int dv3_gl_project_f32_n(const float* y, const float* mag, float* frames, int32_t B, int32_t T, int32_t hop,
+                         int32_t n_fft, void* stream);
 /* outputs (each may be NULL): phasor, spec = the complex STFT [B][T][513][2], mag_bct = |STFT|
  * as [B][513][T] (the channel-major operand of the mel filterbank GEMM)                     */
 int dv3_stft_phase_f32(const float* y, float* phasor, float* spec, float* mag_bct, int32_t B,
                        int32_t T, int32_t hop, void* stream);
+/* y [B][hop * (T - 1)] (longer than n_fft/2) -> phasor, spec [B][T][n_fft/2 + 1][2], mag_bct [B][n_fft/2 + 1][T] */
+int dv3_stft_phase_f32_n(const float* y, float* phasor, float* spec, float* mag_bct, int32_t B,
+                         int32_t T, int32_t hop, int32_t n_fft, void* stream);
 /* Forward analysis (audio.py:21-23,31-35,46-51,79-89): preemphasis, then dv3_stft_phase_f32
  * (mag_bct), the mel filterbank as a 1x1 tap-GEMM (dv3_conv_gemm_f32, M = num_mels, Cin = 513),
  * then amplitude -> dB -> [0,1] normalisation.                                              */
@@ -881,6 +904,17 @@ int dv3_lws_istft_frames_f32(const float* mag, const float* phasor /* NULL: zero
 int dv3_lws_overlap_add_f32(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, void* stream);
 int dv3_lws_gl_project_f32(const float* y, const float* mag, const float* awin, const float* swin, float* frames, int32_t B,
                            int32_t T, int32_t hop, void* stream);
+/* The siblings on `lws.lws(n_fft, hop)`: awin / swin [n_fft] (audio.py: lws_windows(device, hop, scale, n_fft)), n_fft - hop
+ * zeros of padding on both sides, T frames cover L <= (T + 1) * hop - n_fft samples (and more than T - 1 frames do),
+ * n_fft/2 + 1 bins, frames [B][T][n_fft]; overlap-add and gl_project work on y [B][(T + 1) * hop - n_fft], which must be
+ * positive. */
+int dv3_lws_stft_f32_n(const float* y, const float* awin, float* phasor, float* spec, float* mag_bct, int32_t B, int32_t T,
+                       int32_t hop, int32_t L, int32_t n_fft, void* stream);
+int dv3_lws_istft_frames_f32_n(const float* mag, const float* phasor /* NULL: zero phase */, const float* swin, float* frames,
+                               int32_t B, int32_t T, int32_t n_fft, void* stream);
+int dv3_lws_overlap_add_f32_n(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, int32_t n_fft, void* stream);
+int dv3_lws_gl_project_f32_n(const float* y, const float* mag, const float* awin, const float* swin, float* frames, int32_t B,
+                             int32_t T, int32_t hop, int32_t n_fft, void* stream);
 
 /* ABI 44 (per-utterance synthesis): the same inverse on a batch padded to T frames whose item b has only tlen[b] frames
  * (device int32[B]); lws = 1: the lws framing (swin / awin as above), 0: the torch framing.  Item b uses its own frames,
@@ -894,6 +928,16 @@ int dv3_overlap_add_items_f32(const float* frames, float* y, int32_t B, int32_t 
                               int32_t lws, void* stream);
 int dv3_gl_project_items_f32(const float* y, const float* mag, const float* awin, const float* swin, float* frames,
                              int32_t B, int32_t T, int32_t hop, const int32_t* tlen, int32_t lws, void* stream);
+/* The siblings at n_fft: n_fft/2 + 1 bins, frames [B][T][n_fft], L_b = (tlen[b] + 1) * hop - n_fft on the lws framing or
+ * hop * (tlen[b] - 1) on the torch one; the fewest frames are the fewest with L_b > 0 (lws) or L_b > n_fft/2 (torch). */
+int dv3_gl_istft_items_f32_n(const float* mag, const float* phasor /* NULL: zero phase */, const float* swin, float* frames,
+                             int32_t B, int32_t T, int32_t hop, const int32_t* tlen, int32_t lws, int32_t n_fft,
+                             void* stream);
+int dv3_overlap_add_items_f32_n(const float* frames, float* y, int32_t B, int32_t T, int32_t hop, const int32_t* tlen,
+                                int32_t lws, int32_t n_fft, void* stream);
+int dv3_gl_project_items_f32_n(const float* y, const float* mag, const float* awin, const float* swin, float* frames,
+                               int32_t B, int32_t T, int32_t hop, const int32_t* tlen, int32_t lws, int32_t n_fft,
+                               void* stream);
 /* de-emphasis of row b over its own first lens[b] samples (device int32[B]); the rest of the row is written as zeros */
 int dv3_deemphasis_items_f32(const float* x, float* y, int32_t B, int32_t L, const int32_t* lens, float coef,
                              void* stream);
@@ -919,6 +963,12 @@ int dv3_analysis_items_f32(const float* x, const int64_t* soff, const int32_t* f
                            int32_t hop, float preemphasis, const float* awin, const float* gain, const float* mel_basis,
                            const int32_t* mel_band, int32_t n_mels, float min_level_db, float ref_level_db, float* lin,
                            float* mel, void* stream);
+/* The sibling at n_fft: T_b = ceil((L_b + n_fft - 2 hop) / hop) + 1 frames, awin [n_fft], mel_basis [n_mels][n_fft/2 + 1],
+ * mel_band clamped into [0, n_fft/2 + 1], lin [n_frames][n_fft/2 + 1]; n_fft - hop zeros in front of each item. */
+int dv3_analysis_items_f32_n(const float* x, const int64_t* soff, const int32_t* foff, int32_t B, int32_t n_frames,
+                             int32_t hop, float preemphasis, const float* awin, const float* gain, const float* mel_basis,
+                             const int32_t* mel_band, int32_t n_mels, float min_level_db, float ref_level_db, float* lin,
+                             float* mel, int32_t n_fft, void* stream);
 /* hparams.rescaling (ljspeech.py:59-60): gain[b] = rescaling_max / m_b in fp32 (one correctly rounded division),
  * m_b = max |x[i]| over item b's samples; gain[b] = 1 when m_b = 0.  The reference scales as (x / m_b) * rescaling_max;
  * here x * gain[b] (dv3_analysis_items_f32), which differs from it by at most an ulp or two per sample. */
