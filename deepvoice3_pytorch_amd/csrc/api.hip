@@ -254,6 +254,7 @@ extern "C" int dv3_sizeof(const char* name) {
   DV3_SZ(dv3_softmax_desc);
   DV3_SZ(dv3_softmax_bwd_desc);
   DV3_SZ(dv3_spec_loss_desc);
+  DV3_SZ(dv3_spec_items_desc);
   DV3_SZ(dv3_wn_multi_entry);
   DV3_SZ(dv3_conv_step_desc);
   DV3_SZ(dv3_attn_step_desc);

@@ -216,6 +216,12 @@ __global__ __launch_bounds__(256) void spec_loss_finish_kernel(const dv3_spec_lo
 }
 
 // ---- guided attention ---------------------------------------------------------------------
+// W[t][n] of an item with N keys and T decoder steps; train.py:585-591 evaluates this in float64 and stores float32
+__device__ __forceinline__ float guided_w(int nk, int t, int N, int T, double inv2g2) {
+  const double dlt = (double)nk / (double)N - (double)t / (double)T;
+  return (float)(1.0 - exp(-dlt * dlt * inv2g2));
+}
+
 __global__ __launch_bounds__(256) void guided_attn_kernel(const float* __restrict__ attn,
                                                           const int32_t* __restrict__ in_len,
                                                           const int32_t* __restrict__ out_len,
@@ -236,12 +242,7 @@ __global__ __launch_bounds__(256) void guided_attn_kernel(const float* __restric
     const int64_t bt = i / Tk;
     const int t = (int)(bt % Tq), b = (int)(bt / Tq);
     const int N = in_len[b], T = out_len[b];
-    float w = 0.f;
-    if (nk < N && t < T) {
-      // train.py:585-591 evaluates this in float64 and stores float32
-      const double dlt = (double)nk / (double)N - (double)t / (double)T;
-      w = (float)(1.0 - exp(-dlt * dlt * inv2g2));
-    }
+    const float w = (nk < N && t < T) ? guided_w(nk, t, N, T, inv2g2) : 0.f;
     for (int l = 0; l < L; ++l) {
       acc[0] += attn[(int64_t)l * per + i] * w;
       if (dattn) dattn[(int64_t)l * per + i] = gscale * w * inv_n;
@@ -273,6 +274,11 @@ __global__ __launch_bounds__(256) void sum_finish_kernel(const float* __restrict
 }
 
 // ---- BCE (nn.BCELoss, mean; log clamped at -100 as torch does) ------------------------------
+__device__ __forceinline__ float bce_elem(float x, float y) {
+  const float lx = fmaxf(logf(x), -100.f), l1x = fmaxf(logf(1.f - x), -100.f);
+  return -(y * lx + (1.f - y) * l1x);
+}
+
 __global__ __launch_bounds__(256) void bce_kernel(const float* __restrict__ p,
                                                   const float* __restrict__ t,
                                                   float* __restrict__ dp, float* __restrict__ scratch,
@@ -289,11 +295,124 @@ __global__ __launch_bounds__(256) void bce_kernel(const float* __restrict__ p,
       continue;
     }
     const float x = p[i], y = t[i];
-    const float lx = fmaxf(logf(x), -100.f), l1x = fmaxf(logf(1.f - x), -100.f);
-    acc[0] += -(y * lx + (1.f - y) * l1x);
+    acc[0] += bce_elem(x, y);
     if (dp) dp[i] = gscale * inv_n * (x - y) / fmaxf((1.f - x) * x, 1e-12f);
   }
   block_reduce4(acc, scratch + (int64_t)blockIdx.x * 4);
+}
+
+
+// ---- per-item sums (held-out evaluation: train_step.Trainer.evaluate) -------------------------
+// Forward only, one fp32 row per batch item: the masked sums the batch kernels above fold into one mean, kept apart per
+// item, of the SAME fp32 terms (spec_bd, bce_elem, guided_w).  Grid = (slices, items): the item's OWN frames are cut
+// into gridDim.x equal slices, so a long item is spread over as many workgroups as a short one and no workgroup walks
+// padding.  Slice partial sums go to scratch[(b * slices + s) * 4], the finishing pass adds them in slice order.
+constexpr int kItemSliceFrames = 64, kItemMaxSlices = 64;
+
+inline int item_slices(int T) {
+  const int s = dv3_cdiv(T, kItemSliceFrames);
+  return s < 1 ? 1 : (s > kItemMaxSlices ? kItemMaxSlices : s);
+}
+
+__device__ __forceinline__ int clamp_len(int l, int cap) { return l < 0 ? 0 : (l > cap ? cap : l); }
+
+// frames [t0, t1) of this workgroup's slice of an item with n frames
+__device__ __forceinline__ void item_slice(int n, int& t0, int& t1) {
+  const int per = (n + (int)gridDim.x - 1) / (int)gridDim.x;
+  t0 = min((int)blockIdx.x * per, n);
+  t1 = min(t0 + per, n);
+}
+
+// {sum |y_hat - y|, sum z} over the item's frames t < lengths[b] - r (the batch kernels' mask, (t + r) < lengths[b])
+template <bool FAST>
+__global__ __launch_bounds__(kLossBlock) void spec_items_kernel(const dv3_spec_items_desc p) {
+  const int b = blockIdx.y, D = p.D;
+  int t0, t1;
+  item_slice(clamp_len(p.lengths[b] - p.r, p.T - p.r), t0, t1);
+  const int nt = t1 - t0;
+  const int n = nt * D;                 // (the launcher refuses shapes whose slices hold 2^31 elements)
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};  // l1, z
+  // the faster-varying axis of y_hat innermost, as spec_loss_kernel: with a time-fastest prediction the bin-fastest
+  // target is read at a D-element stride (the pattern the batch path left for its tiled kernel; cost: DESIGN.md 3.7a)
+  const bool t_fast = p.yh_ts < p.yh_ds;
+  for (int i = threadIdx.x; i < n; i += kLossBlock) {
+    int dd, t;
+    if (t_fast) {
+      t = t0 + i % nt;
+      dd = i / nt;
+    } else {
+      dd = i % D;
+      t = t0 + i / D;
+    }
+    const float yh = p.y_hat[b * p.yh_bs + t * p.yh_ts + dd * p.yh_ds];
+    const float y = p.y[b * p.y_bs + (int64_t)(t + p.r) * p.y_ts + dd * p.y_ds];
+    const float diff = yh - y;
+    acc[0] += fabsf(diff);
+    float z, dz;
+    spec_bd<FAST>(yh, y, z, dz);
+    acc[1] += z;
+  }
+  block_reduce4(acc, p.scratch + ((int64_t)b * gridDim.x + blockIdx.x) * 4);
+}
+
+__global__ __launch_bounds__(256) void bce_items_kernel(const float* __restrict__ p, const float* __restrict__ t,
+                                                        const int32_t* __restrict__ lengths,
+                                                        float* __restrict__ scratch, int T) {
+  const int b = blockIdx.y;
+  int t0, t1;
+  item_slice(clamp_len(lengths[b], T), t0, t1);
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int i = t0 + threadIdx.x; i < t1; i += 256) acc[0] += bce_elem(p[(int64_t)b * T + i], t[(int64_t)b * T + i]);
+  block_reduce4(acc, scratch + ((int64_t)b * gridDim.x + blockIdx.x) * 4);
+}
+
+__global__ __launch_bounds__(256) void guided_attn_items_kernel(const float* __restrict__ attn,
+                                                                const int32_t* __restrict__ in_len,
+                                                                const int32_t* __restrict__ out_len,
+                                                                float* __restrict__ scratch, int L, int B, int Tq,
+                                                                int Tk, float g) {
+  const int b = blockIdx.y;
+  const int N = in_len[b], T = out_len[b];
+  const int Nc = clamp_len(N, Tk);            // the item's own keys and decoder steps, inside the tensor
+  int t0, t1;
+  item_slice(clamp_len(T, Tq), t0, t1);
+  const int n = (t1 - t0) * Nc;
+  const int64_t per = (int64_t)B * Tq * Tk;
+  const double inv2g2 = 1.0 / (2.0 * (double)g * (double)g);
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int nk = i % Nc, t = t0 + i / Nc;
+    const float w = guided_w(nk, t, N, T, inv2g2);
+    const int64_t at = ((int64_t)b * Tq + t) * Tk + nk;
+    for (int l = 0; l < L; ++l) acc[0] += attn[(int64_t)l * per + at] * w;
+  }
+  block_reduce4(acc, scratch + ((int64_t)b * gridDim.x + blockIdx.x) * 4);
+}
+
+// out[b] = {the first n_sums slice sums of item b, added in slice order; its element count}, one thread per item.
+// count = mult * clamp(len_a[b] - sub_a, 0, cap_a) [* clamp(len_b[b], 0, cap_b)]
+__global__ __launch_bounds__(256) void items_finish_kernel(const float* __restrict__ scratch, int B, int slices,
+                                                           int n_sums, float* __restrict__ out,
+                                                           const int32_t* __restrict__ len_a, int sub_a, int cap_a,
+                                                           const int32_t* __restrict__ len_b, int cap_b,
+                                                           int64_t mult) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  float acc[2] = {0.f, 0.f};
+  for (int s = 0; s < slices; ++s)
+    for (int k = 0; k < n_sums; ++k) acc[k] += scratch[((int64_t)b * slices + s) * 4 + k];
+  int64_t cnt = mult * clamp_len(len_a[b] - sub_a, cap_a);
+  if (len_b) cnt *= clamp_len(len_b[b], cap_b);
+  float* row = out + (int64_t)b * (n_sums + 1);
+  for (int k = 0; k < n_sums; ++k) row[k] = acc[k];
+  row[n_sums] = (float)cnt;         // exact up to 2^24 elements per item (include/dv3hip.h)
+}
+
+// the layouts the tiled spectrogram kernel serves (time-fastest prediction, bin-fastest target); the per-item kernel
+// takes its logarithms the way the batch kernel of the same layouts does
+template <class Desc>
+inline bool spec_time_fast(const Desc& d) {
+  return d.yh_ts == 1 && d.y_ds == 1 && d.yh_ds > 1 && d.y_ts > 1 && (int64_t)d.B * d.yh_bs < (1ll << 40);
 }
 
 inline int loss_blocks(int64_t n) {
@@ -322,7 +441,7 @@ extern "C" int dv3_spec_loss_f32(const dv3_spec_loss_desc* d, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = (int64_t)d->B * (d->T - d->r) * d->D;
   int nb = loss_blocks(n);
-  if (d->yh_ts == 1 && d->y_ds == 1 && d->yh_ds > 1 && d->y_ts > 1 && (int64_t)d->B * d->yh_bs < (1ll << 40)) {
+  if (spec_time_fast(*d)) {
     // time-fastest prediction against a bin-fastest target: the tiled form
     const int t_tiles = dv3_cdiv(d->T - d->r, 64), d_tiles = dv3_cdiv(d->D, 64);
     const int64_t nt = (int64_t)d->B * t_tiles * d_tiles;
@@ -394,4 +513,55 @@ extern "C" int dv3_bce_loss_valid_f32(const float* p, const float* t, float* dp,
   hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(256), 0, st, scratch, nb, 0.f, out1, t_valid, (int)T,
                      (const int32_t*)nullptr, 0, rows);
   return dv3_check_launch("bce_loss_valid_f32");
+}
+
+// ---- per-item sums ------------------------------------------------------------------------------
+extern "C" int dv3_loss_items_scratch_floats(int32_t B, int32_t T) {
+  if (B <= 0 || T <= 0) return 0;
+  return (int)((int64_t)4 * B * item_slices(T));
+}
+
+extern "C" int dv3_spec_loss_items_f32(const dv3_spec_items_desc* d, void* stream) {
+  DV3_REQUIRE(d && d->y_hat && d->y && d->lengths && d->out && d->scratch, "spec_loss_items: null pointer");
+  DV3_REQUIRE(d->B > 0 && d->B <= 65535 && d->D > 0 && d->r >= 0 && d->T > 0, "spec_loss_items: bad dims");
+  hipStream_t st = (hipStream_t)stream;
+  const int Tr = d->T > d->r ? d->T - d->r : 0;      // no frame takes part in a tensor of r frames or fewer: rows of zeros
+  const int S = Tr > 0 ? item_slices(Tr) : 0;
+  if (S > 0) {
+    DV3_REQUIRE((int64_t)dv3_cdiv(Tr, S) * d->D < (1ll << 31), "spec_loss_items: slice too large");
+    if (spec_time_fast(*d) && g_loss_fast_log)
+      hipLaunchKernelGGL(spec_items_kernel<true>, dim3(S, d->B), dim3(kLossBlock), 0, st, *d);
+    else
+      hipLaunchKernelGGL(spec_items_kernel<false>, dim3(S, d->B), dim3(kLossBlock), 0, st, *d);
+  }
+  hipLaunchKernelGGL(items_finish_kernel, dim3(dv3_cdiv(d->B, 256)), dim3(256), 0, st, (const float*)d->scratch, (int)d->B,
+                     S, 2, d->out, d->lengths, (int)d->r, Tr, (const int32_t*)nullptr, 0, (int64_t)d->D);
+  return dv3_check_launch("spec_loss_items_f32");
+}
+
+extern "C" int dv3_bce_loss_items_f32(const float* p, const float* t, const int32_t* lengths, float* out,
+                                      float* scratch, int32_t B, int32_t T, void* stream) {
+  DV3_REQUIRE(p && t && lengths && out && scratch, "bce_loss_items: null pointer");
+  DV3_REQUIRE(B > 0 && B <= 65535 && T > 0, "bce_loss_items: bad dims");
+  hipStream_t st = (hipStream_t)stream;
+  const int S = item_slices(T);
+  hipLaunchKernelGGL(bce_items_kernel, dim3(S, B), dim3(256), 0, st, p, t, lengths, scratch, (int)T);
+  hipLaunchKernelGGL(items_finish_kernel, dim3(dv3_cdiv(B, 256)), dim3(256), 0, st, (const float*)scratch, (int)B, S, 1,
+                     out, lengths, 0, (int)T, (const int32_t*)nullptr, 0, (int64_t)1);
+  return dv3_check_launch("bce_loss_items_f32");
+}
+
+extern "C" int dv3_guided_attn_loss_items_f32(const float* attn, const int32_t* in_len, const int32_t* out_len,
+                                              float* out, float* scratch, int32_t L, int32_t B, int32_t Tq,
+                                              int32_t Tk, float g, void* stream) {
+  DV3_REQUIRE(attn && in_len && out_len && out && scratch, "guided_attn_items: null pointer");
+  DV3_REQUIRE(L > 0 && B > 0 && B <= 65535 && Tq > 0 && Tk > 0 && g > 0.f, "guided_attn_items: bad dims");
+  hipStream_t st = (hipStream_t)stream;
+  const int S = item_slices(Tq);
+  DV3_REQUIRE((int64_t)dv3_cdiv(Tq, S) * Tk < (1ll << 31), "guided_attn_items: slice too large");
+  hipLaunchKernelGGL(guided_attn_items_kernel, dim3(S, B), dim3(256), 0, st, attn, in_len, out_len, scratch, (int)L,
+                     (int)B, (int)Tq, (int)Tk, g);
+  hipLaunchKernelGGL(items_finish_kernel, dim3(dv3_cdiv(B, 256)), dim3(256), 0, st, (const float*)scratch, (int)B, S, 1,
+                     out, out_len, 0, (int)Tq, in_len, (int)Tk, (int64_t)L);
+  return dv3_check_launch("guided_attn_loss_items_f32");
 }

@@ -37,6 +37,7 @@ _softmax_desc = STRUCTS["dv3_softmax_desc"]
 _softmax_bwd_desc = STRUCTS["dv3_softmax_bwd_desc"]
 _attn_fwd_desc = STRUCTS["dv3_attn_fwd_desc"]
 _spec_loss_desc = STRUCTS["dv3_spec_loss_desc"]
+_spec_items_desc = STRUCTS["dv3_spec_items_desc"]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -2452,6 +2453,63 @@ class BCELossFn(torch.autograd.Function):
 
 def bce_loss(p, t, t_valid=None):
     return BCELossFn.apply(p, t, t_valid)
+
+
+# per-item sums (held-out evaluation, train_step.Trainer.evaluate): forward only, no part in autograd.  One fp32 row per
+# batch item -- the masked sums the batch losses above fold into one mean, of the same fp32 terms (include/dv3hip.h)
+def _items_scratch(B, T, device):
+    return torch.empty(_lib.lib().dv3_loss_items_scratch_floats(B, T), dtype=torch.float32, device=device)
+
+
+def spec_loss_items(y_hat, y, lengths, r=1):
+    """y_hat, y: logical (B, T, D) as spec_loss takes them; lengths int32[B] on the device
+    -> (B, 3) = {sum |y_hat[:, t] - y[:, t + r]|, sum z, n_b * D} over t < n_b = max(lengths[b] - r, 0)"""
+    y_hat, y = _dense_or_copy(_chk(y_hat.detach(), "y_hat")), _dense_or_copy(_chk(y, "y"))
+    _chk(lengths, "lengths", torch.int32)
+    B, T, D = y_hat.shape
+    if tuple(y.shape) != (B, T, D) or lengths.numel() != B:
+        raise RuntimeError("spec_loss_items: y %s / %d lengths do not fit y_hat %s" % (
+            tuple(y.shape), lengths.numel(), (B, T, D)))
+    out = torch.empty(B, 3, dtype=torch.float32, device=y_hat.device)
+    scratch = _items_scratch(B, T, y_hat.device)
+    d = _spec_items_desc()
+    d.y_hat, d.y, d.lengths = y_hat.data_ptr(), y.data_ptr(), _c(lengths).data_ptr()
+    d.yh_bs, d.yh_ts, d.yh_ds = y_hat.stride()
+    d.y_bs, d.y_ts, d.y_ds = y.stride()
+    d.out, d.scratch = out.data_ptr(), scratch.data_ptr()
+    d.B, d.T, d.D, d.r = B, T, D, int(r)
+    _lib.call("dv3_spec_loss_items_f32", ctypes.byref(d), _stream())
+    return out
+
+
+def bce_loss_items(p, t, lengths):
+    """p, t: (B, T) or (B, T, 1) -> (B, 2) = {sum over t < lengths[b] of the BCELoss element, lengths[b]}"""
+    p, t = _c(_chk(p.detach(), "p")), _c(_chk(t, "t"))
+    _chk(lengths, "lengths", torch.int32)
+    B = p.shape[0]
+    T = p.numel() // max(B, 1)
+    if p.dim() < 2 or p.shape[1] != T or t.shape != p.shape or lengths.numel() != B:
+        raise RuntimeError("bce_loss_items: (B, T) or (B, T, 1) tensors and B lengths")
+    out = torch.empty(B, 2, dtype=torch.float32, device=p.device)
+    scratch = _items_scratch(B, T, p.device)
+    _lib.call("dv3_bce_loss_items_f32", p.data_ptr(), t.data_ptr(), _c(lengths).data_ptr(), out.data_ptr(),
+              scratch.data_ptr(), B, T, _stream())
+    return out
+
+
+def guided_attention_loss_items(attn, in_len, out_len, g=0.2):
+    """attn (L, B, Tq, Tk); in_len, out_len int32[B] -> (B, 2) = {sum_{l, t < T_b, n < N_b} attn * W, L * T_b * N_b}"""
+    attn = _c(_chk(attn.detach(), "attn"))
+    _chk(in_len, "in_len", torch.int32)
+    _chk(out_len, "out_len", torch.int32)
+    L, B, Tq, Tk = attn.shape
+    if in_len.numel() != B or out_len.numel() != B:
+        raise RuntimeError("guided_attention_loss_items: %d lengths for a batch of %d" % (in_len.numel(), B))
+    out = torch.empty(B, 2, dtype=torch.float32, device=attn.device)
+    scratch = _items_scratch(B, Tq, attn.device)
+    _lib.call("dv3_guided_attn_loss_items_f32", attn.data_ptr(), _c(in_len).data_ptr(), _c(out_len).data_ptr(),
+              out.data_ptr(), scratch.data_ptr(), L, B, Tq, Tk, float(g), _stream())
+    return out
 
 
 # ----------------------------------------------------------------------------------------------

@@ -477,6 +477,109 @@ Please set a larger value for ``max_position`` in hyper parameters.""".format(ma
             ops.SideStream.stream = ops.SideStream.main = None
         return {k: v.detach() for k, v in scal.items()}
 
+    # ------------------------------------------------------------------------------------
+    def evaluate(self, batch):
+        """Held-out evaluation of one batch: the model's eval-mode (dropout off), teacher-forced forward on the batch as
+        collated -- the reference's `model.eval(); model(x, mel, ...)` -- and its losses, without gradients.  -> a dict
+        of device tensors: the batch scalars under the keys step() uses (the existing loss kernels with this trainer's
+        TrainConfig weights), and "items", a (B, len(EVAL_ITEM_COLUMNS)) fp32 table of per-utterance masked sums and
+        counts (ops.*_items; columns of a part that did not run are zero) for EvalTotals.
+        Training is left as it is: parameters, gradients, moments, step counters, the hyper ring and the dropout state
+        (seed, site numbering, step counter, planned masks) are not touched and model.training is restored, so the
+        call may sit between two steps or two replays of a GraphedTrainer / LatticeReplay.  Eager launches on the
+        current stream; not capturable."""
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("Trainer.evaluate: called while a stream capture is in progress (evaluation runs eagerly, "
+                               "between steps)")
+        self.check_lengths(batch)
+        s2s, pn = self.train_seq2seq, self.train_postnet
+        modes = [(m, m.training) for m in self.model.modules()]
+        self.model.eval()
+        mel_out = lin_out = attn = done_hat = None
+        try:
+            with torch.no_grad():
+                ops.valid = getattr(batch, "valid", None)
+                try:
+                    if s2s and pn:
+                        mel_out, lin_out, attn, done_hat = self.model(
+                            batch.text, batch.mel, speaker_ids=batch.speaker_ids, text_positions=batch.text_positions,
+                            frame_positions=batch.frame_positions, input_lengths=batch.input_lengths)
+                    elif s2s:
+                        assert batch.speaker_ids is None
+                        mel_out, attn, done_hat, _ = self.model.seq2seq(
+                            batch.text, batch.mel, text_positions=batch.text_positions,
+                            frame_positions=batch.frame_positions, input_lengths=batch.input_lengths)
+                        mel_out = mel_out.reshape(batch.mel.size(0), -1, batch.mel.size(-1))
+                    else:
+                        assert batch.speaker_ids is None
+                        lin_out = self.model.postnet(batch.mel)
+                finally:
+                    ops.valid = None
+                return self._eval_losses(batch, mel_out, lin_out, attn, done_hat)
+        finally:
+            # every module's own flag back, as it was (train(mode) would set the whole tree to one value); assigning the
+            # attribute is all nn.Module.train() does per module -- no module of the package overrides train()
+            for m, flag in modes:
+                m.training = flag
+
+    def eval_scalar_keys(self):
+        """the names of the batch scalars evaluate() returns with this trainer's modes (EvalTotals(scalar_keys=))"""
+        keys = ["loss"]
+        if self.train_seq2seq:
+            keys += ["mel_l1_loss", "mel_binary_div_loss", "mel_loss", "done_loss"]
+            if self.cfg.use_guided_attention:
+                keys.append("attn_loss")
+        if self.train_postnet:
+            keys += ["linear_l1_loss", "linear_binary_div_loss", "linear_loss"]
+        return tuple(sorted(keys))
+
+    def _eval_losses(self, batch, mel_out, lin_out, attn, done_hat):
+        """the loss block of forward_backward's non-fused path, value only, plus the per-item table"""
+        c = self.cfg
+        r, wm, w = c.outputs_per_step, c.masked_loss_weight, c.binary_divergence_weight
+        vl = getattr(batch, "valid", None)
+        v_mel, v_lin, v_dec, v_in = (vl.tv[2:3], vl.tv[3:4], vl.tv[1:2], vl.tv[0:1]) if vl is not None else (None,) * 4
+        B = batch.text.size(0)
+        zeros = lambda k: torch.zeros(B, k, dtype=torch.float32, device=self.device)
+        scal, terms = {}, []
+        mel_i, lin_i, done_i, attn_i = zeros(3), zeros(3), zeros(2), zeros(2)
+        if mel_out is not None:
+            m4 = ops.spec_loss(mel_out, batch.mel, batch.decoder_lengths if wm > 0 else None, r, wm, w, v_mel)
+            done_loss = ops.bce_loss(done_hat, batch.done, v_dec)
+            scal.update(mel_l1_loss=m4[0], mel_binary_div_loss=m4[1], mel_loss=m4[2])
+            terms.append(m4[2])
+            mel_i = ops.spec_loss_items(mel_out, batch.mel, batch.decoder_lengths, r)
+            done_i = ops.bce_loss_items(done_hat, batch.done, batch.decoder_lengths)
+        if lin_out is not None:
+            lin_len = batch.linear_mask_lengths if wm > 0 else None
+            l4 = ops.spec_loss(lin_out, batch.y, lin_len, r, wm, w, v_lin)
+            lin_loss = l4[2]
+            if c.priority_freq_weight > 0:       # train.py:562-569, as forward_backward
+                n_pri = int(c.priority_freq / (c.sample_rate * 0.5) * lin_out.size(-1))
+                l1_all = ops.spec_loss(lin_out, batch.y, lin_len, r, wm, 0.0, v_lin)[2]
+                l1_pri = ops.spec_loss(lin_out[:, :, :n_pri], batch.y[:, :, :n_pri], lin_len, r, wm, 0.0, v_lin)[2]
+                lin_loss = lin_loss + (1.0 - w) * c.priority_freq_weight * (l1_pri - l1_all)
+            scal.update(linear_l1_loss=l4[0], linear_binary_div_loss=l4[1], linear_loss=lin_loss)
+            terms.append(lin_loss)
+            lin_i = ops.spec_loss_items(lin_out, batch.y, batch.linear_mask_lengths, r)
+        if mel_out is not None:
+            scal["done_loss"] = done_loss[0]
+            terms.append(done_loss[0])
+            if c.use_guided_attention:
+                attn_loss = ops.guided_attention_loss(attn, batch.input_lengths, batch.decoder_lengths,
+                                                      c.guided_attention_sigma, v_dec, v_in)
+                scal["attn_loss"] = attn_loss[0]
+                terms.append(attn_loss[0])
+                attn_i = ops.guided_attention_loss_items(attn, batch.input_lengths, batch.decoder_lengths,
+                                                         c.guided_attention_sigma)
+        loss = terms[0]
+        for t in terms[1:]:
+            loss = loss + t
+        scal["loss"] = loss
+        out = {k: v.detach() for k, v in scal.items()}
+        out["items"] = torch.cat([mel_i, lin_i, done_i, attn_i], dim=1)
+        return out
+
     def optimizer_step(self, reduce=True):
         """reduce=False: the caller has already issued and joined the gradient all-reduces (GraphedTrainer's segmented
         replay issues them from the host between segment launches)"""
@@ -932,6 +1035,11 @@ class GraphedTrainer(object):
                                    "backward streams do not run side by side here; set DV3_FLAG_SYNC=0" % n)
         return self.scal
 
+    def evaluate(self, batch):
+        """Trainer.evaluate on `batch` (any shape, not copied into the static batch): eager launches on the current
+        stream, between two replays; sees the weights the last replay wrote"""
+        return self.t.evaluate(batch)
+
     def bucket_order(self):
         """the bucket ids in the order a replay issues their all-reduces from the host (segmented form under a process
         group; [] otherwise)"""
@@ -1103,6 +1211,10 @@ class LatticeReplay(object):
         self.stats["replays"] += 1
         return g.step(batch)
 
+    def evaluate(self, batch):
+        """Trainer.evaluate on `batch` (lattice-padded or not): eager, no capture is made or replayed for it"""
+        return self.t.evaluate(batch)
+
     def check_range(self):
         """the f16x3 range guard (GraphedTrainer.check_range): > 0 = the process has moved to bf16x3, every capture of
         this object packed f16x3 operands and is dropped -- the next step of each shape captures again.
@@ -1118,6 +1230,124 @@ class LatticeReplay(object):
         while self.graphs:
             _, g = self.graphs.popitem(last=False)
             self._release(g)
+
+
+# ------------------------------------------------------------------------------------------------
+# held-out evaluation over a set of batches
+# ------------------------------------------------------------------------------------------------
+# the columns of Trainer.evaluate()["items"]: per utterance, S* = a masked sum over the item's own frames, *_cnt = the
+# number of elements it runs over (ops.spec_loss_items / bce_loss_items / guided_attention_loss_items)
+EVAL_ITEM_COLUMNS = ("mel_S1", "mel_Sz", "mel_cnt", "linear_S1", "linear_Sz", "linear_cnt", "done_S", "done_cnt",
+                     "attn_S", "attn_cnt")
+# set-level figure -> (numerator column, count column)
+_EVAL_RATIOS = dict(mel_l1=("mel_S1", "mel_cnt"), mel_binary_div=("mel_Sz", "mel_cnt"),
+                    linear_l1=("linear_S1", "linear_cnt"), linear_binary_div=("linear_Sz", "linear_cnt"),
+                    done=("done_S", "done_cnt"), attn=("attn_S", "attn_cnt"))
+
+
+class EvalTotals(object):
+    """Accumulates Trainer.evaluate() results over a held-out set.  Pure torch, any device; add() keeps tensors and does
+    not synchronise with the host, result() makes one transfer and sums in float64.
+
+    The set-level figures are sums of numerators over sums of counts, so they do not depend on how the set was cut
+    into batches (as REDUCTIONS: every item's forward still ran beside its batch mates).  `loss` combines them as the
+    reference combines its terms at masked_loss_weight = 1, the whole set taken as one batch of masked frames:
+        (1 - w) mel_l1 + w mel_binary_div + (1 - w) linear_l1 + w linear_binary_div + done + attn
+    (w = binary_divergence_weight; the terms of parts that ran).  `batch_mean/<key>` are the item-count-weighted means of
+    the reference-defined batch scalars, which DO depend on the batching.
+    The counts come from the fp32 item rows: exact up to 2^24 elements per item (32 703 linear frames of 513 bins),
+    rounded to nearest beyond (include/dv3hip.h).
+    Under a process group result() is a collective: every rank calls it, a rank whose shard is empty included (it
+    contributes zeros; give it `scalar_keys` -- the names of the batch scalars its peers add -- so that the reduced
+    vector has the same length everywhere).  The reduced tensor lives where the group's backend wants it: on
+    `reduce_device` when given, else on the current GPU for a backend that lists "nccl", else on the host."""
+
+    def __init__(self, binary_divergence_weight=0.1, scalar_keys=None, reduce_device=None):
+        self.w = float(binary_divergence_weight)
+        self._items, self._scal, self._n, self.ids = [], [], [], None
+        self._keys = None if scalar_keys is None else tuple(sorted(scalar_keys))
+        self.reduce_device = reduce_device
+
+    def add(self, result, ids=None):
+        items = result["items"].detach()
+        if items.dim() != 2 or items.shape[1] != len(EVAL_ITEM_COLUMNS):
+            raise ValueError("EvalTotals.add: items of shape %s, expected (B, %d)" % (tuple(items.shape), len(EVAL_ITEM_COLUMNS)))
+        keys = tuple(sorted(k for k in result if k != "items"))
+        if self._keys is None:
+            self._keys = keys
+        elif keys != self._keys:
+            raise ValueError("EvalTotals.add: scalars %r, the batches before had %r" % (keys, self._keys))
+        n = int(items.shape[0])
+        if (ids is not None) != (self.ids is not None) and self._items:
+            raise ValueError("EvalTotals.add: ids for every batch or for none")
+        if ids is not None:
+            ids = list(ids)
+            if len(ids) != n:
+                raise ValueError("EvalTotals.add: %d ids for %d items" % (len(ids), n))
+            self.ids = (self.ids or []) + ids
+        self._items.append(items.to(torch.float32))
+        if keys:
+            self._scal.append(torch.stack([result[k].detach().reshape(()).to(torch.float32) for k in keys]))
+        self._n.append(n)
+
+    def result(self, process_group=None):
+        K = len(EVAL_ITEM_COLUMNS)
+        if not self._items and process_group is None:
+            raise ValueError("EvalTotals.result: nothing was added")
+        keys = self._keys or ()
+        n_items = sum(self._n)
+        if self._items:
+            flat = torch.cat([t.reshape(-1) for t in self._items] + [t.reshape(-1) for t in self._scal]).cpu().double()
+        else:                  # an empty shard under a process group: zeros into the collective
+            flat = torch.zeros(0, dtype=torch.float64)
+        items = flat[:n_items * K].view(n_items, K)
+        scal = flat[n_items * K:].view(len(self._n), len(keys))
+        weights = torch.tensor(self._n, dtype=torch.float64)
+        # {K column sums, item count, item-count-weighted sums of the batch scalars}: all a process group has to share
+        tot = torch.cat([items.sum(0), torch.tensor([float(n_items)], dtype=torch.float64),
+                         (scal * weights[:, None]).sum(0)])
+        if process_group is not None:
+            dev = self.reduce_device
+            if dev is None:
+                backend = str(torch.distributed.get_backend(process_group)).lower()
+                dev = torch.device("cuda", torch.cuda.current_device()) if "nccl" in backend else torch.device("cpu")
+            tot = tot.to(dev)
+            torch.distributed.all_reduce(tot, group=process_group)
+            tot = tot.cpu()
+        col = {name: float(tot[i]) for i, name in enumerate(EVAL_ITEM_COLUMNS)}
+        n_all = float(tot[K])
+        out = {}
+        for name, (num, cnt) in _EVAL_RATIOS.items():
+            if col[cnt] > 0:
+                out[name] = col[num] / col[cnt]
+        w, g = self.w, out.get
+        loss, any_part = 0.0, False
+        if "mel_l1" in out:
+            loss, any_part = loss + (1.0 - w) * out["mel_l1"] + w * out["mel_binary_div"] + g("done", 0.0) + g("attn", 0.0), True
+        if "linear_l1" in out:
+            loss, any_part = loss + (1.0 - w) * out["linear_l1"] + w * out["linear_binary_div"], True
+        if any_part:
+            out["loss"] = loss
+        if n_all <= 0:
+            raise ValueError("EvalTotals.result: no item on any rank")
+        for i, k in enumerate(keys):
+            out["batch_mean/" + k] = float(tot[K + 1 + i]) / n_all
+        out["n_items"] = int(round(n_all))
+        out["items"] = items           # this rank's rows, in submission order
+        if self.ids is not None:
+            out["ids"] = list(self.ids)
+        return out
+
+
+def evaluate_loader(trainer, batches, process_group=None):
+    """EvalTotals over `trainer.evaluate(b)` for b in batches (a Trainer, GraphedTrainer or LatticeReplay; a batch's
+    `ids` attribute, when it has one, names its items) -> EvalTotals.result(process_group).  Under a process group
+    every rank calls it, with an empty `batches` where its shard is empty."""
+    t = trainer if isinstance(trainer, Trainer) else trainer.t
+    tot = EvalTotals(t.cfg.binary_divergence_weight, scalar_keys=t.eval_scalar_keys())
+    for b in batches:
+        tot.add(trainer.evaluate(b), getattr(b, "ids", None))
+    return tot.result(process_group)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -676,6 +676,36 @@ int dv3_bce_loss_f32(const float* p, const float* t, float* dp, float* out1, flo
 int dv3_bce_loss_valid_f32(const float* p, const float* t, float* dp, float* out1, float* scratch,
                            int64_t rows, int32_t T, const int32_t* t_valid, float gscale, void* stream);
 
+/* Per-item sums for held-out evaluation (train_step.Trainer.evaluate).  Additions to ABI 49: three forward-only entry
+ * points, one descriptor and a scratch-size query; nothing existing changed, so the version stays 49.
+ * Each writes ONE fp32 row per batch item -- the masked sums its batch counterpart above folds into one mean, of the
+ * same fp32 terms -- and takes no gradient buffer.  Deterministic: the item's own frames are cut into slices (one
+ * workgroup each), slice partial sums go to `scratch` (>= dv3_loss_items_scratch_floats(B, T) floats, T the frame axis
+ * of the tensor: T of the spectrograms and of p, Tq of attn) and a finishing pass adds them in slice order.
+ * Lengths beyond the tensor are clamped to it; an item without frames gets a row of zeros.  The count is computed in
+ * 64-bit integers and stored in the fp32 row: exact up to 2^24 elements per item (n_b * 513 <= 2^24: 32 703 frames),
+ * rounded to nearest beyond -- a caller that needs exact counts there rebuilds them from the lengths.
+ *   spec:   out[b] = {sum |y_hat[b,t,d] - y[b,t+r,d]|, sum z (as dv3_spec_loss_f32), n_b * D},
+ *           t < n_b = max(lengths[b] - r, 0): the frames the batch kernel's mask (t + r) < lengths[b] keeps.  Strides as
+ *           dv3_spec_loss_desc (BTC or BCT memory)
+ *   bce:    p, t [B][T]: out[b] = {sum_{t < lengths[b]} bce(p, t), lengths[b]}
+ *   guided: attn [L][B][Tq][Tk]: out[b] = {sum_{l, t < T_b, n < N_b} attn * W, L * T_b * N_b},
+ *           T_b = out_len[b], N_b = in_len[b]                                                                      */
+typedef struct dv3_spec_items_desc {
+  const float* y_hat; const float* y; const int32_t* lengths;
+  float* out; float* scratch;               /* out: [B][3]                                   */
+  int64_t yh_bs, yh_ts, yh_ds;
+  int64_t y_bs, y_ts, y_ds;
+  int32_t B, T, D, r;
+} dv3_spec_items_desc;
+int dv3_loss_items_scratch_floats(int32_t B, int32_t T);
+int dv3_spec_loss_items_f32(const dv3_spec_items_desc* d, void* stream);
+int dv3_bce_loss_items_f32(const float* p, const float* t, const int32_t* lengths, float* out, float* scratch,
+                           int32_t B, int32_t T, void* stream);
+int dv3_guided_attn_loss_items_f32(const float* attn, const int32_t* in_len, const int32_t* out_len, float* out,
+                                   float* scratch, int32_t L, int32_t B, int32_t Tq, int32_t Tk, float g,
+                                   void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Optimiser tail (train.py:755-759): clip_grad_norm_ + Adam over ONE flat fp32 arena
  * (all trainable parameters / gradients / moments are views into four flat buffers).
