@@ -280,12 +280,22 @@ __global__ __launch_bounds__(256) void stft_phase_kernel(const float* __restrict
 // z = x1 + i x2 (X1[k] = (Z[k] + conj Z[N-k]) / 2, X2[k] = (Z[k] - conj Z[N-k]) / 2i), and the two Hermitian target
 // spectra ride one inverse FFT as V = Y1 + i Y2 (y1 = Re v, y2 = Im v): half the FFT passes -- the LDS traffic that
 // bounds this kernel -- per frame.  Frames (2q, 2q+1) of one batch item; an odd last frame pairs with nothing.
-template <int NFFT, bool LWS>
+//
+// MOM (fast Griffin-Lim, Perraudin, Balazs & Sondergaard 2013): the phase is taken from t = c + alpha (c - c_prev)
+// instead of the consistent spectrum c itself.  cprev [B][T][NBIN] float2 in the frame order of `mag` holds c_prev; every
+// (frame, bin) belongs to one thread of one workgroup, which reads c_prev, stores c in its place and normalises t.  The
+// reads are issued before the forward FFT and held in registers (at most 5 bins x 2 frames x 2 floats per thread at
+// 2048), so their latency lies under the FFT's LDS passes.  `first` (uniform): cprev holds nothing yet -- it is not read
+// (t = c) and still written.  The phantom partner of an unpaired last frame and the frames from Tb on are neither read
+// nor written.  MOM = false is the instruction stream of the kernel without the option.
+template <int NFFT, bool LWS, bool MOM>
 __global__ __launch_bounds__(256) void gl_project2_kernel(const float* __restrict__ y, const float* __restrict__ mag,
                                                           float* __restrict__ frames, int T, int hop, int L, int TP,
                                                           const float* __restrict__ aw, const float* __restrict__ sw,
-                                                          const int32_t* __restrict__ tlen, int tlo) {
+                                                          const int32_t* __restrict__ tlen, int tlo,
+                                                          float2* __restrict__ cprev, float alpha, int first) {
   constexpr int NBIN = NFFT / 2 + 1;
+  constexpr int KPT = NFFT / 512 + 1;        // bins k = tid + 256 q <= NFFT/2 of one thread (the last one: thread 0 alone)
   __shared__ cplx A[NFFT], Bf[NFFT], W[NFFT];
   const int tid = threadIdx.x;
   const int b = blockIdx.x / TP, t1 = 2 * (blockIdx.x - b * TP);
@@ -311,24 +321,68 @@ __global__ __launch_bounds__(256) void gl_project2_kernel(const float* __restric
       A[n] = cplx{yb[i1] * h, two ? yb[i2] * h : 0.f};
     }
   }
+  // c_prev of this thread's bins, in flight under the forward transform.  Unconditional per lane (a lane-dependent
+  // branch would make the compiler wait for the loads where it ends): a lane past the last bin re-reads bin NFFT/2, and
+  // an unpaired last frame, which has no partner row, reads its own row twice -- neither value is used.
+  float2 p1[KPT], p2[KPT];
+  if constexpr (MOM) {
+    if (!first) {
+      const float2* c1 = cprev + ((int64_t)b * T + t1) * NBIN;
+      const float2* c2 = c1 + (two ? NBIN : 0);
+#pragma unroll
+      for (int q = 0; q < KPT; ++q) {
+        const int k = min(tid + 256 * q, NFFT / 2);
+        p1[q] = c1[k];
+        p2[q] = c2[k];
+      }
+    }
+  }
   fft_lds<NFFT, -1>(A, Bf, tid, W);
   const int64_t fr = (int64_t)b * T + t1;
   const float* m1 = mag + fr * NBIN;
   const float* m2 = m1 + (two ? NBIN : 0);
-  for (int k = tid; k <= NFFT / 2; k += 256) {
-    const cplx zk = Bf[k], zn = Bf[(NFFT - k) & (NFFT - 1)];
-    // X1 = (zk + conj zn) / 2, X2 = (zk - conj zn) / (2i) = ((zk.y + zn.y) - i (zk.x - zn.x)) / 2
-    const cplx x1{0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)};
-    const cplx x2{0.5f * (zk.y + zn.y), -0.5f * (zk.x - zn.x)};
-    const float inv1 = 1.0f / fmaxf(sqrtf(x1.x * x1.x + x1.y * x1.y), 1e-8f);
-    const float inv2 = 1.0f / fmaxf(sqrtf(x2.x * x2.x + x2.y * x2.y), 1e-8f);
-    cplx w1{m1[k] * (x1.x * inv1), m1[k] * (x1.y * inv1)};
-    cplx w2{m2[k] * (x2.x * inv2), m2[k] * (x2.y * inv2)};
-    if (k == 0 || k == NFFT / 2) w1.y = w2.y = 0.f;
-    if (!two) w2 = cplx{0.f, 0.f};
-    // V[k] = w1 + i w2 ; V[N-k] = conj(w1) + i conj(w2)
-    A[k] = cplx{w1.x - w2.y, w1.y + w2.x};
-    if (k > 0 && k < NFFT / 2) A[NFFT - k] = cplx{w1.x + w2.y, -w1.y + w2.x};
+  if constexpr (!MOM) {
+    for (int k = tid; k <= NFFT / 2; k += 256) {
+      const cplx zk = Bf[k], zn = Bf[(NFFT - k) & (NFFT - 1)];
+      // X1 = (zk + conj zn) / 2, X2 = (zk - conj zn) / (2i) = ((zk.y + zn.y) - i (zk.x - zn.x)) / 2
+      const cplx x1{0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)};
+      const cplx x2{0.5f * (zk.y + zn.y), -0.5f * (zk.x - zn.x)};
+      const float inv1 = 1.0f / fmaxf(sqrtf(x1.x * x1.x + x1.y * x1.y), 1e-8f);
+      const float inv2 = 1.0f / fmaxf(sqrtf(x2.x * x2.x + x2.y * x2.y), 1e-8f);
+      cplx w1{m1[k] * (x1.x * inv1), m1[k] * (x1.y * inv1)};
+      cplx w2{m2[k] * (x2.x * inv2), m2[k] * (x2.y * inv2)};
+      if (k == 0 || k == NFFT / 2) w1.y = w2.y = 0.f;
+      if (!two) w2 = cplx{0.f, 0.f};
+      // V[k] = w1 + i w2 ; V[N-k] = conj(w1) + i conj(w2)
+      A[k] = cplx{w1.x - w2.y, w1.y + w2.x};
+      if (k > 0 && k < NFFT / 2) A[NFFT - k] = cplx{w1.x + w2.y, -w1.y + w2.x};
+    }
+  } else {
+    // the same loop, unrolled so that p1 / p2 stay in registers: c = (x1, x2) goes to cprev, the phase comes from t
+    float2* c1 = cprev + fr * NBIN;
+#pragma unroll
+    for (int q = 0; q < KPT; ++q) {
+      const int k = tid + 256 * q;
+      if (k > NFFT / 2) continue;
+      const cplx zk = Bf[k], zn = Bf[(NFFT - k) & (NFFT - 1)];
+      const cplx x1{0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)};
+      const cplx x2{0.5f * (zk.y + zn.y), -0.5f * (zk.x - zn.x)};
+      c1[k] = float2{x1.x, x1.y};
+      if (two) c1[NBIN + k] = float2{x2.x, x2.y};
+      cplx u1 = x1, u2 = x2;
+      if (!first) {                            // t = c + alpha (c - c_prev)
+        u1 = cplx{x1.x + alpha * (x1.x - p1[q].x), x1.y + alpha * (x1.y - p1[q].y)};
+        u2 = cplx{x2.x + alpha * (x2.x - p2[q].x), x2.y + alpha * (x2.y - p2[q].y)};
+      }
+      const float inv1 = 1.0f / fmaxf(sqrtf(u1.x * u1.x + u1.y * u1.y), 1e-8f);
+      const float inv2 = 1.0f / fmaxf(sqrtf(u2.x * u2.x + u2.y * u2.y), 1e-8f);
+      cplx w1{m1[k] * (u1.x * inv1), m1[k] * (u1.y * inv1)};
+      cplx w2{m2[k] * (u2.x * inv2), m2[k] * (u2.y * inv2)};
+      if (k == 0 || k == NFFT / 2) w1.y = w2.y = 0.f;
+      if (!two) w2 = cplx{0.f, 0.f};
+      A[k] = cplx{w1.x - w2.y, w1.y + w2.x};
+      if (k > 0 && k < NFFT / 2) A[NFFT - k] = cplx{w1.x + w2.y, -w1.y + w2.x};
+    }
   }
   fft_lds<NFFT, +1>(A, Bf, tid, W);
   float* out = frames + fr * NFFT;
@@ -565,8 +619,8 @@ static int lws_gl_project(const float* y, const float* mag, const float* awin, c
   DV3_REQUIRE(y && mag && frames && awin && swin && B > 0 && T > 1 && hop > 0 && hop <= N && samples_fit(T, hop) &&
               lws_len<N>(T, hop) > 0, "lws_gl_project: bad arguments");
   const int TP = (T + 1) / 2;
-  hipLaunchKernelGGL((gl_project2_kernel<N, true>), dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
-                     frames, T, hop, lws_len<N>(T, hop), TP, awin, swin, (const int32_t*)nullptr, 1);
+  hipLaunchKernelGGL((gl_project2_kernel<N, true, false>), dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
+                     frames, T, hop, lws_len<N>(T, hop), TP, awin, swin, (const int32_t*)nullptr, 1, (float2*)nullptr, 0.f, 0);
   return dv3_check_launch("lws_gl_project");
 }
 
@@ -587,8 +641,8 @@ static int gl_project(const float* y, const float* mag, float* frames, int32_t B
   const int L = hop * (T - 1);
   DV3_REQUIRE(L > N / 2, "gl_project: signal shorter than the reflect padding");
   const int TP = (T + 1) / 2;     // two real frames per complex FFT
-  hipLaunchKernelGGL((gl_project2_kernel<N, false>), dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
-                     frames, T, hop, L, TP, (const float*)nullptr, (const float*)nullptr, (const int32_t*)nullptr, 1);
+  hipLaunchKernelGGL((gl_project2_kernel<N, false, false>), dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
+                     frames, T, hop, L, TP, (const float*)nullptr, (const float*)nullptr, (const int32_t*)nullptr, 1, (float2*)nullptr, 0.f, 0);
   return dv3_check_launch("gl_project");
 }
 
@@ -800,13 +854,46 @@ static int gl_project_items(const float* y, const float* mag, const float* awin,
   const int TP = (T + 1) / 2;
   const int L = lws ? lws_len<N>(T, hop) : hop * (T - 1);
   if (lws)
-    hipLaunchKernelGGL((gl_project2_kernel<N, true>), dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
-                       frames, T, hop, L, TP, awin, swin, tlen, items_tlo<N>(lws, hop));
+    hipLaunchKernelGGL((gl_project2_kernel<N, true, false>), dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
+                       frames, T, hop, L, TP, awin, swin, tlen, items_tlo<N>(lws, hop), (float2*)nullptr, 0.f, 0);
   else
-    hipLaunchKernelGGL((gl_project2_kernel<N, false>), dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
-                       frames, T, hop, L, TP, (const float*)nullptr, (const float*)nullptr, tlen, items_tlo<N>(lws, hop));
+    hipLaunchKernelGGL((gl_project2_kernel<N, false, false>), dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
+                       frames, T, hop, L, TP, (const float*)nullptr, (const float*)nullptr, tlen, items_tlo<N>(lws, hop), (float2*)nullptr, 0.f,
+                       0);
   return dv3_check_launch("gl_project_items");
 }
+// fast Griffin-Lim: gl_project / lws_gl_project (tlen NULL) or gl_project_items with the momentum term of
+// gl_project2_kernel<N, LWS, true>.  T >= items_tlo is the bound of all three (a positive signal length on the lws
+// framing, a signal longer than the reflect padding on the torch one).
+template <int N>
+static int gl_project_momentum(const float* y, const float* mag, const float* awin, const float* swin, float* cprev,
+                               float* frames, int32_t B, int32_t T, int32_t hop, const int32_t* tlen, int32_t lws, float alpha,
+                               int32_t first, void* stream) {
+  DV3_REQUIRE(y && mag && frames && (!lws || (awin && swin)) && B > 0 && T > 1 && hop > 0 && hop <= N && samples_fit(T, hop),
+              "gl_project_momentum: bad arguments");
+  DV3_REQUIRE(cprev && ((uintptr_t)cprev & 7) == 0, "gl_project_momentum: cprev must be a buffer of B * T * (n_fft/2 + 1) float pairs, 8-byte aligned");
+  DV3_REQUIRE(alpha >= 0.f && alpha < 1.f, "gl_project_momentum: alpha = %g must lie in [0, 1)", (double)alpha);
+  const int tlo = items_tlo<N>(lws, hop);
+  DV3_REQUIRE(T >= tlo, "gl_project_momentum: %d frames at hop %d are fewer than the %d the framing takes", (int)T, (int)hop, tlo);
+  const int TP = (T + 1) / 2;
+  const int L = lws ? lws_len<N>(T, hop) : hop * (T - 1);
+  if (lws)
+    hipLaunchKernelGGL((gl_project2_kernel<N, true, true>), dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
+                       frames, T, hop, L, TP, awin, swin, tlen, tlo, reinterpret_cast<float2*>(cprev), alpha, (int)(first != 0));
+  else
+    hipLaunchKernelGGL((gl_project2_kernel<N, false, true>), dim3((unsigned)((int64_t)B * TP)), dim3(256), 0, (hipStream_t)stream, y, mag,
+                       frames, T, hop, L, TP, (const float*)nullptr, (const float*)nullptr, tlen, tlo,
+                       reinterpret_cast<float2*>(cprev), alpha, (int)(first != 0));
+  return dv3_check_launch("gl_project_momentum");
+}
+extern "C" int dv3_gl_project_momentum_f32(const float* y, const float* mag, const float* awin, const float* swin, float* cprev,
+                                           float* frames, int32_t B, int32_t T, int32_t hop, const int32_t* tlen, int32_t lws,
+                                           int32_t n_fft, float alpha, int32_t first, void* stream) {
+  return with_fft_size("gl_project_momentum", n_fft, [&](auto n) {
+    return gl_project_momentum<decltype(n)::value>(y, mag, awin, swin, cprev, frames, B, T, hop, tlen, lws, alpha, first, stream);
+  });
+}
+
 extern "C" int dv3_gl_istft_items_f32(const float* mag, const float* phasor, const float* swin, float* frames, int32_t B,
                                       int32_t T, int32_t hop, const int32_t* tlen, int32_t lws, void* stream) {
   return gl_istft_items<1024>(mag, phasor, swin, frames, B, T, hop, tlen, lws, stream);

@@ -419,13 +419,13 @@ _lib.impl("fused_clip_adam", _fused_clip_adam, "CUDA")
 # ------------------------------------------------------------------------------------------------------------------
 # audio.inv_spectrogram's phase reconstruction (audio.py:37-43; csrc/audio.hip): magnitudes (B, T, n_fft/2+1)
 # ------------------------------------------------------------------------------------------------------------------
-_lib.define("griffin_lim(Tensor mag, int hop, int n_iter, int n_fft=1024) -> Tensor")
+_lib.define("griffin_lim(Tensor mag, int hop, int n_iter, int n_fft=1024, float momentum=0.0) -> Tensor")
 _lib.define("istft(Tensor mag, Tensor phasor, int hop, int n_fft=1024) -> Tensor")
 
 
-def _griffin_lim(mag, hop, n_iter, n_fft=1024):
+def _griffin_lim(mag, hop, n_iter, n_fft=1024, momentum=0.0):
     from . import audio
-    return audio.griffin_lim(mag, hop, n_iter, fft_size=n_fft)
+    return audio.griffin_lim(mag, hop, n_iter, fft_size=n_fft, momentum=momentum)
 
 
 def _istft(mag, phasor, hop, n_fft=1024):
@@ -434,6 +434,8 @@ def _istft(mag, phasor, hop, n_fft=1024):
 
 
 _lib.impl("griffin_lim", _griffin_lim, "CUDA")
+_lib.impl("griffin_lim", lambda mag, hop, n_iter, n_fft=1024, momentum=0.0: mag.new_empty((mag.shape[0], hop * (mag.shape[1] - 1))),
+          "Meta")
 _lib.impl("istft", _istft, "CUDA")
 
 OPERATORS = ("conv1d_glu_fwd", "conv1d_glu_bwd", "conv1d_act_fwd", "conv1d_act_bwd", "convtranspose1d_k2s2_fwd",

@@ -968,6 +968,24 @@ int dv3_overlap_add_items_f32_n(const float* frames, float* y, int32_t B, int32_
 int dv3_gl_project_items_f32_n(const float* y, const float* mag, const float* awin, const float* swin, float* frames,
                                int32_t B, int32_t T, int32_t hop, const int32_t* tlen, int32_t lws, int32_t n_fft,
                                void* stream);
+/* Fast Griffin-Lim (Perraudin, Balazs & Sondergaard 2013): one projection with a momentum term on the consistent
+ * spectrum, for both framings (lws = 1 / 0), the whole batch (tlen NULL) or per item (tlen as above), n_fft = 512, 1024
+ * or 2048.  With c = STFT(y) and c_prev what the previous call left in cprev,
+ *   t = c + alpha (c - c_prev),   frames = window * irfft(mag * t / max(|t|, 1e-8)),   cprev <- c   (in place)
+ * Only the phase of t is used, so alpha is the `momentum` of librosa / torchaudio (their c - alpha / (1 + alpha) c_prev is
+ * t / (1 + alpha)).
+ *   cprev  [B][T][n_fft/2 + 1][2] floats (re, im) in the frame order of mag, 8-byte aligned; rows of frames at or past
+ *          tlen[b] are neither read nor written
+ *   first  nonzero: cprev holds nothing yet -- it is not read (t = c: the call projects as dv3_gl_project_items_f32_n
+ *          does) and is still written.  The first projection of a reconstruction passes 1, the others 0.
+ *   alpha  in [0, 1); alpha = 0 projects as the entry points above do, and still keeps c in cprev
+ * The other arguments and their checks are those of dv3_gl_project_f32_n / dv3_lws_gl_project_f32_n (tlen NULL) and
+ * dv3_gl_project_items_f32_n, and hop <= n_fft on both framings; a NULL or misaligned cprev, alpha outside [0, 1) or NaN:
+ * DV3_EINVAL before anything is launched.  The overlap-add that follows is dv3_overlap_add_f32_n /
+ * dv3_lws_overlap_add_f32_n / dv3_overlap_add_items_f32_n.  (Added under ABI 49: nothing existing changed.) */
+int dv3_gl_project_momentum_f32(const float* y, const float* mag, const float* awin, const float* swin, float* cprev,
+                                float* frames, int32_t B, int32_t T, int32_t hop, const int32_t* tlen, int32_t lws,
+                                int32_t n_fft, float alpha, int32_t first, void* stream);
 /* de-emphasis of row b over its own first lens[b] samples (device int32[B]); the rest of the row is written as zeros */
 int dv3_deemphasis_items_f32(const float* x, float* y, int32_t B, int32_t L, const int32_t* lens, float coef,
                              void* stream);

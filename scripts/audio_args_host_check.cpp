@@ -1,6 +1,7 @@
-// Stand-alone host check of the audio entry points' argument handling (include/dv3hip.h, the `_n` siblings of ABI 49):
+// Stand-alone host check of the audio entry points' argument handling (include/dv3hip.h, the `_n` siblings of ABI 49
+// and dv3_gl_project_momentum_f32):
 // every call below must be refused with DV3_EINVAL on the host -- an unsupported n_fft, too few frames for the framing,
-// a hop above n_fft, a missing pointer -- so nothing is launched and no GPU is needed.  Meant for a sanitizer build of
+// a hop above n_fft, a missing pointer, a momentum outside [0, 1) -- so nothing is launched and no GPU is needed.  Meant for a sanitizer build of
 // the host side of csrc/audio.hip (the frame / sample / offset arithmetic in front of the launches):
 //
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined \
@@ -8,6 +9,7 @@
 //   ./build_tmp/audio_args_host_check
 //
 // It links audio.hip alone, so it brings its own dv3_set_error (api.hip's sits among the other kernels' switches).
+#include <math.h>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -39,6 +41,8 @@ int main() {
   int32_t ibuf[8] = {0};
   int64_t lbuf[8] = {0};
   float *p = buf, *o = buf + 4;
+  alignas(8) float cbuf[8] = {0};
+  float* c = cbuf;
   const int32_t B = 2;
   const int32_t bad[] = {4096, 768, 256, 0, -1024, 1023, INT32_MAX, INT32_MIN};
   for (int32_t nf : bad) {
@@ -56,6 +60,10 @@ int main() {
     expect_einval("gl_project_items n_fft", dv3_gl_project_items_f32_n(p, p, p, p, o, B, 12, 128, ibuf, 1, nf, nullptr), m);
     expect_einval("analysis_items n_fft", dv3_analysis_items_f32_n(p, lbuf, ibuf, B, 12, 128, 0.97f, p, nullptr, p, nullptr, 80,
                                                                    -100.f, 20.f, o, nullptr, nf, nullptr), m);
+    for (int32_t lws = 0; lws < 2; ++lws) {
+      expect_einval("gl_project_momentum n_fft", dv3_gl_project_momentum_f32(p, p, p, p, c, o, B, 12, 128, nullptr, lws, nf, 0.99f, 1, nullptr), m);
+      expect_einval("gl_project_momentum items n_fft", dv3_gl_project_momentum_f32(p, p, p, p, c, o, B, 12, 128, ibuf, lws, nf, 0.99f, 0, nullptr), m);
+    }
   }
   const int32_t sizes[] = {512, 1024, 2048};
   for (int32_t nf : sizes) {
@@ -101,6 +109,28 @@ int main() {
     expect_einval("overlap_add_items huge T", dv3_overlap_add_items_f32_n(p, o, B, INT32_MAX, hop, ibuf, 0, nf, nullptr), nullptr);
     expect_einval("gl_project_items huge T", dv3_gl_project_items_f32_n(p, p, p, p, o, B, 1 << 30, hop, ibuf, 1, nf, nullptr), nullptr);
     expect_einval("gl_project_items no tlen", dv3_gl_project_items_f32_n(p, p, p, p, o, B, 12, hop, nullptr, 1, nf, nullptr), nullptr);
+    // the momentum projection: both framings, the whole batch (tlen NULL) and per item, first call and later ones
+    for (int32_t form = 0; form < 8; ++form) {
+      const int32_t lws = form & 1, first = (form >> 2) & 1;
+      const int32_t* tl = (form & 2) ? ibuf : nullptr;
+      const float* aw = lws ? p : nullptr;                       // the torch framing takes no window tables
+      expect_einval("gl_project_momentum no cprev", dv3_gl_project_momentum_f32(p, p, aw, aw, nullptr, o, B, 12, hop, tl, lws, nf, 0.99f, first, nullptr), "cprev");
+      expect_einval("gl_project_momentum odd cprev", dv3_gl_project_momentum_f32(p, p, aw, aw, c + 1, o, B, 12, hop, tl, lws, nf, 0.99f, first, nullptr), "cprev");
+      expect_einval("gl_project_momentum alpha 1", dv3_gl_project_momentum_f32(p, p, aw, aw, c, o, B, 12, hop, tl, lws, nf, 1.0f, first, nullptr), "alpha");
+      expect_einval("gl_project_momentum alpha -0.1", dv3_gl_project_momentum_f32(p, p, aw, aw, c, o, B, 12, hop, tl, lws, nf, -0.1f, first, nullptr), "alpha");
+      expect_einval("gl_project_momentum alpha nan", dv3_gl_project_momentum_f32(p, p, aw, aw, c, o, B, 12, hop, tl, lws, nf, NAN, first, nullptr), "alpha");
+      expect_einval("gl_project_momentum alpha inf", dv3_gl_project_momentum_f32(p, p, aw, aw, c, o, B, 12, hop, tl, lws, nf, INFINITY, first, nullptr), "alpha");
+      expect_einval("gl_project_momentum T=3", dv3_gl_project_momentum_f32(p, p, aw, aw, c, o, B, 3, hop, tl, lws, nf, 0.99f, first, nullptr), "fewer");
+      expect_einval("gl_project_momentum T=1", dv3_gl_project_momentum_f32(p, p, aw, aw, c, o, B, 1, hop, tl, lws, nf, 0.99f, first, nullptr), nullptr);
+      expect_einval("gl_project_momentum hop > n_fft", dv3_gl_project_momentum_f32(p, p, aw, aw, c, o, B, 12, nf + 1, tl, lws, nf, 0.99f, first, nullptr), nullptr);
+      expect_einval("gl_project_momentum hop=0", dv3_gl_project_momentum_f32(p, p, aw, aw, c, o, B, 12, 0, tl, lws, nf, 0.99f, first, nullptr), nullptr);
+      expect_einval("gl_project_momentum B=0", dv3_gl_project_momentum_f32(p, p, aw, aw, c, o, 0, 12, hop, tl, lws, nf, 0.99f, first, nullptr), nullptr);
+      expect_einval("gl_project_momentum huge T", dv3_gl_project_momentum_f32(p, p, aw, aw, c, o, B, 1 << 30, hop, tl, lws, nf, 0.99f, first, nullptr), nullptr);
+      expect_einval("gl_project_momentum no frames", dv3_gl_project_momentum_f32(p, p, aw, aw, c, nullptr, B, 12, hop, tl, lws, nf, 0.99f, first, nullptr), nullptr);
+      expect_einval("gl_project_momentum no mag", dv3_gl_project_momentum_f32(p, nullptr, aw, aw, c, o, B, 12, hop, tl, lws, nf, 0.99f, first, nullptr), nullptr);
+    }
+    expect_einval("gl_project_momentum T=4 at 3n/16", dv3_gl_project_momentum_f32(p, p, p, p, c, o, B, 4, hop2, ibuf, 1, nf, 0.5f, 0, nullptr), "fewer");
+    expect_einval("gl_project_momentum lws without windows", dv3_gl_project_momentum_f32(p, p, nullptr, nullptr, c, o, B, 12, hop, nullptr, 1, nf, 0.5f, 0, nullptr), nullptr);
   }
   // the entry points without n_fft are the 1024 instantiation: the same refusals
   expect_einval("lws_overlap_add (1024) T=3", dv3_lws_overlap_add_f32(p, o, B, 3, 256, nullptr), nullptr);
