@@ -9,7 +9,13 @@ namespace {
 
 constexpr int kLossBlock = 256;
 
-__device__ __forceinline__ void block_reduce4(float v[4], float* out /* [4] per block */) {
+// what the spectrogram kernels take: the caller's descriptor and the loss head's two pointers (dv3_spec_loss_head_f32)
+struct spec_loss_args : dv3_spec_loss_desc {
+  float* dpre; float* bias_part;
+};
+
+// extra (or null) also receives the block's sum of v[1]: the done head's bias partial (bce_kernel)
+__device__ __forceinline__ void block_reduce4(float v[4], float* out /* [4] per block */, float* extra = nullptr) {
   __shared__ float red[4][4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) v[k] = dv3_wave_sum(v[k]);
@@ -19,8 +25,19 @@ __device__ __forceinline__ void block_reduce4(float v[4], float* out /* [4] per 
     for (int k = 0; k < 4; ++k) red[w][k] = v[k];
   }
   __syncthreads();
-  if (threadIdx.x < 4) out[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] +
-                                          red[2][threadIdx.x] + red[3][threadIdx.x];
+  if (threadIdx.x < 4) {
+    const float sum = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    out[threadIdx.x] = sum;
+    if (extra && threadIdx.x == 1) extra[0] = sum;
+  }
+}
+
+// Loss head (dv3_spec_loss_head_f32): the gradient through the sigmoid that made y_hat,
+// dz = (dyh * alpha) * y_hat * (1 - y_hat) with alpha = 1 -- the three products in the order of gate_bwd_kernel's
+// DV3_EPI_SIGMOID branch (elementwise.hip), so the bits are those of dv3_spec_loss_f32(dyh) followed by dv3_gate_bwd_f32.
+__device__ __forceinline__ float sigmoid_head_dz(float dyh, float yh) {
+  const float d = dyh * 1.0f;
+  return d * yh * (1.0f - yh);
 }
 
 // binary divergence of one element and its derivative (train.py:537-556):
@@ -62,7 +79,7 @@ __device__ __forceinline__ float spec_mask_sum(const dv3_spec_loss_desc& p) {
   return ms * (float)p.D;
 }
 
-__global__ __launch_bounds__(kLossBlock) void spec_loss_kernel(const dv3_spec_loss_desc p) {
+__global__ __launch_bounds__(kLossBlock) void spec_loss_kernel(const spec_loss_args p) {
   const int Tr = p.T - p.r, D = p.D;
   const int Trv = spec_t_valid(p) - p.r;       // == Tr unless the batch is padded beyond its own maximum
   const int64_t n = (int64_t)p.B * Tr * D;
@@ -92,6 +109,7 @@ __global__ __launch_bounds__(kLossBlock) void spec_loss_kernel(const dv3_spec_lo
     const int64_t iy = b * p.y_bs + (int64_t)(t + p.r) * p.y_ts + dd * p.y_ds;  // y[:, r:]
     if (t >= Trv) {
       if (p.dyh) p.dyh[ih] = 0.f;
+      if (p.dpre) p.dpre[ih] = 0.f;
       continue;
     }
     const float yh = p.y_hat[ih], y = p.y[iy];
@@ -107,13 +125,41 @@ __global__ __launch_bounds__(kLossBlock) void spec_loss_kernel(const dv3_spec_lo
       acc[2] += z;
       acc[3] += m * z;
     }
-    if (p.dyh) {
+    if (p.dyh || p.dpre) {
       const float sgn = (diff > 0.f) ? 1.f : ((diff < 0.f) ? -1.f : 0.f);
       const float coef = c_all + c_msk * m;
-      p.dyh[ih] = p.gscale * coef * ((1.f - p.w_bd) * sgn + p.w_bd * dz);
+      const float g = p.gscale * coef * ((1.f - p.w_bd) * sgn + p.w_bd * dz);
+      if (p.dyh) p.dyh[ih] = g;
+      if (p.dpre) p.dpre[ih] = sigmoid_head_dz(g, yh);
+    }
+  }
+  if (p.dpre) {   // the last r frames take no part: dz = 0 from this launch (no spec_loss_tail_zero_kernel in this form)
+    const int64_t nz = (int64_t)p.B * p.r * D;
+    for (int64_t i = (int64_t)blockIdx.x * kLossBlock + threadIdx.x; i < nz; i += stride) {
+      const int dd = (int)(i % D);
+      const int64_t bt = i / D;
+      const int64_t ih = (bt / p.r) * p.yh_bs + (Tr + (bt % p.r)) * p.yh_ts + dd * p.yh_ds;
+      p.dpre[ih] = 0.f;
+      if (p.dyh) p.dyh[ih] = 0.f;
     }
   }
   block_reduce4(acc, p.scratch + (int64_t)blockIdx.x * 4);
+}
+
+// Row sums of dz for the layouts of spec_loss_kernel.  Its flat element walk (which the bits of out4 hang on) has no
+// per-bin structure, so the sums are taken from dz by a second, small launch: one thread per (item, 64-frame tile, bin)
+// adds its 64 frames in a fixed order -> bias_part[bin][item * t_tiles + tile], the layout the tiled kernel writes.
+__global__ __launch_bounds__(256) void spec_head_rowsum_kernel(const spec_loss_args p, int t_tiles) {
+  const int64_t n = (int64_t)p.B * t_tiles * p.D;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int dd = (int)(i % p.D);
+  const int64_t bt = i / p.D;
+  const int tt = (int)(bt % t_tiles), b = (int)(bt / t_tiles);
+  const int t1 = min(tt * 64 + 64, p.T - p.r);
+  float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};     // eight interleaved chains, joined pairwise
+  for (int t = tt * 64; t < t1; ++t) s[t & 7] += p.dpre[b * p.yh_bs + t * p.yh_ts + dd * p.yh_ds];
+  p.bias_part[(int64_t)dd * ((int64_t)p.B * t_tiles) + bt] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
 }
 
 // The same loss when the prediction is time-fastest (the model's (B, T, D) outputs are transposed views of its BCT
@@ -122,8 +168,18 @@ __global__ __launch_bounds__(kLossBlock) void spec_loss_kernel(const dv3_spec_lo
 // takes 64 frames x 64 bins at a time: the target tile is read bin-fastest into LDS, then every thread works
 // frame-fastest -- prediction read, gradient write and the LDS reads (row stride 65) are all unit-stride.  Persistent
 // grid (tiles are walked with a grid stride) so that the block partial sums fit the caller's scratch.
-template <bool FAST>
-__global__ __launch_bounds__(kLossBlock) void spec_loss_tiled_kernel(const dv3_spec_loss_desc p, int t_tiles, int d_tiles,
+// A thread's frame within the tile is fixed (tid & 63) and its bins are tid >> 6, + 4, ...: the frame tests, the mask
+// and the gradient's coefficient are taken once per tile, the element loop keeps the loads, the arithmetic of spec_bd
+// and the stores, and it ends at the tile's last valid bin (D % 64 == 1: the last bin tile costs one bin, not 64).  The
+// elements a thread adds up, and their order, are those of the flat walk q = tid, tid + 256, ... this replaces: out4
+// keeps its bits.  (16 bytes per lane would hand a thread four neighbouring frames -- another assignment of elements to
+// partial sums, so another out4: left out.)
+// HEAD (dpre set, dv3_spec_loss_head_f32): dz = dyh * y_hat * (1 - y_hat) is written too (dyh itself only if set), the last r frames
+// get dz = 0 from the threads of the item's last frame tile, and with bias_part the tile's dz goes back into the LDS
+// slot its target came from: thread (bin = tid >> 2, quarter = tid & 3) adds 16 frames pairwise, two row-local
+// shuffles finish -> bias_part[bin][item * t_tiles + tile].  No atomics; the sums do not depend on the grid.
+template <bool FAST, bool HEAD>
+__global__ __launch_bounds__(kLossBlock) void spec_loss_tiled_kernel(const spec_loss_args p, int t_tiles, int d_tiles,
                                                                      int n_tiles) {
   __shared__ float ys[64 * 65];
   const int Tr = p.T - p.r, D = p.D;
@@ -135,46 +191,107 @@ __global__ __launch_bounds__(kLossBlock) void spec_loss_tiled_kernel(const dv3_s
   const float c_all = (1.f - wm) * inv_n, c_msk = use_mask ? wm / msum : 0.f;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   const int tid = threadIdx.x;
+  const int tl = tid & 63, dw = tid >> 6;
+  const bool sums = HEAD && p.bias_part != nullptr;
+  const int64_t n_part = (int64_t)p.B * t_tiles;
+  // A tile's 16 + 16 values per thread are loaded one tile AHEAD, all at once: with 4 loads in flight per thread between
+  // two barriers, and the grid held at 1024 workgroups by the block partial sums (four waves per SIMD), the kernel ran
+  // at the bytes it had in flight, 1.8 TB/s with its vector units a third busy.
+  float tg[16], yv[16];          // target: rows dw + 4k of the tile, column tl; prediction: frame tl, bins dw + 4k
+  auto fetch = [&](int tile) {
+    const int dt = tile % d_tiles, tt_ = (tile / d_tiles) % t_tiles, b = tile / (d_tiles * t_tiles);
+    const int t0 = tt_ * 64, d0 = dt * 64;
+    const int dd = d0 + tl;
+    const float* __restrict__ yp = p.y + b * p.y_bs + (int64_t)(t0 + dw + p.r) * p.y_ts + dd;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) tg[k] = (t0 + dw + 4 * k < Tr && dd < D) ? yp[(int64_t)(4 * k) * p.y_ts] : 0.f;
+    const int t = t0 + tl;
+    const float* __restrict__ hp = p.y_hat + b * p.yh_bs + t + (int64_t)(d0 + dw) * p.yh_ds;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) yv[k] = (t < Trv && d0 + dw + 4 * k < D) ? hp[(int64_t)(4 * k) * p.yh_ds] : 0.f;
+  };
+  if ((int)blockIdx.x < n_tiles) fetch(blockIdx.x);
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int dt = tile % d_tiles, tt_ = (tile / d_tiles) % t_tiles, b = tile / (d_tiles * t_tiles);
     const int t0 = tt_ * 64, d0 = dt * 64;
+    const int nd = min(64, D - d0);
     __syncthreads();                                   // the previous tile's LDS reads are done
-#pragma unroll 4
-    for (int q = tid; q < 64 * 64; q += kLossBlock) {  // target tile, bin-fastest: y[b][t0 + tl + r][d0 + dl]
-      const int tl = q >> 6, dl = q & 63;
-      const int t = t0 + tl, dd = d0 + dl;
-      ys[tl * 65 + dl] = (t < Tr && dd < D) ? p.y[b * p.y_bs + (int64_t)(t + p.r) * p.y_ts + dd] : 0.f;
-    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) ys[(dw + 4 * k) * 65 + tl] = tg[k];   // target tile, bin-fastest: y[b][t0 + row + r][d0 + col]
+    float yc[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) yc[k] = yv[k];
+    if (tile + (int)gridDim.x < n_tiles) fetch(tile + gridDim.x);
     __syncthreads();
     const int len_b = use_mask ? p.lengths[b] : 0;
-#pragma unroll 4
-    for (int q = tid; q < 64 * 64; q += kLossBlock) {  // frame-fastest
-      const int dl = q >> 6, tl = q & 63;
-      const int t = t0 + tl, dd = d0 + dl;
-      if (t >= Tr || dd >= D) continue;
-      const int64_t ih = b * p.yh_bs + t + (int64_t)dd * p.yh_ds;
-      if (t >= Trv) {
-        if (p.dyh) p.dyh[ih] = 0.f;
-        continue;
+    const int t = t0 + tl;                             // frame-fastest
+    const float m = (use_mask && (t + p.r) < len_b) ? 1.f : 0.f;
+    const float coef = c_all + c_msk * m;
+    const int64_t ih0 = b * p.yh_bs + t + (int64_t)(d0 + dw) * p.yh_ds;
+    const int64_t ihs = 4 * p.yh_ds;
+    if (t < Trv) {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const int dl = dw + 4 * k;
+        if (dl >= nd) break;
+        const int64_t ih = ih0 + k * ihs;
+        const float yh = yc[k], y = ys[tl * 65 + dl];
+        const float diff = yh - y;
+        const float ad = fabsf(diff);
+        acc[0] += ad;
+        acc[1] += m * ad;
+        float dz = 0.f;
+        if (p.w_bd > 0.f) {
+          float z;
+          spec_bd<FAST>(yh, y, z, dz);
+          acc[2] += z;
+          acc[3] += m * z;
+        }
+        if (p.dyh || HEAD) {
+          const float sgn = (diff > 0.f) ? 1.f : ((diff < 0.f) ? -1.f : 0.f);
+          const float g = p.gscale * coef * ((1.f - p.w_bd) * sgn + p.w_bd * dz);
+          if (p.dyh) p.dyh[ih] = g;
+          if (HEAD) {
+            const float gz = sigmoid_head_dz(g, yh);
+            p.dpre[ih] = gz;
+            if (sums) ys[tl * 65 + dl] = gz;
+          }
+        }
       }
-      const float yh = p.y_hat[ih], y = ys[tl * 65 + dl];
-      const float m = (use_mask && (t + p.r) < len_b) ? 1.f : 0.f;
-      const float diff = yh - y;
-      const float ad = fabsf(diff);
-      acc[0] += ad;
-      acc[1] += m * ad;
-      float dz = 0.f;
-      if (p.w_bd > 0.f) {
-        float z;
-        spec_bd<FAST>(yh, y, z, dz);
-        acc[2] += z;
-        acc[3] += m * z;
+    } else {
+      if (t < Tr) {                                    // beyond the batch's own frames (t_valid): zero gradient
+        int64_t ih = ih0;
+        for (int dl = dw; dl < nd; dl += 4, ih += ihs) {
+          if (p.dyh) p.dyh[ih] = 0.f;
+          if (HEAD) p.dpre[ih] = 0.f;
+        }
       }
-      if (p.dyh) {
-        const float sgn = (diff > 0.f) ? 1.f : ((diff < 0.f) ? -1.f : 0.f);
-        const float coef = c_all + c_msk * m;
-        p.dyh[ih] = p.gscale * coef * ((1.f - p.w_bd) * sgn + p.w_bd * dz);
+      if (sums)
+        for (int dl = dw; dl < nd; dl += 4) ys[tl * 65 + dl] = 0.f;
+    }
+    if (HEAD && tt_ == t_tiles - 1) {                  // the last r frames
+      for (int tz = Tr + tl; tz < p.T; tz += 64) {
+        int64_t ih = b * p.yh_bs + tz + (int64_t)(d0 + dw) * p.yh_ds;
+        for (int dl = dw; dl < nd; dl += 4, ih += ihs) {
+          p.dpre[ih] = 0.f;
+          if (p.dyh) p.dyh[ih] = 0.f;
+        }
       }
+    }
+    if (sums) {
+      __syncthreads();
+      const int bin = tid >> 2, part = tid & 3;
+      float v[16];                                     // pairwise, as the row sums of gate_bwd_kernel's wave reduce are
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[i] = ys[(part * 16 + i) * 65 + bin];
+#pragma unroll
+      for (int w = 1; w < 16; w <<= 1)
+#pragma unroll
+        for (int i = 0; i < 16; i += 2 * w) v[i] += v[i + w];
+      float s = v[0];
+      s += __shfl_xor(s, 1, 4);
+      s += __shfl_xor(s, 2, 4);
+      if (part == 0 && bin < nd) p.bias_part[(int64_t)(d0 + bin) * n_part + (int64_t)b * t_tiles + tt_] = s;
     }
   }
   block_reduce4(acc, p.scratch + (int64_t)blockIdx.x * 4);
@@ -283,8 +400,10 @@ __global__ __launch_bounds__(256) void bce_kernel(const float* __restrict__ p,
                                                   const float* __restrict__ t,
                                                   float* __restrict__ dp, float* __restrict__ scratch,
                                                   int64_t n, float gscale, int T = 0,
-                                                  const int32_t* __restrict__ t_valid = nullptr) {
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+                                                  const int32_t* __restrict__ t_valid = nullptr,
+                                                  float* __restrict__ dpre = nullptr,
+                                                  float* __restrict__ bias_part = nullptr) {
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};   // loss terms; dz (loss head)
   // ABI 42: [rows][T] with only the first t_valid[0] columns taking part
   const int Tv = t_valid ? min(t_valid[0], T) : T;
   const float inv_n = 1.0f / (float)(t_valid ? (n / T) * Tv : n);
@@ -292,13 +411,22 @@ __global__ __launch_bounds__(256) void bce_kernel(const float* __restrict__ p,
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
     if (t_valid && (int)(i % T) >= Tv) {
       if (dp) dp[i] = 0.f;
+      if (dpre) dpre[i] = 0.f;
       continue;
     }
     const float x = p[i], y = t[i];
     acc[0] += bce_elem(x, y);
-    if (dp) dp[i] = gscale * inv_n * (x - y) / fmaxf((1.f - x) * x, 1e-12f);
+    if (dp || dpre) {
+      const float g = gscale * inv_n * (x - y) / fmaxf((1.f - x) * x, 1e-12f);
+      if (dp) dp[i] = g;
+      if (dpre) {        // loss head (dv3_spec_loss_head_f32): through the sigmoid that made p, as sigmoid_head_dz
+        const float gz = sigmoid_head_dz(g, x);
+        dpre[i] = gz;
+        acc[1] += gz;
+      }
+    }
   }
-  block_reduce4(acc, scratch + (int64_t)blockIdx.x * 4);
+  block_reduce4(acc, scratch + (int64_t)blockIdx.x * 4, bias_part ? bias_part + blockIdx.x : nullptr);
 }
 
 
@@ -434,11 +562,15 @@ extern "C" int dv3_spec_loss_scratch_floats(int32_t B, int32_t T, int32_t D) {
   return (int)(4 * (tiles > flat ? tiles : flat) + 16);
 }
 
-extern "C" int dv3_spec_loss_f32(const dv3_spec_loss_desc* d, void* stream) {
+static int spec_loss_launch(const dv3_spec_loss_desc* d, float* dpre, float* bias_part, void* stream) {
   DV3_REQUIRE(d && d->y_hat && d->y && d->out4 && d->scratch, "spec_loss: null pointer");
   DV3_REQUIRE(d->B > 0 && d->D > 0 && d->r >= 0 && d->T > d->r, "spec_loss: bad dims");
   DV3_REQUIRE(d->w_masked <= 0.f || d->lengths, "spec_loss: masked weight needs lengths");
   hipStream_t st = (hipStream_t)stream;
+  spec_loss_args a;
+  static_cast<dv3_spec_loss_desc&>(a) = *d;
+  a.dpre = dpre;
+  a.bias_part = bias_part;
   const int64_t n = (int64_t)d->B * (d->T - d->r) * d->D;
   int nb = loss_blocks(n);
   if (spec_time_fast(*d)) {
@@ -446,18 +578,33 @@ extern "C" int dv3_spec_loss_f32(const dv3_spec_loss_desc* d, void* stream) {
     const int t_tiles = dv3_cdiv(d->T - d->r, 64), d_tiles = dv3_cdiv(d->D, 64);
     const int64_t nt = (int64_t)d->B * t_tiles * d_tiles;
     nb = (int)(nt < 1024 ? nt : 1024);
-    if (g_loss_fast_log) hipLaunchKernelGGL(spec_loss_tiled_kernel<true>, dim3(nb), dim3(kLossBlock), 0, st, *d, t_tiles, d_tiles, (int)nt);
-    else hipLaunchKernelGGL(spec_loss_tiled_kernel<false>, dim3(nb), dim3(kLossBlock), 0, st, *d, t_tiles, d_tiles, (int)nt);
+    auto k = dpre ? (g_loss_fast_log ? spec_loss_tiled_kernel<true, true> : spec_loss_tiled_kernel<false, true>)
+                     : (g_loss_fast_log ? spec_loss_tiled_kernel<true, false> : spec_loss_tiled_kernel<false, false>);
+    hipLaunchKernelGGL(k, dim3(nb), dim3(kLossBlock), 0, st, a, t_tiles, d_tiles, (int)nt);
   } else {
-    hipLaunchKernelGGL(spec_loss_kernel, dim3(nb), dim3(kLossBlock), 0, st, *d);
+    hipLaunchKernelGGL(spec_loss_kernel, dim3(nb), dim3(kLossBlock), 0, st, a);
+    if (dpre && bias_part) {
+      const int t_tiles = dv3_cdiv(d->T - d->r, 64);
+      const int64_t ns = (int64_t)d->B * t_tiles * d->D;
+      hipLaunchKernelGGL(spec_head_rowsum_kernel, dim3((unsigned)dv3_cdiv64(ns, 256)), dim3(256), 0, st, a, t_tiles);
+    }
   }
-  if (d->dyh && d->r > 0) {
+  if (d->dyh && !dpre && d->r > 0) {
     const int64_t nt = (int64_t)d->B * d->r * d->D;
     hipLaunchKernelGGL(spec_loss_tail_zero_kernel, dim3((unsigned)dv3_cdiv64(nt, 256)), dim3(256), 0,
                        st, *d);
   }
   hipLaunchKernelGGL(spec_loss_finish_kernel, dim3(1), dim3(256), 0, st, *d, nb);
   return dv3_check_launch("spec_loss_f32");
+}
+
+extern "C" int dv3_spec_loss_f32(const dv3_spec_loss_desc* d, void* stream) {
+  return spec_loss_launch(d, nullptr, nullptr, stream);
+}
+
+extern "C" int dv3_spec_loss_head_f32(const dv3_spec_loss_desc* d, float* dpre, float* bias_part, void* stream) {
+  DV3_REQUIRE(dpre, "spec_loss_head: dpre is required");
+  return spec_loss_launch(d, dpre, bias_part, stream);
 }
 
 extern "C" int dv3_guided_attn_loss_f32(const float* attn, const int32_t* in_len,
@@ -513,6 +660,28 @@ extern "C" int dv3_bce_loss_valid_f32(const float* p, const float* t, float* dp,
   hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(256), 0, st, scratch, nb, 0.f, out1, t_valid, (int)T,
                      (const int32_t*)nullptr, 0, rows);
   return dv3_check_launch("bce_loss_valid_f32");
+}
+
+extern "C" int dv3_bce_loss_head_parts(int64_t n) { return n > 0 ? loss_blocks(n) : 0; }
+
+extern "C" int dv3_bce_loss_head_f32(const float* p, const float* t, float* dp, float* dpre, float* bias_part, float* out1,
+                                     float* scratch, int64_t rows, int32_t T, const int32_t* t_valid, float gscale,
+                                     void* stream) {
+  DV3_REQUIRE(p && t && dpre && out1 && scratch && rows > 0 && T > 0, "bce_loss_head: bad args");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = rows * T;
+  const int nb = loss_blocks(n);
+  if (t_valid) {
+    hipLaunchKernelGGL(bce_kernel, dim3(nb), dim3(256), 0, st, p, t, dp, scratch, n, gscale, (int)T, t_valid, dpre, bias_part);
+    hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(256), 0, st, scratch, nb, 0.f, out1, t_valid, (int)T,
+                       (const int32_t*)nullptr, 0, rows);
+  } else {
+    hipLaunchKernelGGL(bce_kernel, dim3(nb), dim3(256), 0, st, p, t, dp, scratch, n, gscale, 0, (const int32_t*)nullptr, dpre,
+                       bias_part);
+    hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(256), 0, st, scratch, nb, 1.0f / (float)n, out1,
+                       (const int32_t*)nullptr, 0, (const int32_t*)nullptr, 0, (int64_t)0);
+  }
+  return dv3_check_launch("bce_loss_head_f32");
 }
 
 // ---- per-item sums ------------------------------------------------------------------------------

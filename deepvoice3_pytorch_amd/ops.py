@@ -1295,6 +1295,68 @@ class _GateResult(object):
         self.pair, self.version = gate.pair, version
 
 
+# The loss head: the layer whose sigmoid makes a model output (the post-net's and the decoder's last 1x1 layers, the done
+# projection) leaves a token on that output; spec_loss_with_grad / bce_loss_with_grad, handed the output (or the
+# transposed view of it the model returns), then ask their kernel for the gradient of the layer's PRE-activation in the
+# same pass (dv3_spec_loss_head_f32, dv3_bce_loss_head_f32) instead of d loss / d y_hat, and the layer's backward
+# replaces its read-read-write dv3_gate_bwd_f32 launch by that kernel's read-only row-sum form.  Every output of the
+# step keeps its bits.  DV3_FUSE_LOSS_HEAD=0 restores the two passes (A/B runs, the
+# bit-identity tests).  What autograd carries from the loss to the layer is a zero-stride stand-in of zeros (as
+# _spk_dummy_grad): a second consumer of the output makes autograd ADD its gradient to the stand-in, the layer then sees
+# a tensor that is not the stand-in, recomputes d loss / d y_hat with the two-pass kernel, adds what autograd delivered
+# (x + 0 = x: the sum the two-pass path would have seen) and goes on as without the fusion.
+fuse_loss_head = _env_flag("DV3_FUSE_LOSS_HEAD", True)
+loss_head_stats = {"fused": 0, "standalone": 0}     # sigmoid-head layer backwards served either way (tests, bench)
+_head_dummy = {}
+
+
+class _HeadToken(object):
+    """what a sigmoid-head layer leaves on its (B, M, T) output for the loss; `result` is what the loss left for it"""
+    __slots__ = ("shape", "result")
+
+    def __init__(self, shape):
+        self.shape, self.result = tuple(shape), None
+
+
+class _HeadResult(object):
+    __slots__ = ("dz", "version", "redo")
+
+    def __init__(self, dz, redo):
+        self.dz, self.version, self.redo = dz, dz._version, redo
+
+
+def _head_stand_in(shape, device):
+    z = _head_dummy.get(device)
+    if z is None:
+        z = _head_dummy[device] = torch.zeros(1, dtype=torch.float32, device=device)
+    return z.expand(*shape)
+
+
+def _is_head_stand_in(dy):
+    z = _head_dummy.get(dy.device)
+    return z is not None and dy.data_ptr() == z.data_ptr() and z._version == 0 and \
+        all(st == 0 or n == 1 for n, st in zip(dy.shape, dy.stride()))
+
+
+def _loss_head_token(y_hat, transposed_only):
+    """the token of the layer whose output y_hat provably is: the (B, M, T) tensor itself, or a view of it that is its
+    (B, T, M) transpose (same memory, from its first element) -> (token, "self" | "t") or (None, None)"""
+    if not fuse_loss_head or y_hat.dtype != torch.float32:
+        return None, None
+    tok = getattr(y_hat, "_dv3_head", None)
+    if tok is not None and not transposed_only and tuple(y_hat.shape) == tok.shape and y_hat.is_contiguous():
+        return tok, "self"
+    base = getattr(y_hat, "_base", None)
+    tok = getattr(base, "_dv3_head", None) if base is not None else None
+    if tok is None or y_hat.dim() != 3 or tuple(base.shape) != tok.shape or not base.is_contiguous():
+        return None, None
+    B, M, T = tok.shape
+    if tuple(y_hat.shape) == (B, T, M) and y_hat.data_ptr() == base.data_ptr() and \
+            all(n == 1 or st == want for n, st, want in zip(y_hat.shape, y_hat.stride(), (M * T, 1, T))):
+        return tok, "t"
+    return None, None
+
+
 def mark_sole_consumer(y):
     """the caller's promise that exactly one conv layer consumes y (and nothing else does)"""
     if fuse_gate_bwd and getattr(y, "_dv3_tok", None) is not None:
@@ -1451,6 +1513,9 @@ class ConvLayerFn(torch.autograd.Function):
             # round 6 (GateFuse).  As a producer: leave on y what the consumer's input-gradient launch needs to run this
             # layer's gate backward.  As a consumer: remember the producer of x when the caller marked x accordingly.
             ctx.tok = ctx.prod = None
+            ctx.head = None
+            if fuse_loss_head and mode == EPI_SIGMOID and r is None and r2 is None and not cfg.transposed:
+                ctx.head = y._dv3_head = _HeadToken(y.shape)       # the loss head (see fuse_loss_head)
             split_modes = _gemm_mode in ("f16x3", "bf16x3")
             # pair words (include/dv3hip.h): this layer's pre-gate gradient can go to its two gradient GEMMs as the bf16
             # hi / lo pairs they would otherwise build while staging (both on the three-term split kernels, no per-frame
@@ -1477,12 +1542,32 @@ class ConvLayerFn(torch.autograd.Function):
         x, v, g, saved = ctx.saved_tensors
         mode = cfg.mode
         gated = mode in (EPI_GLU, EPI_HIGHWAY)
-        dy = _c(dy)
+        head, tok = None, getattr(ctx, "head", None)      # (torch_ops runs this body on a context of its own)
+        if tok is not None:
+            head, tok.result = tok.result, None
+            if head is not None:
+                if tuple(dy.shape) == tuple(head.dz.shape) and _is_head_stand_in(dy) and head.dz._version == head.version:
+                    dy = None          # the loss kernel already wrote this layer's pre-activation gradient
+                else:
+                    dy = head.redo().view(head.dz.shape) + dy      # somebody else consumes y too: the two passes
+                    head = None
+            loss_head_stats["fused" if head is not None else "standalone"] += 1
+        if dy is not None:
+            dy = _c(dy)
         rs2 = math.sqrt(0.5)
         dr = dr2 = dspk = None
         r_scale = 0.0
         n_part, g_pair, part_t = B, False, False
-        if gated:
+        if head is not None:
+            # The bias row sums are taken from dz by the stand-alone kernel's read-only form (no dpre written: a third of
+            # the bytes of the pass that is gone), in ITS order -- one wave per row, then the batch in item order -- so the
+            # bias gradient keeps the bits of the two passes.  The loss kernel's own per-tile sums (bias_part of
+            # dv3_spec_loss_head_f32) add the same terms in another order; a step that took them would drift from the
+            # two-pass step at rounding level, and training amplifies that over a few hundred steps.
+            gmat = head.dz
+            _, _, part = gate_bwd(gmat, None, None, B=B, C=M, T=Tout, mode=EPI_LINEAR, want_dpre=False)
+            dres, Tg = None, Tout
+        elif gated:
             # the skip path of a residual GLU passes sqrt(.5) * dy: the DGRAD epilogue reads dy itself
             glu_skip = mode == EPI_GLU and cfg.residual
             fused = getattr(dy, "_dv3_gate", None)
@@ -2366,11 +2451,40 @@ class _NoCtx(object):
     needs_input_grad = (True,)
 
 
-def spec_loss_with_grad(y_hat, y, lengths, r=1, w_masked=0.5, w_bd=0.1, t_valid=None):
-    """-> (tensor[4] as spec_loss, d total / d y_hat laid out like y_hat); no autograd graph"""
-    c = _NoCtx()
-    out4 = SpecLossFn.forward(c, y_hat.detach(), y, lengths, r, w_masked, w_bd, t_valid)
-    return out4, c.dyh
+def spec_loss_with_grad(y_hat, y, lengths, r=1, w_masked=0.5, w_bd=0.1, t_valid=None, head=None):
+    """-> (tensor[4] as spec_loss, d total / d y_hat laid out like y_hat); no autograd graph.
+    The loss head (see fuse_loss_head; head=False: never): when y_hat is the transposed view of a sigmoid-head layer's
+    output the gradient goes to that layer directly, as the gradient of its pre-activation, and what is returned for
+    torch.autograd.backward(y_hat, .) is a zero-stride stand-in of zeros."""
+    tok, how = _loss_head_token(y_hat, True) if head is not False else (None, None)
+    yd = y_hat.detach()
+    if tok is None:
+        c = _NoCtx()
+        out4 = SpecLossFn.forward(c, yd, y, lengths, r, w_masked, w_bd, t_valid)
+        return out4, c.dyh
+    y = _dense_or_copy(_chk(y, "y"))
+    B, T, D = yd.shape
+    dev = yd.device
+    out4 = torch.empty(4, dtype=torch.float32, device=dev)
+    scratch = torch.empty(_lib.lib().dv3_spec_loss_scratch_floats(B, T, D), dtype=torch.float32, device=dev)
+    dz = torch.empty((B, D, T), dtype=torch.float32, device=dev)
+    d = _spec_loss_desc()
+    d.y_hat, d.y, d.lengths = yd.data_ptr(), y.data_ptr(), _ptr(lengths)
+    d.yh_bs, d.yh_ts, d.yh_ds = D * T, 1, T
+    d.y_bs, d.y_ts, d.y_ds = y.stride()
+    d.dyh, d.out4, d.scratch = None, out4.data_ptr(), scratch.data_ptr()
+    d.B, d.T, d.D, d.r = B, T, D, r
+    d.w_masked, d.w_bd, d.gscale = w_masked, w_bd, 1.0
+    d.t_valid = _ptr(t_valid)
+    _lib.call("dv3_spec_loss_head_f32", ctypes.byref(d), dz.data_ptr(), None, _stream())
+
+    def redo():     # d loss / d y_hat of the two-pass path, as the layer's (B, D, T) memory
+        c = _NoCtx()
+        SpecLossFn.forward(c, yd, y, lengths, r, w_masked, w_bd, t_valid)
+        return c.dyh.transpose(1, 2)
+
+    tok.result = _HeadResult(dz, redo)
+    return out4, _head_stand_in(yd.shape, dev)
 
 
 def guided_attention_loss_with_grad(attn, in_len, out_len, g=0.2, tq_valid=None, tk_valid=None):
@@ -2379,10 +2493,30 @@ def guided_attention_loss_with_grad(attn, in_len, out_len, g=0.2, tq_valid=None,
     return out1, c.dattn
 
 
-def bce_loss_with_grad(p, t, t_valid=None):
-    c = _NoCtx()
-    out1 = BCELossFn.forward(c, p.detach(), t, t_valid)
-    return out1, c.dp
+def bce_loss_with_grad(p, t, t_valid=None, head=None):
+    """the loss head as spec_loss_with_grad, for a single-channel sigmoid layer (the done projection)"""
+    tok, how = _loss_head_token(p, False) if head is not False else (None, None)
+    pd = p.detach()
+    if tok is None or tok.shape[1] != 1 or not pd.is_contiguous() or (t_valid is not None and how != "t"):
+        c = _NoCtx()
+        out1 = BCELossFn.forward(c, pd, t, t_valid)
+        return out1, c.dp
+    t = _c(_chk(t, "t"))
+    B, _, T = tok.shape
+    dev = pd.device
+    out1 = torch.empty(1, dtype=torch.float32, device=dev)
+    scratch = torch.empty(4 * 1024 + 16, dtype=torch.float32, device=dev)
+    dz = torch.empty(tok.shape, dtype=torch.float32, device=dev)
+    _lib.call("dv3_bce_loss_head_f32", pd.data_ptr(), t.data_ptr(), None, dz.data_ptr(), None, out1.data_ptr(),
+              scratch.data_ptr(), B, T, _ptr(t_valid), 1.0, _stream())
+
+    def redo():
+        c = _NoCtx()
+        BCELossFn.forward(c, pd, t, t_valid)
+        return c.dp
+
+    tok.result = _HeadResult(dz, redo)
+    return out1, _head_stand_in(pd.shape, dev)
 
 
 def sum_scalars(a, b, c=None, d=None):

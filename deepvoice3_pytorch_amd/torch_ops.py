@@ -366,9 +366,9 @@ _lib.define("spec_loss_fwd(Tensor y_hat, Tensor y, Tensor? lengths, int r, float
 _lib.define("guided_attn_loss_fwd(Tensor attn, Tensor in_lens, Tensor out_lens, float g) -> (Tensor loss, Tensor grad_attn)")
 _lib.define("bce_loss_fwd(Tensor p, Tensor target) -> (Tensor loss, Tensor grad_p)")
 _lib.impl("spec_loss_fwd", lambda y_hat, y, lengths, r, w_masked, w_bd: ops.spec_loss_with_grad(y_hat, y, lengths, r, w_masked,
-                                                                                                 w_bd), "CUDA")
+                                                                                                 w_bd, head=False), "CUDA")
 _lib.impl("guided_attn_loss_fwd", lambda attn, il, ol, g: ops.guided_attention_loss_with_grad(attn, il, ol, g), "CUDA")
-_lib.impl("bce_loss_fwd", lambda p, t: ops.bce_loss_with_grad(p, t), "CUDA")
+_lib.impl("bce_loss_fwd", lambda p, t: ops.bce_loss_with_grad(p, t, head=False), "CUDA")
 _lib.impl("spec_loss_fwd", lambda y_hat, y, lengths, r, w_masked, w_bd: (y_hat.new_empty((4,)), torch.empty_like(y_hat)), "Meta")
 _lib.impl("guided_attn_loss_fwd", lambda attn, il, ol, g: (attn.new_empty((1,)), torch.empty_like(attn)), "Meta")
 _lib.impl("bce_loss_fwd", lambda p, t: (p.new_empty((1,)), torch.empty_like(p)), "Meta")

@@ -653,6 +653,18 @@ typedef struct dv3_spec_loss_desc {
                                              * steps, replayed from a lattice of padded shapes)                         */
 } dv3_spec_loss_desc;
 int dv3_spec_loss_f32(const dv3_spec_loss_desc* d, void* stream);
+/* The loss head (an addition to ABI 49: one entry point, no struct changed, so the version stays 49 -- the two pointers
+ * travel beside the descriptor instead of inside it).  y_hat is the output of a sigmoid layer and the caller wants the
+ * gradient of that layer's PRE-activation from the same pass as the loss.  dpre (required), laid out like dyh, gets
+ *     dz = (dyh * alpha) * y_hat * (1 - y_hat),  alpha = 1,
+ * the three products in the order of dv3_gate_bwd_f32 (DV3_EPI_SIGMOID): the bits are those of dv3_spec_loss_f32
+ * writing dyh followed by that call.  The last r frames get dz = 0 from the same launch (no separate zeroing launch).
+ * d->dyh may be NULL; if set it is written too.  out4 has the bits dv3_spec_loss_f32 gives.
+ * bias_part (or NULL): fp32 [D][B * t_tiles], t_tiles = ceil((T - r) / 64) -- the sum of dz over every 64-frame tile of
+ * every item, channel-major: dv3_weight_norm_bwd_f32 takes it with n_part = B * t_tiles, bias_part_t = 1.  No atomics;
+ * the sums do not depend on the grid.  (Time-fastest prediction with bin-fastest target: the sums come from the loss
+ * launch itself; other layouts: from a second small launch over dz.)                                                */
+int dv3_spec_loss_head_f32(const dv3_spec_loss_desc* d, float* dpre, float* bias_part, void* stream);
 int dv3_spec_loss_scratch_floats(int32_t B, int32_t T, int32_t D);
 
 /* guided attention (train.py:585-601,733-740): loss = mean(attn * W),
@@ -675,6 +687,16 @@ int dv3_bce_loss_f32(const float* p, const float* t, float* dp, float* out1, flo
  * rows * t_valid, zero gradient beyond.                                                                             */
 int dv3_bce_loss_valid_f32(const float* p, const float* t, float* dp, float* out1, float* scratch,
                            int64_t rows, int32_t T, const int32_t* t_valid, float gscale, void* stream);
+
+/* The loss head (addition to ABI 49) of p = sigmoid(z), a SINGLE-channel layer's output ([rows][T], the done flag): as
+ * dv3_bce_loss_f32 (t_valid NULL) / dv3_bce_loss_valid_f32, and dpre (required) gets dp * p * (1 - p) as
+ * dv3_gate_bwd_f32 (DV3_EPI_SIGMOID, alpha = 1) would make it from dp; dp itself only when non-NULL.  bias_part (or
+ * NULL): fp32 [dv3_bce_loss_head_parts(rows * T)] workgroup sums of dpre, the one channel's partial bias gradient
+ * (dv3_weight_norm_bwd_f32: n_part = that count, bias_part_t = 1).  out1 keeps the bits of the calls above.          */
+int dv3_bce_loss_head_f32(const float* p, const float* t, float* dp, float* dpre, float* bias_part, float* out1,
+                          float* scratch, int64_t rows, int32_t T, const int32_t* t_valid, float gscale,
+                          void* stream);
+int dv3_bce_loss_head_parts(int64_t n);
 
 /* Per-item sums for held-out evaluation (train_step.Trainer.evaluate).  Additions to ABI 49: three forward-only entry
  * points, one descriptor and a scratch-size query; nothing existing changed, so the version stays 49.
