@@ -83,14 +83,17 @@ class MultiSpeakerTTSModel(nn.Module):
         return mel, linear, alignments, done
 
 
-    def synthesize_batch(self, text_sequences, text_lengths, speaker_ids=None):
+    def synthesize_batch(self, text_sequences, text_lengths, speaker_ids=None, stall_limit=None):
         """Per-utterance batched synthesis: every item of a ragged batch comes back as if it had been synthesised alone
         (the reference's synthesis.tts at B = 1, synthesis.py:42-73, model part).  text_sequences (B, Tt) int ids on
         the device, padded past each item's text_lengths[b]; positions are 1..text_lengths[b].  The encoder and the
         post-net zero each item's columns past its own length after every layer (ops.ItemLengths), the decoder runs in
         its per-utterance mode (Decoder.incremental_forward(text_lengths=...)).  Inference only.
         -> (mel (B, T, mel_dim), linear (B, T * upsampling, linear_dim), alignments, done, frame_lengths): frame_lengths
-        (int64[B], host) are each item's mel frames (decoder steps x r); everything past them is zero."""
+        (int64[B], host) are each item's mel frames (decoder steps x r); everything past them is zero.
+        stall_limit (None: off): the opt-in end-of-text stop -- an item whose attention has reached its last key keeps
+        decode_program.stall_stop(...) steps if its done flag has not fired by then.  Applied after the decode and before
+        the post-net; the decode loop itself still runs until the slowest item's done flag (or the cap)."""
         from . import ops
         if self.training:
             raise RuntimeError("synthesize_batch: eval mode only")
@@ -116,6 +119,17 @@ class MultiSpeakerTTSModel(nn.Module):
                 kw = dict(speaker_embed=speaker_embed) if speaker_embed is not None else {}
                 mel, alignments, done, states, steps = dec.incremental_forward(memory, text_positions,
                                                                                text_lengths=tl, **kw)
+                if stall_limit is not None:
+                    # the end-of-text stop, after the fact: the loop above ran to the slowest item's
+                    # done flag; an item whose attention reached its last key stall_limit steps earlier keeps only those
+                    from .decode_program import end_of_text_stops, item_results
+                    ran = [int(n) for n in steps]
+                    stall = end_of_text_stops(alignments, "btk", ran, tl_dev, stall_limit, dec.min_decoder_steps)
+                    kept = [s or n for n, s in zip(ran, stall)]
+                    if kept != ran:
+                        m = max(kept)
+                        mel, alignments, done, states, steps = item_results(
+                            kept, mel[:, :m], alignments[:, :m], list(done[:m]), states[:, :m])
                 Td = mel.size(1)
                 mel = mel.reshape(B, -1, self.mel_dim)
                 post_in = states.view(B, mel.size(1), -1) if self.use_decoder_state_for_postnet_input else mel

@@ -41,6 +41,42 @@ def item_stops(done_rows, t0, min_steps, max_steps, stops):
     return all(stops)
 
 
+def stall_stop(end_step, stall_limit, min_steps):
+    """The opt-in end-of-text stop: the number of steps after which an item stops once its attention
+    has reached its last key.  end_step: the first step whose argmax sat on the last key (the alignment statistics'
+    column, -1 if none yet) -> 0 while the end has not been reached (the item runs on), otherwise
+    max(end_step + 1 + stall_limit, min_steps + 1): stall_limit more steps after the one that reached the end, and never
+    fewer than the done flag's own rule allows (item_stops: n > min_steps).  The count depends only on rows before it,
+    so it is the same whenever it is evaluated."""
+    end_step, stall_limit, min_steps = int(end_step), int(stall_limit), int(min_steps)
+    if stall_limit < 0:
+        raise ValueError("stall_stop: stall_limit must be >= 0, got %d" % stall_limit)
+    if end_step < 0:
+        return 0
+    return max(end_step + 1 + stall_limit, min_steps + 1)
+
+
+# the columns of an alignment-statistics row (include/dv3hip.h: dv3_alignment_stats_f32), in order
+ALIGNMENT_COLUMNS = ("steps", "keys", "focus_mean", "focus_min", "last_key", "furthest_key", "end_step", "tail_steps",
+                     "covered_keys", "back_steps", "max_jump", "longest_stall", "bad_rows")
+
+
+def end_of_text_stops(attn, layout, steps, key_len, stall_limit, min_steps):
+    """stall_stop for every item of a batch or every slot of a slot program: attn / layout as ops.alignment_stats takes
+    them (read in place), steps: the steps each item has run so far (host ints; 0: not looked at), key_len: device
+    int32[B].  One kernel call and one device read.  -> per item the step count it stops after by the end-of-text rule
+    if that many steps have run, else 0."""
+    dev = attn.device
+    run = torch.tensor([int(n) for n in steps], dtype=torch.int32).to(dev)
+    stats = ops.alignment_stats(attn, run, key_len.to(device=dev, dtype=torch.int32), layout)
+    end = stats[:, ALIGNMENT_COLUMNS.index("end_step")].tolist()
+    out = []
+    for n, e in zip(steps, end):
+        s = stall_stop(e, stall_limit, min_steps) if n > 0 else 0
+        out.append(s if 0 < s <= n else 0)
+    return out
+
+
 def item_results(stops, outputs, alignments, dones, states):
     """the per-utterance decode's results with every frame past item b's own step count stops[b] set to zero (in place
     where the tensor allows) -> (outputs, alignments, dones, states, frame_lengths int64[B] on the host)"""

@@ -2646,6 +2646,32 @@ def guided_attention_loss_items(attn, in_len, out_len, g=0.2):
     return out
 
 
+def alignment_stats(attn, steps, key_len, layout="btk"):
+    """Per-item diagnostics of stored attention rows (dv3_alignment_stats_f32, include/dv3hip.h).
+    attn: fp32, "btk" = (B, T, Tk) or "tbk" = (T, B, Tk) -- the step program's stacked buffer --, any strided view whose
+    key axis is dense: read in place, never copied or written.  steps, key_len: int32[B] on the device; item b's rows
+    t < steps[b] and keys n < key_len[b] are read.  -> (B, DV3_ALIGN_COLS) fp32 on the device, columns
+    synthesis.ALIGNMENT_COLUMNS.  Runs on the current stream; no host synchronisation."""
+    _chk(attn, "attn")
+    _chk(steps, "steps", torch.int32)
+    _chk(key_len, "key_len", torch.int32)
+    if layout not in ("btk", "tbk") or attn.dim() != 3:
+        raise RuntimeError("alignment_stats: a 3-d attn in layout \"btk\" or \"tbk\", got %s in %r" % (tuple(attn.shape), layout))
+    if layout == "btk":
+        (B, T, Tk), (item_stride, step_stride, key_stride) = attn.shape, attn.stride()
+    else:
+        (T, B, Tk), (step_stride, item_stride, key_stride) = attn.shape, attn.stride()
+    if Tk > 1 and key_stride != 1:
+        raise RuntimeError("alignment_stats: the key axis must be dense (stride %d)" % key_stride)
+    if steps.numel() != B or key_len.numel() != B:
+        raise RuntimeError("alignment_stats: %d steps / %d key lengths for %d items" % (steps.numel(), key_len.numel(), B))
+    out = torch.empty(B, _lib.CONSTS["DV3_ALIGN_COLS"], dtype=torch.float32, device=attn.device)
+    scratch = torch.empty(max(_lib.lib().dv3_alignment_stats_scratch_bytes(B, T), 4), dtype=torch.uint8, device=attn.device)
+    _lib.call("dv3_alignment_stats_f32", attn.data_ptr(), item_stride, step_stride, B, T, Tk, _c(steps).data_ptr(),
+              _c(key_len).data_ptr(), out.data_ptr(), scratch.data_ptr(), _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 # optimiser tail on flat arenas
 # ----------------------------------------------------------------------------------------------

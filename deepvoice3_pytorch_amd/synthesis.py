@@ -20,11 +20,74 @@ and retires (post-net + Griffin-Lim) when its own stop rule fires.
     for ticket, mel, linear, alignment, wav in rs.poll(): ...     # one chunk of decoder steps; what retired in it
     for ... in rs.drain(): ...                   # until the queue and the slots are empty
     for index, mel, linear, alignment, wav in synthesis.tts_stream(model, sequences, slots=64): ...   # completion order
+
+Alignment diagnostics and the end-of-text stop, both opt-in on all three entry points:
+diagnostics=True appends to every result the utterance's alignment statistics (ops.alignment_stats: one small reduction
+on the device over the stored attention rows, one device read per returned group) as a dict keyed by ALIGNMENT_COLUMNS
+plus "flags" (alignment_flags); stall_limit=K stops an utterance K steps after its attention first reached its last
+key when the done flag has not fired by then (decode_program.stall_stop).
+
+    for mel, linear, alignment, wav, stats in synthesis.tts_batch(model, seqs, diagnostics=True, stall_limit=8):
+        if stats["flags"]: ...                   # e.g. ("incomplete", "stalled")
 """
+import collections
+
 import torch
 
 from . import audio
-from .decode_program import RollingSchedule, item_stops
+from .decode_program import ALIGNMENT_COLUMNS, RollingSchedule, end_of_text_stops, item_stops
+
+# Thresholds of alignment_flags.  The defaults are starting points for a user to tune on their own voice: they are NOT
+# measured on any trained model (the repository holds no trained weights).
+#   end_tolerance  "incomplete": furthest_key < keys - 1 - end_tolerance
+#   back_steps     "regressed":  back_steps > back_steps
+#   max_jump       "skipped":    max_jump > max_jump
+#   stall          "stalled":    longest_stall > stall
+#   focus          "unfocused":  focus_mean < focus
+AlignmentLimits = collections.namedtuple("AlignmentLimits", "end_tolerance back_steps max_jump stall focus")
+AlignmentLimits.__new__.__defaults__ = (1, 2, 3, 8, 0.3)
+
+
+def alignment_flags(row, max_steps=None, limits=None):
+    """What an alignment-statistics row says went wrong, on the host: row is a dict keyed by ALIGNMENT_COLUMNS (extra
+    keys ignored) or the 13 values in that order; max_steps: the cap the utterance decoded under (None: "capped" is not
+    judged); limits: an AlignmentLimits (None: the untuned defaults).  -> a sorted tuple of
+    "bad_rows" (some row had no usable maximum), "capped" (ran max_steps + 1 steps: the done flag never fired),
+    "incomplete", "regressed", "skipped", "stalled", "unfocused" (see AlignmentLimits)."""
+    if not isinstance(row, dict):
+        row = dict(zip(ALIGNMENT_COLUMNS, row))
+    lim = limits or AlignmentLimits()
+    flags = []
+    if row["bad_rows"] > 0:
+        flags.append("bad_rows")
+    if max_steps is not None and row["steps"] == int(max_steps) + 1:
+        flags.append("capped")
+    if row["furthest_key"] < row["keys"] - 1 - lim.end_tolerance:
+        flags.append("incomplete")
+    if row["back_steps"] > lim.back_steps:
+        flags.append("regressed")
+    if row["max_jump"] > lim.max_jump:
+        flags.append("skipped")
+    if row["longest_stall"] > lim.stall:
+        flags.append("stalled")
+    if row["focus_mean"] < lim.focus:
+        flags.append("unfocused")
+    return tuple(sorted(flags))
+
+
+def _diagnose(alignments, steps, lengths, caps):
+    """alignments (B, T, Tk) on the device, item b's rows < steps[b] and keys < lengths[b]; caps: each item's
+    max_decoder_steps -> one dict per item: its statistics as Python numbers, and "flags" (one device read)"""
+    from . import ops
+    dev = alignments.device
+    as_i32 = lambda v: torch.tensor([int(x) for x in v], dtype=torch.int32).to(dev)
+    rows = ops.alignment_stats(alignments, as_i32(steps), as_i32(lengths), "btk").tolist()
+    out = []
+    for vals, cap in zip(rows, caps):
+        row = {k: (float(v) if k.startswith("focus") else int(v)) for k, v in zip(ALIGNMENT_COLUMNS, vals)}
+        row["flags"] = alignment_flags(row, cap)
+        out.append(row)
+    return out
 
 
 def check_linear_dim(model, audio_cfg, what):
@@ -34,10 +97,12 @@ def check_linear_dim(model, audio_cfg, what):
     audio.check_bins(model.linear_dim, cfg.fft_size, "%s: model.linear_dim = %d" % (what, model.linear_dim))
 
 
-def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None):
+def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=False, stall_limit=None):
     """sequences: a list of int id sequences (one per utterance); speaker_ids: None or one id per utterance.
     -> a list of (mel (T_b, mel_dim), linear (T_b * upsampling, linear_dim), alignment (steps_b, Tt_b), wav (L_b,)),
-    device tensors, each trimmed to its own utterance."""
+    device tensors, each trimmed to its own utterance.  diagnostics: a fifth element, the utterance's alignment
+    statistics (see the module text); stall_limit: the end-of-text stop (synthesize_batch applies it after the decode:
+    the batch still decodes until its slowest item's done flag, the stopped items' frames past the rule are dropped)."""
     if len(sequences) == 0:
         return []
     check_linear_dim(model, audio_cfg, "tts_batch")
@@ -55,16 +120,21 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None):
     if speaker_ids is not None:
         spk = torch.as_tensor(speaker_ids, dtype=torch.long).reshape(-1).to(dev)
     model.eval()
-    mel, linear, alignments, _, frames = model.synthesize_batch(text, lengths, spk)
+    mel, linear, alignments, _, frames = model.synthesize_batch(text, lengths, spk, stall_limit=stall_limit)
     up = linear.size(1) // mel.size(1)
     steps_per_frame = mel.size(1) // alignments.size(1)        # r
     with torch.no_grad():
         wavs, samples = audio.inv_spectrogram_batch(linear, audio_cfg, frame_lengths=frames * up)
+    stats = None
+    if diagnostics:
+        steps = [int(n) // steps_per_frame for n in frames]
+        stats = _diagnose(alignments, steps, lengths, [model.seq2seq.decoder.max_decoder_steps] * B)
     out = []
     for b in range(B):
         n = int(frames[b])
-        out.append((mel[b, :n], linear[b, :n * up], alignments[b, :n // steps_per_frame, :lengths[b]],
-                    wavs[b, :int(samples[b])]))
+        res = (mel[b, :n], linear[b, :n * up], alignments[b, :n // steps_per_frame, :lengths[b]],
+               wavs[b, :int(samples[b])])
+        out.append(res + (stats[b],) if diagnostics else res)
     return out
 
 
@@ -80,9 +150,18 @@ class RollingSynthesizer(object):
     Everything runs on the current stream, admission and retirement included.  Inference only; a decoder the fused
     step kernels do not take is refused (no module-by-module fallback)."""
 
-    def __init__(self, model, slots=64, max_text_len=256, audio_cfg=None, chunk=8):
+    def __init__(self, model, slots=64, max_text_len=256, audio_cfg=None, chunk=8, diagnostics=False, stall_limit=None):
+        """diagnostics: every retired result gains a last element, the utterance's alignment statistics (one device
+        read per retired group); stall_limit: the end-of-text stop -- after every chunk one statistics call runs in
+        place on the program's stacked alignment buffer over the busy slots, and a slot whose attention reached its
+        last key stall_limit steps ago retires then, if its done flag has not retired it first.  An item's step count
+        does not depend on the chunk size.  Both off by default: no launch and no result changes."""
         if slots < 1 or max_text_len < 1 or chunk < 1:
             raise ValueError("RollingSynthesizer: slots, max_text_len and chunk must be positive")
+        if stall_limit is not None and int(stall_limit) < 0:
+            raise ValueError("RollingSynthesizer: stall_limit must be >= 0 (or None: off)")
+        self.diagnostics = bool(diagnostics)
+        self.stall_limit = None if stall_limit is None else int(stall_limit)
         model.eval()
         self.model, self.audio_cfg = model, audio_cfg
         self.max_text_len = int(max_text_len)
@@ -155,7 +234,7 @@ class RollingSynthesizer(object):
             ops.valid = prev
 
     def _retire(self, retired):
-        """retired: [(ticket, slot, steps)] -> [(ticket, mel, linear, alignment, wav)]"""
+        """retired: [(ticket, slot, steps)] -> [(ticket, mel, linear, alignment, wav)] (+ the statistics dict)"""
         from . import ops
         model = self.model
         dev = self.prog.dev
@@ -180,11 +259,14 @@ class RollingSynthesizer(object):
             up = linear.size(1) // mel.size(1)
             frames = torch.tensor(steps, dtype=torch.int64) * r
             wavs, samples = audio.inv_spectrogram_batch(linear, self.audio_cfg, frame_lengths=frames * up)
+        stats = None
+        if self.diagnostics:
+            stats = _diagnose(alignments, steps, lengths, [self._req[t][2] for t in tickets])
         out = []
         for b, t in enumerate(tickets):
             n = int(frames[b])
-            out.append((t, mel[b, :n], linear[b, :n * up], alignments[b, :steps[b], :lengths[b]],
-                        wavs[b, :int(samples[b])]))
+            res = (t, mel[b, :n], linear[b, :n * up], alignments[b, :steps[b], :lengths[b]], wavs[b, :int(samples[b])])
+            out.append(res + (stats[b],) if self.diagnostics else res)
             del self._req[t]
         return out
 
@@ -202,6 +284,12 @@ class RollingSynthesizer(object):
         n = sch.advance()
         self.prog.run_steps(n)
         flags = self.prog.done_flags()
+        stall = None
+        if self.stall_limit is not None:
+            ran = [0] * sch.n_slots
+            for s in busy:
+                ran[s] = min(sch.steps_run(s), self.prog.t_cap)
+            stall = end_of_text_stops(self.prog.aligns, "tbk", ran, self.prog.key_len, self.stall_limit, self.min_steps)
         retired = []
         for s in busy:
             t1 = sch.steps_run(s)
@@ -209,6 +297,8 @@ class RollingSynthesizer(object):
             rows = [[flags[t][s]] for t in range(t0, min(t1, self.prog.t_cap))]
             stop = [0]
             item_stops(rows, t0, self.min_steps, self._req[sch.slot_ticket[s]][2], stop)
+            if stall is not None and stall[s] and (stop[0] == 0 or stall[s] < stop[0]):
+                stop[0] = stall[s]
             if stop[0]:
                 retired.append((sch.retire(s), s, stop[0]))
         return self._retire(retired) if retired else []
@@ -221,18 +311,20 @@ class RollingSynthesizer(object):
 
 
 def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, audio_cfg=None, chunk=8,
-               max_decoder_steps=None):
+               max_decoder_steps=None, diagnostics=False, stall_limit=None):
     """Rolling-admission counterpart of tts_batch, as a generator: sequences (any iterable of id lists; speaker_ids an
     iterable alongside, or None; max_decoder_steps None, one cap, or an iterable of per-utterance caps) are submitted
     in order as slots free -- at most `slots` are queued ahead -- and every utterance is yielded when it retires, in
     COMPLETION order: (index in `sequences`, mel, linear, alignment, wav), the entries as tts_batch returns them.
-    max_text_len None: the longest sequence (the iterable is then read up front)."""
+    max_text_len None: the longest sequence (the iterable is then read up front).  diagnostics, stall_limit: as
+    RollingSynthesizer takes them (a last element per result; the end-of-text stop)."""
     if max_text_len is None:
         sequences = [list(s) for s in sequences]
         if not sequences:
             return
         max_text_len = max(len(s) for s in sequences)
-    rs = RollingSynthesizer(model, slots=slots, max_text_len=max_text_len, audio_cfg=audio_cfg, chunk=chunk)
+    rs = RollingSynthesizer(model, slots=slots, max_text_len=max_text_len, audio_cfg=audio_cfg, chunk=chunk,
+                            diagnostics=diagnostics, stall_limit=stall_limit)
     it = iter(sequences)
     spk = iter(speaker_ids) if speaker_ids is not None else None
     caps = None

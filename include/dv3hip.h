@@ -1094,6 +1094,49 @@ int dv3_trim_items_f32(const float* x, const int64_t* start, const int64_t* len,
 int dv3_gather_spans_f32(const float* x, const int64_t* start, const int64_t* len, const int64_t* ooff, int32_t B,
                          int64_t max_len, float* y, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Alignment diagnostics for free-running synthesis (synthesis.tts_batch / RollingSynthesizer).
+ * Additions to ABI 49: one entry point, a scratch-size query and a constant; nothing existing changed, so the version
+ * stays 49.
+ *
+ * attn[b * item_stride + t * step_stride + n] (strides in elements) is the probability item b gave key n at its OWN
+ * step t -- the rows the step kernels stored.  Both layouts in use are read in place: the step program's stacked buffer
+ * (t_cap or n_max, B, Tk) with item_stride = Tk, step_stride = B * Tk, and a contiguous (B, T, Tk).  steps[b] is clamped
+ * to [0, T] and key_len[b] to [1, Tk] (device int32[B]); only elements t < T_b = steps[b], n < N_b = key_len[b] are
+ * read, and attn is never written.
+ *
+ * Per row t < T_b:  path[t] = argmax over n < N_b, the FIRST maximum (the rule of dv3_attn_step_f32 and
+ * dv3_attn_argmax_i32, deepvoice3.py:445); a NaN never wins.  peak[t] = max / sum_n P[t, n].  A row whose sum is not
+ * finite or is <= 0, or in which no element wins, is BAD: path = 0, peak = 0.
+ *
+ * out[b] = DV3_ALIGN_COLS fp32 columns (path[-1] = 0; names: synthesis.ALIGNMENT_COLUMNS):
+ *    0 steps         T_b                          1 keys           N_b
+ *    2 focus_mean    mean of peak over t < T_b    3 focus_min      their minimum              (both 0 when T_b = 0)
+ *    4 last_key      path[T_b - 1]; 0 when T_b = 0
+ *    5 furthest_key  max_t path[t]
+ *    6 end_step      first t with path[t] >= N_b - 1; -1 if none
+ *    7 tail_steps    T_b - 1 - end_step when end_step >= 0, otherwise 0
+ *    8 covered_keys  distinct values in path[0 .. T_b)
+ *    9 back_steps    number of t >= 1 with path[t] < path[t - 1]
+ *   10 max_jump      max over t >= 0 of path[t] - path[t - 1], floored at 0
+ *   11 longest_stall longest run of equal consecutive path values; 0 when T_b = 0
+ *   12 bad_rows      number of bad rows
+ * Every column but the two focus ones is an integer, exact in fp32.  The focus columns carry the fp32 row sum's
+ * rounding (lane-strided partial sums, then a 64-lane tree: < 4e-6 relative for Tk <= 4096).
+ *
+ * Two launches: a 64-lane wave per row (rows of an item spread over workgroups) writes path / peak to `scratch`
+ * (>= dv3_alignment_stats_scratch_bytes(B, T) bytes, 4-byte aligned; the query returns 0 for B or T < 1 or when
+ * B * T * 8 does not fit an int), then one wave per item scans them.  No floating-point atomics: two calls give
+ * bit-equal output.  Refused (non-zero, dv3_last_error names the argument, nothing launched): a null pointer; B, T or
+ * Tk < 1; B > 65535; Tk > 4096 (the distinct-key bitmap); out or scratch not 4-byte aligned.
+ * ------------------------------------------------------------------------------------ */
+#define DV3_ALIGN_COLS 13
+int dv3_alignment_stats_scratch_bytes(int32_t B, int32_t T);
+int dv3_alignment_stats_f32(const float* attn, int64_t item_stride, int64_t step_stride,
+                            int32_t B, int32_t T, int32_t Tk,
+                            const int32_t* steps, const int32_t* key_len,
+                            float* out /* B x DV3_ALIGN_COLS */, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
