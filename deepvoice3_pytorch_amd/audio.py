@@ -424,6 +424,41 @@ def mel_tables(device, sample_rate=22050, num_mels=80, fmin=125.0, fmax=7600.0, 
     return _MEL_CACHE[key]
 
 
+_CEPSTRA_CACHE = {}
+
+
+def mel_cepstra_table_np(num_mels, order):
+    """(num_mels, order) float64: column k - 1 is (1 / sqrt 2) (1 / M) cos(pi k (m + 1/2) / M), k = 1 .. order"""
+    M = int(num_mels)
+    if not 1 <= int(order) <= M - 1:
+        raise ValueError("mel_cepstra: order = %d outside [1, %d] (M = %d mel bands; c0 is left out)" % (order, M - 1, M))
+    m = np.arange(M, dtype=np.float64)[:, None] + 0.5
+    k = np.arange(1, int(order) + 1, dtype=np.float64)[None, :]
+    return np.cos(np.pi * k * m / M) / (np.sqrt(2.0) * M)
+
+
+def mel_cepstra(mel, cfg=None, order=13):
+    """Cepstral features of the model's and the dataset's NORMALISED mel spectrogram, (..., M) in [0, 1] -> (..., order):
+
+        f_k = (1 / sqrt 2) (1 / M) sum_m dB_m cos(pi k (m + 1/2) / M),   k = 1 .. order   (c0, the level, is left out)
+        dB  = clip(mel, 0, 1) * (-cfg.min_level_db) + cfg.min_level_db
+
+    With c_k the cepstrum of the natural-log amplitude (ln a = dB ln 10 / 20) and the usual
+    MCD = (10 / ln 10) sqrt(2 sum_k (delta c_k)^2), the Euclidean distance of two feature vectors IS the frame's
+    mel-cepstral distortion in dB -- which is what ops.dtw sums along its path (synthesis.mel_distortion).
+    These are cepstra of the M-band (80) mel spectrogram, NOT SPTK mel-generalised cepstra of a spectral envelope: the
+    figures compare checkpoints, presets and ablations of this model with each other, not with MCD values quoted in
+    papers.  One matmul against a cached (M, order) table; any device (no kernel of its own)."""
+    cfg = cfg or AudioConfig()
+    M = int(mel.shape[-1])
+    key = (str(mel.device), M, int(order))
+    if key not in _CEPSTRA_CACHE:
+        _CEPSTRA_CACHE[key] = torch.from_numpy(mel_cepstra_table_np(M, order).astype(np.float32)).to(mel.device)
+    span = -float(cfg.min_level_db)
+    db = mel.to(torch.float32).clamp(0.0, 1.0) * span - span
+    return torch.matmul(db, _CEPSTRA_CACHE[key])
+
+
 def _check_lws(cfg, what):
     if cfg.convention != "lws":
         raise ValueError("%s: only the lws framing (the reference's features) is supported; the torch framing has no "

@@ -2672,6 +2672,40 @@ def alignment_stats(attn, steps, key_len, layout="btk"):
     return out
 
 
+def dtw(x, y, x_len, y_len, want_path=False):
+    """Batched unconstrained dynamic time warping under the Euclidean frame distance (dv3_dtw_f32, include/dv3hip.h;
+    DESIGN.md 3.6e).  x (B, Tx, D), y (B, Ty, D): fp32, any strided views whose feature axis is dense, read in place;
+    x_len, y_len: int32[B] on the device -- frames at or past an item's lengths are never read.
+    -> out (B, DV3_DTW_COLS) fp32 on the device: cost, path_len, n_diag, n_x_only, n_y_only (ties go to the diagonal,
+    then to the x move, then to the y move); with want_path also path (B, Tx + Ty - 1, 2) int32, rows (i, j) in forward
+    order and (-1, -1) past path_len.  Runs on the current stream; no host synchronisation."""
+    _chk(x, "x")
+    _chk(y, "y")
+    _chk(x_len, "x_len", torch.int32)
+    _chk(y_len, "y_len", torch.int32)
+    if x.dim() != 3 or y.dim() != 3 or x.shape[0] != y.shape[0] or x.shape[2] != y.shape[2]:
+        raise RuntimeError("dtw: x (B, Tx, D) and y (B, Ty, D), got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+    (B, Tx, D), Ty = x.shape, y.shape[1]
+    if x_len.numel() != B or y_len.numel() != B:
+        raise RuntimeError("dtw: %d x lengths / %d y lengths for %d items" % (x_len.numel(), y_len.numel(), B))
+    need = ctypes.c_int64(0)
+    _lib.call("dv3_dtw_scratch_bytes", B, Tx, Ty, int(bool(want_path)), ctypes.byref(need))
+    d = _lib.STRUCTS["dv3_dtw_desc"]()
+    d.x, d.y = x.data_ptr(), y.data_ptr()
+    x_len, y_len = _c(x_len), _c(y_len)
+    d.x_len, d.y_len = x_len.data_ptr(), y_len.data_ptr()
+    d.x_batch_stride, d.x_time_stride, d.x_feat_stride = x.stride()
+    d.y_batch_stride, d.y_time_stride, d.y_feat_stride = y.stride()
+    d.B, d.Tx, d.Ty, d.D = B, Tx, Ty, D
+    out = torch.empty(B, _lib.CONSTS["DV3_DTW_COLS"], dtype=torch.float32, device=x.device)
+    path = torch.empty(B, Tx + Ty - 1, 2, dtype=torch.int32, device=x.device) if want_path else None
+    scratch = torch.empty(need.value, dtype=torch.uint8, device=x.device)
+    d.out, d.path = out.data_ptr(), (path.data_ptr() if want_path else None)
+    d.scratch, d.scratch_bytes = scratch.data_ptr(), need.value
+    _lib.call("dv3_dtw_f32", ctypes.byref(d), _stream())
+    return (out, path) if want_path else out
+
+
 # ----------------------------------------------------------------------------------------------
 # optimiser tail on flat arenas
 # ----------------------------------------------------------------------------------------------

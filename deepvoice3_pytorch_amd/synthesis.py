@@ -29,6 +29,16 @@ key when the done flag has not fired by then (decode_program.stall_stop).
 
     for mel, linear, alignment, wav, stats in synthesis.tts_batch(model, seqs, diagnostics=True, stall_limit=8):
         if stats["flags"]: ...                   # e.g. ("incomplete", "stalled")
+
+Free-running evaluation: how far is the model's own synthesis of a held-out sentence from its
+recording?  evaluate_synthesis decodes (no Griffin-Lim), aligns each utterance with its target by dynamic time warping
+(ops.dtw) under the mel-cepstral distance (audio.mel_cepstra) and returns one row per utterance; SynthEvalTotals folds
+the rows of a set into its MCD (dB per aligned frame pair) and duration ratio.
+
+    totals = synthesis.SynthEvalTotals()
+    for ids, seqs, mels in held_out_batches:
+        totals.add(synthesis.evaluate_synthesis(model, seqs, mels, downsample_step=4), ids)
+    print(totals.result()["mcd"], totals.result()["duration_ratio"])
 """
 import collections
 
@@ -342,3 +352,136 @@ def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, 
                       next(caps) if caps is not None else max_decoder_steps)
         for res in rs.poll():
             yield res
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# free-running evaluation: mel-cepstral distortion along a DTW path, and the duration ratio
+# ----------------------------------------------------------------------------------------------------------------------
+SYNTH_EVAL_COLUMNS = ("mcd_sum", "path_len", "n_diag", "n_synth_only", "n_target_only", "frames_synth", "frames_target")
+
+
+def mel_distortion(mel_a, len_a, mel_b, len_b, cfg=None, order=13, want_path=False):
+    """Mel-cepstral distortion of two padded batches of normalised mel spectrograms along their DTW paths.
+    mel_a (B, Ta, M), mel_b (B, Tb, M) fp32 on the device; len_a, len_b: each item's frames (ints or an int tensor;
+    the frames past them are never read and may hold anything).  The features are audio.mel_cepstra -- cepstra of the
+    mel spectrogram, c0 left out, scaled so that a frame pair's Euclidean distance is its distortion in dB --, ONE
+    matmul over the frames of both batches (equal frames get equal features whichever batch holds them); the alignment is
+    ops.dtw.  -> (B, 7) fp32 on the device, columns SYNTH_EVAL_COLUMNS: mcd_sum is the distortion summed over the
+    path (dB), so mcd_sum / path_len is the utterance's MCD; with want_path also the (B, Ta + Tb - 1, 2) int32 paths,
+    rows (frame of a, frame of b).  No host synchronisation."""
+    from . import ops
+    if mel_a.dim() != 3 or mel_b.dim() != 3 or mel_a.shape[0] != mel_b.shape[0] or mel_a.shape[2] != mel_b.shape[2]:
+        raise ValueError("mel_distortion: (B, Ta, M) and (B, Tb, M), got %s and %s" % (tuple(mel_a.shape), tuple(mel_b.shape)))
+    dev = mel_a.device
+    (B, Ta, M), Tb = mel_a.shape, mel_b.shape[1]
+
+    def lengths(v, T, name):
+        v = torch.as_tensor(v).reshape(-1).to(device=dev, dtype=torch.int32)
+        if v.numel() != B:
+            raise ValueError("mel_distortion: %d %s for %d items" % (v.numel(), name, B))
+        return v.clamp(0, T)
+
+    la, lb = lengths(len_a, Ta, "len_a"), lengths(len_b, Tb, "len_b")
+    rows = torch.cat([mel_a.reshape(B * Ta, M).to(torch.float32), mel_b.reshape(B * Tb, M).to(torch.float32)])
+    feats = audio.mel_cepstra(rows, cfg, order)
+    fa, fb = feats[:B * Ta].view(B, Ta, -1), feats[B * Ta:].view(B, Tb, -1)
+    res = ops.dtw(fa, fb, la, lb, want_path=want_path)
+    out = res[0] if want_path else res
+    table = torch.cat([out, la.to(torch.float32)[:, None], lb.to(torch.float32)[:, None]], dim=1)
+    return (table, res[1]) if want_path else table
+
+
+def evaluate_synthesis(model, sequences, target_mels, speaker_ids=None, downsample_step=4, audio_cfg=None, order=13,
+                       diagnostics=False, stall_limit=None):
+    """How far is the model's own (free-running) synthesis of held-out sentences from their recordings?
+    sequences: a list of int id sequences; target_mels: per utterance the recording's normalised mel (T_b, mel_dim) at
+    the dataset's frame rate (tensor or array), downsampled here as the collate does it, mel[::downsample_step].
+    Decodes with model.synthesize_batch (no Griffin-Lim: no waveform is needed) and runs mel_distortion(synthesised,
+    target) on the device.  -> the (B, 7) table (SYNTH_EVAL_COLUMNS; feed it to SynthEvalTotals); with diagnostics
+    (table, rows): per utterance the alignment statistics dict with its "flags", as tts_batch returns it.
+    stall_limit: the end-of-text stop of synthesize_batch."""
+    B = len(sequences)
+    if B == 0 or len(target_mels) != B:
+        raise ValueError("evaluate_synthesis: %d sequences and %d targets" % (B, len(target_mels)))
+    dev = next(model.parameters()).device
+    lengths = [len(s) for s in sequences]
+    if min(lengths) < 1:
+        raise ValueError("evaluate_synthesis: empty sequence")
+    ds = int(downsample_step)
+    if ds < 1:
+        raise ValueError("evaluate_synthesis: downsample_step = %d < 1" % ds)
+    pad = model.seq2seq.encoder.embed_tokens.padding_idx
+    text = torch.full((B, max(lengths)), 0 if pad is None else pad, dtype=torch.long)
+    for b, s in enumerate(sequences):
+        text[b, :len(s)] = torch.as_tensor(s, dtype=torch.long)
+    spk = None
+    if speaker_ids is not None:
+        spk = torch.as_tensor(speaker_ids, dtype=torch.long).reshape(-1).to(dev)
+    targets = [torch.as_tensor(t)[::ds] for t in target_mels]
+    for b, t in enumerate(targets):
+        if t.dim() != 2 or t.shape[1] != model.mel_dim or t.shape[0] < 1:
+            raise ValueError("evaluate_synthesis: target %d of shape %s, expected (T >= 1, %d)" % (
+                b, tuple(torch.as_tensor(target_mels[b]).shape), model.mel_dim))
+    frames_t = [int(t.shape[0]) for t in targets]
+    tgt = torch.zeros(B, max(frames_t), model.mel_dim, dtype=torch.float32, device=dev)
+    for b, t in enumerate(targets):
+        tgt[b, :frames_t[b]] = t.to(device=dev, dtype=torch.float32)
+    model.eval()
+    mel, _, alignments, _, frames = model.synthesize_batch(text.to(dev), lengths, spk, stall_limit=stall_limit)
+    with torch.no_grad():
+        table = mel_distortion(mel, frames, tgt, frames_t, audio_cfg, order)
+    if not diagnostics:
+        return table
+    r = mel.size(1) // alignments.size(1)
+    rows = _diagnose(alignments, [int(n) // r for n in frames], lengths, [model.seq2seq.decoder.max_decoder_steps] * B)
+    return table, rows
+
+
+class SynthEvalTotals(object):
+    """Accumulates evaluate_synthesis / mel_distortion tables over a held-out set (modelled on train_step.EvalTotals).
+    add() keeps tensors and does not synchronise with the host; result() makes one transfer and sums in float64, in
+    the order the rows were added.  The set-level figures are sums over sums, so they are the same however the set was
+    cut into batches:
+        mcd             sum mcd_sum / sum path_len           (dB per aligned frame pair)
+        duration_ratio  sum frames_synth / sum frames_target
+        n_items, and items: one dict per utterance in the order added -- its columns, "mcd" and "duration_ratio" of its
+        own, and "id" when ids were given -- so utterances can be ranked."""
+
+    def __init__(self):
+        self._tables, self.ids = [], None
+
+    def add(self, table, ids=None):
+        table = table.detach()
+        if table.dim() != 2 or table.shape[1] != len(SYNTH_EVAL_COLUMNS):
+            raise ValueError("SynthEvalTotals.add: a table of shape %s, expected (B, %d)" % (
+                tuple(table.shape), len(SYNTH_EVAL_COLUMNS)))
+        n = int(table.shape[0])
+        if (ids is not None) != (self.ids is not None) and self._tables:
+            raise ValueError("SynthEvalTotals.add: ids for every batch or for none")
+        if ids is not None:
+            ids = list(ids)
+            if len(ids) != n:
+                raise ValueError("SynthEvalTotals.add: %d ids for %d items" % (len(ids), n))
+            self.ids = (self.ids or []) + ids
+        self._tables.append(table.to(torch.float32))
+
+    def result(self):
+        if not self._tables:
+            raise ValueError("SynthEvalTotals.result: nothing was added")
+        rows = torch.cat([t.cpu() for t in self._tables]).double()
+        col = {name: rows[:, i] for i, name in enumerate(SYNTH_EVAL_COLUMNS)}
+        tot = {name: float(sum(col[name].tolist())) for name in SYNTH_EVAL_COLUMNS}      # one order: the rows' own
+        out = {"n_items": int(rows.shape[0])}
+        out.update(tot)
+        out["mcd"] = tot["mcd_sum"] / tot["path_len"] if tot["path_len"] > 0 else float("nan")
+        out["duration_ratio"] = tot["frames_synth"] / tot["frames_target"] if tot["frames_target"] > 0 else float("nan")
+        items = []
+        for b, vals in enumerate(rows.tolist()):
+            it = {k: (v if k == "mcd_sum" else int(v)) for k, v in zip(SYNTH_EVAL_COLUMNS, vals)}
+            it["mcd"] = it["mcd_sum"] / it["path_len"] if it["path_len"] > 0 else float("nan")
+            it["duration_ratio"] = it["frames_synth"] / it["frames_target"] if it["frames_target"] > 0 else float("nan")
+            if self.ids is not None:
+                it["id"] = self.ids[b]
+            items.append(it)
+        out["items"] = items
+        return out

@@ -1137,6 +1137,57 @@ int dv3_alignment_stats_f32(const float* attn, int64_t item_stride, int64_t step
                             const int32_t* steps, const int32_t* key_len,
                             float* out /* B x DV3_ALIGN_COLS */, void* scratch, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Batched dynamic time warping (ops.dtw, synthesis.mel_distortion / evaluate_synthesis).
+ * Additions to ABI 49: a descriptor, one entry point, a scratch-size query and three constants; nothing existing
+ * changed, so the version stays 49.
+ *
+ * For every item b, x[b] (Tx, D) and y[b] (Ty, D) fp32 are read in place through their batch and time strides (in
+ * elements; the feature axis is dense), over the frames i < Lx = x_len[b] and j < Ly = y_len[b] (device int32[B],
+ * clamped to [0, Tx] and [0, Ty]).  Frames at or past a length are NEVER read: they may hold anything, NaN included.
+ *
+ *   local cost   d(i, j) = sqrt(sum_k (x[b,i,k] - y[b,j,k])^2): from the differences themselves, summed in feature order
+ *                in fp32, the square root correctly rounded
+ *   recurrence   C(0, 0) = d(0, 0);  C(i, j) = d(i, j) + min(C(i-1, j-1), C(i-1, j), C(i, j-1)), in fp32
+ *   tie-break    the predecessors are tried in that order -- diagonal, x advances, y advances -- and a later one replaces
+ *                an earlier one only when it is STRICTLY smaller.  Part of the interface: the integer outputs depend on it.
+ *
+ * out[b] = DV3_DTW_COLS fp32 columns:  0 cost = C(Lx-1, Ly-1)   1 path_len   2 n_diag   3 n_x_only   4 n_y_only
+ * -- the moves of the chosen path, carried with the cost through the scan (no backtracking); integers, exact in fp32;
+ * path_len = 1 + n_diag + n_x_only + n_y_only, n_diag + n_x_only = Lx - 1, n_diag + n_y_only = Ly - 1.
+ * path (optional, int32 (B, Tx + Ty - 1, 2)): path[b, s] = (i, j) of the s-th cell of the chosen path, s < path_len, in
+ * forward order from (0, 0) to (Lx-1, Ly-1); every row s >= path_len is (-1, -1).  `out` does not depend on `path`.
+ * An item with a zero length: all five columns 0, its path all -1.  An item with a non-finite feature inside its
+ * lengths (or whose squared distance overflows fp32): cost = NaN, its other columns and its path unspecified (valid
+ * memory, no fault); the other items are untouched.
+ *
+ * Three launches (two without a path): a tiled distance pass writes d to scratch, one 64-lane wave per item scans the
+ * recurrence (rows pipelined across lanes, each lane a strip of ceil(Ty / 64) columns), one workgroup per item walks the
+ * stored direction bytes back.  scratch: >= dv3_dtw_scratch_bytes(...) bytes = B * Tx * Ty * (4 + (want_path ? 1 : 0)),
+ * 4-byte aligned; the size goes out through the pointer (it passes 2^31 at accepted sizes).  No atomics: two calls give
+ * bit-equal output.  Refused (DV3_EINVAL, dv3_last_error names the numbers, nothing launched): a null pointer (path
+ * excepted); B < 1; Tx or Ty outside [1, DV3_DTW_MAX_T]; D outside [1, DV3_DTW_MAX_D]; a feature stride other than 1
+ * (D > 1); scratch_bytes below the query; out, path or scratch not 4-byte aligned.
+ * ------------------------------------------------------------------------------------ */
+#define DV3_DTW_COLS 5
+#define DV3_DTW_MAX_T 4096
+#define DV3_DTW_MAX_D 128
+typedef struct dv3_dtw_desc {
+  const float* x;                            /* (B, Tx, D) through the strides below                                  */
+  const float* y;                            /* (B, Ty, D)                                                            */
+  const int32_t* x_len;                      /* device int32[B]                                                       */
+  const int32_t* y_len;
+  int64_t x_batch_stride, x_time_stride, x_feat_stride;     /* in elements; x_feat_stride must be 1 (any when D = 1)  */
+  int64_t y_batch_stride, y_time_stride, y_feat_stride;
+  int32_t B, Tx, Ty, D;
+  float* out;                                /* B x DV3_DTW_COLS                                                      */
+  int32_t* path;                             /* null, or B x (Tx + Ty - 1) x 2                                        */
+  void* scratch;
+  int64_t scratch_bytes;
+} dv3_dtw_desc;
+int dv3_dtw_scratch_bytes(int32_t B, int32_t Tx, int32_t Ty, int32_t want_path, int64_t* bytes_out);
+int dv3_dtw_f32(const dv3_dtw_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
