@@ -2733,6 +2733,37 @@ def clip_adam(p, g, m, v, grad_norm, clip, hyper, beta1, beta2, eps, weight_deca
               float(weight_decay), float(grad_prescale), _stream())
 
 
+def _flat_f32(t, name, n=None):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise RuntimeError("%s: a contiguous fp32 tensor on the GPU is required" % name)
+    if n is not None and t.numel() != n:
+        raise RuntimeError("%s: %d elements, expected %d" % (name, t.numel(), n))
+
+
+def clip_adam_ema(p, g, m, v, ema, grad_norm, clip, hyper, beta1, beta2, eps, weight_decay=0.0, grad_prescale=1.0):
+    """clip_adam (p, m, v bit for bit as there) and, in the same pass, ema += hyper[3] * (p' - ema): `hyper` holds
+    four floats here, {lr, 1 - beta1^t, sqrt(1 - beta2^t), 1 - decay_t} (dv3_clip_adam_ema_f32)"""
+    n = p.numel()
+    for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema")):
+        _flat_f32(t, "clip_adam_ema: " + name, n)
+    _flat_f32(hyper, "clip_adam_ema: hyper")
+    if hyper.numel() < 4:
+        raise RuntimeError("clip_adam_ema: hyper holds %d floats, four are read" % hyper.numel())
+    bump_param_epoch()
+    _lib.call("dv3_clip_adam_ema_f32", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), n,
+              _ptr(grad_norm), float(clip), hyper.data_ptr(), float(beta1), float(beta2), float(eps),
+              float(weight_decay), float(grad_prescale), _stream())
+
+
+def swap_(a, b):
+    """exchange the contents of two fp32 buffers of one size in place (dv3_swap_f32: one pass, no third buffer; the
+    same or overlapping buffers are refused).  Either may be a parameter arena: the parameter epoch moves on."""
+    _flat_f32(a, "swap_: a")
+    _flat_f32(b, "swap_: b", a.numel())
+    bump_param_epoch()
+    _lib.call("dv3_swap_f32", a.data_ptr(), b.data_ptr(), a.numel(), _stream())
+
+
 def conv_step_fits(k, cin):
     """does dv3_conv_step_f32 (the fused decode step, csrc/decode_step.hip) take a k-tap layer with `cin` input
     channels?  Asked of the library itself (dv3_conv_step_lds_bytes), so the Python predicate can not drift from the

@@ -33,7 +33,7 @@ class TrainConfig(object):
                  guided_attention_sigma=0.2, clip_thresh=0.1, adam_beta1=0.5, adam_beta2=0.9,
                  adam_eps=1e-6, weight_decay=0.0, initial_learning_rate=5e-4,
                  lr_schedule="noam_learning_rate_decay", lr_schedule_kwargs=None, max_positions=512,
-                 range_check_every=0, amsgrad=False):
+                 range_check_every=0, amsgrad=False, ema_decay=0.0, ema_warmup=True):
         self.outputs_per_step = outputs_per_step
         self.downsample_step = downsample_step
         self.masked_loss_weight = masked_loss_weight
@@ -60,6 +60,23 @@ class TrainConfig(object):
         # bf16x3 mode when operands left the fp16 range; 0 = never read it on the host (the counter is still in
         # every step's scalars as a device tensor, "f16_range_events")
         self.range_check_every = range_check_every
+        # weight averaging: an exponential moving average of the arena's parameters, taken inside the
+        # fused clip + Adam pass.  0 = off (nothing is allocated, the step is the one it was); ema_warmup: the decay of
+        # step t is min(ema_decay, (1 + t) / (10 + t)) (ema_decay_at)
+        ema_decay = float(ema_decay)
+        if ema_decay != 0.0 and not 0.0 < ema_decay < 1.0:
+            raise ValueError("ema_decay must be 0 (no averaging) or lie strictly between 0 and 1, got %r" % (ema_decay,))
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
+
+
+def ema_decay_at(t, ema_decay, warmup=True):
+    """The decay d_t of the moving average at optimiser step t = 1, 2, ... (Trainer.adam_step):
+    e_t = d_t e_(t-1) + (1 - d_t) p_t.  With warm-up d_t = min(ema_decay, (1 + t) / (10 + t)) -- the `num_updates` rule
+    of tf.train.ExponentialMovingAverage: early steps weigh the young average lightly -- else ema_decay throughout."""
+    d = float(ema_decay)
+    if warmup:
+        d = min(d, (1.0 + t) / (10.0 + t))
+    return d
 
 
 def noam_learning_rate_decay(init_lr, global_step, warmup_steps=4000):
@@ -124,7 +141,7 @@ class FlatArena(object):
     registration order and bucket from the tail (converter -> decoder -> encoder), which is the
     order backward produces gradients in."""
 
-    def __init__(self, params):
+    def __init__(self, params, ema=False):
         params = list(params)
         self.params = params
         dev = params[0].device
@@ -144,6 +161,8 @@ class FlatArena(object):
             p.data = self.flat[o:o + n].view(p.shape)
             p.grad = self.grad[o:o + n].view(p.shape)
             p._dv3_grad_inplace = True   # ops.ConvLayerFn accumulates straight into p.grad
+        # the moving average of `flat` (TrainConfig.ema_decay > 0 only): starts as the parameters themselves
+        self.ema = self.flat.clone() if ema else None
 
     def rebind(self):
         """Every parameter's .grad must BE its slice of the gradient arena (clip/Adam and the all-reduce
@@ -191,7 +210,9 @@ class Trainer(object):
             late = set(id(p) for n, p in model.named_parameters() if ".speaker_proj." in "." + n)
             self.late_group = [p for p in params if id(p) in late]
             params = [p for p in params if id(p) not in late] + self.late_group
-        self.arena = FlatArena(params)
+        self.ema_on = cfg.ema_decay > 0
+        self.arena = FlatArena(params, ema=self.ema_on)
+        self._swapped = False             # inside averaged(): arena.flat holds the average, arena.ema the raw weights
         # parameters the optimizer does not own (the frozen position tables, the text embedding under
         # freeze_embedding; reference __init__.py:48-63) take no gradient at all: a .grad outside the arena
         # would never be zeroed and only cost backward work
@@ -204,13 +225,14 @@ class Trainer(object):
         dev = self.arena.flat.device
         self.device = dev
         self._prepack = None
-        self.hyper = torch.zeros(3, dtype=torch.float32, device=dev)
-        # (lr, 1-b1^t, sqrt(1-b2^t)) travel through a RING of pinned host slots: step() never waits for the
+        self.hyper = torch.zeros(4, dtype=torch.float32, device=dev)
+        # (lr, 1-b1^t, sqrt(1-b2^t), 1-d_t -- the last read by the averaging step only) travel through
+        # a RING of pinned host slots: step() never waits for the
         # GPU, so the host may run steps ahead of it; a single staging buffer would be overwritten by step
         # N+1 before step N's queued copy has executed.  A slot is reused only after the copy that read it
         # has completed (its event), i.e. the host can lead by at most HYPER_SLOTS - 1 steps.
-        self._hyper_ring = [(torch.zeros(3, dtype=torch.float32).pin_memory() if dev.type == "cuda"
-                             else torch.zeros(3)) for _ in range(self.HYPER_SLOTS)]
+        self._hyper_ring = [(torch.zeros(4, dtype=torch.float32).pin_memory() if dev.type == "cuda"
+                             else torch.zeros(4)) for _ in range(self.HYPER_SLOTS)]
         self._hyper_events = [None] * self.HYPER_SLOTS
         self._hyper_slot = 0
         self.norm_partial = torch.empty(1024, dtype=torch.float32, device=dev)
@@ -290,6 +312,8 @@ class Trainer(object):
         h[0] = float(self.current_lr())
         h[1] = 1.0 - c.adam_beta1 ** t
         h[2] = math.sqrt(1.0 - c.adam_beta2 ** t)
+        # 1 - d_t in double, rounded once: on the device, so a replayed graph takes each step's own decay
+        h[3] = 1.0 - ema_decay_at(t, c.ema_decay, c.ema_warmup) if self.ema_on else 0.0
         self.hyper.copy_(h, non_blocking=True)
         if self.device.type == "cuda":
             ev = self._hyper_events[i] or torch.cuda.Event()
@@ -478,7 +502,60 @@ Please set a larger value for ``max_position`` in hyper parameters.""".format(ma
         return {k: v.detach() for k, v in scal.items()}
 
     # ------------------------------------------------------------------------------------
-    def evaluate(self, batch):
+    def _refuse_swapped(self, what):
+        if self._swapped:
+            raise RuntimeError("%s inside Trainer.averaged(): the arena holds the averaged weights; an update there would "
+                               "train the average and average the raw weights" % what)
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """`with trainer.averaged():` -- the model computes with the moving average of its trained parameters
+        (TrainConfig.ema_decay > 0): evaluate(), synthesis, export.  arena.flat and arena.ema are exchanged BY CONTENT
+        (ops.swap_, one pass; on a CPU trainer with torch copies) and exchanged back on exit: the parameter views and
+        every captured graph keep their addresses into arena.flat, the raw weights return bit for bit, and the
+        parameter epoch moves both times, so the eval-mode packed weights and the decode-step graph are rebuilt.
+        Inside, step(), optimizer_step(), a replay, checkpoint_dict() and load_checkpoint() raise RuntimeError; so does
+        nesting.  Parameters outside the arena (frozen tables, the other sub-module of a split mode) are not touched."""
+        if not self.ema_on:
+            raise ValueError("Trainer.averaged: weight averaging is off (TrainConfig(ema_decay=...) is 0)")
+        if self._swapped:
+            raise RuntimeError("Trainer.averaged: already inside averaged() (the context does not nest)")
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("Trainer.averaged: called while a stream capture is in progress")
+        self._exchange()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._exchange()
+            self._swapped = False
+
+    def _exchange(self):
+        a = self.arena
+        if self.device.type == "cuda":
+            ops.swap_(a.flat, a.ema)
+        else:
+            with torch.no_grad():
+                raw = a.flat.clone()
+                a.flat.copy_(a.ema)
+                a.ema.copy_(raw)
+            ops.bump_param_epoch()
+
+    def averaged_state(self):
+        """{state_dict name (of checkpoint_module()): averaged tensor} for the arena's parameters, as copies"""
+        if not self.ema_on:
+            raise ValueError("Trainer.averaged_state: weight averaging is off (TrainConfig(ema_decay=...) is 0)")
+        a = self.arena
+        avg = a.flat if self._swapped else a.ema
+        slot = {id(p): (o, n) for o, n, p in zip(a.offsets, a.sizes, a.params)}
+        out = {}
+        for name, p in self.checkpoint_module().named_parameters():
+            if id(p) in slot:
+                o, n = slot[id(p)]
+                out[name] = avg[o:o + n].view(p.shape).detach().clone()
+        return out
+
+    def evaluate(self, batch, averaged=False):
         """Held-out evaluation of one batch: the model's eval-mode (dropout off), teacher-forced forward on the batch as
         collated -- the reference's `model.eval(); model(x, mel, ...)` -- and its losses, without gradients.  -> a dict
         of device tensors: the batch scalars under the keys step() uses (the existing loss kernels with this trainer's
@@ -487,7 +564,14 @@ Please set a larger value for ``max_position`` in hyper parameters.""".format(ma
         Training is left as it is: parameters, gradients, moments, step counters, the hyper ring and the dropout state
         (seed, site numbering, step counter, planned masks) are not touched and model.training is restored, so the
         call may sit between two steps or two replays of a GraphedTrainer / LatticeReplay.  Eager launches on the
-        current stream; not capturable."""
+        current stream; not capturable.
+        averaged=True: the same with the moving average of the trained parameters in their place, i.e. inside
+        `with self.averaged():` (ValueError when TrainConfig.ema_decay is 0)."""
+        if averaged:
+            if not self.ema_on:
+                raise ValueError("Trainer.evaluate(averaged=True): weight averaging is off (TrainConfig(ema_decay=...) is 0)")
+            with self.averaged():
+                return self.evaluate(batch)
         if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("Trainer.evaluate: called while a stream capture is in progress (evaluation runs eagerly, "
                                "between steps)")
@@ -584,17 +668,23 @@ Please set a larger value for ``max_position`` in hyper parameters.""".format(ma
         """reduce=False: the caller has already issued and joined the gradient all-reduces (GraphedTrainer's segmented
         replay issues them from the host between segment launches)"""
         c, a = self.cfg, self.arena
+        self._refuse_swapped("Trainer.optimizer_step")
         if self.comm is not None and reduce:
             self.comm.finish()           # all buckets reduced (sum); 1/world folded into grad_prescale
         prescale = 1.0 / self.world
         if c.clip_thresh > 0:
             ops.grad_sqnorm(a.grad, self.norm_partial, self.norm_out)   # norm of the SUMMED gradient
-        ops.clip_adam(a.flat, a.grad, a.exp_avg, a.exp_avg_sq, self.norm_out if c.clip_thresh > 0 else None,
-                      c.clip_thresh, self.hyper, c.adam_beta1, c.adam_beta2, c.adam_eps, c.weight_decay,
-                      prescale)
+        norm = self.norm_out if c.clip_thresh > 0 else None
+        if self.ema_on:      # the same update (bit for bit) and the average of its result, one pass over the arena
+            ops.clip_adam_ema(a.flat, a.grad, a.exp_avg, a.exp_avg_sq, a.ema, norm, c.clip_thresh, self.hyper,
+                              c.adam_beta1, c.adam_beta2, c.adam_eps, c.weight_decay, prescale)
+        else:
+            ops.clip_adam(a.flat, a.grad, a.exp_avg, a.exp_avg_sq, norm, c.clip_thresh, self.hyper, c.adam_beta1,
+                          c.adam_beta2, c.adam_eps, c.weight_decay, prescale)
 
     def step(self, batch):
         """One full optimisation step; returns device scalars (loss terms, grad_norm, lr)."""
+        self._refuse_swapped("Trainer.step")
         self.check_lengths(batch)        # host-side numpy on the batch's length vectors: no device sync
         self._set_hyper()
         self._zero_grad()
@@ -723,6 +813,7 @@ class GraphedTrainer(object):
         self.t = trainer
         self.batch = static_batch
         self._pool = pool
+        trainer._refuse_swapped("GraphedTrainer: a capture")
         trainer.check_lengths(static_batch)
         dev = trainer.device
         if split_streams is None:
@@ -974,6 +1065,7 @@ class GraphedTrainer(object):
         st.decoder_lengths_host, st.n_frames = batch.decoder_lengths_host, batch.n_frames
 
     def step(self, batch=None):
+        self.t._refuse_swapped("GraphedTrainer.step")
         if batch is not None:
             self.load(batch)
         self.t._set_hyper()
@@ -1035,10 +1127,10 @@ class GraphedTrainer(object):
                                    "backward streams do not run side by side here; set DV3_FLAG_SYNC=0" % n)
         return self.scal
 
-    def evaluate(self, batch):
+    def evaluate(self, batch, averaged=False):
         """Trainer.evaluate on `batch` (any shape, not copied into the static batch): eager launches on the current
-        stream, between two replays; sees the weights the last replay wrote"""
-        return self.t.evaluate(batch)
+        stream, between two replays; sees the weights the last replay wrote (averaged=True: their moving average)"""
+        return self.t.evaluate(batch, averaged=averaged)
 
     def bucket_order(self):
         """the bucket ids in the order a replay issues their all-reduces from the host (segmented form under a process
@@ -1192,6 +1284,7 @@ class LatticeReplay(object):
 
     def step(self, batch):
         import time
+        self.t._refuse_swapped("LatticeReplay.step")
         key = self.key_of(batch)
         g = self.graphs.get(key)
         if g is None:
@@ -1211,9 +1304,9 @@ class LatticeReplay(object):
         self.stats["replays"] += 1
         return g.step(batch)
 
-    def evaluate(self, batch):
+    def evaluate(self, batch, averaged=False):
         """Trainer.evaluate on `batch` (lattice-padded or not): eager, no capture is made or replayed for it"""
-        return self.t.evaluate(batch)
+        return self.t.evaluate(batch, averaged=averaged)
 
     def check_range(self):
         """the f16x3 range guard (GraphedTrainer.check_range): > 0 = the process has moved to bf16x3, every capture of
@@ -1339,14 +1432,19 @@ class EvalTotals(object):
         return out
 
 
-def evaluate_loader(trainer, batches, process_group=None):
+def evaluate_loader(trainer, batches, process_group=None, averaged=False):
     """EvalTotals over `trainer.evaluate(b)` for b in batches (a Trainer, GraphedTrainer or LatticeReplay; a batch's
     `ids` attribute, when it has one, names its items) -> EvalTotals.result(process_group).  Under a process group
-    every rank calls it, with an empty `batches` where its shard is empty."""
+    every rank calls it, with an empty `batches` where its shard is empty.
+    averaged=True: the whole set under the moving average of the trained parameters (one exchange in, one out;
+    ValueError when TrainConfig.ema_decay is 0)."""
     t = trainer if isinstance(trainer, Trainer) else trainer.t
+    if averaged and not t.ema_on:
+        raise ValueError("evaluate_loader(averaged=True): weight averaging is off (TrainConfig(ema_decay=...) is 0)")
     tot = EvalTotals(t.cfg.binary_divergence_weight, scalar_keys=t.eval_scalar_keys())
-    for b in batches:
-        tot.add(trainer.evaluate(b), getattr(b, "ids", None))
+    with (t.averaged() if averaged else contextlib.nullcontext()):
+        for b in batches:
+            tot.add(trainer.evaluate(b), getattr(b, "ids", None))
     return tot.result(process_group)
 
 
@@ -1354,10 +1452,14 @@ def evaluate_loader(trainer, batches, process_group=None):
 # checkpoint interop with the reference (train.py:788-867): same file name, same dict
 #   {"state_dict", "optimizer" (torch.optim.Adam.state_dict() layout), "global_step", "global_epoch"}
 # so a run can move between the reference trainer and this one in either direction.
+# With weight averaging on (TrainConfig.ema_decay > 0) one more key, "ema_state_dict": the averaged tensors under the
+# "state_dict" names of the arena's parameters.  The reference's loader reads its own four keys and ignores it.
 # ------------------------------------------------------------------------------------------------
 def checkpoint_dict(trainer, global_epoch=0, save_optimizer_state=True):
-    """The dict train.save_checkpoint writes (train.py:800-807), from the flat arena."""
+    """The dict train.save_checkpoint writes (train.py:800-807), from the flat arena (plus "ema_state_dict" when the
+    trainer averages its weights; exactly the reference's keys when it does not)."""
     a, c = trainer.arena, trainer.cfg
+    trainer._refuse_swapped("checkpoint_dict")
     opt = None
     if save_optimizer_state:
         state = {}
@@ -1374,8 +1476,26 @@ def checkpoint_dict(trainer, global_epoch=0, save_optimizer_state=True):
                      weight_decay=c.weight_decay, amsgrad=False, maximize=False, foreach=None, capturable=False,
                      differentiable=False, fused=None, params=list(range(len(trainer.optimizer_order))))
         opt = dict(state=state, param_groups=[group])
-    return {"state_dict": {k: v.detach().clone() for k, v in trainer.checkpoint_module().state_dict().items()},
-            "optimizer": opt, "global_step": trainer.global_step, "global_epoch": global_epoch}
+    ck = {"state_dict": {k: v.detach().clone() for k, v in trainer.checkpoint_module().state_dict().items()},
+          "optimizer": opt, "global_step": trainer.global_step, "global_epoch": global_epoch}
+    if trainer.ema_on:
+        ck["ema_state_dict"] = trainer.averaged_state()
+    return ck
+
+
+def export_averaged(trainer, path=None, global_epoch=0):
+    """What a user ships: a checkpoint whose "state_dict" holds the AVERAGED weights for the arena's parameters and the
+    current values for everything else (frozen tables, buffers), without optimizer state and without "ema_state_dict" --
+    the reference's four keys, so train.load_checkpoint, load_checkpoint(..., reset_optimizer=True) and restore_parts
+    all take it.  Covers checkpoint_module() (the trained sub-module in a split mode), as checkpoint_dict does.
+    -> the dict; written to `path` when one is given."""
+    sd = {k: v.detach().clone() for k, v in trainer.checkpoint_module().state_dict().items()}
+    for k, v in trainer.averaged_state().items():
+        sd[k] = v
+    ck = {"state_dict": sd, "optimizer": None, "global_step": trainer.global_step, "global_epoch": global_epoch}
+    if path is not None:
+        torch.save(ck, path)
+    return ck
 
 
 def save_checkpoint(trainer, checkpoint_dir, global_epoch=0, save_optimizer_state=True):
@@ -1419,9 +1539,15 @@ def load_checkpoint(path_or_dict, trainer, reset_optimizer=False, unsafe=False, 
     sub-module.  The optimizer state of such a partial file covers its own parameters only: the moments of the others
     stay as they are, and since one `adam_step` serves the whole arena the file's step count is taken only when
     EVERY parameter of the arena got a state (otherwise the moments are loaded and the bias corrections keep the
-    trainer's own count: pass reset_optimizer=True for the reference's behaviour of a fresh optimizer)."""
+    trainer's own count: pass reset_optimizer=True for the reference's behaviour of a fresh optimizer).
+
+    Weight averaging (TrainConfig.ema_decay > 0): the file's "ema_state_dict" is restored into arena.ema; its names and
+    shapes must be those of the arena's parameters inside the loaded module (RuntimeError naming the keys otherwise).
+    A file without the key -- the reference's, or a run that did not average -- is not an error: the average of the
+    loaded parameters starts again from the loaded weights.  A trainer that does not average ignores the key."""
     ck = path_or_dict if isinstance(path_or_dict, dict) else _load_file(path_or_dict, unsafe)
     a = trainer.arena
+    trainer._refuse_swapped("load_checkpoint")
     with torch.no_grad():     # copy INTO the arena views (load_state_dict would keep them too; be explicit)
         target = module if module is not None else trainer.checkpoint_module()
         if module is None and target is trainer.model:
@@ -1434,8 +1560,24 @@ def load_checkpoint(path_or_dict, trainer, reset_optimizer=False, unsafe=False, 
         unexpected = [k for k in ck["state_dict"] if k not in own]
         if missing or unexpected:
             raise RuntimeError("state_dict mismatch: missing %s unexpected %s" % (missing, unexpected))
+        avg = mine = None
+        if trainer.ema_on:        # (checked before anything is written)
+            slot = {id(p): (o, n) for o, n, p in zip(a.offsets, a.sizes, a.params)}
+            mine = {k: p for k, p in target.named_parameters() if id(p) in slot}
+            avg = ck.get("ema_state_dict")
+            if avg is not None:
+                missing = [k for k in mine if k not in avg]
+                unexpected = [k for k in avg if k not in mine]
+                shapes = [k for k in mine if k in avg and tuple(avg[k].shape) != tuple(mine[k].shape)]
+                if missing or unexpected or shapes:
+                    raise RuntimeError("ema_state_dict mismatch: missing %s unexpected %s wrong shape %s"
+                                       % (missing, unexpected, shapes))
         for k, v in ck["state_dict"].items():
             own[k].copy_(v)
+        if mine is not None:      # the file's average, or (no key) the loaded weights themselves
+            for k, p in mine.items():
+                o, n = slot[id(p)]
+                a.ema[o:o + n].copy_((avg[k] if avg is not None else p.detach()).reshape(-1))
     opt = ck.get("optimizer")
     if opt is not None and not reset_optimizer:
         if len(opt["param_groups"]) != 1 or len(opt["param_groups"][0]["params"]) != len(trainer.optimizer_order):

@@ -740,6 +740,21 @@ int dv3_clip_adam_f32(float* p, const float* g, float* m, float* v, int64_t n,
                       const float* grad_norm, float clip, const float* hyper, float beta1,
                       float beta2, float eps, float weight_decay, float grad_prescale,
                       void* stream);
+/* Weight averaging (additive entry points, ABI 49 as before).  dv3_clip_adam_ema_f32 is
+ * dv3_clip_adam_f32 -- p, m, v come out bit for bit as there -- followed, for the same element in the same pass, by the
+ * exponential moving average of the updated parameter in its increment form
+ *     ema' = ema + hyper[3] * (p' - ema),      hyper (device) = {lr, 1-beta1^t, sqrt(1-beta2^t), 1 - decay_t}
+ * (hyper[3] = 0 leaves ema as it is, hyper[3] = 1 copies p'; both exactly).  5 reads + 4 writes of 4 B per parameter.
+ * 16 bytes per lane when p, g, m, v and ema are all 16-byte aligned (slices of the flat arenas are), one element at a
+ * time otherwise.  ema must not overlap p.
+ * dv3_swap_f32 exchanges the contents of two buffers of n floats in place, in one pass: a == b or overlapping ranges
+ * are refused (DV3_EINVAL).  Parameter views and captured graphs hold raw addresses into the parameter arena, so
+ * averaged weights are put in their place by content.                                                              */
+int dv3_clip_adam_ema_f32(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
+                          const float* grad_norm, float clip, const float* hyper, float beta1,
+                          float beta2, float eps, float weight_decay, float grad_prescale,
+                          void* stream);
+int dv3_swap_f32(float* a, float* b, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Autoregressive decode step (Decoder.incremental_forward, deepvoice3.py:397-473): two fused kernels per
