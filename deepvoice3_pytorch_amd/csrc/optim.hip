@@ -2,7 +2,8 @@
 // (torch.nn.utils.clip_grad_norm_) + Adam, over ONE flat fp32 parameter arena (all trainable
 // parameters are views into it; so are the gradients, which is also what the RCCL all-reduce
 // buckets slice).  HBM-bound: 4 reads + 3 writes of 4 B per parameter; 5 + 4 with the moving average of the
-// parameters taken in the same pass.
+// parameters taken in the same pass.  The guarded forms of both passes return before
+// the streaming loop when the gradient norm is not finite.
 #include "common.h"
 
 namespace {
@@ -43,14 +44,32 @@ __global__ __launch_bounds__(256) void sqnorm_finish_kernel(const float* __restr
   }
 }
 
+// The guard of the guarded passes: s = grad_norm[0] is the same word in every workgroup, so the whole
+// grid takes one decision.  Not finite (a NaN / Inf gradient element, or a sum of squares past the fp32 range): true is
+// returned and the caller leaves before its streaming loop -- nothing of p, m, v (, ema) is read or written.  Lane 0 of
+// block 0 is the single writer of the two health words (plain stores): health[0] counts the skipped passes (fp32, exact
+// to 2^24), health[1] is 1 after a skipped pass and 0 after an applied one.
+__device__ __forceinline__ bool guard_skips(const float* __restrict__ grad_norm, float* __restrict__ health) {
+  const bool skip = (__float_as_uint(grad_norm[0]) & 0x7f800000u) == 0x7f800000u;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (skip) health[0] += 1.0f;
+    health[1] = skip ? 1.0f : 0.0f;
+  }
+  return skip;
+}
+
 // hyper = {lr, 1 - beta1^t, sqrt(1 - beta2^t)} on the device (graph-replay friendly).
-__global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p,
-                                                        const float* __restrict__ g,
-                                                        float* __restrict__ m, float* __restrict__ v,
-                                                        int64_t n, const float* __restrict__ grad_norm,
-                                                        float clip, const float* __restrict__ hyper,
-                                                        float beta1, float beta2, float eps,
-                                                        float weight_decay, float grad_prescale) {
+// GUARD: the guarded pass (dv3_clip_adam_guard_f32); after the early return the code is the unguarded kernel's, so an
+// applied step writes the same bits (tests/test_gpu_health.py holds the two together).
+template <bool GUARD>
+__device__ __forceinline__ void clip_adam_body(float* __restrict__ p, const float* __restrict__ g,
+                                               float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                               const float* __restrict__ grad_norm, float clip,
+                                               const float* __restrict__ hyper, float beta1, float beta2, float eps,
+                                               float weight_decay, float grad_prescale, float* __restrict__ health) {
+  if (GUARD) {
+    if (guard_skips(grad_norm, health)) return;
+  }
   float coef = grad_prescale;
   if (clip > 0.f && grad_norm) {
     // clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
@@ -72,6 +91,25 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p,
     const float denom = sqrtf(vi) / bc2s + eps;
     p[i] = pi - step_size * (mi / denom);
   }
+}
+
+__global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p,
+                                                        const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v,
+                                                        int64_t n, const float* __restrict__ grad_norm,
+                                                        float clip, const float* __restrict__ hyper,
+                                                        float beta1, float beta2, float eps,
+                                                        float weight_decay, float grad_prescale) {
+  clip_adam_body<false>(p, g, m, v, n, grad_norm, clip, hyper, beta1, beta2, eps, weight_decay, grad_prescale, nullptr);
+}
+
+__global__ __launch_bounds__(256) void clip_adam_guard_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                              float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                              const float* __restrict__ grad_norm, float clip,
+                                                              const float* __restrict__ hyper, float beta1, float beta2,
+                                                              float eps, float weight_decay, float grad_prescale,
+                                                              float* __restrict__ health) {
+  clip_adam_body<true>(p, g, m, v, n, grad_norm, clip, hyper, beta1, beta2, eps, weight_decay, grad_prescale, health);
 }
 
 // One element of clip_adam_kernel followed by the moving average of the updated parameter, in its increment form
@@ -111,14 +149,19 @@ __device__ __forceinline__ void adam_ema_elem(float& p_io, const float g_in, flo
 // step and nowhere else before the next one: their 16-byte accesses are non-temporal (measured on the arena of the
 // 25.6 M-parameter preset: 140 us against 166 us with plain accesses); the updated parameters, which the
 // next forward reads first, are stored plainly (storing them non-temporally too measured slower).
-__global__ __launch_bounds__(256) void clip_adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                            float* __restrict__ m, float* __restrict__ v,
-                                                            float* __restrict__ e, int64_t n, int64_t n4,
-                                                            const float* __restrict__ grad_norm, float clip,
-                                                            const float* __restrict__ hyper, float beta1,
-                                                            float beta2, float eps, float weight_decay,
-                                                            float grad_prescale) {
+// GUARD: the guarded pass (dv3_clip_adam_ema_guard_f32), as in clip_adam_body.
+template <bool GUARD>
+__device__ __forceinline__ void clip_adam_ema_body(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v,
+                                                   float* __restrict__ e, int64_t n, int64_t n4,
+                                                   const float* __restrict__ grad_norm, float clip,
+                                                   const float* __restrict__ hyper, float beta1, float beta2,
+                                                   float eps, float weight_decay, float grad_prescale,
+                                                   float* __restrict__ health) {
 #pragma clang fp contract(off)
+  if (GUARD) {
+    if (guard_skips(grad_norm, health)) return;
+  }
   float coef = grad_prescale;
   if (clip > 0.f && grad_norm) {
     // clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
@@ -153,6 +196,28 @@ __global__ __launch_bounds__(256) void clip_adam_ema_kernel(float* __restrict__ 
     adam_ema_elem(pk, g[i], mk, vk, ek, coef, step_size, bc2s, beta1, beta2, eps, weight_decay, w, w_zero, w_one);
     p[i] = pk, m[i] = mk, v[i] = vk, e[i] = ek;
   }
+}
+
+__global__ __launch_bounds__(256) void clip_adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v,
+                                                            float* __restrict__ e, int64_t n, int64_t n4,
+                                                            const float* __restrict__ grad_norm, float clip,
+                                                            const float* __restrict__ hyper, float beta1,
+                                                            float beta2, float eps, float weight_decay,
+                                                            float grad_prescale) {
+  clip_adam_ema_body<false>(p, g, m, v, e, n, n4, grad_norm, clip, hyper, beta1, beta2, eps, weight_decay, grad_prescale,
+                            nullptr);
+}
+
+__global__ __launch_bounds__(256) void clip_adam_ema_guard_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                  float* __restrict__ m, float* __restrict__ v,
+                                                                  float* __restrict__ e, int64_t n, int64_t n4,
+                                                                  const float* __restrict__ grad_norm, float clip,
+                                                                  const float* __restrict__ hyper, float beta1,
+                                                                  float beta2, float eps, float weight_decay,
+                                                                  float grad_prescale, float* __restrict__ health) {
+  clip_adam_ema_body<true>(p, g, m, v, e, n, n4, grad_norm, clip, hyper, beta1, beta2, eps, weight_decay, grad_prescale,
+                           health);
 }
 
 // a <-> b in one pass, no third buffer; [0, n4) 16 B per lane, [n4, n) one element at a time (as clip_adam_ema_kernel)
@@ -219,6 +284,34 @@ extern "C" int dv3_clip_adam_ema_f32(float* p, const float* g, float* m, float* 
   hipLaunchKernelGGL(clip_adam_ema_kernel, dim3(stream_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
                      ema, n, n4, grad_norm, clip, hyper, beta1, beta2, eps, weight_decay, grad_prescale);
   return dv3_check_launch("clip_adam_ema_f32");
+}
+
+// The guarded passes (include/dv3hip.h): the launch geometry of their unguarded forms.
+extern "C" int dv3_clip_adam_guard_f32(float* p, const float* g, float* m, float* v, int64_t n,
+                                       const float* grad_norm, float clip, const float* hyper, float beta1,
+                                       float beta2, float eps, float weight_decay, float grad_prescale,
+                                       float* health, void* stream) {
+  DV3_REQUIRE(p && g && m && v && hyper && n > 0, "clip_adam_guard: bad args");
+  DV3_REQUIRE(grad_norm && health, "clip_adam_guard: the gradient norm and the health words are mandatory");
+  int64_t nb = dv3_cdiv64(n, 256 * 4);
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(clip_adam_guard_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
+                     grad_norm, clip, hyper, beta1, beta2, eps, weight_decay, grad_prescale, health);
+  return dv3_check_launch("clip_adam_guard_f32");
+}
+
+extern "C" int dv3_clip_adam_ema_guard_f32(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
+                                           const float* grad_norm, float clip, const float* hyper, float beta1,
+                                           float beta2, float eps, float weight_decay, float grad_prescale,
+                                           float* health, void* stream) {
+  DV3_REQUIRE(p && g && m && v && ema && hyper && n > 0, "clip_adam_ema_guard: bad args");
+  DV3_REQUIRE(grad_norm && health, "clip_adam_ema_guard: the gradient norm and the health words are mandatory");
+  DV3_REQUIRE(ema + n <= p || p + n <= ema, "clip_adam_ema_guard: the average overlaps the parameters");
+  const uintptr_t bits = (uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema;
+  const int64_t n4 = (bits & 15) == 0 ? (n & ~(int64_t)3) : 0;
+  hipLaunchKernelGGL(clip_adam_ema_guard_kernel, dim3(stream_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                     ema, n, n4, grad_norm, clip, hyper, beta1, beta2, eps, weight_decay, grad_prescale, health);
+  return dv3_check_launch("clip_adam_ema_guard_f32");
 }
 
 extern "C" int dv3_swap_f32(float* a, float* b, int64_t n, void* stream) {

@@ -2726,7 +2726,21 @@ def bump_param_epoch():
     param_epoch += 1
 
 
-def clip_adam(p, g, m, v, grad_norm, clip, hyper, beta1, beta2, eps, weight_decay=0.0, grad_prescale=1.0):
+def clip_adam(p, g, m, v, grad_norm, clip, hyper, beta1, beta2, eps, weight_decay=0.0, grad_prescale=1.0, health=None):
+    """health (two fp32 words on the GPU, zeroed once by their owner): the GUARDED pass (dv3_clip_adam_guard_f32,
+    DESIGN.md 3.7c) -- `grad_norm` is then mandatory and read whatever `clip` is; a norm that is not finite leaves
+    p, m, v bit for bit as they were and counts in health[0] (health[1] = 1), a finite one applies the same update bit
+    for bit (health[1] = 0).  The parameter epoch moves either way: the host does not know which it was."""
+    if health is not None:
+        n = p.numel()
+        for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
+            _flat_f32(t, "clip_adam: " + name, n)
+        _guard_args("clip_adam", grad_norm, hyper, 3, health)
+        bump_param_epoch()
+        _lib.call("dv3_clip_adam_guard_f32", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n,
+                  grad_norm.data_ptr(), float(clip), hyper.data_ptr(), float(beta1), float(beta2), float(eps),
+                  float(weight_decay), float(grad_prescale), health.data_ptr(), _stream())
+        return
     bump_param_epoch()
     _lib.call("dv3_clip_adam_f32", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
               _ptr(grad_norm), float(clip), hyper.data_ptr(), float(beta1), float(beta2), float(eps),
@@ -2740,19 +2754,73 @@ def _flat_f32(t, name, n=None):
         raise RuntimeError("%s: %d elements, expected %d" % (name, t.numel(), n))
 
 
-def clip_adam_ema(p, g, m, v, ema, grad_norm, clip, hyper, beta1, beta2, eps, weight_decay=0.0, grad_prescale=1.0):
+def _guard_args(what, grad_norm, hyper, n_hyper, health):
+    """the arguments a guarded pass reads beyond its arenas"""
+    if grad_norm is None:
+        raise RuntimeError("%s: the guarded pass decides on grad_norm[0]: a norm is required (also at clip = 0)" % what)
+    _flat_f32(grad_norm, what + ": grad_norm")
+    _flat_f32(hyper, what + ": hyper")
+    _flat_f32(health, what + ": health")
+    if grad_norm.numel() < 1 or hyper.numel() < n_hyper or health.numel() < 2:
+        raise RuntimeError("%s: grad_norm holds %d floats (1 is read), hyper %d (%d), health %d (2)" % (
+            what, grad_norm.numel(), hyper.numel(), n_hyper, health.numel()))
+
+
+def clip_adam_ema(p, g, m, v, ema, grad_norm, clip, hyper, beta1, beta2, eps, weight_decay=0.0, grad_prescale=1.0,
+                  health=None):
     """clip_adam (p, m, v bit for bit as there) and, in the same pass, ema += hyper[3] * (p' - ema): `hyper` holds
-    four floats here, {lr, 1 - beta1^t, sqrt(1 - beta2^t), 1 - decay_t} (dv3_clip_adam_ema_f32)"""
+    four floats here, {lr, 1 - beta1^t, sqrt(1 - beta2^t), 1 - decay_t} (dv3_clip_adam_ema_f32).
+    health: the guarded pass (dv3_clip_adam_ema_guard_f32), as in clip_adam -- a skipped step leaves the average as it
+    was, too."""
     n = p.numel()
     for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema")):
         _flat_f32(t, "clip_adam_ema: " + name, n)
     _flat_f32(hyper, "clip_adam_ema: hyper")
     if hyper.numel() < 4:
         raise RuntimeError("clip_adam_ema: hyper holds %d floats, four are read" % hyper.numel())
+    if health is not None:
+        _guard_args("clip_adam_ema", grad_norm, hyper, 4, health)
+        bump_param_epoch()
+        _lib.call("dv3_clip_adam_ema_guard_f32", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(),
+                  n, grad_norm.data_ptr(), float(clip), hyper.data_ptr(), float(beta1), float(beta2), float(eps),
+                  float(weight_decay), float(grad_prescale), health.data_ptr(), _stream())
+        return
     bump_param_epoch()
     _lib.call("dv3_clip_adam_ema_f32", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(), n,
               _ptr(grad_norm), float(clip), hyper.data_ptr(), float(beta1), float(beta2), float(eps),
               float(weight_decay), float(grad_prescale), _stream())
+
+
+def arena_stats(p, g, m, v, hyper, health, chunks, ranges, grad_prescale=1.0, eps=1e-6, scratch=None):
+    """The per-tensor table of four flat arenas (dv3_arena_stats_f32) -> float64
+    [n_tensors][DV3_TENSOR_STAT_COLS] on the device (train_step.TENSOR_STAT_COLUMNS names the columns), two launches on
+    the current stream, no host sync.  chunks int64 [n_chunks][3], ranges int64 [n_tensors][2]: train_step.arena_chunks,
+    moved to the device.  hyper / eps: what the last update pass read; health: its two words, or None (not skipped).
+    scratch: n_chunks * DV3_TENSOR_STAT_COLS floats to reuse between calls (allocated here when None)."""
+    cols = CONSTS["DV3_TENSOR_STAT_COLS"]
+    n = p.numel()
+    for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
+        _flat_f32(t, "arena_stats: " + name, n)
+    _flat_f32(hyper, "arena_stats: hyper")
+    if hyper.numel() < 3:
+        raise RuntimeError("arena_stats: hyper holds %d floats, three are read" % hyper.numel())
+    if health is not None:
+        _flat_f32(health, "arena_stats: health", 2)
+    for t, name, w in ((chunks, "chunks", 3), (ranges, "ranges", 2)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 2 and
+                t.shape[1] == w and t.shape[0] > 0):
+            raise RuntimeError("arena_stats: %s must be a contiguous int64 [rows][%d] tensor on the GPU" % (name, w))
+    n_chunks, n_tensors = chunks.shape[0], ranges.shape[0]
+    if scratch is None:
+        scratch = torch.empty(n_chunks * cols, dtype=torch.float32, device=p.device)
+    _flat_f32(scratch, "arena_stats: scratch")
+    if scratch.numel() < n_chunks * cols:
+        raise RuntimeError("arena_stats: scratch holds %d floats, %d are needed" % (scratch.numel(), n_chunks * cols))
+    out = torch.empty(n_tensors, cols, dtype=torch.float64, device=p.device)
+    _lib.call("dv3_arena_stats_f32", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, hyper.data_ptr(),
+              _ptr(health), chunks.data_ptr(), n_chunks, ranges.data_ptr(), n_tensors, float(grad_prescale), float(eps),
+              scratch.data_ptr(), out.data_ptr(), _stream())
+    return out
 
 
 def swap_(a, b):

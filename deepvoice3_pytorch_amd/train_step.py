@@ -33,7 +33,7 @@ class TrainConfig(object):
                  guided_attention_sigma=0.2, clip_thresh=0.1, adam_beta1=0.5, adam_beta2=0.9,
                  adam_eps=1e-6, weight_decay=0.0, initial_learning_rate=5e-4,
                  lr_schedule="noam_learning_rate_decay", lr_schedule_kwargs=None, max_positions=512,
-                 range_check_every=0, amsgrad=False, ema_decay=0.0, ema_warmup=True):
+                 range_check_every=0, amsgrad=False, ema_decay=0.0, ema_warmup=True, skip_nonfinite=False):
         self.outputs_per_step = outputs_per_step
         self.downsample_step = downsample_step
         self.masked_loss_weight = masked_loss_weight
@@ -67,6 +67,10 @@ class TrainConfig(object):
         if ema_decay != 0.0 and not 0.0 < ema_decay < 1.0:
             raise ValueError("ema_decay must be 0 (no averaging) or lie strictly between 0 and 1, got %r" % (ema_decay,))
         self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
+        # training health: the update pass itself refuses a step whose gradient norm is not finite --
+        # on the device, so a replayed step refuses it too -- and counts it (Trainer.health()).  Off: the step is the
+        # one it was, launch for launch
+        self.skip_nonfinite = bool(skip_nonfinite)
 
 
 def ema_decay_at(t, ema_decay, warmup=True):
@@ -77,6 +81,40 @@ def ema_decay_at(t, ema_decay, warmup=True):
     if warmup:
         d = min(d, (1.0 + t) / (10.0 + t))
     return d
+
+
+# the columns of ops.arena_stats / Trainer.tensor_stats (include/dv3hip.h: DV3_TENSOR_STAT_COLS of them)
+TENSOR_STAT_COLUMNS = ("grad_sumsq", "grad_absmax", "grad_nonfinite", "param_sumsq", "param_absmax", "update_sumsq")
+
+
+def arena_chunks(offsets, sizes, chunk=4096):
+    """The chunk table of ops.arena_stats for tensors of `sizes` elements at element `offsets` of a flat arena (each a
+    multiple of 4, ascending, no overlap: FlatArena's).  Host logic only.
+    -> (chunks int64 [n_chunks][3] = (element offset, length <= chunk, tensor index),
+        ranges int64 [n_tensors][2] = (first chunk row, number of rows)).
+    A chunk lies inside one tensor and starts a multiple of `chunk` elements into it, so every start is 16-byte aligned
+    and the 0-3 padding elements behind a tensor are in no chunk; a tensor's chunks are consecutive rows, ascending."""
+    chunk = int(chunk)
+    if chunk <= 0 or chunk % 4 or chunk > ops.CONSTS["DV3_ARENA_CHUNK_MAX"]:
+        raise ValueError("arena_chunks: chunk must be a positive multiple of 4, at most %d, got %r" % (
+            ops.CONSTS["DV3_ARENA_CHUNK_MAX"], chunk))
+    offsets, sizes = [int(o) for o in offsets], [int(n) for n in sizes]
+    if len(offsets) != len(sizes) or not sizes:
+        raise ValueError("arena_chunks: %d offsets for %d sizes" % (len(offsets), len(sizes)))
+    end = 0
+    for o, n in zip(offsets, sizes):
+        if n <= 0 or o % 4 or o < end:
+            raise ValueError("arena_chunks: tensor of %d elements at offset %d (previous tensor ends at %d): sizes must be "
+                             "positive, offsets multiples of 4, ascending and free of overlap" % (n, o, end))
+        end = o + n
+    counts = np.array([(n + chunk - 1) // chunk for n in sizes], dtype=np.int64)
+    first = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+    tensor = np.repeat(np.arange(len(sizes), dtype=np.int64), counts)
+    within = (np.arange(int(counts.sum()), dtype=np.int64) - first[tensor]) * chunk      # the chunk's start in its tensor
+    length = np.minimum(np.asarray(sizes, dtype=np.int64)[tensor] - within, chunk)
+    chunks = np.stack([np.asarray(offsets, dtype=np.int64)[tensor] + within, length, tensor], axis=1)
+    ranges = np.stack([first, counts], axis=1)
+    return torch.from_numpy(np.ascontiguousarray(chunks)), torch.from_numpy(np.ascontiguousarray(ranges))
 
 
 def noam_learning_rate_decay(init_lr, global_step, warmup_steps=4000):
@@ -163,6 +201,16 @@ class FlatArena(object):
             p._dv3_grad_inplace = True   # ops.ConvLayerFn accumulates straight into p.grad
         # the moving average of `flat` (TrainConfig.ema_decay > 0 only): starts as the parameters themselves
         self.ema = self.flat.clone() if ema else None
+        self._stat_tables = None          # stat_tables(): built at the first Trainer.tensor_stats()
+
+    def stat_tables(self):
+        """(chunks, ranges, scratch) of ops.arena_stats for this arena, on its device: built once"""
+        if self._stat_tables is None:
+            dev = self.flat.device
+            chunks, ranges = arena_chunks(self.offsets, self.sizes)
+            scratch = torch.empty(chunks.shape[0] * len(TENSOR_STAT_COLUMNS), dtype=torch.float32, device=dev)
+            self._stat_tables = (chunks.to(dev), ranges.to(dev), scratch)
+        return self._stat_tables
 
     def rebind(self):
         """Every parameter's .grad must BE its slice of the gradient arena (clip/Adam and the all-reduce
@@ -237,6 +285,15 @@ class Trainer(object):
         self._hyper_slot = 0
         self.norm_partial = torch.empty(1024, dtype=torch.float32, device=dev)
         self.norm_out = torch.zeros(2, dtype=torch.float32, device=dev)
+        # TrainConfig.skip_nonfinite: {skipped steps, 1 if the last update pass skipped} -- written by the guarded pass
+        # alone.  A tensor of the trainer, not of a capture: every captured step of this trainer counts into it
+        self.health_words = None
+        self._stat_names = None           # tensor_stats(): the arena's tensors by name, looked up once
+        if cfg.skip_nonfinite:
+            if dev.type != "cuda":
+                raise ValueError("TrainConfig(skip_nonfinite=True) needs the trainer on a GPU: the guard is part of the "
+                                 "fused update pass")
+            self.health_words = torch.zeros(2, dtype=torch.float32, device=dev)
         # weight-norm backward of 8 layers per launch (ops.WnBwdBatch): opt-in (DV3_WN_BWD_BATCH=1).  Bit-identical, but
         # measured 2 % SLOWER in the step (15.62 vs 15.29 ms, nyanko bf16 11.79 vs 11.53): the per-layer launches
         # already overlap with the input-gradient chain on the side stream, a fat launch every 8 layers competes with it
@@ -672,15 +729,18 @@ Please set a larger value for ``max_position`` in hyper parameters.""".format(ma
         if self.comm is not None and reduce:
             self.comm.finish()           # all buckets reduced (sum); 1/world folded into grad_prescale
         prescale = 1.0 / self.world
-        if c.clip_thresh > 0:
+        # skip_nonfinite: the guarded pass decides on the norm, so the norm is taken at clip_thresh = 0 too.  Under data
+        # parallel it is the norm of the all-reduced arena, the same bits on every rank: all ranks skip or apply together
+        guard = self.health_words
+        if c.clip_thresh > 0 or guard is not None:
             ops.grad_sqnorm(a.grad, self.norm_partial, self.norm_out)   # norm of the SUMMED gradient
-        norm = self.norm_out if c.clip_thresh > 0 else None
+        norm = self.norm_out if (c.clip_thresh > 0 or guard is not None) else None
         if self.ema_on:      # the same update (bit for bit) and the average of its result, one pass over the arena
             ops.clip_adam_ema(a.flat, a.grad, a.exp_avg, a.exp_avg_sq, a.ema, norm, c.clip_thresh, self.hyper,
-                              c.adam_beta1, c.adam_beta2, c.adam_eps, c.weight_decay, prescale)
+                              c.adam_beta1, c.adam_beta2, c.adam_eps, c.weight_decay, prescale, health=guard)
         else:
             ops.clip_adam(a.flat, a.grad, a.exp_avg, a.exp_avg_sq, norm, c.clip_thresh, self.hyper, c.adam_beta1,
-                          c.adam_beta2, c.adam_eps, c.weight_decay, prescale)
+                          c.adam_beta2, c.adam_eps, c.weight_decay, prescale, health=guard)
 
     def step(self, batch):
         """One full optimisation step; returns device scalars (loss terms, grad_norm, lr)."""
@@ -701,10 +761,44 @@ Please set a larger value for ``max_position`` in hyper parameters.""".format(ma
         self.optimizer_step()
         scal["grad_norm"] = self._scalar(self.norm_out[0:1], 1.0 / self.world)
         scal["learning_rate"] = self._scalar(self.hyper[0:1])
+        if self.health_words is not None:
+            scal["step_skipped"] = self._scalar(self.health_words[1:2])
         if ops.gemm_precision() == "f16x3" and self.device.type == "cuda":
             scal["f16_range_events"] = ops.f16_range_events_tensor(self.device)
         self.global_step += 1
         return scal
+
+    def health(self):
+        """TrainConfig(skip_nonfinite=True): {"skipped_steps": update passes refused so far because the gradient norm
+        was not finite, "last_step_skipped": whether the last one was}.  One host synchronisation.  The count is the
+        device's (eager steps, warm-up steps and replays alike); it is not checkpointed -- a resumed run starts at 0.
+        The host's own counters (global_step, adam_step, the averaging warm-up) advance on a skipped step as on any
+        other: DESIGN.md 3.7c."""
+        if self.health_words is None:
+            raise RuntimeError("Trainer.health: the guard is off (TrainConfig(skip_nonfinite=True) turns it on)")
+        n, last = self.health_words.tolist()
+        return dict(skipped_steps=int(n), last_step_skipped=bool(last))
+
+    def tensor_stats(self):
+        """-> (names, table): per-tensor figures of the step that has just run.  names: the arena's
+        tensors by their model.named_parameters() names, in arena order; table: a float64 device tensor
+        [len(names)][len(TENSOR_STAT_COLUMNS)] (ops.arena_stats: two launches on the current stream, no host sync).
+        The gradient figures are those of the averaged gradient under data parallel (grad_prescale = 1 / world).  Call it
+        after a step or a replay and before the next one: the gradient arena and `hyper` hold that step's values until
+        the next one zeroes and sets them.  With or without skip_nonfinite; with it, a skipped step shows update_sumsq 0
+        everywhere and its non-finite gradient elements per tensor in grad_nonfinite."""
+        self._refuse_swapped("Trainer.tensor_stats")
+        if self.device.type != "cuda":
+            raise RuntimeError("Trainer.tensor_stats: the table is a GPU reduction over the arena")
+        a = self.arena
+        if self._stat_names is None:
+            name_of = {id(p): n for n, p in self.model.named_parameters()}
+            self._stat_names = [name_of[id(p)] for p in a.params]
+        names = list(self._stat_names)
+        chunks, ranges, scratch = a.stat_tables()
+        table = ops.arena_stats(a.flat, a.grad, a.exp_avg, a.exp_avg_sq, self.hyper, self.health_words, chunks, ranges,
+                                grad_prescale=1.0 / self.world, eps=self.cfg.adam_eps, scratch=scratch)
+        return names, table
 
     def _zero_grad(self):
         """optimizer.zero_grad() (train.py:683) on the flat gradient arena: one hipMemsetAsync through the library"""
@@ -1025,6 +1119,8 @@ class GraphedTrainer(object):
         # inside the segmented capture the all-reduces are not part of the tail graph (class docstring)
         t.optimizer_step(reduce=not (self.split and torch.cuda.is_current_stream_capturing()))
         scal["grad_norm"] = t._scalar(t.norm_out[0:1], 1.0 / t.world)
+        if t.health_words is not None:
+            scal["step_skipped"] = t._scalar(t.health_words[1:2])
         if ops.gemm_precision() == "f16x3":
             scal["f16_range_events"] = ops.f16_range_events_tensor(t.device)
         self.seed_offset.add_(1)
@@ -1149,8 +1245,19 @@ class GraphedTrainer(object):
         when operands left the fp16 range on any rank it switches the process to bf16x3 (Trainer.check_range) and
         returns the event count -- the caller must then discard this object (`close()`), restore the parameters from
         its last checkpoint if the step's `grad_norm` was not finite, and capture a new GraphedTrainer (the new
-        capture packs bf16x3 operands).  0 = in range, keep replaying."""
+        capture packs bf16x3 operands).  0 = in range, keep replaying.
+        With TrainConfig(skip_nonfinite=True) there is nothing to restore from a checkpoint: the captured update pass
+        itself refused the step whose gradient norm was not finite (health() counts it), so the parameters, the moments
+        and the weight average are those of the last finite step."""
         return self.t.check_range()
+
+    def health(self):
+        """Trainer.health: the skipped-step counter of the trainer these replays drive (one host sync)"""
+        return self.t.health()
+
+    def tensor_stats(self):
+        """Trainer.tensor_stats of the step the last replay ran (eager launches on the current stream)"""
+        return self.t.tensor_stats()
 
     def close(self):
         """Give the process-wide dropout state back: the device seed offset installed for the replays would
@@ -1318,6 +1425,14 @@ class LatticeReplay(object):
         if n:
             self.close()
         return n
+
+    def health(self):
+        """Trainer.health: the skipped-step counter, over every shape's replays (one host sync)"""
+        return self.t.health()
+
+    def tensor_stats(self):
+        """Trainer.tensor_stats of the step the last replay ran (eager launches on the current stream)"""
+        return self.t.tensor_stats()
 
     def close(self):
         while self.graphs:

@@ -755,6 +755,44 @@ int dv3_clip_adam_ema_f32(float* p, const float* g, float* m, float* v, float* e
                           float beta2, float eps, float weight_decay, float grad_prescale,
                           void* stream);
 int dv3_swap_f32(float* a, float* b, int64_t n, void* stream);
+/* Training health (additive entry points, ABI 49 as before).
+ * The GUARDED passes are dv3_clip_adam_f32 / dv3_clip_adam_ema_f32 with a decision taken on the device, where a captured
+ * graph can take it.  grad_norm is mandatory here and read whatever `clip` is (clip = 0 still means no clipping);
+ * health points at two floats the caller owns, zeroed once.  With s = grad_norm[0]:
+ *   s not finite   nothing of p, m, v (, ema) is read or written -- every workgroup returns before its loop, the step
+ *                  costs no arena traffic -- and health[0] += 1, health[1] = 1;
+ *   s finite       p, m, v (, ema) come out bit for bit as the unguarded entry point writes them, and health[1] = 0.
+ * health[0] counts in fp32 (exact to 2^24 skipped steps).  One lane of the grid writes both words with ordinary stores.
+ * s is the norm dv3_grad_sqnorm_f32 left, so s is +Inf also for a FINITE gradient whose sum of squares leaves the fp32
+ * range (|g| of order 1e19): such a step is skipped too, which is the wanted behaviour.                               */
+int dv3_clip_adam_guard_f32(float* p, const float* g, float* m, float* v, int64_t n,
+                            const float* grad_norm, float clip, const float* hyper, float beta1,
+                            float beta2, float eps, float weight_decay, float grad_prescale,
+                            float* health, void* stream);
+int dv3_clip_adam_ema_guard_f32(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
+                                const float* grad_norm, float clip, const float* hyper, float beta1,
+                                float beta2, float eps, float weight_decay, float grad_prescale,
+                                float* health, void* stream);
+/* The per-tensor table: out[n_tensors][DV3_TENSOR_STAT_COLS] (float64) over four arenas of n floats each, in two
+ * launches, no atomics (two runs on the same data give the same bits).  Columns:
+ *   0 grad_sumsq      sum of (grad_prescale * g)^2 over the tensor's FINITE gradient elements
+ *   1 grad_absmax     max |grad_prescale * g| over them (0 if there is none)
+ *   2 grad_nonfinite  number of NaN / +-Inf gradient elements (exact)
+ *   3 param_sumsq     sum of p^2                  4 param_absmax   max |p|
+ *   5 update_sumsq    sum of d^2, d = (hyper[0] / hyper[1]) * m / (sqrt(v) / hyper[2] + eps): the update the last pass
+ *                     applied, from the moments it left; 0 when health != NULL and health[1] != 0 (a skipped pass
+ *                     moved nothing; the moments are not read then).  health may be NULL: not skipped.
+ * chunks[n_chunks][3] = (element offset, length <= DV3_ARENA_CHUNK_MAX, tensor index), int64, on the device: a chunk
+ * lies inside one tensor (the padding between tensors is in no chunk) and the chunks of a tensor are consecutive rows;
+ * ranges[n_tensors][2] = (first chunk row, number of rows).  A row that points outside [0, n) is read as empty.
+ * scratch: n_chunks * DV3_TENSOR_STAT_COLS floats.  The sums are fp32 inside a chunk and fp64 across chunks: at most 39
+ * fp32 roundings deep, all terms non-negative.  The arenas must be 16-byte aligned.                 */
+#define DV3_TENSOR_STAT_COLS 6
+#define DV3_ARENA_CHUNK_MAX 4096
+int dv3_arena_stats_f32(const float* p, const float* g, const float* m, const float* v, int64_t n,
+                        const float* hyper, const float* health, const int64_t* chunks, int64_t n_chunks,
+                        const int64_t* ranges, int32_t n_tensors, float grad_prescale, float eps,
+                        float* scratch, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Autoregressive decode step (Decoder.incremental_forward, deepvoice3.py:397-473): two fused kernels per
