@@ -9,7 +9,13 @@ B = 64 references are float64 matrix products on the GPU); the SPLITS always run
 device does with fp16 subnormals is the thing under test.
 
 Operand forms (`form`): ("f16", s) -- a = v * 2^s as an fp16 hi / lo pair; ("bf16",) -- a bf16 hi / lo pair of v;
-None -- the fp32 value itself (mode "f32").
+("bf16_1",) -- the single bf16 value bf16_rn(v), no lo plane (mode "bf16": split_terms == 1 / split_bf16 == 2; csrc/common.h
+converts with (__bf16)v, round to nearest even); None -- the fp32 value itself (mode "f32").
+
+The single-term mode is held to the SAME-ROUNDING reference: the float64 GEMM of the rounded operands (`reference` with the
+forms given, = `three_term`).  Its operand term is zero by construction and only the accumulation term remains; where the
+result is stored as bf16 (the c8 tensors, DV3_IO_AB_BF16) `bf16_out_bound` adds the one rounding of the store.  tests/
+test_cpu_gemm_bf16_ref.py proves these parts without a GPU; tests/test_gpu_gemm_bf16.py holds the kernels to them.
 
 The bound of one output element, both parts tensors of the output's shape:
   operand term       sum |w| d(a) + d(w) |a| + |lo_a| |lo_w|      d() = the header's per-operand statement:
@@ -41,6 +47,8 @@ def forms(gemm, mode):
     gradient GEMM of both split modes on bf16 pairs (deepvoice3_pytorch_amd/ops.py, "GEMM arithmetic")."""
     if mode == "f32":
         return None, None
+    if mode == "bf16":          # one bf16 MFMA per product in all three GEMMs
+        return ("bf16_1",), ("bf16_1",)
     if mode == "f16x3" and gemm == "fwd":
         return ("f16", F16_ACT_SHIFT), ("f16", F16_WEIGHT_SHIFT)
     assert mode in ("f16x3", "bf16x3"), mode
@@ -82,6 +90,11 @@ def _rn_bf16(v64):
     return t.to(torch.bfloat16).to(torch.float64).numpy()  # round to nearest even on the host
 
 
+def bf16_rn(v):
+    """(__bf16)v of csrc/common.h: round to nearest, ties to even -- on the host, as float64"""
+    return _rn_bf16(_np64(v))
+
+
 def split_bf16_pair(v):
     """dv3_pair_word / split8 of the gradient GEMMs: hi = bf16_rn(v), lo = bf16_rn(v - hi).  -> (hi, lo), float64."""
     v = _np64(v)
@@ -106,14 +119,26 @@ def split(v, form, flush=False):
     if form[0] == "f16":
         hi, lo = split_f16(v, form[1], flush)
         return hi, lo, form[1]
+    if form[0] == "bf16_1":
+        hi = bf16_rn(v)
+        return hi, np.zeros_like(hi), 0
     hi, lo = split_bf16_pair(v)
     return hi, lo, 0
+
+
+def single(form):
+    return form is not None and form[0] == "bf16_1"
+
+
+def rounded(v, form):
+    """the operand the reference of a mode multiplies: bf16_rn(v) in the single-term mode, v itself otherwise"""
+    return bf16_rn(v) if single(form) else _np64(v)
 
 
 def delta(v, form):
     """the header's per-operand statement |a - hi - lo| <= delta, in v-units (float64 array)"""
     v = np.abs(_np64(v))
-    if form is None:
+    if form is None or single(form):        # single-term: the reference multiplies the rounded operand itself
         return np.zeros_like(v)
     if form[0] == "f16":
         return np.maximum(2.0 ** -23 * v, 2.0 ** (-25 - form[1]))
@@ -173,7 +198,9 @@ def n_products(gemm, mode, *, J, K, B, T, n_slabs=1, k_split=False):
     the host), three terms each in the split modes -- a k-split launch cuts the B ceil(T / 32) frame chunks into n_slabs
     contiguous ranges of ceil(. / n_slabs) chunks, the others give slab s the batch items s, s + n_slabs, ...
     (csrc/wgrad_gemm.hip, wgrad_gemm_bf16x3.hip, wgrad_taps2.hip)."""
-    terms = 1 if mode == "f32" else 3
+    terms = 1 if mode in ("f32", "bf16") else 3
+    if mode == "bf16" and gemm != "wgrad":
+        return J * ((K + 31) // 32 * 32)        # one term, over the 32-channel chunks the MFMAs consume
     if gemm == "wgrad":
         if k_split:
             chunks = B * ((T + 31) // 32)
@@ -187,8 +214,9 @@ def n_products(gemm, mode, *, J, K, B, T, n_slabs=1, k_split=False):
 # ---------------------------------------------------------------------------------------------------------------
 # expectation and bound
 # ---------------------------------------------------------------------------------------------------------------
-def reference(mm, act, wgt, addend=None, device=None):
-    y = mm(_t64(_np64(act), device), _t64(_np64(wgt), device))
+def reference(mm, act, wgt, addend=None, device=None, form_a=None, form_w=None):
+    """the float64 GEMM -- of the operands as given, or (single-term forms) of the operands rounded as the kernel rounds"""
+    y = mm(_t64(rounded(act, form_a), device), _t64(rounded(wgt, form_w), device))
     return y if addend is None else y + _t64(_np64(addend), device)
 
 
@@ -203,7 +231,7 @@ def three_term(mm, act, wgt, form_a, form_w, addend=None, flush=False, drop_lo=N
         wl = np.where(drop_lo[1], 0.0, wl) if drop_lo[0] == "wgt" else wl
     ah, al, wh, wl = (_t64(t, device) for t in (ah, al, wh, wl))
     y = mm(ah, wh)
-    if form_a is not None:
+    if form_a is not None and not single(form_a):
         y = y + mm(ah, wl) + mm(al, wh)
     y = y * 2.0 ** -(sa + sw)
     return y if addend is None else y + _t64(_np64(addend), device)
@@ -211,13 +239,13 @@ def three_term(mm, act, wgt, form_a, form_w, addend=None, flush=False, drop_lo=N
 
 def bound(mm, act, wgt, form_a, form_w, n, addend=None, device=None):
     """per-element bound of |kernel - float64 reference| (module docstring) -> (bound, operand term, accumulation term)"""
-    A, W = np.abs(_np64(act)), np.abs(_np64(wgt))
+    A, W = np.abs(rounded(act, form_a)), np.abs(rounded(wgt, form_w))
     At, Wt = _t64(A, device), _t64(W, device)
     mag = mm(At, Wt)
     if addend is not None:
         mag = mag + _t64(np.abs(_np64(addend)), device)
     acc = (n + EPILOGUE_OPS) * U32 * mag
-    if form_a is None:
+    if form_a is None or single(form_a):
         return acc, torch.zeros_like(acc), acc
     _, al, sa = split(act, form_a)
     _, wl, sw = split(wgt, form_w)
@@ -234,7 +262,7 @@ def emulate(gemm, act, wgt, form_a, form_w, *, J, dil, padL, addend=None, flush=
     if drop_lo is not None:
         al = np.where(drop_lo[1], 0.0, al) if drop_lo[0] == "act" else al
         wl = np.where(drop_lo[1], 0.0, wl) if drop_lo[0] == "wgt" else wl
-    planes = [(ah, wh)] if form_a is None else [(ah, wh), (ah, wl), (al, wh)]
+    planes = [(ah, wh)] if (form_a is None or single(form_a)) else [(ah, wh), (ah, wl), (al, wh)]
     terms = []                                            # each (n_k, outputs...) of exact float64 products
     for a, w in planes:
         a, w = _t64(a), _t64(w)
@@ -275,6 +303,7 @@ BENCH_SHAPES = [(64, 512, 150, 3, 1, False), (64, 512, 150, 3, 27, False)]
 # tiles and 2 units per CU, power-of-two chunk and row-tile counts) -- those of test_stream_k_form_of_the_256x256_tap_gemm
 STREAMK_SHAPES = [(24, 256, 410, 3, 1, False), (48, 256, 201, 3, 3, False)]
 EXACT = ("E1", "E2", "E3", "E4")
+EXACT_BF16 = EXACT + ("E5",)                    # E5 (bf16 midpoints in fp32 storage) belongs to the single-term mode
 BOUNDED = ("B1", "B2", "B3", "B4", "B5")
 SMALL_MAGNITUDE = ("B2", "B3")                  # where a lost subnormal or a lost lo plane must show (with E2 / E4)
 
@@ -323,11 +352,11 @@ def family(fam, gemm, mode, shape, seed=0):
     fwd: act = x (B, C, T), wgt = w (M, C, k) with M = 2 C, addend = bias (M);  dgrad: act = g (B, M, T), wgt = w;
     wgrad: act = g (B, M, T), wgt = x (B, C, T).  quantum (exact families): every product, partial sum and the addend is
     a whole multiple of it."""
-    B, C, T, k, d, causal = shape
-    M = 2 * C
+    B, C, T, k, d, causal = shape[:6]
+    M = shape[6] if len(shape) > 6 else 2 * C         # (the plain c8 shapes name their output channels)
     rng = np.random.RandomState(seed + 1000 * (ord(fam[0]) + int(fam[1])) + C + T + k + d)
     fa, fw = forms(gemm, mode)
-    kind = "f32" if fa is None else fa[0]
+    kind = "f32" if fa is None else "bf16" if single(fa) else fa[0]     # E1 .. E4: the single-term form takes bf16's values
     sa = fa[1] if kind == "f16" else 0
     sw = fw[1] if kind == "f16" else 0
     a_shape = (B, C, T) if gemm == "fwd" else (B, M, T)
@@ -358,6 +387,26 @@ def family(fam, gemm, mode, shape, seed=0):
         lexp = {"f16": -4, "bf16": -4, "f32": -2}[kind]
         # hi lo' and lo hi' are multiples of 2^(hexp + lexp); the f32 mode also sums lo lo': 2^(2 lexp)
         quantum = 2.0 ** ((2 * lexp if kind == "f32" else ({"f16": 8, "bf16": 5}[kind] + lexp)) - sa - sw)
+    elif fam == "E5":
+        # bf16 midpoints and their fp32 neighbours: with the bf16 value h 2^(e-7), h in 128 .. 255, the midpoint to the next
+        # one is (2h + 1) 2^(e-8); one fp32 ulp is 2^(e-23).  Round to nearest even gives h (h even) or h + 1 (h odd) at the
+        # midpoint, truncation always h, round-half-away always h + 1; below / above the midpoint all but truncation agree.
+        # The rounded operands are 9-bit integers times 2^(e-7): with e in -1 .. 1 (act) and 0 .. 1 (wgt) and at most
+        # 8 products per sum every partial sum stays below 2^(18 + 2 + 1 + 3) / 2 = 2^23 quanta
+        def mid(shape_, exps):
+            h = rng.randint(128, 256, size=shape_).astype(np.float64)
+            e = rng.choice(exps, size=shape_).astype(np.float64)
+            off = rng.choice([-1.0, 0.0, 0.0, 1.0], size=shape_)
+            return ((2 * h + 1) * 2.0 ** (e - 8) + off * 2.0 ** (e - 23)) * rng.choice([-1.0, 1.0], size=shape_)
+        act, wgt = mid(a_shape, [-1, 0, 1]), mid(w_shape, [0, 1])
+        keep = np.zeros(a_shape, bool)
+        if gemm == "wgrad":
+            for b, t in _sparse_frames(B, T):
+                keep[b, :, t] = True
+        else:
+            keep[:, _sparse_channels(Ka, 8 // k), :] = True
+        act = np.where(keep, act, 0.0)
+        quantum = 2.0 ** (-1 - 7 + 0 - 7)
     else:
         # the weight gradient sums over (b, t): its second operand is an activation, scaled like the first
         if gemm == "wgrad":
@@ -386,7 +435,7 @@ def family(fam, gemm, mode, shape, seed=0):
     out = dict(act=act.astype(np.float32), wgt=wgt.astype(np.float32), quantum=quantum,
                addend=None if addend is None else addend.astype(np.float32))
     for key in ("act", "wgt", "addend"):      # the families are stated in fp32: nothing may have been rounded away
-        if out[key] is not None and fam in EXACT:
+        if out[key] is not None and fam in EXACT_BF16:
             assert np.array_equal(out[key].astype(np.float64), {"act": act, "wgt": wgt, "addend": addend}[key]), (fam, key)
     return out
 
@@ -394,3 +443,190 @@ def family(fam, gemm, mode, shape, seed=0):
 def bias_bcast(addend):
     """bias (M,) -> broadcastable against (B, M, T)"""
     return None if addend is None else np.asarray(addend).reshape(1, -1, 1)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# channel-blocked bf16 storage ("c8", include/dv3hip.h), numpy only
+# ---------------------------------------------------------------------------------------------------------------
+def c8_groups(C):
+    return (C + 31) // 32 * 4
+
+
+def bf16_bits(v):
+    """bf16 values (asserted) -> their 16 bits, uint16"""
+    v32 = np.ascontiguousarray(np.asarray(v, dtype=np.float32))
+    bits = v32.view(np.uint32)
+    assert not np.any(bits & 0xffff), "not bf16 values"
+    return (bits >> 16).astype(np.uint16)
+
+
+def bf16_from_bits(bits):
+    return (np.asarray(bits).astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+
+
+def c8_pack(v):
+    """(B, C, T) bf16 values -> uint16 [B][round_up(C, 32) / 8][T][8]: channel c of frame t is element c % 8 of unit
+    (b, c / 8, t); channels >= C are zero"""
+    v = np.asarray(v)
+    B, C, T = v.shape
+    full = np.zeros((B, c8_groups(C) * 8, T), np.uint16)
+    full[:, :C] = bf16_bits(v)
+    return np.ascontiguousarray(full.reshape(B, c8_groups(C), 8, T).transpose(0, 1, 3, 2))
+
+
+def c8_unpack(bits, C):
+    """uint16 [B][G][T][8] -> ((B, C, T) float64, largest |padding channel| -- zero in a well-formed tensor)"""
+    bits = np.asarray(bits)
+    B, G, T, e = bits.shape
+    assert e == 8 and G == c8_groups(C), (bits.shape, C)
+    full = bf16_from_bits(bits.transpose(0, 1, 3, 2).reshape(B, G * 8, T))
+    pad = float(np.abs(full[:, C:]).max()) if G * 8 > C else 0.0
+    return full[:, :C], pad
+
+
+def keep_bytes(keep):
+    """keep (B, C, T) bool -> uint8 [B][round_up(C, 32) / 8][T]: bit e of byte (b, g, t) keeps channel 8 g + e"""
+    keep = np.asarray(keep, bool)
+    B, C, T = keep.shape
+    full = np.zeros((B, c8_groups(C) * 8, T), np.uint8)
+    full[:, :C] = keep
+    full = full.reshape(B, c8_groups(C), 8, T)
+    out = np.zeros((B, c8_groups(C), T), np.uint8)
+    for e in range(8):
+        out |= (full[:, :, e, :] << e).astype(np.uint8)
+    return out
+
+
+def keep_bits_words(keep):
+    """keep (B, C, T) bool -> the keep-BITS form int32 [B * C][ceil(T / 32)]: bit t % 32 of word t / 32 (dv3_conv_desc.xmask)"""
+    keep = np.asarray(keep, bool)
+    B, C, T = keep.shape
+    rs = (T + 31) // 32
+    full = np.zeros((B * C, rs * 32), np.uint64)
+    full[:, :T] = keep.reshape(B * C, T)
+    w = (full.reshape(B * C, rs, 32) << np.arange(32, dtype=np.uint64)).sum(-1)
+    return w.astype(np.uint32).view(np.int32), rs
+
+
+def ulp_bf16(a):
+    """spacing of the bf16 numbers in the binade of |a| (8 significand bits; the subnormal spacing 2^-133 below 2^-126)"""
+    a = np.abs(np.asarray(a, np.float64))
+    e = np.frexp(np.maximum(a, 2.0 ** -126))[1] - 1           # a in [2^e, 2^(e+1))
+    return np.ldexp(1.0, e - 7)
+
+
+def bf16_out_bound(ref, bnd):
+    """A value stored as bf16 (round to nearest) from an fp32 tail within `bnd` of `ref`: the tail t has |t| <= |ref| + bnd,
+    the store moves it by at most half a bf16 ulp of its own binade: |got - ref| <= bnd + ulp_bf16(|ref| + bnd) / 2."""
+    if torch.is_tensor(ref):
+        r, b = ref.detach().cpu().numpy(), bnd.detach().cpu().numpy()
+        return torch.from_numpy(b + 0.5 * ulp_bf16(np.abs(r) + b)).to(ref.device)
+    return bnd + 0.5 * ulp_bf16(np.abs(ref) + bnd)
+
+
+def expect_bf16(mm, act, wgt, n, *, act_keep=None, wgt_keep=None, out_keep=None, scale=1.0, addend=None,
+                ops=EPILOGUE_OPS, device=None):
+    """The single-term mode's same-rounding expectation with the dropout forms of the kernels:
+        tail = out_keep * scale * mm(bf16_rn(act) * act_keep, bf16_rn(wgt) * wgt_keep) + addend
+    in float64 -- the exact value of the kernel's fp32 tail (keeps are 0 / 1 arrays of the operand's / output's shape, scale
+    the 1 / (1 - p) the kernel multiplies its ACCUMULATORS by, addend the bias or the input gradient's r_scale * r) -- and
+    the bound of the kernel's fp32 tail against it: (n + ops) 2^-24 (out_keep * scale * sum |a| |w| + |addend|), n products
+    added in fp32 plus `ops` further roundings in the epilogue (the caller states which).  -> (tail, bound)"""
+    a, w = bf16_rn(act), bf16_rn(wgt)
+    if act_keep is not None:
+        a = a * np.asarray(act_keep, np.float64)
+    if wgt_keep is not None:
+        w = w * np.asarray(wgt_keep, np.float64)
+    y = mm(_t64(a, device), _t64(w, device)) * scale
+    mag = mm(_t64(np.abs(a), device), _t64(np.abs(w), device)) * abs(scale)
+    if out_keep is not None:
+        k = _t64(np.asarray(out_keep, np.float64), device)
+        y, mag = y * k, mag * k
+    if addend is not None:
+        r = _t64(np.asarray(addend, np.float64), device)
+        y, mag = y + r, mag + r.abs()
+    return y, (n + ops) * U32 * mag
+
+
+def check_bf16(exact, got, tail, bnd, what, out_bf16=False):
+    """One output of a single-term kernel against expect_bf16's (tail, bound).  exact (the E families): every element equals
+    the tail -- stored as bf16: equals bf16_rn(tail), nothing else.  Otherwise every element lies inside `bnd` -- stored as
+    bf16: inside bf16_out_bound(tail, bnd).  -> the worst ratio to the bound (0 for an exact match)"""
+    return check_prepared(exact, got, *prepare_bf16(exact, tail, bnd, what, out_bf16), what=what)
+
+
+def prepare_bf16(exact, tail, bnd, what="", out_bf16=False):
+    """-> (want, bound) of check_bf16, for the callers that check several outputs against one expectation"""
+    if exact:
+        want = tail
+        if out_bf16:
+            t32 = tail.float()
+            assert torch.equal(t32.double(), tail), what + ": the exact value is not an fp32 value"
+            want = t32.cpu().to(torch.bfloat16).double().to(tail.device)        # round to nearest even, on the host
+        return want, None
+    if out_bf16:
+        a = (tail.abs() + bnd).clamp_min(2.0 ** -126)
+        bnd = bnd + 0.5 * torch.ldexp(torch.ones_like(a), torch.frexp(a)[1] - 8)     # = bf16_out_bound, on the tensor's device
+    return tail, bnd
+
+
+def check_prepared(exact, got, want, bnd, what):
+    got = got.detach().double()
+    assert got.shape == want.shape, "%s: shape %s != %s" % (what, tuple(got.shape), tuple(want.shape))
+    assert bool(torch.isfinite(got).all()), what + ": not finite"
+    if exact:
+        if not torch.equal(got, want):
+            bad = got != want
+            i = tuple(int(v) for v in bad.nonzero()[0])
+            raise AssertionError("%s: %d of %d elements differ; first at %s: got %r want %r" %
+                                 (what, int(bad.sum()), bad.numel(), i, float(got[i]), float(want[i])))
+        return 0.0
+    err = (got - want).abs()          # decide where the tensors live, fetch them only to report a failure
+    if bool((err <= bnd).all()):
+        return float(torch.where(err == 0, torch.zeros_like(err), err / bnd).max())
+    from tests.util import assert_close_elementwise
+    return assert_close_elementwise(got, want, 0, bnd, what)
+
+
+def c8_slabs(B, T, S):
+    """the K-split of wgrad_c8 (csrc/wgrad_c8.hip): the B ceil(T / 32) (batch item, 32-frame chunk) steps in order, cut into
+    S slabs of q = ceil(B ceil(T / 32) / S) steps; trailing slabs may be empty.  -> bool (S, B, T): frames of each slab"""
+    n_tc = (T + 31) // 32
+    total = B * n_tc
+    q = -(-total // S)
+    own = np.zeros((S, B, T), bool)
+    for s in range(S):
+        for gs in range(s * q, min((s + 1) * q, total)):
+            b, tc = divmod(gs, n_tc)
+            own[s, b, tc * 32: min(T, tc * 32 + 32)] = True
+    return own
+
+
+def c8_slab_frames(B, T, S):
+    """frames of the largest slab: the accumulation depth of one element of a wgrad_c8 slab"""
+    return int(c8_slabs(B, T, S).reshape(S, -1).sum(1).max())
+
+
+# (B, C, T, k, d, causal[, M]): what the c8 kernels accept -- J in {1, 3}, (J - 1) d <= 64, same length, Cg % 8 == 0 for the
+# gated forms (M = 2 C).  The eligible edge shapes; the halo limit (J - 1) d = 64, causal; a plain 1 x 1 pair whose channel
+# counts are multiples of nothing (these two carry M and run the plain forms only)
+C8_SHAPES = [(3, 64, 200, 3, 1, False), (3, 96, 150, 3, 27, True), (2, 128, 513, 3, 9, True), (1, 8, 1, 3, 1, True),
+             (1, 16, 3, 3, 2, False), (2, 8, 33, 1, 1, False), (2, 40, 50, 3, 4, True), (5, 24, 37, 3, 3, False),
+             (2, 32, 70, 3, 32, True), (2, 513, 40, 1, 1, False, 64), (2, 64, 40, 1, 1, False, 513)]
+C8_HALO_MAX = 64
+
+
+def c8_shape_M(shape):
+    return shape[6] if len(shape) > 6 else 2 * shape[1]
+
+
+def c8_reach(shape):
+    """which of the places a c8 kernel can go wrong this shape reaches (tests/test_cpu_gemm_bf16_ref.py asserts the set
+    C8_SHAPES reaches every one; the tile sizes are those of csrc/conv_planes.hip, conv_c8pp.hip, wgrad_c8.hip)"""
+    B, C, T, k, d, causal = shape[:6]
+    M = c8_shape_M(shape)
+    return dict(spans_items=B > 1 and T % 64 != 0,          # a 64 / 128 / 256-column tile of the flat (b, t) axis holds two items
+                one_frame=T == 1, short=T < 4, ragged_chunk=T % 32 != 0, ragged_channels=C % 32 != 0 or M % 32 != 0,
+                wgrad_row_tiles=M > 128, wgrad_col_tiles=C > 128,
+                wgrad_wide=16 * (32 + (k - 1) * d) > 1024, wgrad_narrow=16 * (32 + (k - 1) * d) <= 1024,
+                halo_limit=(k - 1) * d == C8_HALO_MAX, gated_ok=len(shape) == 6 and C % 8 == 0)
