@@ -100,7 +100,9 @@ def parse_header(path=_HEADER):
                     base = re.match(r"(?:const\s+)?(\w+)", a).group(1)
                     argtypes.append(_CTYPES[base])
         funcs[name] = (restype, argtypes)
-    consts = {k: int(v) for k, v in re.findall(r"#define\s+(DV3_\w+)\s+\(?(-?\d+)\)?", src)}
+    consts = {k: int(v) for k, v in re.findall(r"#define\s+(DV3_\w+)\s+\(?(-?\d+)(?![\w.])\)?", src)}
+    # a float constant (1e-20f): its value as a Python float, never its leading digits as an int
+    consts.update({k: float(v) for k, v in re.findall(r"#define\s+(DV3_\w+)\s+(-?\d+(?:\.\d*)?e-?\d+)f\b", src)})
     for em in re.finditer(r"enum\s*\{(.*?)\}\s*;", src, flags=re.S):
         nxt = 0
         for item in em.group(1).split(","):

@@ -265,6 +265,7 @@ extern "C" int dv3_sizeof(const char* name) {
   DV3_SZ(dv3_spk_desc);
   DV3_SZ(dv3_dropout_site);
   DV3_SZ(dv3_dtw_desc);
+  DV3_SZ(dv3_mono_desc);
 #undef DV3_SZ
   return -1;
 }

@@ -2706,6 +2706,47 @@ def dtw(x, y, x_len, y_len, want_path=False):
     return (out, path) if want_path else out
 
 
+_MONO_LAYOUTS = ("btk", "tbk", "lbtk")       # the axis letters in order: layer, batch (item), time (step), key
+
+
+def monotonic_path(attn, steps, key_len, layout="btk", max_advance=1):
+    """The best monotonic path through stored attention rows and the steps it gives every key (dv3_mono_path_f32,
+    include/dv3hip.h).  attn: fp32, "btk" = (B, T, Tk), "tbk" = (T, B, Tk) -- the step program's stacked
+    buffer -- or "lbtk" = (L, B, T, Tk), the teacher-forced layers, whose mean is searched; any strided view whose key
+    axis is dense: read in place, never copied or written.  steps, key_len: int32[B] on the device; item b's rows
+    t < steps[b] and keys n < key_len[b] are read.  max_advance = J in [1, DV3_MONO_MAX_ADVANCE]: a step stays or
+    advances by up to J keys; the path starts within the first J keys and ends within the last J.
+    -> (out (B, DV3_MONO_COLS) fp32, columns synthesis.TIMING_COLUMNS; path (B, T) int32, -1 past steps[b];
+    durations (B, Tk) int32, 0 past key_len[b]) on the device.  Runs on the current stream; no host synchronisation."""
+    _chk(attn, "attn")
+    _chk(steps, "steps", torch.int32)
+    _chk(key_len, "key_len", torch.int32)
+    if layout not in _MONO_LAYOUTS or attn.dim() != len(layout):
+        raise RuntimeError("monotonic_path: attn in layout \"btk\", \"tbk\" (3-d) or \"lbtk\" (4-d), got %s in %r" % (
+            tuple(attn.shape), layout))
+    size, stride = dict(zip(layout, attn.shape)), dict(zip(layout, attn.stride()))
+    L, B, T, Tk = size.get("l", 1), size["b"], size["t"], size["k"]
+    if Tk > 1 and stride["k"] != 1:
+        raise RuntimeError("monotonic_path: the key axis must be dense (stride %d)" % stride["k"])
+    if steps.numel() != B or key_len.numel() != B:
+        raise RuntimeError("monotonic_path: %d steps / %d key lengths for %d items" % (steps.numel(), key_len.numel(), B))
+    need = ctypes.c_int64(0)
+    _lib.call("dv3_mono_path_scratch_bytes", B, T, Tk, ctypes.byref(need))
+    d = _lib.STRUCTS["dv3_mono_desc"]()
+    steps, key_len = _c(steps), _c(key_len)
+    d.attn, d.steps, d.key_len = attn.data_ptr(), steps.data_ptr(), key_len.data_ptr()
+    d.layer_stride, d.item_stride, d.step_stride = stride.get("l", 0), stride["b"], stride["t"]
+    d.n_layers, d.B, d.T, d.Tk, d.max_advance = L, B, T, Tk, int(max_advance)
+    out = torch.empty(B, _lib.CONSTS["DV3_MONO_COLS"], dtype=torch.float32, device=attn.device)
+    path = torch.empty(B, T, dtype=torch.int32, device=attn.device)
+    durations = torch.empty(B, Tk, dtype=torch.int32, device=attn.device)
+    scratch = torch.empty(need.value, dtype=torch.uint8, device=attn.device)
+    d.out, d.path, d.durations = out.data_ptr(), path.data_ptr(), durations.data_ptr()
+    d.scratch, d.scratch_bytes = scratch.data_ptr(), need.value
+    _lib.call("dv3_mono_path_f32", ctypes.byref(d), _stream())
+    return out, path, durations
+
+
 # ----------------------------------------------------------------------------------------------
 # optimiser tail on flat arenas
 # ----------------------------------------------------------------------------------------------

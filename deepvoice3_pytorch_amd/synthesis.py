@@ -30,6 +30,15 @@ key when the done flag has not fired by then (decode_program.stall_stop).
     for mel, linear, alignment, wav, stats in synthesis.tts_batch(model, seqs, diagnostics=True, stall_limit=8):
         if stats["flags"]: ...                   # e.g. ("incomplete", "stalled")
 
+Token timings, opt-in on all three entry points: timings=True appends to every result (after the
+diagnostics element, if there is one) the utterance's timing dict -- the best monotonic path through its stored
+attention rows (ops.monotonic_path) and, from it, the span of the waveform every input token is spoken in.  Device
+tensors, no host read.  They are the best monotonic reading of THIS model's attention at decoder-step resolution (one
+step is r mel frames, r * upsampling hops of the waveform), not a phonetic aligner's output.
+
+    for mel, linear, alignment, wav, timing in synthesis.tts_batch(model, seqs, timings=True):
+        for token, t0, t1 in zip(seq, timing["start"].tolist(), timing["end"].tolist()): ...     # seconds
+
 Free-running evaluation: how far is the model's own synthesis of a held-out sentence from its
 recording?  evaluate_synthesis decodes (no Griffin-Lim), aligns each utterance with its target by dynamic time warping
 (ops.dtw) under the mel-cepstral distance (audio.mel_cepstra) and returns one row per utterance; SynthEvalTotals folds
@@ -100,6 +109,48 @@ def _diagnose(alignments, steps, lengths, caps):
     return out
 
 
+# the columns of a timing summary row (include/dv3hip.h: dv3_mono_path_f32), in order
+TIMING_COLUMNS = ("feasible", "steps", "keys", "score", "skipped_keys", "longest")
+
+
+def seconds_per_step(audio_cfg, r, upsampling):
+    """the waveform time of one decoder step: r mel frames of `upsampling` linear frames of hop_size samples each"""
+    cfg = audio_cfg or audio.AudioConfig()
+    return float(int(r) * int(upsampling) * cfg.hop_size) / float(cfg.sample_rate)
+
+
+def token_spans(durations, seconds_per_step):
+    """durations (..., N) integer steps per key -> (start, end) float64 of the same shape, in seconds:
+    start[n] = seconds_per_step * sum_{m < n} durations[m], end[n] = start[n] + seconds_per_step * durations[n] (both as
+    seconds_per_step times an exact integer sum, so end[-1] is exactly the steps times seconds_per_step)"""
+    upto = torch.cumsum(durations.to(torch.int64), dim=-1)
+    sps = float(seconds_per_step)
+    return (upto - durations).to(torch.float64) * sps, upto.to(torch.float64) * sps
+
+
+def token_timings(alignments, steps, lengths, seconds_per_step, layout="btk", max_advance=1):
+    """Where every input token is spoken: alignments / layout as ops.monotonic_path takes them (read in place), item b's
+    rows < steps[b] and keys < lengths[b] (host ints); seconds_per_step: the waveform time of one decoder step;
+    max_advance: the search's J (1: no token is skipped).  One library call for the batch, no host synchronisation.
+    -> one dict of device tensors per item, trimmed to the item: "path" (T_b,) int32, the key of every step;
+    "durations" (N_b,) int32, the steps of every key; "start" and "end" (N_b,) float64, token_spans of them in seconds;
+    "summary" (len(TIMING_COLUMNS),) fp32, the item's row.  An item without an admissible path (summary[0] = 0) has a
+    path of -1, zero durations and empty spans at 0."""
+    from . import ops
+    dev = alignments.device
+    steps, lengths = [int(n) for n in steps], [int(n) for n in lengths]
+    as_i32 = lambda v: torch.tensor(v, dtype=torch.int32).to(dev)
+    out, path, durations = ops.monotonic_path(alignments, as_i32(steps), as_i32(lengths), layout, max_advance)
+    start, end = token_spans(durations, seconds_per_step)
+    T, Tk = path.size(1), durations.size(1)
+    res = []
+    for b, (t, n) in enumerate(zip(steps, lengths)):
+        t, n = min(max(t, 0), T), min(max(n, 1), Tk)
+        res.append({"path": path[b, :t], "durations": durations[b, :n], "start": start[b, :n], "end": end[b, :n],
+                    "summary": out[b]})
+    return res
+
+
 def check_linear_dim(model, audio_cfg, what):
     """the model's linear_dim must be the audio config's fft_size // 2 + 1 (513 at 1024, 257 at 512, 1025 at 2048):
     refused here, once, with both numbers, instead of inside Griffin-Lim after the decode"""
@@ -107,12 +158,15 @@ def check_linear_dim(model, audio_cfg, what):
     audio.check_bins(model.linear_dim, cfg.fft_size, "%s: model.linear_dim = %d" % (what, model.linear_dim))
 
 
-def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=False, stall_limit=None):
+def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=False, stall_limit=None, timings=False,
+              timing_advance=1):
     """sequences: a list of int id sequences (one per utterance); speaker_ids: None or one id per utterance.
     -> a list of (mel (T_b, mel_dim), linear (T_b * upsampling, linear_dim), alignment (steps_b, Tt_b), wav (L_b,)),
     device tensors, each trimmed to its own utterance.  diagnostics: a fifth element, the utterance's alignment
     statistics (see the module text); stall_limit: the end-of-text stop (synthesize_batch applies it after the decode:
-    the batch still decodes until its slowest item's done flag, the stopped items' frames past the rule are dropped)."""
+    the batch still decodes until its slowest item's done flag, the stopped items' frames past the rule are dropped).
+    timings: one more element, after the statistics if they are there: the utterance's timing dict (token_timings, with
+    max_advance = timing_advance and the seconds per decoder step of audio_cfg); off: nothing is launched for it."""
     if len(sequences) == 0:
         return []
     check_linear_dim(model, audio_cfg, "tts_batch")
@@ -139,12 +193,20 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=Fa
     if diagnostics:
         steps = [int(n) // steps_per_frame for n in frames]
         stats = _diagnose(alignments, steps, lengths, [model.seq2seq.decoder.max_decoder_steps] * B)
+    spans = None
+    if timings:
+        spans = token_timings(alignments, [int(n) // steps_per_frame for n in frames], lengths,
+                              seconds_per_step(audio_cfg, steps_per_frame, up), "btk", timing_advance)
     out = []
     for b in range(B):
         n = int(frames[b])
         res = (mel[b, :n], linear[b, :n * up], alignments[b, :n // steps_per_frame, :lengths[b]],
                wavs[b, :int(samples[b])])
-        out.append(res + (stats[b],) if diagnostics else res)
+        if diagnostics:
+            res += (stats[b],)
+        if timings:
+            res += (spans[b],)
+        out.append(res)
     return out
 
 
@@ -160,17 +222,21 @@ class RollingSynthesizer(object):
     Everything runs on the current stream, admission and retirement included.  Inference only; a decoder the fused
     step kernels do not take is refused (no module-by-module fallback)."""
 
-    def __init__(self, model, slots=64, max_text_len=256, audio_cfg=None, chunk=8, diagnostics=False, stall_limit=None):
+    def __init__(self, model, slots=64, max_text_len=256, audio_cfg=None, chunk=8, diagnostics=False, stall_limit=None,
+                 timings=False, timing_advance=1):
         """diagnostics: every retired result gains a last element, the utterance's alignment statistics (one device
         read per retired group); stall_limit: the end-of-text stop -- after every chunk one statistics call runs in
         place on the program's stacked alignment buffer over the busy slots, and a slot whose attention reached its
         last key stall_limit steps ago retires then, if its done flag has not retired it first.  An item's step count
-        does not depend on the chunk size.  Both off by default: no launch and no result changes."""
+        does not depend on the chunk size.  timings: every retired result gains one more element, after the statistics
+        if they are there: the utterance's timing dict (token_timings with max_advance = timing_advance), searched in
+        place on the program's stacked alignment buffer over the retiring slots.  All off by default: no launch and
+        no result changes."""
         if slots < 1 or max_text_len < 1 or chunk < 1:
             raise ValueError("RollingSynthesizer: slots, max_text_len and chunk must be positive")
         if stall_limit is not None and int(stall_limit) < 0:
             raise ValueError("RollingSynthesizer: stall_limit must be >= 0 (or None: off)")
-        self.diagnostics = bool(diagnostics)
+        self.diagnostics, self.timings, self.timing_advance = bool(diagnostics), bool(timings), int(timing_advance)
         self.stall_limit = None if stall_limit is None else int(stall_limit)
         model.eval()
         self.model, self.audio_cfg = model, audio_cfg
@@ -272,13 +338,35 @@ class RollingSynthesizer(object):
         stats = None
         if self.diagnostics:
             stats = _diagnose(alignments, steps, lengths, [self._req[t][2] for t in tickets])
+        spans = None
+        if self.timings:            # a released slot's stacked rows stay as they are until it is admitted again
+            spans = self._timings(retired, lengths, alignments, seconds_per_step(self.audio_cfg, r, up))
         out = []
         for b, t in enumerate(tickets):
             n = int(frames[b])
             res = (t, mel[b, :n], linear[b, :n * up], alignments[b, :steps[b], :lengths[b]], wavs[b, :int(samples[b])])
-            out.append(res + (stats[b],) if self.diagnostics else res)
+            if self.diagnostics:
+                res += (stats[b],)
+            if self.timings:
+                res += (spans[b],)
+            out.append(res)
             del self._req[t]
         return out
+
+    def _timings(self, retired, lengths, alignments, sps):
+        """the timing dicts of a retiring group, in its order.  The search reads the program's stacked (t_cap, slots, Tk)
+        buffer in place ("tbk") with zero steps for every slot that is not retiring; a program whose stored rows carry
+        a scale (align_scale != 1: they are not the probabilities the results hold) is searched on the group's scaled
+        copy instead, so that either way the dict is that of the returned alignment."""
+        prog = self.prog
+        steps = [n for _, _, n in retired]
+        if prog.align_scale != 1.0:
+            return token_timings(alignments, steps, lengths, sps, "btk", self.timing_advance)
+        ran, keys = [0] * prog.B, [1] * prog.B
+        for (_, s, n), k in zip(retired, lengths):
+            ran[s], keys[s] = n, k
+        rows = token_timings(prog.aligns, ran, keys, sps, "tbk", self.timing_advance)
+        return [rows[s] for _, s, _ in retired]
 
     def poll(self):
         """one round: admit what fits, run one chunk of decoder steps, retire what stopped
@@ -321,20 +409,22 @@ class RollingSynthesizer(object):
 
 
 def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, audio_cfg=None, chunk=8,
-               max_decoder_steps=None, diagnostics=False, stall_limit=None):
+               max_decoder_steps=None, diagnostics=False, stall_limit=None, timings=False, timing_advance=1):
     """Rolling-admission counterpart of tts_batch, as a generator: sequences (any iterable of id lists; speaker_ids an
     iterable alongside, or None; max_decoder_steps None, one cap, or an iterable of per-utterance caps) are submitted
     in order as slots free -- at most `slots` are queued ahead -- and every utterance is yielded when it retires, in
     COMPLETION order: (index in `sequences`, mel, linear, alignment, wav), the entries as tts_batch returns them.
     max_text_len None: the longest sequence (the iterable is then read up front).  diagnostics, stall_limit: as
-    RollingSynthesizer takes them (a last element per result; the end-of-text stop)."""
+    RollingSynthesizer takes them (a last element per result; the end-of-text stop); timings, timing_advance: as there
+    (one more element per result, the utterance's timing dict)."""
     if max_text_len is None:
         sequences = [list(s) for s in sequences]
         if not sequences:
             return
         max_text_len = max(len(s) for s in sequences)
     rs = RollingSynthesizer(model, slots=slots, max_text_len=max_text_len, audio_cfg=audio_cfg, chunk=chunk,
-                            diagnostics=diagnostics, stall_limit=stall_limit)
+                            diagnostics=diagnostics, stall_limit=stall_limit, timings=timings,
+                            timing_advance=timing_advance)
     it = iter(sequences)
     spk = iter(speaker_ids) if speaker_ids is not None else None
     caps = None

@@ -629,9 +629,15 @@ Please set a larger value for ``max_position`` in hyper parameters.""".format(ma
                 raise ValueError("Trainer.evaluate(averaged=True): weight averaging is off (TrainConfig(ema_decay=...) is 0)")
             with self.averaged():
                 return self.evaluate(batch)
+        return self._eval_forward(batch, "evaluate", self._eval_losses)
+
+    def _eval_forward(self, batch, what, then):
+        """the eval-mode, teacher-forced forward evaluate() and align_batch() share: no gradients, ops.valid taken from
+        the batch and cleared, every module's training flag restored.  -> then(batch, mel_out, lin_out, attn, done_hat),
+        called inside the same no-grad, eval-mode scope (the outputs of a part that did not run are None)"""
         if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("Trainer.evaluate: called while a stream capture is in progress (evaluation runs eagerly, "
-                               "between steps)")
+            raise RuntimeError("Trainer.%s: called while a stream capture is in progress (evaluation runs eagerly, "
+                               "between steps)" % what)
         self.check_lengths(batch)
         s2s, pn = self.train_seq2seq, self.train_postnet
         modes = [(m, m.training) for m in self.model.modules()]
@@ -656,12 +662,29 @@ Please set a larger value for ``max_position`` in hyper parameters.""".format(ma
                         lin_out = self.model.postnet(batch.mel)
                 finally:
                     ops.valid = None
-                return self._eval_losses(batch, mel_out, lin_out, attn, done_hat)
+                return then(batch, mel_out, lin_out, attn, done_hat)
         finally:
             # every module's own flag back, as it was (train(mode) would set the whole tree to one value); assigning the
             # attribute is all nn.Module.train() does per module -- no module of the package overrides train()
             for m, flag in modes:
                 m.training = flag
+
+    def align(self, batch, max_advance=1, averaged=False):
+        """Forced alignment of one batch of recordings (align_batch): the forward of evaluate(), then the monotonic
+        search over all attention layers at once -> (out, path, durations) of ops.monotonic_path on the device."""
+        if not self.train_seq2seq:
+            raise ValueError("Trainer.align: this trainer runs the post-net only (train_seq2seq=False): no attention")
+        if averaged:
+            if not self.ema_on:
+                raise ValueError("Trainer.align(averaged=True): weight averaging is off (TrainConfig(ema_decay=...) is 0)")
+            with self.averaged():
+                return self.align(batch, max_advance)
+
+        def search(batch, mel_out, lin_out, attn, done_hat):
+            attn = attn if attn.stride(-1) == 1 else attn.contiguous()       # any other stride is read in place
+            return ops.monotonic_path(attn, batch.decoder_lengths, batch.input_lengths, "lbtk", max_advance)
+
+        return self._eval_forward(batch, "align", search)
 
     def eval_scalar_keys(self):
         """the names of the batch scalars evaluate() returns with this trainer's modes (EvalTotals(scalar_keys=))"""
@@ -1561,6 +1584,20 @@ def evaluate_loader(trainer, batches, process_group=None, averaged=False):
         for b in batches:
             tot.add(trainer.evaluate(b), getattr(b, "ids", None))
     return tot.result(process_group)
+
+
+def align_batch(trainer, batch, max_advance=1, averaged=False):
+    """Forced alignment of a batch of recordings under teacher forcing: per-token durations of a
+    corpus, for dataset checks (tokens that get no frames, transcripts that do not match their audio) and as duration
+    targets.  trainer: a Trainer, GraphedTrainer or LatticeReplay, as evaluate_loader takes them; batch: as collated.
+    Runs the eval-mode teacher-forced forward exactly as evaluate() does (nothing of the training state is touched, the
+    module flags are restored; refused during stream capture) and searches the mean of ALL attention layers
+    (ops.monotonic_path, layout "lbtk") over batch.decoder_lengths steps and batch.input_lengths keys.
+    -> (out (B, 6) fp32, columns synthesis.TIMING_COLUMNS; path (B, Td) int32; durations (B, Tt) int32) on the device;
+    one step is outputs_per_step * downsample_step frames of the recording.  averaged=True: under the moving average of
+    the trained parameters.  A trainer with train_seq2seq=False computes no attention: ValueError."""
+    t = trainer if isinstance(trainer, Trainer) else trainer.t
+    return t.align(batch, max_advance=max_advance, averaged=averaged)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1241,6 +1241,76 @@ typedef struct dv3_dtw_desc {
 int dv3_dtw_scratch_bytes(int32_t B, int32_t Tx, int32_t Ty, int32_t want_path, int64_t* bytes_out);
 int dv3_dtw_f32(const dv3_dtw_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Monotonic alignment search: token timings from stored attention rows (ops.monotonic_path, synthesis.token_timings,
+ * train_step.align_batch).  Additions to ABI 49: a descriptor, one entry point, a scratch-size query
+ * and five constants; nothing existing changed, so the version stays 49.
+ *
+ * attn[l * layer_stride + b * item_stride + t * step_stride + n] (fp32, strides in elements, the key axis dense) is the
+ * probability layer l of item b gave key n at step t.  Read in place: the step program's stacked (T, B, Tk), a
+ * contiguous (B, T, Tk) and the teacher-forced (L, B, T, Tk) are all strides of it; with n_layers = L = 1 the layer
+ * stride is ignored.  steps[b] is clamped to [0, T] and key_len[b] to [1, Tk] (device int32[B]) as in
+ * dv3_alignment_stats_f32; only elements t < T_b = steps[b], n < N_b = key_len[b] are read -- the others may hold
+ * anything, NaN included -- and attn is never written.
+ *
+ *   score        Pm[t, n] = (sum over l = 0 .. L-1, in that order, of attn[l, b, t, n]) / L, in fp32;
+ *                s[t, n] = logf(fmaxf(Pm[t, n], DV3_MONO_FLOOR)), the full-precision logf; a NaN scores as the floor
+ *   path rules   J = max_advance in [1, DV3_MONO_MAX_ADVANCE].  path[t] in [0, N_b) for t < T_b with
+ *                path[0] <= J - 1;   0 <= path[t] - path[t-1] <= J;   path[T_b - 1] >= N_b - J
+ *                -- at most J - 1 consecutive keys are skipped anywhere, the two ends included.  J = 1 is the classic
+ *                search: start on the first key, end on the last, stay or advance by one.
+ *   recurrence   Q[0, n] = s[0, n];   Q[t, n] = s[t, n] + max over 0 <= j <= J of Q[t-1, n-j], over the predecessors that
+ *                exist and can be reached, in fp32.  The chosen path maximises the sum of s along it.
+ *   tie-break    the advances are tried in the order j = 0, 1, .. J and a larger one replaces a smaller one only when it
+ *                is STRICTLY greater; among the admissible end keys N_b - 1 is tried first and a smaller key replaces it
+ *                only when STRICTLY greater.  Part of the interface: the integer outputs depend on it.
+ *
+ * out[b] = DV3_MONO_COLS fp32 columns (names: synthesis.TIMING_COLUMNS):
+ *    0 feasible      1 when a path satisfies the rules, else 0
+ *    1 steps         T_b                          2 keys           N_b
+ *    3 score         Q of the chosen end cell (the fp32 recurrence's value)
+ *    4 skipped_keys  keys n < N_b with duration 0
+ *    5 longest       the largest duration
+ * path (B, T) int32: the key of every step, -1 at t >= T_b.  durations (B, Tk) int32: the number of steps assigned to
+ * each key (the histogram of path), 0 at n >= N_b; for a feasible item they sum to T_b.  All three are always fully
+ * written.  An INFEASIBLE item -- no path satisfies the rules, e.g. N_b > (T_b + 1) * J - 1, or T_b = 0 -- has
+ * feasible = 0, score = 0, columns 4 and 5 = 0, its path all -1 and its durations all 0; steps and keys are still
+ * written, and the other items are untouched.
+ *
+ * What the figures are: the best monotonic reading of THIS model's attention, at decoder-step resolution (one step is
+ * r mel frames; r * downsample_step frames of a recording under teacher forcing).  They are not a phonetic aligner's
+ * output.
+ *
+ * Three launches: a score pass (one wave per row) writes s to scratch inside each item's lengths; one 64-lane wave per
+ * item scans the recurrence (key n in lane n % 64, the predecessors by cross-lane moves, the rows of the next steps in
+ * flight) and stores one back-pointer byte per cell; one wave per item walks the bytes back through LDS.  scratch:
+ * >= dv3_mono_path_scratch_bytes(...) bytes = 4 * B * T * Tk + (B * T * Tk rounded up to a multiple of 4), 4-byte
+ * aligned; the size goes out through the pointer (it passes 2^31 at accepted sizes).  No floating-point atomics: two
+ * calls give bit-equal output.  Refused (DV3_EINVAL, dv3_last_error names the argument, nothing launched): a null
+ * pointer; B < 1 or B > 65535; T outside [1, DV3_MONO_MAX_T]; Tk outside [1, DV3_MONO_MAX_TK]; max_advance outside
+ * [1, DV3_MONO_MAX_ADVANCE]; n_layers < 1; scratch_bytes below the query; out, path, durations or scratch not 4-byte
+ * aligned.
+ * ------------------------------------------------------------------------------------ */
+#define DV3_MONO_COLS 6
+#define DV3_MONO_MAX_T 8192
+#define DV3_MONO_MAX_TK 2048
+#define DV3_MONO_MAX_ADVANCE 8
+#define DV3_MONO_FLOOR 1e-20f
+typedef struct dv3_mono_desc {
+  const float* attn;                         /* (L, B, T, Tk) through the strides below                               */
+  const int32_t* steps;                      /* device int32[B]                                                       */
+  const int32_t* key_len;
+  int64_t layer_stride, item_stride, step_stride;           /* in elements; layer_stride ignored when n_layers = 1   */
+  int32_t n_layers, B, T, Tk, max_advance;
+  float* out;                                /* B x DV3_MONO_COLS                                                     */
+  int32_t* path;                             /* B x T                                                                 */
+  int32_t* durations;                        /* B x Tk                                                                */
+  void* scratch;
+  int64_t scratch_bytes;
+} dv3_mono_desc;
+int dv3_mono_path_scratch_bytes(int32_t B, int32_t T, int32_t Tk, int64_t* bytes_out);
+int dv3_mono_path_f32(const dv3_mono_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
