@@ -83,7 +83,7 @@ class MultiSpeakerTTSModel(nn.Module):
         return mel, linear, alignments, done
 
 
-    def synthesize_batch(self, text_sequences, text_lengths, speaker_ids=None, stall_limit=None):
+    def synthesize_batch(self, text_sequences, text_lengths, speaker_ids=None, stall_limit=None, postnet=True):
         """Per-utterance batched synthesis: every item of a ragged batch comes back as if it had been synthesised alone
         (the reference's synthesis.tts at B = 1, synthesis.py:42-73, model part).  text_sequences (B, Tt) int ids on
         the device, padded past each item's text_lengths[b]; positions are 1..text_lengths[b].  The encoder and the
@@ -93,7 +93,9 @@ class MultiSpeakerTTSModel(nn.Module):
         (int64[B], host) are each item's mel frames (decoder steps x r); everything past them is zero.
         stall_limit (None: off): the opt-in end-of-text stop -- an item whose attention has reached its last key keeps
         decode_program.stall_stop(...) steps if its done flag has not fired by then.  Applied after the decode and before
-        the post-net; the decode loop itself still runs until the slowest item's done flag (or the cap)."""
+        the post-net; the decode loop itself still runs until the slowest item's done flag (or the cap).
+        postnet=False: the post-net is not run and linear comes back None (a model trained without its post-net has
+        nothing to say there; synthesis.tts_batch(from_mel=...) vocodes the mel instead); nothing else differs."""
         from . import ops
         if self.training:
             raise RuntimeError("synthesize_batch: eval mode only")
@@ -133,12 +135,14 @@ class MultiSpeakerTTSModel(nn.Module):
                 Td = mel.size(1)
                 mel = mel.reshape(B, -1, self.mel_dim)
                 post_in = states.view(B, mel.size(1), -1) if self.use_decoder_state_for_postnet_input else mel
-                vl.set_dec(steps, Td)
-                linear = self.postnet(post_in, speaker_embed).contiguous()
-                ops.zero_frames(linear, vl.dec_len, int(steps.min()), linear.size(1) // Td)
+                linear = None
+                if postnet:
+                    vl.set_dec(steps, Td)
+                    linear = self.postnet(post_in, speaker_embed).contiguous()
+                    ops.zero_frames(linear, vl.dec_len, int(steps.min()), linear.size(1) // Td)
         finally:
             ops.valid = prev
-        assert linear.size(-1) == self.linear_dim
+        assert linear is None or linear.size(-1) == self.linear_dim
         return mel, linear, alignments, done, steps * (mel.size(1) // Td)
 
 

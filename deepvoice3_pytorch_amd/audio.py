@@ -21,6 +21,9 @@ Conventions (AudioConfig.convention):
 Frame size: AudioConfig.fft_size is 512, 1024 (every reference preset) or 2048 -- the sizes the FFT kernels are built for
 (FFT_SIZES); 16 kHz corpora use 512 / 128, 44.1 and 48 kHz voices 2048 / 512.  The functions below that take a hop
 instead of a config take the size as `fft_size=` (default 1024).
+
+A mel spectrogram is vocoded through the same path: mel_to_linear inverts the filterbank per frame (csrc/mel_inverse.hip),
+inv_melspectrogram_batch / inv_melspectrogram put its result through inv_spectrogram_batch.
 """
 import numpy as np
 import torch
@@ -416,12 +419,68 @@ def mel_tables(device, sample_rate=22050, num_mels=80, fmin=125.0, fmax=7600.0, 
     key = (str(device), int(sample_rate), int(num_mels), float(fmin), float(fmax), int(fft_size))
     if key not in _MEL_CACHE:
         w = mel_basis(sample_rate, fft_size, num_mels, fmin, fmax)
-        band = np.zeros((num_mels, 2), dtype=np.int32)
-        for m in range(num_mels):
-            nz = np.nonzero(w[m])[0]
-            band[m] = (nz[0], nz[-1] + 1) if nz.size else (0, 0)
-        _MEL_CACHE[key] = (torch.from_numpy(w).to(device), torch.from_numpy(band).to(device))
+        _MEL_CACHE[key] = (torch.from_numpy(w).to(device), torch.from_numpy(filter_bands_np(w)).to(device))
     return _MEL_CACHE[key]
+
+
+def filter_bands_np(w):
+    """(num_mels, 2) int32: band[m] = [first, last + 1) of filter m's nonzero bins, (0, 0) for an empty filter"""
+    band = np.zeros((w.shape[0], 2), dtype=np.int32)
+    for m in range(w.shape[0]):
+        nz = np.nonzero(w[m])[0]
+        band[m] = (nz[0], nz[-1] + 1) if nz.size else (0, 0)
+    return band
+
+
+def bin_bands_np(band, n_bins):
+    """(n_bins, 2) int32 from filter_bands_np's table: [first, last + 1) of the filters whose band holds bin k, (0, 0)
+    for a bin under no filter.  A filterbank whose filters over some bin are not a contiguous range is refused (the
+    inversion kernel walks the range)."""
+    band = np.asarray(band, dtype=np.int64)
+    k = np.arange(int(n_bins), dtype=np.int64)[:, None]
+    over = (band[None, :, 0] <= k) & (k < band[None, :, 1])                  # (n_bins, num_mels)
+    count = over.sum(axis=1)
+    first = np.where(count > 0, over.argmax(axis=1), 0)
+    last = np.where(count > 0, over.shape[1] - over[:, ::-1].argmax(axis=1), 0)
+    if np.any(last - first != count):
+        raise ValueError("bin_bands_np: the filters over bin %d are not a contiguous range"
+                         % int(np.nonzero(last - first != count)[0][0]))
+    return np.stack([first, last], axis=1).astype(np.int32)
+
+
+_MEL_INVERSE_CACHE = {}
+
+
+def mel_inverse_tables(device, sample_rate=22050, num_mels=80, fmin=125.0, fmax=7600.0, fft_size=N_FFT):
+    """mel_tables' (basis, band) with what the inversion adds, cached beside them: (basis, band, bin_band int32
+    (fft_size // 2 + 1, 2) on `device`, 1 / sum(basis) as a float)"""
+    key = (str(device), int(sample_rate), int(num_mels), float(fmin), float(fmax), int(fft_size))
+    if key not in _MEL_INVERSE_CACHE:
+        basis, band = mel_tables(device, sample_rate, num_mels, fmin, fmax, fft_size)
+        w = mel_basis(sample_rate, fft_size, num_mels, fmin, fmax)
+        total = float(w.astype(np.float64).sum())
+        if not total > 0.0:
+            raise ValueError("mel_inverse_tables: the filterbank (%d bands, %g .. %g Hz at %d Hz, fft_size=%d) is empty"
+                             % (num_mels, fmin, fmax, sample_rate, fft_size))
+        bins = torch.from_numpy(bin_bands_np(filter_bands_np(w), w.shape[1])).to(device)
+        _MEL_INVERSE_CACHE[key] = (basis, band, bins, 1.0 / total)
+    return _MEL_INVERSE_CACHE[key]
+
+
+class MelInverse(object):
+    """Options of the mel-to-linear inversion (mel_to_linear): iters, the number of multiplicative updates, an int in
+    [0, DV3_MELINV_MAX_ITERS] (0: the flat start; 32 leaves a mean round-trip error below 1e-3 of the normalised range
+    on speech-like frames); fmin, fmax: the band edges in Hz the mel was made with (hparams.fmin /
+    fmax), 0 <= fmin < fmax.  Refused by value (ValueError naming it)."""
+
+    def __init__(self, iters=32, fmin=125.0, fmax=7600.0):
+        top = _lib.CONSTS["DV3_MELINV_MAX_ITERS"]
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 0 <= int(iters) <= top:
+            raise ValueError("MelInverse: iters=%r must be an int in [0, %d]" % (iters, top))
+        number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+        if not number(fmin) or not number(fmax) or not 0.0 <= float(fmin) < float(fmax) < float("inf"):
+            raise ValueError("MelInverse: fmin=%r, fmax=%r must be numbers with 0 <= fmin < fmax" % (fmin, fmax))
+        self.iters, self.fmin, self.fmax = int(iters), float(fmin), float(fmax)
 
 
 _CEPSTRA_CACHE = {}
@@ -457,6 +516,70 @@ def mel_cepstra(mel, cfg=None, order=13):
     span = -float(cfg.min_level_db)
     db = mel.to(torch.float32).clamp(0.0, 1.0) * span - span
     return torch.matmul(db, _CEPSTRA_CACHE[key])
+
+
+# ---------------------------------------------------------------------------------------------
+# vocoding from a mel spectrogram: the filterbank inverted per frame, then the path above
+# ---------------------------------------------------------------------------------------------
+def _host_lengths(frame_lengths, B, lo, hi, what):
+    fl = torch.as_tensor(frame_lengths).reshape(-1).to(torch.int64).cpu()
+    if fl.numel() != B or int(fl.min()) < lo or int(fl.max()) > hi:
+        raise ValueError("%s: %d frame lengths in [%d, %d] expected, got %s" % (what, B, lo, hi, fl.tolist()))
+    return fl
+
+
+def mel_to_linear(mel, cfg=None, frame_lengths=None, upsample=1, options=None):
+    """(B, T, num_mels) normalised mel on the device (the model's mel outputs, or the rows features_items / preprocess
+    write) -> (B, T * upsample, cfg.fft_size // 2 + 1) normalised linear spectrogram, the model's linear_outputs format:
+    per frame the non-negative magnitudes s that best explain the mel amplitudes under the filterbank W =
+    mel_basis(cfg.sample_rate, cfg.fft_size, num_mels, options.fmin, options.fmax) -- options.iters multiplicative
+    updates s <- s * W^T a / W^T W s from a flat start (include/dv3hip.h: dv3_mel_to_linear_f32 states every step).
+    num_mels is mel's last dimension.  upsample (1 .. 16): output frame t is interpolated in the normalised domain
+    between mel frames t // upsample and the next one of the same item (frame i * upsample is mel frame i exactly; the
+    last upsample - 1 frames hold the item's last frame).  frame_lengths (B host ints, in mel frames, 0 .. T): item b has
+    only its first frame_lengths[b] frames; its output rows past upsample * frame_lengths[b] are zero.  Every row depends
+    on its own item alone.  Bins under no filter (outside fmin .. fmax) come back as 0.  options: a MelInverse."""
+    cfg = cfg or AudioConfig()
+    opt = options if options is not None else MelInverse()
+    if not isinstance(opt, MelInverse):
+        raise ValueError("mel_to_linear: options must be a MelInverse, got %r" % (options,))
+    mel = _c(_chk(mel, "mel"))
+    if mel.dim() != 3 or min(mel.shape) < 1:
+        raise ValueError("mel_to_linear: a non-empty (B, T, num_mels) mel expected, got %s" % (tuple(mel.shape),))
+    B, T, M = mel.shape
+    if isinstance(upsample, bool) or not isinstance(upsample, (int, np.integer)) or not 1 <= int(upsample) <= 16:
+        raise ValueError("mel_to_linear: upsample=%r must be an int in [1, 16]" % (upsample,))
+    if M > _lib.CONSTS["DV3_MELINV_MAX_MELS"]:
+        raise ValueError("mel_to_linear: %d mel bands, at most %d" % (M, _lib.CONSTS["DV3_MELINV_MAX_MELS"]))
+    u, F = int(upsample), cfg.fft_size // 2 + 1
+    tlen = None
+    if frame_lengths is not None:
+        tlen = _host_lengths(frame_lengths, B, 0, T, "mel_to_linear").to(torch.int32).to(mel.device)
+    basis, band, bins, inv_sum = mel_inverse_tables(mel.device, cfg.sample_rate, M, opt.fmin, opt.fmax, cfg.fft_size)
+    lin = torch.empty((B, T * u, F), dtype=torch.float32, device=mel.device)
+    _lib.call("dv3_mel_to_linear_f32", mel.data_ptr(), tlen.data_ptr() if tlen is not None else None, basis.data_ptr(),
+              band.data_ptr(), bins.data_ptr(), inv_sum, lin.data_ptr(), B, T, M, F, u, opt.iters,
+              float(cfg.min_level_db), float(cfg.ref_level_db), _stream())
+    return lin
+
+
+def inv_melspectrogram_batch(mel, cfg=None, frame_lengths=None, upsample=1, options=None, init_phasor=None):
+    """(B, T, num_mels) normalised mel on the device -> waveforms: exactly inv_spectrogram_batch(mel_to_linear(mel, cfg,
+    frame_lengths, upsample, options), cfg, init_phasor, frame_lengths * upsample), with its return forms (the waveforms;
+    with frame_lengths, in mel frames: (waveforms, sample lengths))."""
+    cfg = cfg or AudioConfig()
+    lin = mel_to_linear(mel, cfg, frame_lengths, upsample, options)
+    if frame_lengths is None:
+        return inv_spectrogram_batch(lin, cfg, init_phasor)
+    fl = torch.as_tensor(frame_lengths).reshape(-1).to(torch.int64).cpu()
+    return inv_spectrogram_batch(lin, cfg, init_phasor, fl * int(upsample))
+
+
+def inv_melspectrogram(mel, cfg=None, device="cuda:0", options=None):
+    """The numpy sibling of inv_spectrogram for a mel: (num_mels, T) normalised numpy -> waveform numpy."""
+    m = torch.as_tensor(np.ascontiguousarray(np.asarray(mel, dtype=np.float32).T)).unsqueeze(0)
+    y = inv_melspectrogram_batch(m.to(device), cfg, options=options)
+    return y[0].cpu().numpy()
 
 
 def _check_lws(cfg, what):

@@ -39,6 +39,14 @@ step is r mel frames, r * upsampling hops of the waveform), not a phonetic align
     for mel, linear, alignment, wav, timing in synthesis.tts_batch(model, seqs, timings=True):
         for token, t0, t1 in zip(seq, timing["start"].tolist(), timing["end"].tolist()): ...     # seconds
 
+Vocoding from the mel, opt-in on all three entry points: from_mel=True (or an audio.MelInverse) skips
+the post-net -- a model trained with train_postnet=False has a random one -- and inverts the decoder's mel instead:
+`linear` is audio.mel_to_linear of the utterance's own mel frames at the post-net's upsampling, `wav` its Griffin-Lim
+inversion.  A preview of the seq2seq half: the mel is interpolated in time and bins outside the mel band stay at the
+floor.
+
+    for mel, linear, alignment, wav in synthesis.tts_batch(model, seqs, from_mel=True): ...
+
 Free-running evaluation: how far is the model's own synthesis of a held-out sentence from its
 recording?  evaluate_synthesis decodes (no Griffin-Lim), aligns each utterance with its target by dynamic time warping
 (ops.dtw) under the mel-cepstral distance (audio.mel_cepstra) and returns one row per utterance; SynthEvalTotals folds
@@ -158,18 +166,43 @@ def check_linear_dim(model, audio_cfg, what):
     audio.check_bins(model.linear_dim, cfg.fft_size, "%s: model.linear_dim = %d" % (what, model.linear_dim))
 
 
+def postnet_upsampling(model):
+    """linear frames per mel frame of the model's post-net, without a forward: the product of the strides of its
+    transposed convolutions, 2 ** (the number of conv layers with transposed = True)"""
+    from . import conv
+    return 2 ** sum(1 for m in model.postnet.modules() if isinstance(m, conv._WNLayer) and m.transposed)
+
+
+def mel_options(from_mel):
+    """the `from_mel=` keyword of the entry points -> None (off), or the audio.MelInverse to vocode the mel with:
+    True means MelInverse(), an instance is used as given"""
+    if from_mel is None or from_mel is False:
+        return None
+    if from_mel is True:
+        return audio.MelInverse()
+    if not isinstance(from_mel, audio.MelInverse):
+        raise ValueError("from_mel must be False, True or an audio.MelInverse, got %r" % (from_mel,))
+    return from_mel
+
+
 def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=False, stall_limit=None, timings=False,
-              timing_advance=1):
+              timing_advance=1, from_mel=False):
     """sequences: a list of int id sequences (one per utterance); speaker_ids: None or one id per utterance.
     -> a list of (mel (T_b, mel_dim), linear (T_b * upsampling, linear_dim), alignment (steps_b, Tt_b), wav (L_b,)),
     device tensors, each trimmed to its own utterance.  diagnostics: a fifth element, the utterance's alignment
     statistics (see the module text); stall_limit: the end-of-text stop (synthesize_batch applies it after the decode:
     the batch still decodes until its slowest item's done flag, the stopped items' frames past the rule are dropped).
     timings: one more element, after the statistics if they are there: the utterance's timing dict (token_timings, with
-    max_advance = timing_advance and the seconds per decoder step of audio_cfg); off: nothing is launched for it."""
+    max_advance = timing_advance and the seconds per decoder step of audio_cfg); off: nothing is launched for it.
+    from_mel (False; True or an audio.MelInverse): vocode the decoder's MEL instead of the post-net's output -- the
+    post-net is not run (a model trained without it has a random one), `linear` is audio.mel_to_linear of the
+    utterance's own mel frames at the post-net's upsampling (postnet_upsampling; audio_cfg's bins, not the model's
+    linear_dim) and `wav` its inversion.  A preview of the seq2seq half, not the post-net's quality."""
     if len(sequences) == 0:
         return []
-    check_linear_dim(model, audio_cfg, "tts_batch")
+    mel_opt = mel_options(from_mel)
+    if mel_opt is None:
+        check_linear_dim(model, audio_cfg, "tts_batch")
     dev = next(model.parameters()).device
     lengths = [len(s) for s in sequences]
     if min(lengths) < 1:
@@ -184,10 +217,13 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=Fa
     if speaker_ids is not None:
         spk = torch.as_tensor(speaker_ids, dtype=torch.long).reshape(-1).to(dev)
     model.eval()
-    mel, linear, alignments, _, frames = model.synthesize_batch(text, lengths, spk, stall_limit=stall_limit)
-    up = linear.size(1) // mel.size(1)
+    mel, linear, alignments, _, frames = model.synthesize_batch(text, lengths, spk, stall_limit=stall_limit,
+                                                                postnet=mel_opt is None)
+    up = linear.size(1) // mel.size(1) if mel_opt is None else postnet_upsampling(model)
     steps_per_frame = mel.size(1) // alignments.size(1)        # r
     with torch.no_grad():
+        if mel_opt is not None:
+            linear = audio.mel_to_linear(mel, audio_cfg, frames, up, mel_opt)
         wavs, samples = audio.inv_spectrogram_batch(linear, audio_cfg, frame_lengths=frames * up)
     stats = None
     if diagnostics:
@@ -223,15 +259,16 @@ class RollingSynthesizer(object):
     step kernels do not take is refused (no module-by-module fallback)."""
 
     def __init__(self, model, slots=64, max_text_len=256, audio_cfg=None, chunk=8, diagnostics=False, stall_limit=None,
-                 timings=False, timing_advance=1):
+                 timings=False, timing_advance=1, from_mel=False):
         """diagnostics: every retired result gains a last element, the utterance's alignment statistics (one device
         read per retired group); stall_limit: the end-of-text stop -- after every chunk one statistics call runs in
         place on the program's stacked alignment buffer over the busy slots, and a slot whose attention reached its
         last key stall_limit steps ago retires then, if its done flag has not retired it first.  An item's step count
         does not depend on the chunk size.  timings: every retired result gains one more element, after the statistics
         if they are there: the utterance's timing dict (token_timings with max_advance = timing_advance), searched in
-        place on the program's stacked alignment buffer over the retiring slots.  All off by default: no launch and
-        no result changes."""
+        place on the program's stacked alignment buffer over the retiring slots.  from_mel (True or an
+        audio.MelInverse): retirement vocodes the group's mel instead of running the post-net, as tts_batch does.
+        All off by default: no launch and no result changes."""
         if slots < 1 or max_text_len < 1 or chunk < 1:
             raise ValueError("RollingSynthesizer: slots, max_text_len and chunk must be positive")
         if stall_limit is not None and int(stall_limit) < 0:
@@ -245,7 +282,9 @@ class RollingSynthesizer(object):
         if not hasattr(self.dec, "slot_program"):
             raise RuntimeError("RollingSynthesizer: %r has no slot-mode step program" % type(self.dec))
         self.prog = self.dec.slot_program(slots, self.max_text_len)
-        check_linear_dim(model, audio_cfg, "RollingSynthesizer")     # retirement ends in Griffin-Lim on audio_cfg's framing
+        self.mel_options = mel_options(from_mel)
+        if self.mel_options is None:
+            check_linear_dim(model, audio_cfg, "RollingSynthesizer")     # retirement ends in Griffin-Lim on audio_cfg's framing
         self.schedule = RollingSchedule(slots, chunk)
         self.min_steps = int(self.dec.min_decoder_steps)
         self.max_steps = int(self.dec.max_decoder_steps)        # = the program's t_cap - 1
@@ -322,18 +361,22 @@ class RollingSynthesizer(object):
             outputs, alignments, states = self.prog.read_slots([s for _, s, _ in retired], steps)
             self.prog.release([s for _, s, _ in retired])
             mel = outputs.reshape(G, -1, model.mel_dim)
-            post_in = states.view(G, mel.size(1), -1) if model.use_decoder_state_for_postnet_input else mel
-            vl = ops.ItemLengths(lengths, max(lengths), dev)
-            vl.set_dec(steps, Td)
-            prev, ops.valid = ops.valid, vl
-            try:
-                linear = model.postnet(post_in, self._speaker_embed(tickets, dev)).contiguous()
-                ops.zero_frames(linear, vl.dec_len, min(steps), linear.size(1) // Td)
-            finally:
-                ops.valid = prev
             r = mel.size(1) // Td
-            up = linear.size(1) // mel.size(1)
             frames = torch.tensor(steps, dtype=torch.int64) * r
+            if self.mel_options is not None:        # vocode the mel: no post-net
+                up = postnet_upsampling(model)
+                linear = audio.mel_to_linear(mel, self.audio_cfg, frames, up, self.mel_options)
+            else:
+                post_in = states.view(G, mel.size(1), -1) if model.use_decoder_state_for_postnet_input else mel
+                vl = ops.ItemLengths(lengths, max(lengths), dev)
+                vl.set_dec(steps, Td)
+                prev, ops.valid = ops.valid, vl
+                try:
+                    linear = model.postnet(post_in, self._speaker_embed(tickets, dev)).contiguous()
+                    ops.zero_frames(linear, vl.dec_len, min(steps), linear.size(1) // Td)
+                finally:
+                    ops.valid = prev
+                up = linear.size(1) // mel.size(1)
             wavs, samples = audio.inv_spectrogram_batch(linear, self.audio_cfg, frame_lengths=frames * up)
         stats = None
         if self.diagnostics:
@@ -409,14 +452,16 @@ class RollingSynthesizer(object):
 
 
 def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, audio_cfg=None, chunk=8,
-               max_decoder_steps=None, diagnostics=False, stall_limit=None, timings=False, timing_advance=1):
+               max_decoder_steps=None, diagnostics=False, stall_limit=None, timings=False, timing_advance=1,
+               from_mel=False):
     """Rolling-admission counterpart of tts_batch, as a generator: sequences (any iterable of id lists; speaker_ids an
     iterable alongside, or None; max_decoder_steps None, one cap, or an iterable of per-utterance caps) are submitted
     in order as slots free -- at most `slots` are queued ahead -- and every utterance is yielded when it retires, in
     COMPLETION order: (index in `sequences`, mel, linear, alignment, wav), the entries as tts_batch returns them.
     max_text_len None: the longest sequence (the iterable is then read up front).  diagnostics, stall_limit: as
     RollingSynthesizer takes them (a last element per result; the end-of-text stop); timings, timing_advance: as there
-    (one more element per result, the utterance's timing dict)."""
+    (one more element per result, the utterance's timing dict); from_mel: as tts_batch takes it (the mel is vocoded, the
+    post-net is not run)."""
     if max_text_len is None:
         sequences = [list(s) for s in sequences]
         if not sequences:
@@ -424,7 +469,7 @@ def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, 
         max_text_len = max(len(s) for s in sequences)
     rs = RollingSynthesizer(model, slots=slots, max_text_len=max_text_len, audio_cfg=audio_cfg, chunk=chunk,
                             diagnostics=diagnostics, stall_limit=stall_limit, timings=timings,
-                            timing_advance=timing_advance)
+                            timing_advance=timing_advance, from_mel=from_mel)
     it = iter(sequences)
     spk = iter(speaker_ids) if speaker_ids is not None else None
     caps = None

@@ -1311,6 +1311,43 @@ typedef struct dv3_mono_desc {
 int dv3_mono_path_scratch_bytes(int32_t B, int32_t T, int32_t Tk, int64_t* bytes_out);
 int dv3_mono_path_f32(const dv3_mono_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Mel-to-linear inversion: a normalised linear spectrogram estimated from a normalised mel spectrogram, so that a mel
+ * can be put through Griffin-Lim (audio.mel_to_linear, audio.inv_melspectrogram_batch, synthesis `from_mel=`; DESIGN.md
+ * 3.6g).  Additions to ABI 49: one entry point and two constants; nothing existing changed, so the version stays 49.
+ *
+ * mel [B][T][n_mels] fp32, normalised; tlen device int32[B] (item b has tlen[b] frames in [0, T]; NULL: all have T);
+ * basis [n_mels][n_bins] fp32, the filterbank W; mel_band int32[n_mels][2], [first, last + 1) of filter m's nonzero bins
+ * (the table of dv3_analysis_items_f32); bin_band int32[n_bins][2], [first, last + 1) of the filters whose band holds
+ * bin k; inv_basis_sum = 1 / (the sum of all of W); lin [B][T * upsample][n_bins].  Output frame t < upsample * tlen[b]
+ * of item b, with u = upsample, i0 = t / u, i1 = min(i0 + 1, tlen[b] - 1), f = (t % u) / u:
+ *
+ *   x_m = fmaf(f, clip(mel[b][i1][m], 0, 1), (1 - f) * clip(mel[b][i0][m], 0, 1))        frame i u is mel frame i exactly
+ *   a_m = 10^((x_m * (-min_level_db) + min_level_db + ref_level_db) / 20)                 > 0
+ *   b_k = sum_m W[m][k] a_m;   s_k = covered_k * (sum_m a_m) * inv_basis_sum,   covered_k = (sum_m W[m][k] > 0)
+ *   iters times:   r_m = sum_k W[m][k] s_k;   d_k = sum_m W[m][k] r_m;   s_k = s_k * (b_k / max(d_k, 1e-30))
+ *   lin[b][t][k] = clip((20 log10(max(10^(min_level_db / 20), s_k)) - ref_level_db - min_level_db) / -min_level_db, 0, 1)
+ *
+ * the last line being dv3_amp_to_db_norm_f32's expression.  Every sum over k is one fmaf chain over the filter's band in
+ * ascending bin order, every sum over m one fmaf chain over the bin's filters in ascending filter order, from 0; sum_m
+ * a_m is a fixed tree.  The division is IEEE.  A bin under no filter is 0 throughout and comes out as 0.0.  Rows
+ * t >= upsample * tlen[b] are written as zeros: every element of lin is written.  A row depends on its own item's rows
+ * alone -- not on B, the order of the items, its neighbours or the padding.  The kernel relies on each filter's support
+ * lying inside its mel_band and on the filters over a bin lying inside its bin_band (entries are clamped to the
+ * arrays, so a wrong table gives wrong numbers, never a wild access); it assumes no number of filters per bin.
+ * One 64-lane wave per output frame, s and r in LDS, no workgroup barrier inside the iteration, no atomics: two calls
+ * give bit-equal output.  Refused (DV3_EINVAL, dv3_last_error names the argument, nothing launched): a null mel, basis,
+ * mel_band, bin_band or lin; B < 1; T < 1; B * T * upsample >= 2^31; n_mels outside [1, DV3_MELINV_MAX_MELS]; n_bins
+ * outside [1, 1025]; upsample outside [1, 16]; iters outside [0, DV3_MELINV_MAX_ITERS]; min_level_db not < 0;
+ * inv_basis_sum not a positive finite number.  tlen[b] lives on the device and is clamped to [0, T] there.
+ * ------------------------------------------------------------------------------------ */
+#define DV3_MELINV_MAX_MELS 256
+#define DV3_MELINV_MAX_ITERS 1024
+int dv3_mel_to_linear_f32(const float* mel, const int32_t* tlen, const float* basis, const int32_t* mel_band,
+                          const int32_t* bin_band, float inv_basis_sum, float* lin, int32_t B, int32_t T, int32_t n_mels,
+                          int32_t n_bins, int32_t upsample, int32_t iters, float min_level_db, float ref_level_db,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
