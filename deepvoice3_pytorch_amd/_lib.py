@@ -7,6 +7,7 @@ not drift from the C side; `dv3_sizeof` double-checks every struct at load time.
 The product path has NO fallback: if the shared library is missing or was built for another
 ABI, importing an op raises (the reference's torch ops are only ever used by `oracle/`).
 """
+import contextlib
 import ctypes
 import os
 import re
@@ -64,6 +65,12 @@ def _field_ctype(base, stars):
     return ("struct", base)          # a descriptor nested by value: resolved when the classes are made
 
 
+def parse_switches(src):
+    """the rows of the header's DV3_SWITCHES list -> {NAME: (id, default, lo, hi)}, in the header's order"""
+    rows = re.findall(r'^\s*X\((\d+),\s*(\w+),\s*(-?\d+),\s*(-?\d+),\s*(-?\d+),\s*"[^"]*"\)', src, flags=re.M)
+    return {name: (int(i), int(d), int(lo), int(hi)) for i, name, d, lo, hi in rows}
+
+
 def parse_header(path=_HEADER):
     """-> (structs: {name: [(field, ctype)]}, funcs: {name: (restype, [argtypes])}, consts)"""
     src = _strip_comments(open(path).read())
@@ -103,11 +110,12 @@ def parse_header(path=_HEADER):
     consts = {k: int(v) for k, v in re.findall(r"#define\s+(DV3_\w+)\s+\(?(-?\d+)(?![\w.])\)?", src)}
     # a float constant (1e-20f): its value as a Python float, never its leading digits as an int
     consts.update({k: float(v) for k, v in re.findall(r"#define\s+(DV3_\w+)\s+(-?\d+(?:\.\d*)?e-?\d+)f\b", src)})
+    consts.update({"DV3_SW_" + name: row[0] for name, row in parse_switches(src).items()})
     for em in re.finditer(r"enum\s*\{(.*?)\}\s*;", src, flags=re.S):
         nxt = 0
         for item in em.group(1).split(","):
             item = item.strip()
-            if not item:
+            if not item or "(" in item:       # (the DV3_SW_* enum is the expanded switch list: taken above)
                 continue
             if "=" in item:
                 k, v = [s.strip() for s in item.split("=")]
@@ -120,6 +128,8 @@ def parse_header(path=_HEADER):
 
 
 STRUCT_FIELDS, FUNCS, CONSTS = parse_header()
+# the library's run-time switches, "DV3_SW_<NAME>" -> (id, default, lo, hi): read from the header, no library load
+SWITCHES = {"DV3_SW_" + name: row for name, row in parse_switches(open(_HEADER).read()).items()}
 
 
 def _make_structs(all_fields):
@@ -192,3 +202,26 @@ def check(rc, what=""):
 def call(name, *args):
     """Call an int-returning entry point and raise on error."""
     check(getattr(lib(), name)(*args), name)
+
+
+def switch_value(what):
+    """-> (current value, default) of a run-time switch, named by its "DV3_SW_*" name or its id"""
+    value, dflt = ctypes.c_int32(), ctypes.c_int32()
+    call("dv3_switch_query", SWITCHES[what][0] if isinstance(what, str) else what, ctypes.byref(value), ctypes.byref(dflt))
+    return value.value, dflt.value
+
+
+@contextlib.contextmanager
+def switches(mapping):
+    """Run the body with the library's run-time switches of `mapping` ("DV3_SW_*" name or id -> value) set, then put back
+    the values they had on entry (not the defaults: scopes nest), also when the body raises.  A value the library refuses
+    raises, with the switches set so far put back."""
+    ids = [SWITCHES[k][0] if isinstance(k, str) else k for k in mapping]
+    before = [switch_value(i)[0] for i in ids]
+    try:
+        for i, v in zip(ids, mapping.values()):
+            call("dv3_debug_set", i, v)
+        yield
+    finally:
+        for i, v in zip(ids, before):
+            call("dv3_debug_set", i, v)

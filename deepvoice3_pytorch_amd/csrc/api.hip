@@ -170,50 +170,56 @@ extern "C" int dv3_debug_get(int what) {
   return 0;
 }
 
-// Run-time switches for measurement and bit-identity tests (include/dv3hip.h), each an int defined beside the host code
-// that reads it.  An unknown code is an error: a script that names a retired switch must not time the production kernel
-// believing it timed something else.
-extern int g_x3_pingpong, g_x3_rel2, g_x3_pp2, g_x3_prio, g_x3_wide, g_x3_pp2_sk_units, g_x3_j1_flat, g_x3_rel8;   // conv_gemm_bf16x3.hip
-extern int g_x3_ks, g_x3_ks_max_blocks, g_x3_ks_min_steps;                                       // conv_gemm_bf16x3.hip
-extern int g_pp2_ord_u, g_pp2_ord_m, g_pp2_sk, g_pp2_sk_overhead, g_pp2_sk_gain, g_pp2_fast_tail;   // conv_gemm_pp2.hip
-extern int g_planes_tile;                                                                        // conv_planes.hip
-extern int g_c8pp_min_tiles, g_c8pp_rf, g_c8pp_nw4, g_c8pp_stagger, g_c8pp_stagger_mask;          // conv_c8pp.hip
-extern int g_wgrad_tile, g_wgrad_prio, g_wgrad_taps2_default, g_wgrad_t2_window, g_wgrad_t2_il;   // wgrad_gemm_bf16x3.hip, wgrad_taps2.hip
-extern int g_wgrad_c8_pf2, g_wgrad_c8_il, g_wgrad_c8_tr;                                         // wgrad_c8.hip
-extern int g_spk_prefetch;                                                                       // speaker_bias.hip
-extern int g_gate_c8_fast, g_gate_vec;                                                           // elementwise.hip
-extern int g_loss_fast_log;                                                                      // loss.hip
-extern int g_wn_bwd_vec4;                                                                        // weight_norm.hip
+// Run-time switches (the DV3_SWITCHES list of include/dv3hip.h): storage, defaults and checks all come from that list;
+// the dispatchers read them through dv3_sw() (common.h).  An unknown id is an error: a script that names a retired
+// switch must not time the production kernel believing it timed something else.
+namespace {
+struct SwitchRow {
+  int id, dflt, lo, hi;
+  const char* name;
+};
+#define DV3_SW_ROW_(id, name, dflt, lo, hi, doc) {id, dflt, lo, hi, #name},
+constexpr SwitchRow kSwitchRows[] = {DV3_SWITCHES(DV3_SW_ROW_)};
+#undef DV3_SW_ROW_
+constexpr Dv3SwitchValues switch_defaults() {
+  Dv3SwitchValues s{};
+  for (const SwitchRow& r : kSwitchRows) s.v[r.id] = r.dflt;
+  return s;
+}
+#define DV3_SW_FITS_(id, name, dflt, lo, hi, doc) static_assert(id >= 0 && id < DV3_SW_SLOTS && lo <= dflt && dflt <= hi, #name);
+DV3_SWITCHES(DV3_SW_FITS_)
+#undef DV3_SW_FITS_
+const SwitchRow* find_switch(int what) {
+  for (const SwitchRow& r : kSwitchRows)
+    if (r.id == what) return &r;
+  return nullptr;
+}
+}  // namespace
+Dv3SwitchValues g_dv3_sw = switch_defaults();
+
 int dv3_conv_census_set(int on);                 // conv_gemm.hip
 extern "C" int dv3_debug_set(int what, int value) {
   if (what == 40) return dv3_conv_census_set(value);
-  if (what == 29 || what == 31) {   // ORD of the 256 x 256 kernel's unmasked / masked instantiations: the shipped forms
-    DV3_REQUIRE(value == 0 || value == 17 || value == 81, "debug_set(%d, %d): LOAD-phase order 0, 17 or 81", what, value);
-    (what == 29 ? g_pp2_ord_u : g_pp2_ord_m) = value;
-    return DV3_OK;
-  }
-  DV3_REQUIRE(what != 52 || (value >= 0 && value <= 4), "debug_set(52, %d): wgrad_c8 form 0..4", value);
-  static const struct {
-    int what;
-    int* var;
-  } kSwitches[] = {
-      {2, &g_wgrad_tile},        {3, &g_x3_pingpong},         {4, &g_planes_tile},      {9, &g_x3_rel2},
-      {12, &g_x3_pp2},           {14, &g_x3_prio},            {15, &g_wgrad_prio},      {17, &g_wgrad_taps2_default},
-      {18, &g_x3_wide},          {19, &g_c8pp_min_tiles},     {20, &g_wgrad_c8_pf2},    {22, &g_pp2_sk},
-      {23, &g_pp2_sk_overhead},  {24, &g_pp2_sk_gain},        {25, &g_x3_pp2_sk_units}, {27, &g_x3_j1_flat},
-      {30, &g_c8pp_rf},          {34, &g_c8pp_nw4},           {35, &g_c8pp_stagger},    {36, &g_c8pp_stagger_mask},
-      {42, &g_x3_rel8},          {44, &g_x3_ks},              {45, &g_x3_ks_max_blocks}, {46, &g_x3_ks_min_steps},
-      {47, &g_wgrad_t2_window},  {48, &g_wgrad_t2_il},        {49, &g_wgrad_c8_il},     {50, &g_pp2_fast_tail},
-      {51, &g_wn_bwd_vec4},      {52, &g_wgrad_c8_tr},        {54, &g_spk_prefetch},    {55, &g_gate_vec},
-      {56, &g_gate_c8_fast},     {57, &g_loss_fast_log},
-  };
-  for (const auto& sw : kSwitches)
-    if (sw.what == what) {
-      *sw.var = value;
-      return DV3_OK;
-    }
-  dv3_set_error("debug_set(%d, %d): no such switch", what, value);
-  return DV3_EINVAL;
+  const SwitchRow* sw = find_switch(what);
+  DV3_REQUIRE(sw, "debug_set(%d, %d): no such switch", what, value);
+  // ORD of the 256 x 256 kernel's unmasked / masked instantiations: the shipped forms
+  DV3_REQUIRE((what != DV3_SW_PP2_ORD_U && what != DV3_SW_PP2_ORD_M) || value == 0 || value == 17 || value == 81,
+              "debug_set(%d, %d): LOAD-phase order 0, 17 or 81", what, value);
+  DV3_REQUIRE(what != DV3_SW_WGRAD_C8_TR || (value >= sw->lo && value <= sw->hi), "debug_set(52, %d): wgrad_c8 form 0..4", value);
+  DV3_REQUIRE(value >= sw->lo && value <= sw->hi, "debug_set(%d, %d): %s takes %d..%d", what, value, sw->name, sw->lo, sw->hi);
+  g_dv3_sw.v[what] = value;
+  return DV3_OK;
+}
+extern "C" int dv3_debug_reset(void) {
+  g_dv3_sw = switch_defaults();
+  return DV3_OK;
+}
+extern "C" int dv3_switch_query(int what, int32_t* value, int32_t* dflt) {
+  const SwitchRow* sw = find_switch(what);
+  DV3_REQUIRE(sw, "switch_query(%d): no such switch", what);
+  if (value) *value = g_dv3_sw.v[what];
+  if (dflt) *dflt = sw->dflt;
+  return DV3_OK;
 }
 
 int dv3_decode_read_stamps(void* dst, int64_t bytes);  // decode_step.hip

@@ -34,6 +34,15 @@ static inline int dv3_check_launch(const char* what) {
 // dv3_debug_get(10 / 11): which kernel variant the last tap-GEMM / wgrad call launched (api.hip)
 extern int g_dv3_last_conv, g_dv3_last_wgrad;
 
+// Run-time switches (the DV3_SWITCHES list of include/dv3hip.h): one slot per id, defined with its defaults in api.hip.
+// Host code reads a switch as dv3_sw(DV3_SW_<NAME>); only dv3_debug_set / dv3_debug_reset write.
+constexpr int DV3_SW_SLOTS = 64;
+struct Dv3SwitchValues {
+  int v[DV3_SW_SLOTS];
+};
+extern Dv3SwitchValues g_dv3_sw;
+static inline int dv3_sw(int id) { return g_dv3_sw.v[id]; }
+
 static inline int dv3_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t dv3_cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -368,20 +368,20 @@ int launch_c8pp(const ConvArgs& a, size_t lds, hipStream_t st) {
 
 }  // namespace
 
-// dv3_debug_set(30, v): fragment reads first in a LOAD phase (RF instantiations; 0 = the round-4 order).  Default since
+// DV3_SW_C8PP_RF: fragment reads first in a LOAD phase (RF instantiations; 0 = the round-4 order).  Default since
 // round 5: bit-identical, 0.87-0.93 of the staging-first time over the presets' shapes in one process
 // (scripts/r5_ship_check.py, profiles/r05_c8pp_reads_first.txt: north star eval 63.9 -> 59.3 us, masked training forward
 // 77.4 -> 72.0 us, input gradient 58.5 -> 54.3 us; C = 512, T = 800: 201.5 -> 183.0 / 241.0 -> 209.0 / 186.0 -> 164.2 us)
-int g_c8pp_rf = 1;
-int g_c8pp_nw4 = 2;            // dv3_debug_set(34, v): two 4-wave workgroups per CU on 256 x 128 tiles (NW = 4): 0 never, 1 always, 2 by the rule in the dispatcher
-int g_c8pp_stagger = 0, g_c8pp_stagger_mask = 1;   // dv3_debug_set(35 / 36, v): start delay (x 64 cycles) of the blocks with (blockIdx & mask) != 0
-int g_c8pp_min_tiles = 128;   // dv3_debug_set(19, v): the 256 x 256 c8 kernel serves eligible shapes whose grid has at
-                              // least v tiles (0 = never; 1 = always)
+// DV3_SW_C8PP_NW4: two 4-wave workgroups per CU on 256 x 128 tiles (NW = 4): 0 never, 1 always, 2 by the rule in the dispatcher
+// DV3_SW_C8PP_STAGGER / _STAGGER_MASK: start delay (x 64 cycles) of the blocks with (blockIdx & mask) != 0
+// DV3_SW_C8PP_MIN_TILES (default 128): the 256 x 256 c8 kernel serves eligible shapes whose grid has at least that many
+// tiles (0 = never; 1 = always)
 
 // Called by dv3_conv_planes_dispatch (conv_planes.hip) for single-term bf16 layers on c8 input.  Returns 1 when the
 // shape is not eligible (the caller continues with the 128-row planes kernel), else a DV3_* code.
 int dv3_conv_c8pp_dispatch(const dv3_conv_desc* d, hipStream_t st) {
-  if (g_c8pp_min_tiles <= 0 || d->split_terms != 1 || !d->a_split || !d->x_c8) return 1;
+  const int min_tiles = dv3_sw(DV3_SW_C8PP_MIN_TILES), nw4_form = dv3_sw(DV3_SW_C8PP_NW4);
+  if (min_tiles <= 0 || d->split_terms != 1 || !d->a_split || !d->x_c8) return 1;
   if ((d->J != 1 && d->J != 3) || (d->J - 1) * d->dil > HALO_MAX) return 1;
   if (d->a_bs != 0 || (d->lda & 3) || d->Tin != d->Tout) return 1;
   const bool gated = d->mode == DV3_EPI_GLU || d->mode == DV3_EPI_HIGHWAY;
@@ -400,12 +400,12 @@ int dv3_conv_c8pp_dispatch(const dv3_conv_desc* d, hipStream_t st) {
   //   * below that the 128-row planes kernel (return 1).
   const bool is_dgrad = d->mode == DV3_EPI_DGRAD;
   const bool masked_fwd = d->xmask_c8 != nullptr && !is_dgrad;
-  bool use_nw4 = g_c8pp_nw4 == 1 || d->tile_hint == 41;
-  if (g_c8pp_nw4 == 2 && d->tile_hint != 40 && d->tile_hint != 41) {   // (a forcing hint survives the size rule: ADVICE r5)
+  bool use_nw4 = nw4_form == 1 || d->tile_hint == 41;
+  if (nw4_form == 2 && d->tile_hint != 40 && d->tile_hint != 41) {   // (a forcing hint survives the size rule: ADVICE r5)
     if (masked_fwd) use_nw4 = nb >= 100;
     else if (is_dgrad) use_nw4 = nb >= 64 && nb < 192;   // (201 tiles: 8-wave 49 us, 4-wave 55: profiles/r05_conv_census_nyanko_bf16_c8.txt)
   }
-  if (d->tile_hint != 40 && !use_nw4 && nb < g_c8pp_min_tiles) return 1;
+  if (d->tile_hint != 40 && !use_nw4 && nb < min_tiles) return 1;
   const int XI = (KB * (BN + (d->J > 1 ? HALO_MAX : 0)) + NT - 1) / NT;
   const size_t lds = (size_t)(2 * KB * BM + 2 * XI * NT) * 16;
   ConvArgs a;
@@ -427,13 +427,13 @@ int dv3_conv_c8pp_dispatch(const dv3_conv_desc* d, hipStream_t st) {
     const int64_t nb4 = m_tiles * a.n_tiles;
     DV3_REQUIRE(nb4 < (1ll << 31), "conv_c8pp: grid too large");
     a.n_blocks = (int)nb4;
-    a.stagger = g_c8pp_stagger;
-    a.stagger_mask = g_c8pp_stagger_mask;
+    a.stagger = dv3_sw(DV3_SW_C8PP_STAGGER);
+    a.stagger_mask = dv3_sw(DV3_SW_C8PP_STAGGER_MASK);
     g_dv3_last_conv = 9000 + 110 + 1;   // ... 256 x 128 tile, two workgroups per CU
     if (d->J == 3) return mask ? launch_c8pp<3, true, true, 4>(a, lds4, st) : launch_c8pp<3, false, true, 4>(a, lds4, st);
     return mask ? launch_c8pp<1, true, true, 4>(a, lds4, st) : launch_c8pp<1, false, true, 4>(a, lds4, st);
   }
-  if (g_c8pp_rf) {
+  if (dv3_sw(DV3_SW_C8PP_RF)) {
     if (d->J == 3) return mask ? launch_c8pp<3, true, true>(a, lds, st) : launch_c8pp<3, false, true>(a, lds, st);
     return mask ? launch_c8pp<1, true, true>(a, lds, st) : launch_c8pp<1, false, true>(a, lds, st);
   }

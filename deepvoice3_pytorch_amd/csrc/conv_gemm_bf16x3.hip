@@ -37,18 +37,9 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// Run-time switches of this file's launchers and tile picker (set through dv3_debug_set, api.hip)
-// main loop of the 8-wave tiles, dv3_debug_set(3, v): 0 = in-phase, 1 = ping-pong (default)
-int g_x3_pingpong = 1;
-int g_x3_ks = 1;        // dv3_debug_set(44, v): k-split form of the 128 x 64 tile: 0 never, 1 by the rule in the dispatcher, 2 wherever eligible
-int g_x3_ks_max_blocks = 256, g_x3_ks_min_steps = 8;   // dv3_debug_set(45 / 46, v): the rule's bounds
-int g_x3_rel8 = 86;     // dv3_debug_set(42, v): relative cost (percent) of the 256 x 128 ping-pong tile in the tile picker (pick_tile_x3).  Rounds 2-4: 93
-                        // (north-star sweep).  Round 5's census of a real step (profiles/r05_conv_census_dv3lj_b64.txt) has it ahead
-                        // of the 128 x 256 tile stand-alone wherever the two tie on rounds (the encoder's input gradients, the
-                        // 1 x 1 layers at T = 804); whole steps at 86: 15.56 -> 15.45 ms at B = 64, 7.75 -> 7.71 at B = 16
-                        // (profiles/r05_rel8_step_ab.txt)
-int g_x3_j1_flat = 1;   // dv3_debug_set(27, v)
-int g_x3_rel2 = 112;   // dv3_debug_set(9, v): relative cost (percent) of the 128x64 tile in the tile picker (pick_tile_x3)
+// Run-time switches of this file's launchers (the DV3_SWITCHES list of include/dv3hip.h, read through dv3_sw()):
+// DV3_SW_X3_PINGPONG = main loop of the 8-wave tiles, 0 = in-phase, 1 = ping-pong (default); DV3_SW_X3_KS = k-split form of
+// the 128 x 64 tile: 0 never, 1 by the rule in the dispatcher, 2 wherever eligible
 
 namespace {
 
@@ -679,7 +670,7 @@ int launch_x3_big_pp(const ConvArgs& a, size_t lds, hipStream_t st) {
 template <int WM, int WN, int NI, int MI>
 int launch_x3_big(const ConvArgs& a, size_t lds, hipStream_t st) {
   if constexpr (WM * WN == 8 && MI == 1) {
-    if (g_x3_pingpong) return launch_x3_big_pp<WM, WN, NI, MI, true>(a, lds, st);
+    if (dv3_sw(DV3_SW_X3_PINGPONG)) return launch_x3_big_pp<WM, WN, NI, MI, true>(a, lds, st);
   }
   return launch_x3_big_pp<WM, WN, NI, MI, false>(a, lds, st);
 }
@@ -724,12 +715,19 @@ const TileCfg* pick_tile_x3(const dv3_conv_desc* d, bool gated, int want_tile) {
     // 8-wave 256-wide tiles (one workgroup per CU): less weight-panel traffic per MFMA; the
     // 128-row-per-wave tile (7, one wave per SIMD) measured slower everywhere: opt-in only (hint 27)
     static const double kRel[10] = {0, 1.0, 1.12, 2.0, 2.2, 1.8, 2.0, 9.9, 0.93, 0.87};
-    double rel = c.id == 2 ? g_x3_rel2 * 0.01 : c.id == 8 ? g_x3_rel8 * 0.01 : kRel[c.id];
+    // Percentages of the two tiles whose cost was swept at run time (the retired switches 9 and 42).  The 256 x 128
+    // ping-pong tile: 93 in rounds 2-4 (north-star sweep).  Round 5's census of a real step
+    // (profiles/r05_conv_census_dv3lj_b64.txt) has it ahead of the 128 x 256 tile stand-alone wherever the two tie on
+    // rounds (the encoder's input gradients, the 1 x 1 layers at T = 804); whole steps at 86: 15.56 -> 15.45 ms at
+    // B = 64, 7.75 -> 7.71 at B = 16 (profiles/r05_rel8_step_ab.txt)
+    constexpr int kRel2Percent = 112, kRel8Percent = 86;
+    double rel = c.id == 2 ? kRel2Percent * 0.01 : c.id == 8 ? kRel8Percent * 0.01 : kRel[c.id];
     // 1 x 1 convolutions / Linear layers with K <= 512 (8-16 k32 steps per tile): prologue and tail dominate and the wide
     // tiles' staging advantage is gone -- measured per unit of modeled work the 128 x 64, 128 x 128, 256 x 128 and
     // 128 x 256 tiles cost the same (scripts/small_gemm_tiles.py: with the J = 3 weights the picker took the 128 x 256
     // tile for 64 x 804 columns x 512 rows at 135 us where the 128 x 64 tile runs 107), so only the rounds decide
-    if (g_x3_j1_flat && d->J == 1 && d->Cin <= 512 && (c.id == 1 || c.id == 2 || c.id == 8 || c.id == 9)) rel = 1.0;
+    // (whole steps with and without this rule: the retired switch 27, round 4)
+    if (d->J == 1 && d->Cin <= 512 && (c.id == 1 || c.id == 2 || c.id == 8 || c.id == 9)) rel = 1.0;
     const double cost = rounds * BM * BN * rel;
     if (!best || cost < best_cost) {
       best = &c;
@@ -741,16 +739,13 @@ const TileCfg* pick_tile_x3(const dv3_conv_desc* d, bool gated, int want_tile) {
 
 }  // namespace
 
-int g_x3_pp2 = 128;  // dv3_debug_set(12, v): the 256 x 256 k16 ping-pong kernel (conv_gemm_pp2.hip) serves eligible shapes
-                     // whose grid has at least v tiles (0 = never).  Measured at B=64 over the presets' conv shapes
-                     // (scripts/pp2_sweep.py, profiles/r03_pp2_sweep.txt): 0.73-0.88 of the 128 x 256 / 128 x 64 kernels'
-                     // time from 152 tiles up, 1.3-1.9 x at 50-100 tiles (half the chip idle).
-extern int g_pp2_ord_u, g_pp2_ord_m, g_pp2_sk, g_pp2_sk_overhead, g_pp2_sk_gain, g_pp2_fast_tail;
-int g_x3_pp2_sk_units = 8;   // measured (scripts/pp2_sk_check.py): at 9.5 units per CU (the encoder layers: 152 / 76 tiles) the
-                             // stream-K form beats the 128-wide kernels by 6-8 %, at 6.3 (101 tiles x 16) it loses to them
+// DV3_SW_X3_PP2_MIN_TILES (default 128): the 256 x 256 k16 ping-pong kernel (conv_gemm_pp2.hip) serves eligible shapes
+// whose grid has at least that many tiles (0 = never).  Measured at B=64 over the presets' conv shapes
+// (scripts/pp2_sweep.py, profiles/r03_pp2_sweep.txt): 0.73-0.88 of the 128 x 256 / 128 x 64 kernels'
+// time from 152 tiles up, 1.3-1.9 x at 50-100 tiles (half the chip idle).
+// DV3_SW_X3_WIDE: 16-byte input-gradient epilogue through LDS (conv_common.h), 0 off; DV3_SW_X3_PRIO: wave priority
+// scheme of the ping-pong main loop.
 int dv3_conv_gemm_pp2_dispatch(const dv3_conv_desc* d, hipStream_t st);   // conv_gemm_pp2.hip
-int g_x3_wide = 1;  // dv3_debug_set(18, v): 16-byte epilogue through LDS (conv_common.h): 0 off, 1 DGRAD, 
-int g_x3_prio = 0; // dv3_debug_set(14, v): wave priority scheme of the ping-pong main loop
 
 // called by dv3_conv_gemm_f32 (conv_gemm.hip) when d->a_split != NULL; returns 1 when the shape
 // is not eligible (caller falls back to the exact kernel), else a DV3_* code.
@@ -762,12 +757,16 @@ int dv3_conv_gemm_bf16x3_dispatch(const dv3_conv_desc* d, hipStream_t st) {
   if ((int64_t)d->B * d->Tout >= (1ll << 30) || (int64_t)d->B * d->x_bs >= (1ll << 30)) return 1;
   if (d->xmask && (int64_t)d->B * d->Cin * d->xmask_rs >= (1ll << 30)) return 1;
   if ((int64_t)d->J * ((d->Cin + 31) / 32 * 4) * d->lda >= (1ll << 27)) return 1;
-  // 256 x 256 tile, k16 ping-pong (conv_gemm_pp2.hip): tile_hint 30 forces it, dv3_debug_set(12, 1) prefers it
+  // 256 x 256 tile, k16 ping-pong (conv_gemm_pp2.hip): tile_hint 30 forces it, DV3_SW_X3_PP2_MIN_TILES = 1 prefers it
   const int64_t pp2_tiles = (int64_t)(gated ? dv3_cdiv(d->Cg, 128) : dv3_cdiv(d->M, 256)) * dv3_cdiv64((int64_t)d->B * d->Tout, 256);
+  const int pp2_min = dv3_sw(DV3_SW_X3_PP2_MIN_TILES), pp2_sk = dv3_sw(DV3_SW_PP2_SK);
   // with a stream-K workspace the 256 x 256 kernel no longer needs a grid that fills the chip: enough (tile, chunk)
-  // units for every CU instead (g_x3_pp2_sk_units per CU, dv3_debug_set(25, v))
-  const bool sk_fill = d->sk_ws && g_pp2_sk && (d->mode != DV3_EPI_DGRAD || g_pp2_sk >= 2) && g_x3_pp2 > 0 && pp2_tiles * (d->Cin / 32) >= (int64_t)g_x3_pp2_sk_units * 256;
-  if (d->tile_hint == 30 || (g_x3_pp2 > 0 && d->tile_hint == 0 && (pp2_tiles >= g_x3_pp2 || sk_fill))) {
+  // units for every CU instead.  How many per CU (the retired switch 25), measured (scripts/pp2_sk_check.py): at 9.5 (the
+  // encoder layers: 152 / 76 tiles) the stream-K form beats the 128-wide kernels by 6-8 %, at 6.3 (101 tiles x 16) it
+  // loses to them
+  constexpr int kPp2SkUnitsPerCu = 8;
+  const bool sk_fill = d->sk_ws && pp2_sk && (d->mode != DV3_EPI_DGRAD || pp2_sk >= 2) && pp2_min > 0 && pp2_tiles * (d->Cin / 32) >= (int64_t)kPp2SkUnitsPerCu * 256;
+  if (d->tile_hint == 30 || (pp2_min > 0 && d->tile_hint == 0 && (pp2_tiles >= pp2_min || sk_fill))) {
     const int rc = dv3_conv_gemm_pp2_dispatch(d, st);
     if (rc != 1) return rc;
     if (d->tile_hint == 30) return 1;
@@ -779,14 +778,16 @@ int dv3_conv_gemm_bf16x3_dispatch(const dv3_conv_desc* d, hipStream_t st) {
   // one 128 x 64 tile per CU, k-ranges of at least 8 steps (profiles/r05_k_split.txt: 0.76-0.94 x there, 1.15-2 x the
   // time from 300 tiles up, nothing below 8 steps).  Where the picker went to a smaller tile for such a grid (64 x 64,
   // 128 x 32: more, lonelier workgroups) the k-split 128 x 64 tile is the faster way to more waves per CU.
+  constexpr int kKsMaxBlocks = 256, kKsMinSteps = 8;   // the rule's bounds (the retired switches 45 / 46)
   bool ks_ok = false;
-  if (g_x3_ks && d->split_terms != 1 && (d->tile_hint == 0 || d->tile_hint == 22)) {
+  const int ks_form = dv3_sw(DV3_SW_X3_KS);
+  if (ks_form && d->split_terms != 1 && (d->tile_hint == 0 || d->tile_hint == 22)) {
     const int64_t nb2 = (int64_t)(gated ? dv3_cdiv(d->Cg, 64) : dv3_cdiv(d->M, 128)) * dv3_cdiv64((int64_t)d->B * d->Tout, 64);
     const int nch = (d->Cin + 31) / 32;
     // (8 ... 15 k-steps: only grids of at most 160 tiles -- at B = 64 the 201-tile M = 80 layers measured 0.93-0.95 x
     //  stand-alone and +0.3 % on the step, where they share the chip with the weight-gradient stream)
     const int ksteps = nch * d->J;
-    ks_ok = nch >= 2 && (g_x3_ks == 2 || (ksteps >= g_x3_ks_min_steps && nb2 <= (ksteps >= 16 ? g_x3_ks_max_blocks : g_x3_ks_max_blocks * 5 / 8)));
+    ks_ok = nch >= 2 && (ks_form == 2 || (ksteps >= kKsMinSteps && nb2 <= (ksteps >= 16 ? kKsMaxBlocks : kKsMaxBlocks * 5 / 8)));
     if (ks_ok && d->tile_hint == 0 && (best->id == 4 || best->id == 6)) best = &kCfgs[1];
   }
   const int BM = best->wm * best->mi * 64, BMH = best->wm * best->mi * 32, BN = best->wn * best->ni * 32;
@@ -796,8 +797,8 @@ int dv3_conv_gemm_bf16x3_dispatch(const dv3_conv_desc* d, hipStream_t st) {
   ConvArgs a;
   a.d = *d;
   a.a_scalar = 0;
-  a.wide = g_x3_wide;
-  a.prio = g_x3_prio;
+  a.wide = dv3_sw(DV3_SW_X3_WIDE);
+  a.prio = dv3_sw(DV3_SW_X3_PRIO);
   a.range_ctr = d->split_terms == DV3_SPLIT_F16X3 ? dv3_range_ctr() : nullptr;
   a.kp = (d->Cin + 31) / 32 * 32;
   a.m_tiles = gated ? dv3_cdiv(d->Cg, BMH) : dv3_cdiv(d->M, BM);
@@ -807,7 +808,7 @@ int dv3_conv_gemm_bf16x3_dispatch(const dv3_conv_desc* d, hipStream_t st) {
   a.n_blocks = (int)nb;
   a.ks = (ks_ok && best->id == 2 && 2 * lds <= 160 * 1024) ? 2 : 0;
   g_dv3_last_conv = (d->split_terms == 1 ? 4000 : d->split_terms == DV3_SPLIT_F16X3 ? 5000 : 3000) + best->id * 10 +
-                    ((best->id >= 8 && g_x3_pingpong) ? 1 : 0) + (a.ks == 2 ? 2 : 0);
+                    ((best->id >= 8 && dv3_sw(DV3_SW_X3_PINGPONG)) ? 1 : 0) + (a.ks == 2 ? 2 : 0);
   if (d->pg) {
     // round 6: the fused gate backward lives in its own instantiations (bf16 pair, no dropout) of four tiles
     if (d->xmask || d->split_terms == DV3_SPLIT_F16X3 || d->split_terms == 1) return 1;

@@ -818,27 +818,25 @@ int launch_pp2(const ConvArgs& a, size_t lds, hipStream_t st) {
 }  // namespace
 
 #ifndef DV3_PP2_ISA_ONLY
-extern int g_x3_wide;
-// dv3_debug_set(29 / 31, v): ORD of the unmasked / masked instantiations (0, 17, 81).  Round 5 default 81 (weight
+// DV3_SW_PP2_ORD_U / DV3_SW_PP2_ORD_M: ORD of the unmasked / masked instantiations (0, 17, 81).  Round 5 default 81 (weight
 // fragments first, activation items converted between the MFMAs): bit-identical to ORD 0, measured in one process at the
 // north-star shape (scripts/r5_ship_check.py, profiles/r05_pp2_load_phase.txt): fp16-pair forward 152.3 -> 148.8 us, masked
 // training forward 169.8 -> 166.9 us, bf16-pair input gradient 134.3 -> 132.3 us.  The masked bf16-pair instantiation
 // (legacy bf16x3 mode) keeps ORD 0: there the compiler contracts the mask multiply differently in the two forms.
-int g_pp2_ord_u = 81, g_pp2_ord_m = 81;
-int g_pp2_fast_tail = 1;   // dv3_debug_set(50, v): interior sub-tiles of a gated launch take the straight-line tail (0 = the guarded tail everywhere)
+// DV3_SW_PP2_FAST_TAIL: interior sub-tiles of a gated launch take the straight-line tail (0 = the guarded tail everywhere)
 
 // Stream-K (round 4).  A 256 x 256 tile grid rarely divides the 256 CUs: the encoder layers of the benchmark step are 152
 // tiles (41 % of the chip idle for the whole launch), the 512-channel converter layers 808 (3.16 rounds: the last one a
 // sixth full), the decoder's 102.  With a caller-provided workspace (dv3_conv_desc.sk_ws) the launch is instead ONE
 // workgroup per CU, each walking an equal share of the (tile, 32-channel chunk) units; a tile cut between workgroups
-// is summed by the one that holds its first chunk.  Taken when the share (+ g_pp2_sk_overhead chunks for the extra
-// prologue, the hand-over and the wait) is below g_pp2_sk_gain % of the tile-per-workgroup schedule's chunks per CU.
+// is summed by the one that holds its first chunk.  Taken when the share (+ kSkOverheadChunks chunks for the extra
+// prologue, the hand-over and the wait) is below kSkGainPercent % of the tile-per-workgroup schedule's chunks per CU
+// (the round-4 values of the retired switches 23 / 24).
 // Results differ from the tile-per-workgroup launch by the fp32 summation order of the cut tiles only (deterministic:
 // the cut is a function of the shape).
-int g_pp2_sk = 1;            // dv3_debug_set(22, v): 0 never, 1 by the rule above (forward launches), 2 whenever a workspace is given,
-                             // 3 by the rule in both directions
-int g_pp2_sk_overhead = 2;   // dv3_debug_set(23, v)
-int g_pp2_sk_gain = 80;      // dv3_debug_set(24, v)
+// DV3_SW_PP2_SK: 0 never, 1 by the rule above (forward launches), 2 whenever a workspace is given, 3 by the rule in both
+// directions
+constexpr int kSkOverheadChunks = 2, kSkGainPercent = 80;
 static int pp2_cu_count() {
   static int n = 0;
   if (!n) {
@@ -866,8 +864,8 @@ int dv3_conv_gemm_pp2_dispatch(const dv3_conv_desc* d, hipStream_t st) {
   ConvArgs a;
   a.d = *d;
   a.a_scalar = 0;
-  a.wide = g_x3_wide;
-  a.fast_tail = g_pp2_fast_tail;
+  a.wide = dv3_sw(DV3_SW_X3_WIDE);
+  a.fast_tail = dv3_sw(DV3_SW_PP2_FAST_TAIL);
   a.range_ctr = f16 ? dv3_range_ctr() : nullptr;
   a.kp = (d->Cin + 31) / 32 * 32;
   a.m_tiles = gated ? dv3_cdiv(d->Cg, BMH) : dv3_cdiv(d->M, BM);
@@ -889,17 +887,18 @@ int dv3_conv_gemm_pp2_dispatch(const dv3_conv_desc* d, hipStream_t st) {
   {
     const int P = pp2_cu_count(), S = d->Cin / BKC;
     const int64_t units = nb * S;
-    const int64_t dp = dv3_cdiv64(nb, P) * S, sk = dv3_cdiv64(units, P) + g_pp2_sk_overhead;
+    const int sk_form = dv3_sw(DV3_SW_PP2_SK);
+    const int64_t dp = dv3_cdiv64(nb, P) * S, sk = dv3_cdiv64(units, P) + kSkOverheadChunks;
     const bool ws_ok = d->sk_ws && d->sk_ws_bytes >= dv3_pp2_sk_ws_bytes() && units < (1ll << 30);
-    // Forward launches only by default (g_pp2_sk 1): the input-gradient launches of a training step run beside the
+    // Forward launches only by default (DV3_SW_PP2_SK 1): the input-gradient launches of a training step run beside the
     // weight-gradient stream, whose workgroups take the CUs a short grid leaves idle -- there the one-workgroup-per-CU
     // form gains nothing for the step (measured: forward alone -1.7 %, whole step +-0.1 % with both directions in this
     // form, scripts/r4_sk_step_ab.py).  3 = both directions.
-    const bool dir_ok = d->mode != DV3_EPI_DGRAD || g_pp2_sk >= 2;
+    const bool dir_ok = d->mode != DV3_EPI_DGRAD || sk_form >= 2;
     // per-XCD unit ranges: P / 8 workgroups (a power of two) per group, every group at least one tile
     const int q = P / 8;
     const bool grp_ok = (P % 8) == 0 && q > 0 && (q & (q - 1)) == 0 && nb >= 8;
-    if (ws_ok && dir_ok && grp_ok && g_pp2_sk && (S & (S - 1)) == 0 && (a.m_tiles & (a.m_tiles - 1)) == 0 && units >= 2 * P && (g_pp2_sk == 2 || sk * 100 < dp * g_pp2_sk_gain)) {
+    if (ws_ok && dir_ok && grp_ok && sk_form && (S & (S - 1)) == 0 && (a.m_tiles & (a.m_tiles - 1)) == 0 && units >= 2 * P && (sk_form == 2 || sk * 100 < dp * kSkGainPercent)) {
       a.sk_units = (int)units;
       a.sk_tg = (int)(nb / 8);
       a.sk_tr = (int)(nb % 8);
@@ -921,9 +920,9 @@ int dv3_conv_gemm_pp2_dispatch(const dv3_conv_desc* d, hipStream_t st) {
     }
   }
   {
-    // LOAD-phase structure (ORD, see the kernel): measured variants, selectable at run time (dv3_debug_set(29, v) for the
-    // unmasked instantiations, (31, v) for the masked ones)
-    const int o = mask ? (f16 ? g_pp2_ord_m : 0) : g_pp2_ord_u;
+    // LOAD-phase structure (ORD, see the kernel): measured variants, selectable at run time (DV3_SW_PP2_ORD_U for the
+    // unmasked instantiations, DV3_SW_PP2_ORD_M for the masked ones)
+    const int o = mask ? (f16 ? dv3_sw(DV3_SW_PP2_ORD_M) : 0) : dv3_sw(DV3_SW_PP2_ORD_U);
 #define DV3_PP2_ORD_SHIP(oo) \
     if (o == oo) { \
       if (f16) return mask ? launch_pp2<true, true, false, oo>(a, lds, st) : launch_pp2<false, true, false, oo>(a, lds, st); \

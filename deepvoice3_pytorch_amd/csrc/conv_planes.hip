@@ -530,7 +530,7 @@ extern "C" int dv3_mask_bits_to_c8(const uint32_t* bits, int32_t bits_rs, uint8_
   return dv3_check_launch("mask_bits_to_c8");
 }
 
-int g_planes_tile = 0;   // dv3_debug_set(4, v): 1 / 2 / 9 force that tile of this kernel (and keep conv_c8pp out), 0 = auto
+// DV3_SW_PLANES_TILE: 1 / 2 / 9 force that tile of this kernel (and keep conv_c8pp out), 0 = auto
 
 // called by dv3_conv_gemm_f32 (conv_gemm.hip) when d->x_c8 != NULL, which has required split_terms == 1 by then;
 // returns 1 when the shape is not eligible (the caller reports it), else a DV3_* code.
@@ -546,14 +546,14 @@ int dv3_conv_planes_dispatch(const dv3_conv_desc* d, hipStream_t st) {
   const int64_t ntot = (int64_t)d->B * d->Tout;
   if (ntot >= (1ll << 30)) return 1;
   // the 256 x 256 k32 ping-pong kernel (conv_c8pp.hip) where its grid fills the chip
-  // (tile_hint 40 forces it, dv3_debug_set(19, v) moves the threshold)
-  if ((d->tile_hint == 40 || (d->tile_hint == 0 && g_planes_tile == 0))) {
+  // (tile_hint 40 forces it, DV3_SW_C8PP_MIN_TILES moves the threshold)
+  if ((d->tile_hint == 40 || (d->tile_hint == 0 && dv3_sw(DV3_SW_PLANES_TILE) == 0))) {
     const int rc = dv3_conv_c8pp_dispatch(d, st);
     if (rc != 1) return rc;
     if (d->tile_hint == 40) return 1;
   }
   // tile: 1 = 128x128 (4 waves, two workgroups per CU), 2 = 128x64 (4 waves), 9 = 128x256 (8 waves, one per CU)
-  int id = g_planes_tile;
+  int id = dv3_sw(DV3_SW_PLANES_TILE);
   if (id != 1 && id != 2 && id != 9) {
     const int64_t mt = gated ? dv3_cdiv(d->Cg, 64) : dv3_cdiv(d->M, 128);
     // measured at the north-star shape (profiles/r02c_planes_kernel_ablation.md): the 8-wave 128x256 tile is the

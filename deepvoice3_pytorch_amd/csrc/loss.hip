@@ -45,7 +45,7 @@ __device__ __forceinline__ float sigmoid_head_dz(float dyh, float yh) {
 // With a = y_hat + eps, b = 1 - y_hat + eps:  exp(L) = a / b,  log1p(exp(L)) = log(a + b) - log(b),
 // sigmoid(L) = a / (a + b): two logarithms and two reciprocals instead of four transcendental calls -- the loss kernels
 // were VALU-bound on them (round 2: 145 us per launch whatever the access pattern).  a + b = 1 + 2 eps.
-// FAST (the tiled kernel, default; dv3_debug_set(57, 0) = libm): the three logarithms by v_log_f32 (__logf: 1 ulp of
+// FAST (the tiled kernel, default; DV3_SW_LOSS_FAST_LOG = 0: libm): the three logarithms by v_log_f32 (__logf: 1 ulp of
 // log2 x, i.e. ~1e-7 absolute here) -- with logf the tiled kernel was still bound by its vector work (~100 instructions per
 // element; 103 us for the 64 x 804 x 513 linear-spectrogram loss, round 6).  The gradient takes no logarithm.
 template <bool FAST = false>
@@ -552,7 +552,7 @@ inline int loss_blocks(int64_t n) {
 
 }  // namespace
 
-int g_loss_fast_log = 1;   // dv3_debug_set(57, v): the tiled spectrogram loss takes its logarithms by v_log_f32 (0 = logf)
+// DV3_SW_LOSS_FAST_LOG: the tiled spectrogram loss takes its logarithms by v_log_f32 (0 = logf)
 
 extern "C" int dv3_spec_loss_scratch_floats(int32_t B, int32_t T, int32_t D) {
   // block partial sums of either form: the flat grid, or one block per 64 x 64 tile (at most 1024)
@@ -578,8 +578,9 @@ static int spec_loss_launch(const dv3_spec_loss_desc* d, float* dpre, float* bia
     const int t_tiles = dv3_cdiv(d->T - d->r, 64), d_tiles = dv3_cdiv(d->D, 64);
     const int64_t nt = (int64_t)d->B * t_tiles * d_tiles;
     nb = (int)(nt < 1024 ? nt : 1024);
-    auto k = dpre ? (g_loss_fast_log ? spec_loss_tiled_kernel<true, true> : spec_loss_tiled_kernel<false, true>)
-                     : (g_loss_fast_log ? spec_loss_tiled_kernel<true, false> : spec_loss_tiled_kernel<false, false>);
+    const bool fast_log = dv3_sw(DV3_SW_LOSS_FAST_LOG);
+    auto k = dpre ? (fast_log ? spec_loss_tiled_kernel<true, true> : spec_loss_tiled_kernel<false, true>)
+                     : (fast_log ? spec_loss_tiled_kernel<true, false> : spec_loss_tiled_kernel<false, false>);
     hipLaunchKernelGGL(k, dim3(nb), dim3(kLossBlock), 0, st, a, t_tiles, d_tiles, (int)nt);
   } else {
     hipLaunchKernelGGL(spec_loss_kernel, dim3(nb), dim3(kLossBlock), 0, st, a);
@@ -698,7 +699,7 @@ extern "C" int dv3_spec_loss_items_f32(const dv3_spec_items_desc* d, void* strea
   const int S = Tr > 0 ? item_slices(Tr) : 0;
   if (S > 0) {
     DV3_REQUIRE((int64_t)dv3_cdiv(Tr, S) * d->D < (1ll << 31), "spec_loss_items: slice too large");
-    if (spec_time_fast(*d) && g_loss_fast_log)
+    if (spec_time_fast(*d) && dv3_sw(DV3_SW_LOSS_FAST_LOG))
       hipLaunchKernelGGL(spec_items_kernel<true>, dim3(S, d->B), dim3(kLossBlock), 0, st, *d);
     else
       hipLaunchKernelGGL(spec_items_kernel<false>, dim3(S, d->B), dim3(kLossBlock), 0, st, *d);

@@ -300,7 +300,7 @@ int fill_args(SpkArgs& a, const dv3_spk_desc* d, const dv3_spk_layer* layers, bo
 
 }  // namespace
 
-int g_spk_prefetch = 1;   // dv3_debug_set(54, v): the backward's tile loads one tile ahead (0 = at the top of the tile)
+// DV3_SW_SPK_PREFETCH: the backward's tile loads one tile ahead (0 = at the top of the tile)
 
 extern "C" int dv3_speaker_bias_fwd_f32(const dv3_spk_desc* d, const dv3_spk_layer* layers, void* stream) {
   SpkArgs a;
@@ -341,7 +341,7 @@ extern "C" int dv3_speaker_bias_bwd_f32(const dv3_spk_desc* d, const dv3_spk_lay
   float* part = d->scratch;
   float* de_l = d->scratch + rows * d->B * nT * (EM + 1);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(spk_bwd_kernel, dim3(nT, d->B, d->n_layers), dim3(NT), 0, st, a, part, de_l, g_spk_prefetch);
+  hipLaunchKernelGGL(spk_bwd_kernel, dim3(nT, d->B, d->n_layers), dim3(NT), 0, st, a, part, de_l, dv3_sw(DV3_SW_SPK_PREFETCH));
   int rc2 = dv3_check_launch("speaker_bias_bwd");
   if (rc2 != DV3_OK) return rc2;
   hipLaunchKernelGGL(spk_finish_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a, (const float*)part, d->B * nT);

@@ -7,7 +7,7 @@
 //   ConvTranspose1d      v [I][O][J]  norm per INPUT channel i (dim 0 of its weight)
 #include "common.h"
 
-int g_wn_bwd_vec4 = 1;     // dv3_debug_set(51, v): 0 = the 4-byte gather everywhere (A/B, bit-identity tests)
+// DV3_SW_WN_BWD_VEC4: 0 = the 4-byte gather everywhere (A/B, bit-identity tests)
 
 namespace {
 
@@ -466,14 +466,14 @@ extern "C" int dv3_weight_norm_bwd_f32(const dv3_wn_bwd_desc* d, void* stream) {
   size_t lds = 0;
   const int rc = wn_bwd_check(d, &rows, &lds);
   if (rc != DV3_OK) return rc;
-  hipLaunchKernelGGL(wn_bwd_kernel, dim3(rows), dim3(256), lds, (hipStream_t)stream, *d, g_wn_bwd_vec4);
+  hipLaunchKernelGGL(wn_bwd_kernel, dim3(rows), dim3(256), lds, (hipStream_t)stream, *d, dv3_sw(DV3_SW_WN_BWD_VEC4));
   return dv3_check_launch("weight_norm_bwd_f32");
 }
 
 extern "C" int dv3_weight_norm_bwd_multi(const dv3_wn_bwd_desc* descs, int32_t n, void* stream) {
   DV3_REQUIRE(descs && n > 0 && n <= DV3_WN_BWD_MULTI_MAX, "wn_bwd_multi: 1..%d descriptors", DV3_WN_BWD_MULTI_MAX);
   WnBwdMultiArgs a;
-  a.vec4_ok = g_wn_bwd_vec4;
+  a.vec4_ok = dv3_sw(DV3_SW_WN_BWD_VEC4);
   size_t lds_max = 0;
   int total = 0;
   for (int l = 0; l < n; ++l) {

@@ -579,11 +579,10 @@ int launch_c8_tr(const WgradC8TrArgs& a, int64_t nb, hipStream_t st) {
 
 }  // namespace
 
-// dv3_debug_set(52, v): operand fragments by ds_read_b64_tr_b16 from the untransposed tile -- 0 = the register-transposing
+// DV3_SW_WGRAD_C8_TR: operand fragments by ds_read_b64_tr_b16 from the untransposed tile -- 0 = the register-transposing
 // forms, 1 = plain, 2 = staging between the MFMAs, 3 = one barrier per two K steps, 4 = both (default; one tap: as 3)
-int g_wgrad_c8_tr = 4;
-int g_wgrad_c8_il = 1;    // dv3_debug_set(49, v): the three-tap form stages the next tile between the MFMAs (0 = after them)
-int g_wgrad_c8_pf2 = 1;   // dv3_debug_set(20, v): 1 = operands fetched two steps ahead (default), 0 = the round-2 one-step form
+// DV3_SW_WGRAD_C8_IL: the three-tap register-transposing form stages the next tile between the MFMAs (0 = after them)
+// DV3_SW_WGRAD_C8_PF2: 1 = operands fetched two steps ahead (default), 0 = the round-2 one-step form
 
 // called by dv3_wgrad_gemm_f32 (wgrad_gemm.hip) when d->c8 is set
 int dv3_wgrad_c8_dispatch(const dv3_wgrad_desc* d, hipStream_t st) {
@@ -602,14 +601,15 @@ int dv3_wgrad_c8_dispatch(const dv3_wgrad_desc* d, hipStream_t st) {
   const int64_t nb = (int64_t)a.m_tiles * a.c_tiles * d->n_slabs;
   DV3_REQUIRE(nb < (1ll << 31), "wgrad_gemm: grid too large");
   const int wx = 32 + (d->J - 1) * d->dil;
-  if (g_wgrad_c8_tr && wx <= 96 && d->padL >= 0 && d->padL <= (d->J - 1) * d->dil) {
+  const int tr = dv3_sw(DV3_SW_WGRAD_C8_TR);
+  if (tr && wx <= 96 && d->padL >= 0 && d->padL <= (d->J - 1) * d->dil) {
     WgradC8TrArgs t;
     t.d = *d; t.m_tiles = a.m_tiles; t.c_tiles = a.c_tiles; t.wx = wx;
     for (t.twx = wx; (t.twx & 15) != 4 && (t.twx & 15) != 12; ++t.twx) {}
     g_dv3_last_wgrad = 5100 + d->J;       // 5101 / 5103: fragments by the transposing LDS read
     const bool wide = 16 * wx > 1024;     // a third x unit per thread (dilation 27)
-    if (d->J == 3 && (g_wgrad_c8_tr == 3 || g_wgrad_c8_tr == 4)) {
-      const bool il = g_wgrad_c8_tr == 4;
+    if (d->J == 3 && (tr == 3 || tr == 4)) {
+      const bool il = tr == 4;
       g_dv3_last_wgrad += il ? 240 : 200;             // 5303 / 5343: one barrier per two K steps
       if (wide) {
         if (il) return d->xmask_c8 ? launch_c8_tr<3, true, 3, true, true>(t, nb, st) : launch_c8_tr<3, false, 3, true, true>(t, nb, st);
@@ -618,11 +618,11 @@ int dv3_wgrad_c8_dispatch(const dv3_wgrad_desc* d, hipStream_t st) {
       if (il) return d->xmask_c8 ? launch_c8_tr<3, true, 2, true, true>(t, nb, st) : launch_c8_tr<3, false, 2, true, true>(t, nb, st);
       return d->xmask_c8 ? launch_c8_tr<3, true, 2, false, true>(t, nb, st) : launch_c8_tr<3, false, 2, false, true>(t, nb, st);
     }
-    if (d->J == 1 && (g_wgrad_c8_tr == 3 || g_wgrad_c8_tr == 4)) {
+    if (d->J == 1 && (tr == 3 || tr == 4)) {
       g_dv3_last_wgrad += 200;
       return d->xmask_c8 ? launch_c8_tr<1, true, 1, false, true>(t, nb, st) : launch_c8_tr<1, false, 1, false, true>(t, nb, st);
     }
-    if (d->J == 3 && g_wgrad_c8_tr == 2) {
+    if (d->J == 3 && tr == 2) {
       g_dv3_last_wgrad += 40;             // 5143: staging between the MFMAs
       if (wide) return d->xmask_c8 ? launch_c8_tr<3, true, 3, true>(t, nb, st) : launch_c8_tr<3, false, 3, true>(t, nb, st);
       return d->xmask_c8 ? launch_c8_tr<3, true, 2, true>(t, nb, st) : launch_c8_tr<3, false, 2, true>(t, nb, st);
@@ -631,9 +631,9 @@ int dv3_wgrad_c8_dispatch(const dv3_wgrad_desc* d, hipStream_t st) {
     if (d->J == 3) return d->xmask_c8 ? launch_c8_tr<3, true, 2>(t, nb, st) : launch_c8_tr<3, false, 2>(t, nb, st);
     return d->xmask_c8 ? launch_c8_tr<1, true, 1>(t, nb, st) : launch_c8_tr<1, false, 1>(t, nb, st);
   }
-  if (g_wgrad_c8_pf2) {
+  if (dv3_sw(DV3_SW_WGRAD_C8_PF2)) {
     g_dv3_last_wgrad = 5000 + 20 + d->J;
-    if (d->J == 3 && g_wgrad_c8_il) {
+    if (d->J == 3 && dv3_sw(DV3_SW_WGRAD_C8_IL)) {
       g_dv3_last_wgrad += 40;            // 5063: staging between the MFMAs
       return d->xmask_c8 ? launch_c8<3, true, true, true>(a, nb, st) : launch_c8<3, false, true, true>(a, nb, st);
     }

@@ -500,12 +500,12 @@ __global__ __launch_bounds__(512, 2) void wgrad_taps_kernel(const WgradArgs args
 
 }  // namespace
 
-int g_wgrad_taps2_default = 1;   // the two-steps-ahead form of the all-taps kernel (wgrad_taps2.hip; masked 205 -> 173 us, unmasked
-                                 // 164 -> 150 us at the north-star shape, bit-identical slabs); dv3_debug_set(17, 0) = the one-step form
+// DV3_SW_WGRAD_TAPS2 (default 1): the two-steps-ahead form of the all-taps kernel (wgrad_taps2.hip; masked 205 -> 173 us,
+// unmasked 164 -> 150 us at the north-star shape, bit-identical slabs); 0 = the one-step form
 int dv3_wgrad_taps2_dispatch(const dv3_wgrad_desc* d, hipStream_t st);
 int g_wgrad_taps_default = 1;   // the all-taps form measured 7-14 % faster at every model shape (scripts/wgrad_ab.py)
-int g_wgrad_prio = 0;   // debug (dv3_debug_set(15, v))
-int g_wgrad_tile = 0;   // debug (dv3_debug_set(2, v)): 0 auto, 1 force 128x128 per tap, 2 force 256x128 per tap, 3 force all-taps
+// DV3_SW_WGRAD_PRIO: wave priority scheme of the all-taps kernel.  DV3_SW_WGRAD_TILE: 0 auto, 1 force 128x128 per tap,
+// 2 force 256x128 per tap, 3 force all-taps, 4 force the two-steps-ahead all-taps kernel
 
 template <bool MASK, int TERMS>
 static int launch_wgrad_taps_t(const WgradArgs& a, int64_t nb, hipStream_t st) {
@@ -558,13 +558,14 @@ int dv3_wgrad_gemm_bf16x3_dispatch(const dv3_wgrad_desc* d, hipStream_t st) {
     return 1;   // caller falls back to the exact kernel
   WgradArgs a;
   a.d = *d;
-  a.prio = g_wgrad_prio;
-  if (d->J == 3 && d->k_split && d->split_bf16 != 2 && (g_wgrad_tile == 4 || (g_wgrad_tile == 0 && g_wgrad_taps2_default)) &&
+  a.prio = dv3_sw(DV3_SW_WGRAD_PRIO);
+  const int tile = dv3_sw(DV3_SW_WGRAD_TILE);
+  if (d->J == 3 && d->k_split && d->split_bf16 != 2 && (tile == 4 || (tile == 0 && dv3_sw(DV3_SW_WGRAD_TAPS2))) &&
       (int64_t)(d->B - 1) * d->g_bs + (int64_t)(d->M - 1) * d->g_rs + d->T >= 8 &&
       (int64_t)(d->B - 1) * d->x_bs + (int64_t)(d->Cin - 1) * d->x_rs + d->Tin >= 8)
     return dv3_wgrad_taps2_dispatch(d, st);
   // three taps, K split over contiguous ranges: one 8-wave workgroup per (m-tile, c-tile, slab) serves all taps
-  if (d->J == 3 && d->k_split && (g_wgrad_tile == 3 || (g_wgrad_tile == 0 && g_wgrad_taps_default))) {
+  if (d->J == 3 && d->k_split && (tile == 3 || (tile == 0 && g_wgrad_taps_default))) {
     a.m_tiles = dv3_cdiv(d->M, 128);
     a.c_tiles = dv3_cdiv(d->Cin, 128);
     const int64_t nb = (int64_t)a.m_tiles * a.c_tiles * d->n_slabs;
@@ -574,7 +575,7 @@ int dv3_wgrad_gemm_bf16x3_dispatch(const dv3_wgrad_desc* d, hipStream_t st) {
   }
   // 128 x 128 (4 waves, two workgroups per CU).  The 256 x 128 8-wave variant (one workgroup per CU)
   // measured within run-to-run noise of it (+-5 %, scripts/x3_check.py): kept behind the debug knob.
-  const bool big = g_wgrad_tile == 2;
+  const bool big = tile == 2;
   const int bm = big ? 256 : 128;
   a.m_tiles = dv3_cdiv(d->M, bm);
   a.c_tiles = dv3_cdiv(d->Cin, 128);

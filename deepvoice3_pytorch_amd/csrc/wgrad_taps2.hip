@@ -565,8 +565,8 @@ int launch_wgrad_taps2(const WgradT2Args& a, int64_t nb, hipStream_t st) {
 
 }  // namespace
 
-int g_wgrad_t2_il = 1;       // dv3_debug_set(48, v): the window forms stage the next tile between the MFMAs (0 = after them)
-int g_wgrad_t2_window = 1;   // dv3_debug_set(47, v): the one-window-for-three-taps form of d = 1 / 3 launches (0 = the per-tap form)
+// DV3_SW_WGRAD_T2_IL: the window forms stage the next tile between the MFMAs (0 = after them)
+// DV3_SW_WGRAD_T2_WINDOW: the one-window-for-three-taps form of d = 1 / 3 launches (0 = the per-tap form)
 
 // three taps, three-term split, K split over contiguous ranges (called by dv3_wgrad_gemm_bf16x3_dispatch)
 int dv3_wgrad_taps2_dispatch(const dv3_wgrad_desc* d, hipStream_t st) {
@@ -578,9 +578,9 @@ int dv3_wgrad_taps2_dispatch(const dv3_wgrad_desc* d, hipStream_t st) {
   DV3_REQUIRE(nb < (1ll << 31), "wgrad_gemm: grid too large");
   g_dv3_last_wgrad = 3000 + 40;
   // window form (kernel template DIL): d = 1 or 3, a tensor long enough for the window's loads
-  const int win = (g_wgrad_t2_window && (d->dil == 1 || d->dil == 3) &&
+  const int win = (dv3_sw(DV3_SW_WGRAD_T2_WINDOW) && (d->dil == 1 || d->dil == 3) &&
                    (int64_t)(d->B - 1) * d->x_bs + (int64_t)(d->Cin - 1) * d->x_rs + d->Tin >= 16) ? d->dil : 0;
-  const bool il = win && g_wgrad_t2_il;
+  const bool il = win && dv3_sw(DV3_SW_WGRAD_T2_IL);
   g_dv3_last_wgrad += (d->g_pair ? 1 : 0) + (win ? 2 : 0) + (il ? 4 : 0);   // ...41 pair-word g, 42 window form, 43 both; +4 interleaved staging
 #define DV3_T2(M, G) \
   (win == 1 ? (il ? launch_wgrad_taps2<M, G, 1, true>(a, nb, st) : launch_wgrad_taps2<M, G, 1>(a, nb, st)) \

@@ -30,26 +30,65 @@ extern "C" {
 #define DV3_ELAUNCH (-2)  /* hipLaunch / runtime error        */
 
 /* ABI version, bumped on any struct change; checked by the Python loader. */
-#define DV3_ABI_VERSION 49
+#define DV3_ABI_VERSION 50
 int dv3_abi_version(void);
 const char* dv3_last_error(void);
 /* Fills name (<=255 chars) of device `dev`, number of CUs; returns 0/err. */
 int dv3_device_info(int dev, char* name, int name_len, int* n_cu);
 /* sizeof(struct <name>) or -1: lets a foreign-language mirror of the descriptors self-check */
 int dv3_sizeof(const char* name);
-/* Developer knobs for measurements (what = 2: bf16x3 wgrad tile, 0 auto / 1 = 128x128 / 2 = 256x128; what = 3: 8-wave bf16x3
- * tap-GEMM tiles on the in-phase (0) or ping-pong (1, default) main loop; what = 4: tile of the planes
- * tap-GEMM (c8 input), 0 auto, conv_c8pp where its grid fills the chip / 1 = 128x128 (4 waves, two workgroups per CU) /
- * 2 = 128x64 / 9 = 128x256 (8 waves): the only way to force a planes tile; what = 5, 7, 8 (its stagger, steady state
- * and mid-tile threshold) are retired;
- * what = 34: conv_c8pp form, 0 = 8 waves on 256x256 only / 1 = two 4-wave workgroups per CU on 256x128 / 2 = by rule;
- * what = 40: launch census of dv3_conv_gemm_f32, 1 = clear and record / 0 = stop; what = 42: relative cost (percent)
- * of the 256x128 ping-pong tile in the split kernels' tile picker; what = 44: k-split form of the 128x64 split tile,
- * 0 never / 1 by rule (default) / 2 wherever eligible; what = 29 / 31: LOAD-phase order of the 256x256 split tap-GEMM,
- * 0 / 17 / 81 only; what = 52: wgrad_c8 form, 0..4 only.  The full list: INTEGRATION.md, section 2.)  Returns
- * DV3_EINVAL, with a dv3_last_error() message, for a code the library does not handle (the retired timing-only
- * ablation codes among them) and for a value outside a switch's forms. */
+/*
+ * Run-time switches of the library's dispatchers: THE list.  One row per switch --
+ *   X(id, NAME, default, lowest, highest accepted value, "meaning")
+ * -- from which the DV3_SW_* ids below, the library's storage and defaults, the checks of dv3_debug_set and the Python
+ * side's table (_lib.SWITCHES) are all generated.  The ids are ABI: a retired id is never reused.  The defaults are
+ * what the benchmark times; the other forms exist so that tests can route a small shape to the kernel form the large
+ * shapes get, or keep an earlier form as a bit-identity reference.  Where each rule was measured: the comment beside
+ * the dispatcher that reads the switch, and INTEGRATION.md, section 2.
+ */
+#define DV3_SWITCHES(X) \
+  X(2, WGRAD_TILE, 0, 0, 4, "split weight gradient: 0 by rule / 1 128x128 per tap / 2 256x128 per tap / 3 all-taps / 4 two-steps-ahead all-taps") \
+  X(3, X3_PINGPONG, 1, 0, 1, "8-wave split tap-GEMM tiles: 0 in-phase / 1 ping-pong main loop") \
+  X(4, PLANES_TILE, 0, 0, 9, "planes tap-GEMM tile: 0 by rule, conv_c8pp first / 1 128x128 / 2 128x64 / 9 128x256; any other value: by rule, conv_c8pp kept out") \
+  X(12, X3_PP2_MIN_TILES, 128, 0, 2147483647, "256x256 split tap-GEMM serves eligible grids of at least this many tiles (0 never)") \
+  X(14, X3_PRIO, 0, 0, 4, "wave priority scheme of the ping-pong split main loop (kernel argument; 0 none)") \
+  X(15, WGRAD_PRIO, 0, 0, 2, "wave priority scheme of the all-taps weight gradient (kernel argument; 0 none)") \
+  X(17, WGRAD_TAPS2, 1, 0, 1, "all-taps weight gradient by rule: 0 one step ahead / 1 two steps ahead") \
+  X(18, X3_WIDE, 1, 0, 1, "16-byte input-gradient epilogue through LDS of the split tap-GEMMs (kernel argument): 0 off / 1 on") \
+  X(19, C8PP_MIN_TILES, 128, 0, 2147483647, "conv_c8pp serves eligible grids of at least this many tiles (0 never, 1 always)") \
+  X(20, WGRAD_C8_PF2, 1, 0, 1, "register-transposing wgrad_c8: operands fetched 0 one / 1 two steps ahead") \
+  X(22, PP2_SK, 1, 0, 3, "stream-K form of the 256x256 split tap-GEMM: 0 never / 1 by rule, forward / 2 whenever a workspace is given / 3 by rule, both directions") \
+  X(29, PP2_ORD_U, 81, 0, 81, "LOAD-phase order of the unmasked 256x256 split instantiations: 0, 17 or 81 only") \
+  X(30, C8PP_RF, 1, 0, 1, "conv_c8pp LOAD phase: 0 staging first / 1 fragment reads first") \
+  X(31, PP2_ORD_M, 81, 0, 81, "LOAD-phase order of the masked 256x256 split instantiations: 0, 17 or 81 only") \
+  X(34, C8PP_NW4, 2, 0, 2, "conv_c8pp form: 0 8 waves on 256x256 only / 1 two 4-wave workgroups per CU on 256x128 / 2 by rule") \
+  X(35, C8PP_STAGGER, 0, 0, 1024, "conv_c8pp, 4-wave form: start delay (x 64 cycles) of the delayed blocks (kernel argument)") \
+  X(36, C8PP_STAGGER_MASK, 1, 0, 2147483647, "conv_c8pp, 4-wave form: blocks with (blockIdx & mask) != 0 are the delayed ones (kernel argument)") \
+  X(44, X3_KS, 1, 0, 2, "k-split form of the 128x64 split tile: 0 never / 1 by rule / 2 wherever eligible") \
+  X(47, WGRAD_T2_WINDOW, 1, 0, 1, "two-steps-ahead weight gradient, d = 1 / 3: 0 per-tap form / 1 one window for three taps") \
+  X(48, WGRAD_T2_IL, 1, 0, 1, "its window forms stage the next tile 0 after / 1 between the MFMAs") \
+  X(49, WGRAD_C8_IL, 1, 0, 1, "register-transposing wgrad_c8, three taps: next tile staged 0 after / 1 between the MFMAs") \
+  X(50, PP2_FAST_TAIL, 1, 0, 1, "256x256 split tap-GEMM, gated launch: 0 guarded tail everywhere / 1 straight-line tail on interior sub-tiles (kernel argument)") \
+  X(51, WN_BWD_VEC4, 1, 0, 1, "weight-norm backward gather: 0 4-byte everywhere / 1 16-byte where aligned") \
+  X(52, WGRAD_C8_TR, 4, 0, 4, "wgrad_c8 form: 0 register-transposing / 1 transposing LDS read / 2 + staging between the MFMAs / 3 + one barrier per two K steps / 4 both") \
+  X(54, SPK_PREFETCH, 1, 0, 1, "speaker-bias backward tile loads: 0 at the top of the tile / 1 one tile ahead") \
+  X(55, GATE_VEC, 1, 0, 1, "gate backward 16-byte accesses: 0 gated layers with T % 4 == 0 only / 1 rows of any length") \
+  X(56, GATE_C8_FAST, 1, 0, 1, "c8 gate backward sigmoid: 0 expf and a division / 1 v_exp_f32 + v_rcp_f32") \
+  X(57, LOSS_FAST_LOG, 1, 0, 1, "tiled spectrogram loss logarithms: 0 logf / 1 v_log_f32")
+#define DV3_SW_ENUM_(id, name, dflt, lo, hi, doc) DV3_SW_##name = id,
+enum { DV3_SWITCHES(DV3_SW_ENUM_) };
+/* Sets switch `what` (a DV3_SW_* id) of this process.  DV3_EINVAL, with a dv3_last_error() message that starts
+ * "debug_set(<what>, <value>): ", for an id that is not in the list -- "no such switch": the retired ids 1, 5-9, 13, 16,
+ * 21, 23-28, 32, 42, 43, 45, 46 among them, so that a stale script cannot time the shipped kernel believing it timed
+ * something else -- and for a value outside the row's range (29 / 31: outside {0, 17, 81}); the stored value is then
+ * unchanged.  Not in the list: what = DV3_DEBUG_CENSUS, the launch census of dv3_conv_gemm_f32 (1 = clear and record /
+ * 0 = stop). */
+#define DV3_DEBUG_CENSUS 40
 int dv3_debug_set(int what, int value);
+/* Every switch of the list back to its default.  The launch census is not touched. */
+int dv3_debug_reset(void);
+/* *value = the switch's current value, *dflt = its default (either may be NULL).  DV3_EINVAL for an id not in the list. */
+int dv3_switch_query(int what, int32_t* value, int32_t* dflt);
 /* what = 3: phase stamps of the persistent decode program.  what = 40 / 41: the launch census -- the recorded dv3_conv_desc
  * structs (bytes <= count * sizeof(dv3_conv_desc)) / the kernel variant (int32 each, encoded as dv3_debug_get(10))
  * that served each; count = dv3_debug_get(40).  Any other what: DV3_EINVAL. */

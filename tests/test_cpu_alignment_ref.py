@@ -131,7 +131,7 @@ def test_alignment_flags():
 def test_header_declares_the_entry_points():
     import ctypes
     from deepvoice3_pytorch_amd import _lib, synthesis
-    assert _lib.CONSTS["DV3_ABI_VERSION"] == 49
+    assert _lib.CONSTS["DV3_ABI_VERSION"] == 50
     assert _lib.CONSTS["DV3_ALIGN_COLS"] == 13 == len(synthesis.ALIGNMENT_COLUMNS)
     i32, i64, ptr = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
     assert _lib.FUNCS["dv3_alignment_stats_scratch_bytes"] == (ctypes.c_int, [i32, i32])

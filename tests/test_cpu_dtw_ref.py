@@ -147,7 +147,7 @@ def test_parseval_pins_audio_mel_cepstra():
 def test_header_declares_the_entry_points():
     import ctypes
     from deepvoice3_pytorch_amd import _lib
-    assert _lib.CONSTS["DV3_ABI_VERSION"] == 49
+    assert _lib.CONSTS["DV3_ABI_VERSION"] == 50
     assert _lib.CONSTS["DV3_DTW_COLS"] == 5 == len(DR.COLUMNS)
     assert _lib.CONSTS["DV3_DTW_MAX_T"] == 4096 and _lib.CONSTS["DV3_DTW_MAX_D"] == 128
     i32, ptr = ctypes.c_int32, ctypes.c_void_p

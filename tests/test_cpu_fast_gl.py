@@ -89,7 +89,7 @@ def test_header_declares_the_momentum_projection():
     restype, args = _lib.FUNCS["dv3_gl_project_momentum_f32"]
     # y, mag, awin, swin, cprev, frames, B, T, hop, tlen, lws, n_fft, alpha, first, stream
     assert restype is ctypes.c_int and args == [p, p, p, p, p, p, i32, i32, i32, p, i32, i32, f32, i32, p]
-    assert _lib.CONSTS["DV3_ABI_VERSION"] == 49
+    assert _lib.CONSTS["DV3_ABI_VERSION"] == 50
     assert sum(1 for f in _lib.FUNCS if f.endswith("_n")) == 12
     assert [f for f in _lib.FUNCS if "momentum" in f] == ["dv3_gl_project_momentum_f32"]
 

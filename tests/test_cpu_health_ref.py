@@ -44,7 +44,7 @@ def test_the_columns_are_named_once():
 
 def test_the_library_exports_the_entry_points_under_the_same_abi():
     from deepvoice3_pytorch_amd import _lib
-    assert _lib.CONSTS["DV3_ABI_VERSION"] == 49
+    assert _lib.CONSTS["DV3_ABI_VERSION"] == 50
     f, i32, i64, ptr = ctypes.c_float, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
     tail = [ptr, f, ptr, f, f, f, f, f]                    # grad_norm, clip, hyper, beta1, beta2, eps, wd, prescale
     assert _lib.FUNCS["dv3_clip_adam_f32"] == (ctypes.c_int, [ptr] * 4 + [i64] + tail + [ptr])
@@ -54,7 +54,7 @@ def test_the_library_exports_the_entry_points_under_the_same_abi():
     assert _lib.FUNCS["dv3_arena_stats_f32"] == (ctypes.c_int, [ptr] * 4 + [i64, ptr, ptr, ptr, i64, ptr, i32, f, f,
                                                                    ptr, ptr, ptr])
     h = _lib.lib()                                         # (raises when a declared symbol is missing)
-    assert h.dv3_abi_version() == 49
+    assert h.dv3_abi_version() == 50
     for name in ("dv3_clip_adam_guard_f32", "dv3_clip_adam_ema_guard_f32", "dv3_arena_stats_f32"):
         assert getattr(h, name) is not None
     mk = open(os.path.join(ROOT, "deepvoice3_pytorch_amd", "csrc", "Makefile")).read()

@@ -52,5 +52,5 @@ def test_rule_takes_the_small_grids_of_batch_16_and_leaves_batch_64_alone():
     # B = 64: the grids are past one tile per CU, and the 201-tile M = 80 layers have 8 steps only
     assert not rule(64, 150, 512, 1024, 3) and not rule(64, 201, 256, 512, 3) and not rule(64, 201, 80, 256, 1)
     assert not rule(64, 201, 256, 256, 1)
-    # forced (dv3_debug_set(44, 2)) needs two chunks; off is off
+    # forced (DV3_SW_X3_KS = 2) needs two chunks; off is off
     assert rule(64, 804, 512, 64, 3, mode=2) and not rule(64, 804, 512, 32, 3, mode=2) and not rule(16, 150, 512, 1024, 3, mode=0)

@@ -142,7 +142,7 @@ def test_at_most_two_filters_over_a_bin(case):
 # ---------------------------------------------------------------------------------------------------------------------
 def test_header_declares_the_entry_point():
     from deepvoice3_pytorch_amd import _lib
-    assert _lib.CONSTS["DV3_ABI_VERSION"] == 49
+    assert _lib.CONSTS["DV3_ABI_VERSION"] == 50
     assert _lib.CONSTS["DV3_MELINV_MAX_MELS"] == 256 and _lib.CONSTS["DV3_MELINV_MAX_ITERS"] == 1024
     i32, f32, ptr = ctypes.c_int32, ctypes.c_float, ctypes.c_void_p
     assert _lib.FUNCS["dv3_mel_to_linear_f32"] == (

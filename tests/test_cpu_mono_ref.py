@@ -116,7 +116,7 @@ def test_end_key_and_advance_ties_by_hand():
 def test_header_declares_the_entry_points():
     import ctypes
     from deepvoice3_pytorch_amd import _lib, synthesis
-    assert _lib.CONSTS["DV3_ABI_VERSION"] == 49
+    assert _lib.CONSTS["DV3_ABI_VERSION"] == 50
     assert _lib.CONSTS["DV3_MONO_COLS"] == 6 == len(synthesis.TIMING_COLUMNS) == len(MR.COLUMNS)
     assert synthesis.TIMING_COLUMNS == MR.COLUMNS
     assert _lib.CONSTS["DV3_MONO_MAX_T"] == 8192 and _lib.CONSTS["DV3_MONO_MAX_TK"] == 2048

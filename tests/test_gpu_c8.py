@@ -144,12 +144,12 @@ def test_c8_input_is_refused_unless_single_term(dev, modes):
     ops.set_gemm_precision("bf16")
     ops.bf16_storage = True
     x8 = ops.to_c8(torch.randn(B, C, T, device=dev))
-    L.dv3_debug_set(40, 1)
+    L.dv3_debug_set(_lib.DV3_DEBUG_CENSUS, 1)
     try:
         with torch.no_grad():
             y8 = layer(x8)
     finally:
-        L.dv3_debug_set(40, 0)
+        L.dv3_debug_set(_lib.DV3_DEBUG_CENSUS, 0)
     n = L.dv3_debug_get(40)
     assert n >= 1 and ops.is_c8(y8)
     Desc = ops._conv_desc
@@ -361,18 +361,13 @@ def test_c8pp_kernel_is_bit_identical_to_the_planes_kernel(dev, modes, kind, C, 
         layer.conv.bias.uniform_(-0.1, 0.1)
     x = torch.randn(B, C, T, device=dev)
     out = {}
-    try:
-        # planes kernel | 8 waves on 256 x 256 | two 4-wave workgroups per CU on 256 x 128 (round 5: dv3_debug_set(34, 1))
-        for tag, thr, nw4, want in (("planes", 0, 0, 8), ("c8pp", 1, 0, 9101), ("c8pp 4-wave", 1, 1, 9111)):
-            L.dv3_debug_set(19, thr)
-            L.dv3_debug_set(34, nw4)
+    # planes kernel | 8 waves on 256 x 256 | two 4-wave workgroups per CU on 256 x 128 (round 5: DV3_SW_C8PP_NW4 = 1)
+    for tag, thr, nw4, want in (("planes", 0, 0, 8), ("c8pp", 1, 0, 9101), ("c8pp 4-wave", 1, 1, 9111)):
+        with _lib.switches({"DV3_SW_C8PP_MIN_TILES": thr, "DV3_SW_C8PP_NW4": nw4}):
             out[tag] = _run(layer, x, True, "bf16", ops)
             # the last tap-GEMM of backward is the input gradient: served by the kernel under test
             v = L.dv3_debug_get(10)
-            assert (v // 1000 == want) if want < 10 else (v == want), (tag, v)
-    finally:
-        L.dv3_debug_set(19, 128)
-        L.dv3_debug_set(34, 2)
+        assert (v // 1000 == want) if want < 10 else (v == want), (tag, v)
     y0, dx0, dp0 = out["planes"]
     for tag in ("c8pp", "c8pp 4-wave"):
         y1, dx1, dp1 = out[tag]
@@ -391,8 +386,8 @@ def test_north_star_c8pp_is_the_kernel_the_bench_times(dev, modes, d, causal):
         oracle evaluated with the same roundings (bf16 operands from the HIP path's own weight image, fp32 accumulate and
         tail), the boundary flips counted;
       * training forward (keep-bytes, pre-gate save) + backward (input gradient, weight / gain / bias gradients): variant
-        9101 again, and bit-identical to the 128-row planes kernel at this very shape (dv3_debug_set(19, 0)), which the
-        small-shape tests above hold to the oracle -- both LOAD-phase orders of the kernel (dv3_debug_set(30, v))."""
+        9101 again, and bit-identical to the 128-row planes kernel at this very shape (DV3_SW_C8PP_MIN_TILES = 0), which the
+        small-shape tests above hold to the oracle -- both LOAD-phase orders of the kernel (DV3_SW_C8PP_RF)."""
     ops = modes
     from deepvoice3_pytorch_amd import modules, _lib
     L = _lib.lib()
@@ -434,23 +429,16 @@ def test_north_star_c8pp_is_the_kernel_the_bench_times(dev, modes, d, causal):
     # training forward + backward: the benchmarked kernel against the planes kernel at the benchmarked shape
     layer.train()
     out = {}
-    try:
-        # (34: 0 = 8-wave form only, 1 = the 4-wave form everywhere, 2 = the dispatcher's rule -- what a training step runs:
-        #  masked forward on two 4-wave workgroups per CU, this 256-tile input gradient on the 8-wave form)
-        for tag, thr, rf, nw4 in (("planes", 0, 1, 0), ("c8pp", 128, 1, 0), ("c8pp staging first", 128, 0, 0),
-                                  ("c8pp 4-wave", 128, 1, 1), ("c8pp by the rule", 128, 1, 2)):
-            L.dv3_debug_set(19, thr)
-            L.dv3_debug_set(30, rf)
-            L.dv3_debug_set(34, nw4)
+    # (C8PP_NW4: 0 = 8-wave form only, 1 = the 4-wave form everywhere, 2 = the dispatcher's rule -- what a training step
+    #  runs: masked forward on two 4-wave workgroups per CU, this 256-tile input gradient on the 8-wave form)
+    for tag, thr, rf, nw4 in (("planes", 0, 1, 0), ("c8pp", 128, 1, 0), ("c8pp staging first", 128, 0, 0),
+                              ("c8pp 4-wave", 128, 1, 1), ("c8pp by the rule", 128, 1, 2)):
+        with _lib.switches({"DV3_SW_C8PP_MIN_TILES": thr, "DV3_SW_C8PP_RF": rf, "DV3_SW_C8PP_NW4": nw4}):
             out[tag] = _run(layer, x, True, "bf16", ops)
             v = L.dv3_debug_get(10)
-            assert (v // 1000 == 9) == bool(thr), (tag, v)
-            if thr:
-                assert v == (9111 if nw4 == 1 else 9101), (tag, v)
-    finally:
-        L.dv3_debug_set(19, 128)
-        L.dv3_debug_set(30, 1)
-        L.dv3_debug_set(34, 2)
+        assert (v // 1000 == 9) == bool(thr), (tag, v)
+        if thr:
+            assert v == (9111 if nw4 == 1 else 9101), (tag, v)
     y0, dx0, dp0 = out["planes"]
     for tag in ("c8pp", "c8pp staging first", "c8pp 4-wave", "c8pp by the rule"):
         y1, dx1, dp1 = out[tag]
@@ -542,9 +530,8 @@ def test_c8pp_plain_and_fp32_output_forms(dev, modes):
     ops.set_gemm_precision("bf16")
     ops.bf16_storage = True
     res = {}
-    try:
-        for tag, thr in (("planes", 0), ("c8pp", 1)):
-            L.dv3_debug_set(19, thr)
+    for tag, thr in (("planes", 0), ("c8pp", 1)):
+        with _lib.switches({"DV3_SW_C8PP_MIN_TILES": thr}):
             outs = []
             for (Ci, Co, mode, o8) in ((64, 128, ops.EPI_RELU, True), (128, 64, ops.EPI_LINEAR, True),
                                        (64, 513, ops.EPI_SIGMOID, False), (513, 64, ops.EPI_LINEAR, True),
@@ -565,8 +552,6 @@ def test_c8pp_plain_and_fp32_output_forms(dev, modes):
             (y * torch.linspace(-1, 1, y.numel(), device=dev).view_as(y)).sum().backward()
             outs += [y.detach()] + [t.grad.detach() for t in ins]
             res[tag] = outs
-    finally:
-        L.dv3_debug_set(19, 128)
     for i, (a, b) in enumerate(zip(res["planes"], res["c8pp"])):
         assert torch.equal(a, b), (i, float((a - b).abs().max()))
 
@@ -589,24 +574,18 @@ def test_wgrad_c8_two_steps_ahead_is_bit_identical(dev, modes, kind, C, k, d, ca
     layer = layer.to(dev).train()
     x = torch.randn(B, C, T, device=dev)
     out = {}
-    try:
-        # register-transposing forms: one step ahead | two steps ahead, staging after the MFMAs | ... between them (three
-        # taps: variant 5063); transposing-read forms (round 6, dv3_debug_set(52, v)): plain 51xx | staging between the
-        # MFMAs 5143 | one barrier per two K steps 53xx | both 5343 (the default)
-        for tag, tr, pf2, il in ((0, 0, 0, 0), (1, 0, 1, 0), (2, 0, 1, 1), (3, 1, 1, 1), (4, 2, 1, 1), (5, 3, 1, 1), (6, 4, 1, 1)):
-            L.dv3_debug_set(52, tr)
-            L.dv3_debug_set(20, pf2)
-            L.dv3_debug_set(49, il)
+    # register-transposing forms: one step ahead | two steps ahead, staging after the MFMAs | ... between them (three
+    # taps: variant 5063); transposing-read forms (round 6, DV3_SW_WGRAD_C8_TR): plain 51xx | staging between the
+    # MFMAs 5143 | one barrier per two K steps 53xx | both 5343 (the default)
+    for tag, tr, pf2, il in ((0, 0, 0, 0), (1, 0, 1, 0), (2, 0, 1, 1), (3, 1, 1, 1), (4, 2, 1, 1), (5, 3, 1, 1), (6, 4, 1, 1)):
+        with _lib.switches({"DV3_SW_WGRAD_C8_TR": tr, "DV3_SW_WGRAD_C8_PF2": pf2, "DV3_SW_WGRAD_C8_IL": il}):
             out[tag] = _run(layer, x, True, "bf16", ops)
-            if tr == 0:
-                want = 5000 + 20 * pf2 + k + (40 if (il and pf2 and k == 3) else 0)
-            else:
-                want = 5100 + k + (40 if (tr in (2, 4) and k == 3) else 0) + (200 if tr in (3, 4) else 0)
-            assert L.dv3_debug_get(11) == want, (tag, L.dv3_debug_get(11), want)
-    finally:
-        L.dv3_debug_set(20, 1)
-        L.dv3_debug_set(49, 1)
-        L.dv3_debug_set(52, 4)
+            got = L.dv3_debug_get(11)
+        if tr == 0:
+            want = 5000 + 20 * pf2 + k + (40 if (il and pf2 and k == 3) else 0)
+        else:
+            want = 5100 + k + (40 if (tr in (2, 4) and k == 3) else 0) + (200 if tr in (3, 4) else 0)
+        assert got == want, (tag, got, want)
     for tag in range(1, 7):
         for n in out[0][2]:
             assert torch.equal(out[0][2][n], out[tag][2][n]), (tag, n)

@@ -42,7 +42,7 @@ from tests.util import rel_err  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 SPLIT_FORMS, F32_FORMS, CONV_CASES = OPS_T.SPLIT_FORMS, OPS_T.F32_FORMS, OPS_T.CONV_CASES
-_Switches, _conv_reached = OPS_T._Switches, OPS_T._conv_reached
+_form, _conv_reached = OPS_T._form, OPS_T._conv_reached
 MODES = OPS_T.MODES
 # (mode, B, C, T) of test_gate_backward_16_byte_rows_of_any_length: head, quads and tail; T = 1, 2, 3; C = 513
 _BWD_PARAMS = [m.args[1] for m in KERN_T.test_gate_backward_16_byte_rows_of_any_length.pytestmark
@@ -143,7 +143,7 @@ def _run_gated(dev, mode, form, kind, shape):
     assert ops.f16_range_events(reset=True) == 0
     epi, residual = _mode_consts(ops, kind)
     outs = []
-    with _Switches(switches, sk):
+    with _form(switches, sk):
         for _ in range(2):
             ab = torch.empty(B, M, T, device=dev)
             try:
@@ -292,15 +292,12 @@ def test_gated_tail_of_both_c8_kernels(dev, kind):
             r8 = None if kind == "glu" else ops.to_c8(case["r_dev"])
             bits = {}
             for tag, thr in (("planes", 0), ("c8pp", 1)):
-                L.dv3_debug_set(19, thr)
-                try:
+                with _form({"DV3_SW_C8PP_MIN_TILES": thr}):
                     ab8 = ops._c8_empty(B, 2 * C, T, dev)
                     y8 = ops.conv_gemm(None, None, pk.lda, pk.a_half, B=B, Cin=C, Tin=T, M=2 * C, Tout=T, J=k, dil=d,
                                        padL=R.pad_left(k, d, causal), mode=epi, Cg=C, bias=fam["bias"], residual=residual,
                                        ab=ab8, r=r8, a_split=pk.fwd_s, x_c8=x8, out_c8=True)
                     census = L.dv3_debug_get(10)
-                finally:
-                    L.dv3_debug_set(19, 128)
                 assert census // 1000 == (8 if tag == "planes" else 9), (tag, shape, census)
                 what = "%s c8 %s %s" % (kind, tag, shape)
                 with torch.no_grad():
@@ -450,13 +447,10 @@ def test_gate_backward_elementwise(dev, kind, B, C, T):
             (ref, bnd), dres_ref, part_ref = _bwd_reference(kind, inp, T, depth)
             plain = None
             for pair in ((False, True) if gated else (False,)):
-                L.dv3_debug_set(55, sw)
-                try:
+                with _form({"DV3_SW_GATE_VEC": sw}):
                     dab, dres, part = ops.gate_bwd(dy, saved, x, B=B, C=C, T=T, mode=epi, residual=int(kind == "glu_res"),
                                                    pair=pair, want_dres=gated, alpha=1.0 if gated else ALPHA)
                     torch.cuda.synchronize()
-                finally:
-                    L.dv3_debug_set(55, 1)
                 what = "%s (%d, %d, %d) switch55=%d pair=%d ab16=%d" % (kind, B, C, T, sw, pair, ab16)
                 if pair:
                     words = dab.cpu().numpy().view(np.int32)
@@ -497,13 +491,10 @@ def test_gate_backward_c8_elementwise(dev, kind, B, C, T):
     x8 = ops.to_c8(_t(inp["x"], dev)) if kind == "highway" else None
     rows = 2 * C if gated else C
     for fast in (1, 0):
-        L.dv3_debug_set(56, fast)
-        try:
+        with _form({"DV3_SW_GATE_C8_FAST": fast}):
             dab8, dres8, part = ops.gate_bwd_c8(dy8, saved, x8, B=B, C=C, T=T, mode=epi, residual=int(kind == "glu_res"),
                                                 want_dres=gated, alpha=1.0 if gated else ALPHA)
             torch.cuda.synchronize()
-        finally:
-            L.dv3_debug_set(56, 1)
         what = "c8 %s (%d, %d, %d) switch56=%d" % (kind, B, C, T, fast)
         with torch.no_grad():
             dab = ops.from_c8(dab8, rows).cpu().numpy()

@@ -34,23 +34,32 @@ pytestmark = pytest.mark.gpu
 MODE = "bf16"
 FAMILIES = R.EXACT_BF16 + R.BOUNDED
 RS2 = float(np.float32(0.70710678118654752440))           # the sqrt(.5) a residual layer hands to r_scale, as fp32
-# dv3_debug_set switches this file moves, with the library's defaults
-SWITCH_DEFAULTS = {2: 0, 47: 1, 4: 0, 19: 128, 34: 2, 52: 4, 20: 1, 49: 1}
 # fp32 storage, tap-GEMM: form -> tile_hint (tile ids 1 .. 9 of csrc/conv_gemm_bf16x3.hip; the 256 x 256 and k-split kernels
 # do not take split_terms == 1)
 CONV_FORMS = dict([("auto", 0)] + [("tile%d" % t, t) for t in range(21, 30)])
 # fp32 storage, weight gradient: form -> (k_split, masked, switches, census for three taps).  With split_bf16 == 2 the
 # dispatcher keeps the two-steps-ahead kernel out (it is a three-term kernel): its switch leads to the per-tap tile
 WGRAD_FORMS = {"auto": None, "slabs": (False, False, {}, 4010), "k_split": (True, False, {}, 4030),
-               "k_split_masked": (True, True, {}, 4030), "all_taps": (True, False, {2: 3}, 4030),
-               "two_steps_ahead": (True, False, {2: 4, 47: 0}, 4010)}
+               "k_split_masked": (True, True, {}, 4030), "all_taps": (True, False, {"DV3_SW_WGRAD_TILE": 3}, 4030),
+               "two_steps_ahead": (True, False, {"DV3_SW_WGRAD_TILE": 4, "DV3_SW_WGRAD_T2_WINDOW": 0}, 4010)}
 # c8 tap-GEMM: form -> (switches, census)
-C8_FORMS = {"auto": ({}, None), "planes1": ({4: 1}, 8010), "planes2": ({4: 2}, 8020), "planes9": ({4: 9}, 8090),
-            "c8pp": ({19: 1, 34: 0}, 9101), "c8pp_nw4": ({19: 1, 34: 1}, 9111)}
-# wgrad_c8: form -> (switches 52 / 20 / 49, census without the tap count, + when three taps)
-WGRAD_C8_FORMS = {"reg_pf1": ({52: 0, 20: 0, 49: 0}, 5000, 0), "reg_pf2": ({52: 0, 20: 1, 49: 0}, 5020, 0),
-                  "reg_pf2_il": ({52: 0, 20: 1, 49: 1}, 5020, 40), "tr": ({52: 1}, 5100, 0), "tr_il": ({52: 2}, 5100, 40),
-                  "tr_pair": ({52: 3}, 5300, 0), "tr_pair_il": ({52: 4}, 5300, 40)}
+C8_FORMS = {"auto": ({}, None), "planes1": ({"DV3_SW_PLANES_TILE": 1}, 8010), "planes2": ({"DV3_SW_PLANES_TILE": 2}, 8020),
+            "planes9": ({"DV3_SW_PLANES_TILE": 9}, 8090),
+            "c8pp": ({"DV3_SW_C8PP_MIN_TILES": 1, "DV3_SW_C8PP_NW4": 0}, 9101),
+            "c8pp_nw4": ({"DV3_SW_C8PP_MIN_TILES": 1, "DV3_SW_C8PP_NW4": 1}, 9111)}
+
+
+def _wgrad_c8(tr, pf2=None, il=None):
+    sw = {"DV3_SW_WGRAD_C8_TR": tr}
+    if pf2 is not None:
+        sw.update({"DV3_SW_WGRAD_C8_PF2": pf2, "DV3_SW_WGRAD_C8_IL": il})
+    return sw
+
+
+# wgrad_c8: form -> (switches, census without the tap count, + when three taps)
+WGRAD_C8_FORMS = {"reg_pf1": (_wgrad_c8(0, 0, 0), 5000, 0), "reg_pf2": (_wgrad_c8(0, 1, 0), 5020, 0),
+                  "reg_pf2_il": (_wgrad_c8(0, 1, 1), 5020, 40), "tr": (_wgrad_c8(1), 5100, 0), "tr_il": (_wgrad_c8(2), 5100, 40),
+                  "tr_pair": (_wgrad_c8(3), 5300, 0), "tr_pair_il": (_wgrad_c8(4), 5300, 40)}
 
 
 @pytest.fixture(scope="module")
@@ -67,7 +76,7 @@ def _lib():
 
 @pytest.fixture()
 def bf16_mode():
-    """the GEMM mode, the storage switch and every debug switch of this file as they were"""
+    """the GEMM mode and the storage switch as they were (the library's switches: _lib.switches, scoped in each test)"""
     ops, L = _lib()
     prev = (ops.gemm_precision(), ops.bf16_storage)
     ops.set_gemm_precision(MODE)
@@ -76,22 +85,11 @@ def bf16_mode():
     finally:
         ops.set_gemm_precision(prev[0])
         ops.bf16_storage = prev[1]
-        for k, v in SWITCH_DEFAULTS.items():
-            L.dv3_debug_set(k, v)
 
 
-class _Switches(object):
-    def __init__(self, switches):
-        self.switches = switches
-
-    def __enter__(self):
-        for k, v in self.switches.items():
-            assert _lib()[1].dv3_debug_set(k, v) == 0, (k, v)
-
-    def __exit__(self, *exc):
-        for k in self.switches:
-            _lib()[1].dv3_debug_set(k, SWITCH_DEFAULTS[k])
-        return False
+def _switches(switches):
+    from deepvoice3_pytorch_amd import _lib
+    return _lib.switches(switches)
 
 
 _by_output = {}
@@ -295,7 +293,7 @@ def _run_wgrad_f32(dev, form, fam, shape):
                             wgt_keep=keep, scale=2.0 if masked else 1.0, ops=1 if masked else 0)
     g, x = _up(act, dev), _up(wgt, dev)
     outs = []
-    with _Switches(switches):
+    with _switches(switches):
         for _ in range(2):
             o = ops.wgrad_gemm(g, x, B=B, M=M, Cin=C, T=T, Tin=T, J=k, dil=d, padL=padL, n_slabs=S, xmask=bits,
                                xmask_rs=rs or 0, drop_scale=2.0 if masked else 1.0, split_bf16=not small, k_split=ksplit)
@@ -416,7 +414,7 @@ def _run_conv_c8(dev, form, fam, shape, variants=None):
                 kw2.update(ymask_c8=_up(R.keep_bytes(keep), dev), r=None if r is None else _to_c8(r, dev), r_scale=r_scale)
             args = (None, pk.bwd, pk.ldb, 0)
         outs = []
-        with _Switches(switches):
+        with _switches(switches):
             for _ in range(2):
                 ab = ops._c8_empty(B, M, T, dev) if gated else None
                 y = ops.conv_gemm(*args, ab=ab, **kw, **kw2)
@@ -496,7 +494,7 @@ def _run_wgrad_c8(dev, form, fam, shape):
     g8, x8 = _to_c8(act, dev), _to_c8(wgt, dev)
     chunks = B * ((T + 31) // 32)
     worst = 0.0
-    with _Switches(switches):
+    with _switches(switches):
         for masked in (False, True):
             keep = _keep((B, C, T), 19) if masked else None
             kb = _up(R.keep_bytes(keep), dev) if masked else None

@@ -20,6 +20,7 @@ kernel has shapes of its own (gemm_split_ref.STREAMK_SHAPES: none of the edge sh
 which every family runs forward, gated and as input gradient with the form asserted; the benchmarked layer reaches it by
 the dispatcher's own rule.
 """
+import contextlib
 import os
 import sys
 
@@ -37,16 +38,16 @@ pytestmark = pytest.mark.gpu
 
 MODES = ("f16x3", "bf16x3", "f32")
 FAMILIES = R.EXACT + R.BOUNDED
-# form -> (tile_hint, {dv3_debug_set switch: value}, ops.streamk)
+# form -> (tile_hint, {library switch (include/dv3hip.h, DV3_SWITCHES): value}, ops.streamk)
 SPLIT_FORMS = dict([("auto", (0, {}, None))] + [("tile%d" % t, (t, {}, None)) for t in range(21, 30)] +
-                   [("pp2", (30, {}, None)), ("pp2_streamk", (30, {22: 2}, "force")), ("ksplit", (22, {44: 2}, None))])
+                   [("pp2", (30, {}, None)), ("pp2_streamk", (30, {"DV3_SW_PP2_SK": 2}, "force")),
+                    ("ksplit", (22, {"DV3_SW_X3_KS": 2}, None))])
 F32_FORMS = dict([("auto", (0, {}, None))] + [("tile%d" % t, (t, {}, None)) for t in (1, 2, 3, 4, 5, 6, 11, 12, 13, 14, 15, 16)])
-SWITCH_DEFAULTS = {22: 1, 44: 1, 2: 0, 47: 1}
 CONV_CASES = [(m, f) for m in MODES for f in (F32_FORMS if m == "f32" else SPLIT_FORMS)]
 # weight gradient: form -> (split_bf16, k_split, g_pair, masked, switches)
 WGRAD_SPLIT_FORMS = {"auto": None, "split_bf16": (True, False, False, False, {}), "k_split": (True, True, False, False, {}),
-                     "k_split_masked": (True, True, False, True, {}), "all_taps": (True, True, False, False, {2: 3}),
-                     "two_steps_ahead_per_tap": (True, True, False, False, {2: 4, 47: 0}),
+                     "k_split_masked": (True, True, False, True, {}), "all_taps": (True, True, False, False, {"DV3_SW_WGRAD_TILE": 3}),
+                     "two_steps_ahead_per_tap": (True, True, False, False, {"DV3_SW_WGRAD_TILE": 4, "DV3_SW_WGRAD_T2_WINDOW": 0}),
                      "g_pair": (True, True, True, False, {})}
 WGRAD_F32_FORMS = {"auto": None, "slabs_masked": (False, False, False, True, {})}
 WGRAD_CASES = [(m, f) for m in MODES for f in (WGRAD_F32_FORMS if m == "f32" else WGRAD_SPLIT_FORMS)]
@@ -123,24 +124,18 @@ def _check(fam, got, want, ref, bnd, what):
     return assert_close_elementwise(got, ref, 0, bnd, what)
 
 
-class _Switches(object):
-    def __init__(self, switches, streamk=None):
-        self.switches, self.streamk = switches, streamk
-
-    def __enter__(self):
-        ops, L = _lib()
-        self.prev_sk = ops.streamk
-        if self.streamk is not None:
-            ops.streamk = self.streamk
-        for k, v in self.switches.items():
-            L.dv3_debug_set(k, v)
-
-    def __exit__(self, *exc):
-        ops, L = _lib()
-        ops.streamk = self.prev_sk
-        for k in self.switches:
-            L.dv3_debug_set(k, SWITCH_DEFAULTS[k])
-        return False
+@contextlib.contextmanager
+def _form(switches, streamk=None):
+    """a form's library switches (_lib.switches puts back what was there) and, for the stream-K forms, ops.streamk"""
+    from deepvoice3_pytorch_amd import ops, _lib as LIB
+    prev_sk = ops.streamk
+    if streamk is not None:
+        ops.streamk = streamk
+    try:
+        with LIB.switches(switches):
+            yield
+    finally:
+        ops.streamk = prev_sk
 
 
 def _conv_reached(mode, gemm, form, census, Kin):
@@ -179,7 +174,7 @@ def _run_conv(dev, gemm, mode, form, fam, shape, want_three=True):
     packed = ops.f16_range_events(reset=True)
     assert packed == 0 or (gemm == "dgrad" and fam == "E3"), "%d units counted while packing in-range weights" % packed
     outs = []
-    with _Switches(switches, sk):
+    with _form(switches, sk):
         for _ in range(2):
             try:
                 if gemm == "dgrad":
@@ -256,7 +251,7 @@ def _run_wgrad(dev, mode, form, fam, shape):
     if g_pair:
         g = R.pair_words(f["act"]).to(dev)
     outs = []
-    with _Switches(switches):
+    with _form(switches):
         for _ in range(2):
             o = ops.wgrad_gemm(g, x, B=B, M=M, Cin=C, T=T, Tin=T, J=k, dil=d, padL=padL, n_slabs=S, xmask=bits,
                                xmask_rs=rs, drop_scale=2.0 if masked else 1.0, split_bf16=split, k_split=ksplit,

@@ -42,7 +42,8 @@ def dev():
     return torch.device("cuda:0")
 
 
-KS_DEFAULT = 1      # dv3_debug_set(44, v): the k-split form of the 128 x 64 tile (conv_gemm_bf16x3.hip): 0 off / 1 by rule / 2 wherever eligible
+# ids whose switch became a constant beside its dispatch rule (tile-picker costs, stream-K and k-split rule bounds)
+NEWLY_RETIRED_SWITCHES = (9, 23, 24, 25, 27, 42, 45, 46)
 
 
 def _ops():
@@ -158,15 +159,13 @@ def test_conv_gemm_bf16x3_pingpong_equals_inphase(dev, gemm_mode, tile, B, C, T,
     ys = []
     try:
         for mode in (0, 1):
-            _lib.call("dv3_debug_set", 3, mode)
-            ys.append(ops.conv_gemm(xg, pk.fwd, pk.lda, pk.a_half, B=B, Cin=C, Tin=T, M=2 * C, Tout=T, J=k, dil=d,
-                                    padL=padL, mode=ops.EPI_GLU, Cg=C, bias=sd["l.conv.bias"].to(dev), r=xg,
-                                    residual=1, tile_hint=tile, a_split=pk.fwd_s, **kw))
+            with _lib.switches({"DV3_SW_X3_PINGPONG": mode}):
+                ys.append(ops.conv_gemm(xg, pk.fwd, pk.lda, pk.a_half, B=B, Cin=C, Tin=T, M=2 * C, Tout=T, J=k, dil=d,
+                                        padL=padL, mode=ops.EPI_GLU, Cg=C, bias=sd["l.conv.bias"].to(dev), r=xg,
+                                        residual=1, tile_hint=tile, a_split=pk.fwd_s, **kw))
     except RuntimeError as e:
         assert "needs split-bf16" in str(e)
         pytest.skip("tile %d not eligible for this shape" % tile)
-    finally:
-        _lib.call("dv3_debug_set", 3, 1)
     assert torch.equal(ys[0], ys[1])
     if not masked:
         assert rel_err(ys[1].cpu(), O.conv1d_glu(sd, "l", x, k, d, causal, True)) < KTOL
@@ -572,7 +571,7 @@ def test_two_steps_ahead_wgrad_equals_the_all_taps_wgrad(dev, mode, B, M, C, T, 
     and accumulation order), ragged channel counts, dilations up to 27 and masked operands included; the variant each
     call served is read back (dv3_debug_get(11)).  Round 6: for d = 1 and 3 the default is the WINDOW form (one window of
     8 + 2 d elements per unit fetched, masked and converted once for the three taps: variant ...42): bit-identical to the
-    per-tap form (dv3_debug_set(47, 0)) and to the all-taps kernel, same-padded (d > 0 here) and causal (d < 0: padL = 2 |d|),
+    per-tap form (DV3_SW_WGRAD_T2_WINDOW = 0) and to the all-taps kernel, same-padded (d > 0 here) and causal (d < 0: padL = 2 |d|),
     sequences shorter than a window included."""
     from deepvoice3_pytorch_amd import ops, _lib
     L = _lib.lib()
@@ -588,18 +587,14 @@ def test_two_steps_ahead_wgrad_equals_the_all_taps_wgrad(dev, mode, B, M, C, T, 
             ops.dropout_state.manual_seed(3)
             bits, rs = ops.dropout_bits(B * C, T, 0.05, dev)
         outs = []
-        # dv3_debug_set(2, .): 3 = all-taps kernel, 4 = two-steps-ahead kernel; (47, .): its window form on / off
+        # WGRAD_TILE: 3 = all-taps kernel, 4 = two-steps-ahead kernel; T2_WINDOW: its window form on / off; T2_IL: the
+        # window form's staging between the MFMAs (default) / after them
         for tile, win, il in ((3, 1, 1), (4, 1, 1), (4, 0, 0), (4, 1, 0)):
-            L.dv3_debug_set(2, tile)
-            L.dv3_debug_set(47, win)
-            L.dv3_debug_set(48, il)         # the window form's staging between the MFMAs (default) / after them
-            o = ops.wgrad_gemm(g, x, B=B, M=M, Cin=C, T=T, Tin=T, J=3, dil=d, padL=padL, n_slabs=S, xmask=bits,
-                               xmask_rs=rs or 0, drop_scale=1 / 0.95 if masked else 1.0, split_bf16=True, k_split=True)
-            outs.append((o.clone(), L.dv3_debug_get(11)))
+            with _lib.switches({"DV3_SW_WGRAD_TILE": tile, "DV3_SW_WGRAD_T2_WINDOW": win, "DV3_SW_WGRAD_T2_IL": il}):
+                o = ops.wgrad_gemm(g, x, B=B, M=M, Cin=C, T=T, Tin=T, J=3, dil=d, padL=padL, n_slabs=S, xmask=bits,
+                                   xmask_rs=rs or 0, drop_scale=1 / 0.95 if masked else 1.0, split_bf16=True, k_split=True)
+                outs.append((o.clone(), L.dv3_debug_get(11)))
     finally:
-        L.dv3_debug_set(2, 0)
-        L.dv3_debug_set(47, 1)
-        L.dv3_debug_set(48, 1)
         ops.set_gemm_precision(prev)
     windowed = d in (1, 3) and (B - 1) * C * T + (C - 1) * T + T >= 16
     assert [o[1] % 1000 for o in outs] == [30, 46 if windowed else 40, 40, 42 if windowed else 40], [o[1] for o in outs]
@@ -654,17 +649,14 @@ def test_256x256_k16_pingpong_tap_gemm_equals_the_128_wide_kernels(dev, gemm_mod
     dkw = dict(B=B, Cin=2 * C, Tin=T, M=C, Tout=T, J=k, dil=d, padL=(k - 1) * d - padL, mode=ops.EPI_DGRAD,
                r=dres, ymask=bits, ymask_rs=rs or 0, drop_scale=1 / 0.95 if masked else 1.0, a_split=pk.bwd_s)
     dxs = []
-    try:
-        # (the picker's kernel for these small grids is the k-split form since round 5 -- first half + second half of the
-        #  chunk range: compared with the running sum of the 256 x 256 kernel it is held to the tolerance, the one-group
-        #  loop bit for bit)
-        for hint, ks in ((0, 0), (30, 0), (0, KS_DEFAULT)):
-            _lib.lib().dv3_debug_set(44, ks)
+    # (the picker's kernel for these small grids is the k-split form since round 5 -- first half + second half of the
+    #  chunk range: compared with the running sum of the 256 x 256 kernel it is held to the tolerance, the one-group
+    #  loop bit for bit)
+    for hint, ks in ((0, 0), (30, 0), (0, _lib.SWITCHES["DV3_SW_X3_KS"][1])):        # [1]: the default, by rule
+        with _lib.switches({"DV3_SW_X3_KS": ks}):
             dx = torch.empty(B, C, T, device=dev)
             ops.conv_gemm(gm, None, pk.ldb, 0, y=dx, tile_hint=hint, **dkw)
             dxs.append(dx)
-    finally:
-        _lib.lib().dv3_debug_set(44, KS_DEFAULT)
     assert torch.equal(dxs[0], dxs[1])
     assert rel_err(dxs[2].cpu(), dxs[1].cpu()) < (5e-6 if gemm_mode == "f16x3" else KTOL)
 
@@ -675,7 +667,7 @@ def test_256x256_k16_pingpong_tap_gemm_equals_the_128_wide_kernels(dev, gemm_mod
                                                      (2, 512, 150, 3, 3, False, True), (16, 256, 201, 1, 1, False, True),
                                                      (1, 72, 17, 3, 27, True, False), (3, 24, 50, 3, 1, False, False)])
 def test_k_split_form_of_the_128x64_tile(dev, gemm_mode, B, C, T, k, d, causal, masked):
-    """conv_gemm_bf16x3.hip, template KS = 2 (round 5; dv3_debug_set(44, 0 | 1 | 2)): two wave groups of one workgroup
+    """conv_gemm_bf16x3.hip, template KS = 2 (round 5; DV3_SW_X3_KS = 0 | 1 | 2): two wave groups of one workgroup
     take the first / second half of the input-channel chunks of the same 128 x 64 tile and the second hands its
     accumulators to the first through LDS.  The sum is (first half) + (second half) instead of one running sum:
     not bit-identical to the one-group loop, but a fixed function of the shape -- checked: equal to the one-group
@@ -708,9 +700,8 @@ def test_k_split_form_of_the_128x64_tile(dev, gemm_mode, B, C, T, k, d, causal, 
                r=dres, ymask=bits, ymask_rs=rs or 0, drop_scale=1 / 0.95 if masked else 1.0, a_split=pk.bwd_s, tile_hint=22)
     eligible = (C + 31) // 32 >= 2
     outs = []
-    try:
-        for ks in (0, 2, 2):
-            L.dv3_debug_set(44, ks)
+    for ks in (0, 2, 2):
+        with _lib.switches({"DV3_SW_X3_KS": ks}):
             y = torch.empty(B, C, T, device=dev)
             ab = torch.empty(B, 2 * C, T, device=dev)
             dx = torch.empty(B, C, T, device=dev)
@@ -718,11 +709,9 @@ def test_k_split_form_of_the_128x64_tile(dev, gemm_mode, B, C, T, k, d, causal, 
             v0 = L.dv3_debug_get(10)
             ops.conv_gemm(gm, None, pk.ldb, 0, y=dx, **dkw)
             v1 = L.dv3_debug_get(10)
-            assert (v0 % 10, v1 % 10) == ((2, 2) if ks and eligible else (0, 2 if ks else 0)), (ks, v0, v1)
-            assert v0 % 1000 // 10 == 2 and v1 % 1000 // 10 == 2
-            outs.append((y, ab, dx))
-    finally:
-        L.dv3_debug_set(44, KS_DEFAULT)
+        assert (v0 % 10, v1 % 10) == ((2, 2) if ks and eligible else (0, 2 if ks else 0)), (ks, v0, v1)
+        assert v0 % 1000 // 10 == 2 and v1 % 1000 // 10 == 2
+        outs.append((y, ab, dx))
     tol = 5e-6 if gemm_mode == "f16x3" else KTOL
     for a, b, c, name in zip(outs[0], outs[1], outs[2], ("y", "pre-gate", "dx")):
         assert torch.equal(b.view(torch.int32), c.view(torch.int32)), name          # repeatable
@@ -816,15 +805,14 @@ def test_stream_k_form_of_the_256x256_tap_gemm(dev, gemm_mode, B, C, T, d, maske
     try:
         res = {}
         for sk in (0, 2, 2, 2):
-            L.dv3_debug_set(22, sk)
-            y, ab, dx = torch.empty(B, C, T, device=dev), torch.empty(B, 2 * C, T, device=dev), torch.empty(B, C, T, device=dev)
-            ops.conv_gemm(x, None, pk.lda, pk.a_half, y=y, ab=ab, **kw)
-            vf = L.dv3_debug_get(10)
-            ops.conv_gemm(gm, None, pk.ldb, 0, y=dx, **dkw)
-            vd = L.dv3_debug_get(10)
+            with _lib.switches({"DV3_SW_PP2_SK": sk}):
+                y, ab, dx = torch.empty(B, C, T, device=dev), torch.empty(B, 2 * C, T, device=dev), torch.empty(B, C, T, device=dev)
+                ops.conv_gemm(x, None, pk.lda, pk.a_half, y=y, ab=ab, **kw)
+                vf = L.dv3_debug_get(10)
+                ops.conv_gemm(gm, None, pk.ldb, 0, y=dx, **dkw)
+                vd = L.dv3_debug_get(10)
             res.setdefault(sk, []).append((y, ab, dx, vf % 1000, vd % 1000))
     finally:
-        L.dv3_debug_set(22, 1)
         ops.streamk = prev
     torch.cuda.synchronize()
     (y0, ab0, dx0, vf0, vd0), sks = res[0][0], res[2]
@@ -839,7 +827,7 @@ def test_stream_k_form_of_the_256x256_tap_gemm(dev, gemm_mode, B, C, T, d, maske
                                            (96, 64, 5, 9, False), (513, 512, 1, 3, True), (64, 36, 3, 17, True)])
 def test_weight_norm_backward_16_byte_gather_is_the_4_byte_one(dev, O_, I, J, S, rows):
     """dv3_weight_norm_bwd_f32 sums the K-split partial slabs four columns per thread (round 6) with the scalar loop's
-    order of additions per element: dv, dg and dbias must be the same bits as with dv3_debug_set(51, 0)."""
+    order of additions per element: dv, dg and dbias must be the same bits as with DV3_SW_WN_BWD_VEC4 = 0."""
     from deepvoice3_pytorch_amd import ops, _lib
     rng = np.random.RandomState(O_ + I + J + S)
     ldo = I
@@ -850,11 +838,8 @@ def test_weight_norm_backward_16_byte_gather_is_the_4_byte_one(dev, O_, I, J, S,
     part = torch.from_numpy(rng.randn(7, O_).astype(np.float32)).to(dev)
     outs = []
     for sw in (0, 1):
-        _lib.lib().dv3_debug_set(51, sw)
-        try:
+        with _lib.switches({"DV3_SW_WN_BWD_VEC4": sw}):
             outs.append(ops.weight_norm_bwd(slabs, S, ldo, v, g, scale, part, 7, O_, I, J, rows_of_slabs=rows))
-        finally:
-            _lib.lib().dv3_debug_set(51, 1)
     for a, b in zip(*outs):
         assert torch.equal(a, b)
     # and it is the weight-norm backward: dW = sum of the slabs, dg = <dW, v> / |v|, dv = g / |v| (dW - <dW, v> v / |v|^2)
@@ -877,7 +862,7 @@ def test_weight_norm_backward_16_byte_gather_is_the_4_byte_one(dev, O_, I, J, S,
 @pytest.mark.parametrize("pair", [False, True])
 def test_gate_backward_16_byte_rows_of_any_length(dev, mode, B, C, T, pair):
     """dv3_gate_bwd_f32 reads and writes 16 bytes per lane for ANY T (head / aligned quads / tail of a row whose start is
-    only 4-byte aligned; round 6, default) -- element gradients must be the bits of the 4-byte form (dv3_debug_set(55, 0)),
+    only 4-byte aligned; round 6, default) -- element gradients must be the bits of the 4-byte form (DV3_SW_GATE_VEC = 0),
     the row sums differ by the order of their additions only, and both are the autograd of modules.py:157-164 / :224-226."""
     from deepvoice3_pytorch_amd import ops, _lib
     gated = mode in ("glu", "glu16", "highway")
@@ -897,13 +882,10 @@ def test_gate_backward_16_byte_rows_of_any_length(dev, mode, B, C, T, pair):
     x = torch.randn(B, C, T, generator=g).to(dev) if mode == "highway" else None
     res = []
     for sw in (0, 1):
-        _lib.lib().dv3_debug_set(55, sw)
-        try:
+        with _lib.switches({"DV3_SW_GATE_VEC": sw}):
             res.append(ops.gate_bwd(dy, None if mode == "linear" else ab, x, B=B, C=C, T=T, mode=M,
                                     residual=1 if mode.startswith("glu") else 0, pair=pair, want_dres=mode == "highway",
                                     alpha=1.0 if gated else 0.7))
-        finally:
-            _lib.lib().dv3_debug_set(55, 1)
     for a, b in zip(res[0][:2], res[1][:2]):
         assert (a is None) == (b is None)
         if a is not None:
@@ -963,16 +945,105 @@ def test_debug_set_refuses_retired_and_unknown_switches(dev):
     """dv3_debug_set (include/dv3hip.h) is an error for a code it does not handle -- the timing-only ablations and retired
     experiment switches among them -- and for values outside a switch's shipped forms, so that a stale script cannot
     time the production kernel believing it timed something else; the shipped switches the tests use still take their
-    values (each set to its default)."""
+    values (every row of the header's list, each set to its default)."""
     from deepvoice3_pytorch_amd import _lib
     L = _lib.lib()
     for what, value, why in ((999, 0, b"no such switch"), (1, 1, b"no such switch"), (13, 1, b"no such switch"),
                              (5, 0, b"no such switch"), (7, 1, b"no such switch"), (8, 2, b"no such switch"),
-                             (52, 11, b"wgrad_c8 form 0..4"), (29, 5, b"LOAD-phase order 0, 17 or 81")):
+                             (52, 11, b"wgrad_c8 form 0..4"), (29, 5, b"LOAD-phase order 0, 17 or 81")) + \
+            tuple((what, 1, b"no such switch") for what in NEWLY_RETIRED_SWITCHES):
         assert L.dv3_debug_set(what, value) != 0, (what, value)
         msg = L.dv3_last_error()
         assert msg and msg.startswith(b"debug_set(%d, " % what) and why in msg, (what, value, msg)
-    defaults = ((2, 0), (3, 1), (4, 0), (19, 128), (20, 1), (22, 1), (29, 81), (30, 1), (31, 81), (34, 2), (44, KS_DEFAULT),
-                (47, 1), (48, 1), (49, 1), (51, 1), (52, 4), (55, 1), (57, 1))
-    for what, value in defaults:
-        assert L.dv3_debug_set(what, value) == 0, (what, value, L.dv3_last_error())
+    assert len(_lib.SWITCHES) == 28
+    for name, (what, default, lo, hi) in _lib.SWITCHES.items():
+        assert L.dv3_debug_set(what, default) == 0, (name, default, L.dv3_last_error())
+        assert _lib.switch_value(name) == (default, default), name
+
+
+def test_debug_reset_puts_every_switch_at_its_default(dev):
+    """dv3_debug_reset: afterwards dv3_switch_query gives value == default == the row of the header's list, for every
+    switch, whatever was set before; an id outside the list is DV3_EINVAL for the query"""
+    from deepvoice3_pytorch_amd import _lib
+    L = _lib.lib()
+    try:
+        for name, (what, default, lo, hi) in _lib.SWITCHES.items():
+            _lib.call("dv3_debug_set", what, lo if default != lo else hi)        # away from the default
+            assert _lib.switch_value(what)[0] != default, name
+    finally:
+        assert L.dv3_debug_reset() == 0
+    for name, (what, default, lo, hi) in _lib.SWITCHES.items():
+        assert _lib.switch_value(name) == (default, default), name
+    assert L.dv3_switch_query(999, None, None) == _lib.DV3_EINVAL and L.dv3_switch_query(9, None, None) == _lib.DV3_EINVAL
+    assert L.dv3_switch_query(_lib.DV3_SW_X3_KS, None, None) == 0            # either pointer may be null
+
+
+def test_switches_helper_restores_previous_values(dev):
+    """_lib.switches puts back the values it found, not the defaults: nested scopes, and a body that raises"""
+    from deepvoice3_pytorch_amd import _lib
+    ks, tr = "DV3_SW_X3_KS", "DV3_SW_WGRAD_C8_TR"
+    entry = (_lib.switch_value(ks)[0], _lib.switch_value(tr)[0])
+    assert _lib.SWITCHES[ks][1] != 2 and _lib.SWITCHES[tr][1] != 3        # the outer scope's values are not the defaults
+    with _lib.switches({ks: 2, _lib.SWITCHES[tr][0]: 3}):                 # keys: names or ids
+        assert (_lib.switch_value(ks)[0], _lib.switch_value(tr)[0]) == (2, 3)
+        with _lib.switches({ks: 0}):
+            assert (_lib.switch_value(ks)[0], _lib.switch_value(tr)[0]) == (0, 3)
+        assert (_lib.switch_value(ks)[0], _lib.switch_value(tr)[0]) == (2, 3)      # the outer scope's, not the defaults
+        with pytest.raises(ZeroDivisionError):
+            with _lib.switches({ks: 0, tr: 1}):
+                1 / 0
+        assert (_lib.switch_value(ks)[0], _lib.switch_value(tr)[0]) == (2, 3)
+        with pytest.raises(RuntimeError, match="wgrad_c8 form 0..4"):       # a refused value raises; what was set goes back
+            with _lib.switches({ks: 0, tr: 5}):
+                pass
+        assert (_lib.switch_value(ks)[0], _lib.switch_value(tr)[0]) == (2, 3)
+    assert (_lib.switch_value(ks)[0], _lib.switch_value(tr)[0]) == entry
+
+
+def test_debug_set_refuses_values_outside_a_switch_range(dev):
+    """every switch refuses hi + 1 (where hi is INT_MAX no int lies above it: lo - 1 there) and lo - 1; the message names
+    the id and the stored value stays what it was"""
+    from deepvoice3_pytorch_amd import _lib
+    L = _lib.lib()
+    for name, (what, default, lo, hi) in _lib.SWITCHES.items():
+        before = _lib.switch_value(what)[0]
+        for bad in ([hi + 1] if hi < 2 ** 31 - 1 else []) + [lo - 1]:
+            assert L.dv3_debug_set(what, bad) == _lib.DV3_EINVAL, (name, bad)
+            msg = L.dv3_last_error()
+            assert msg and msg.startswith(b"debug_set(%d, " % what), (name, bad, msg)
+            assert _lib.switch_value(what)[0] == before, (name, bad)
+
+
+def test_default_dispatch_census_codes(dev):
+    """with every switch at its default (dv3_debug_reset) a launch gets what the `auto` forms of the operand tests assert
+    (tests/test_gpu_gemm_operands.py, test_gpu_gemm_bf16.py): dv3_debug_get(10) family 5 (scaled fp16 pairs) / 3 (bf16
+    pairs) / 1 (exact fp32); dv3_debug_get(11) 304x, the two-steps-ahead three-tap weight gradient without pair words,
+    1010 in fp32, and 5343 for wgrad_c8, the form its switch's default 4 names"""
+    from deepvoice3_pytorch_amd import ops, _lib
+    L = _lib.lib()
+    assert L.dv3_debug_reset() == 0
+    B, C, T, k = 2, 96, 75, 3
+    M = 2 * C
+    torch.manual_seed(0)
+    x = torch.randn(B, C, T, device=dev)
+    w = torch.randn(M, C, k, device=dev) * 0.1
+    gm = torch.randn(B, M, T, device=dev)
+    prev = ops.gemm_precision()
+    try:
+        for mode, family in (("f16x3", 5), ("bf16x3", 3), ("f32", 1)):
+            ops.set_gemm_precision(mode)
+            pk = ops.pack_weights(w, None, glu_cg=0, need_bwd=False)
+            ops.conv_gemm(x, pk.fwd, pk.lda, 0, B=B, Cin=C, Tin=T, M=M, Tout=T, J=k, dil=1, padL=1, mode=ops.EPI_LINEAR,
+                          a_split=pk.fwd_s)
+            assert L.dv3_debug_get(10) // 1000 == family, (mode, L.dv3_debug_get(10))
+            x3, S = ops.wgrad_plan(B, M, C, T, k)
+            assert x3 == (mode != "f32")
+            ops.wgrad_gemm(gm, x, B=B, M=M, Cin=C, T=T, Tin=T, J=k, dil=1, padL=1, n_slabs=S, split_bf16=x3, k_split=x3)
+            census = L.dv3_debug_get(11)
+            assert (census // 10 == 304 and census % 2 == 0) if x3 else census == 1010, (mode, census)
+        ops.set_gemm_precision("bf16")
+        ops.wgrad_gemm_c8(ops.to_c8(gm), ops.to_c8(x), B=B, M=M, Cin=C, T=T, J=k, dil=1, padL=1, n_slabs=2)
+        assert L.dv3_debug_get(11) == 5343
+    finally:
+        ops.set_gemm_precision(prev)
+    torch.cuda.synchronize()

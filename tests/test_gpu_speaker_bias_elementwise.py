@@ -80,14 +80,6 @@ def dev():
     return torch.device("cuda:0")
 
 
-@pytest.fixture(autouse=True)
-def _restore_prefetch_switch():
-    yield
-    if torch.cuda.is_available():
-        from deepvoice3_pytorch_amd import _lib
-        _lib.lib().dv3_debug_set(54, 1)
-
-
 def _env():
     from deepvoice3_pytorch_amd import ops, _lib
     return ops, _lib.lib(), _lib.STRUCTS
@@ -238,12 +230,9 @@ def _backward(dev, case, dout_kind, e_layout, prefill, prefetch=1, seed=0, tampe
     d.de, d.scratch, d.scratch_floats = de.data_ptr(), scratch.data_ptr(), need
     if tamper is not None:
         tamper(d, arr)
-    L.dv3_debug_set(54, prefetch)
-    try:
+    with ops._lib.switches({"DV3_SW_SPK_PREFETCH": prefetch}):
         rc = L.dv3_speaker_bias_bwd_f32(ctypes.byref(d), arr, ops._stream())
         torch.cuda.synchronize()
-    finally:
-        L.dv3_debug_set(54, 1)
     res = dict(rc=rc, de=de[:B * E * T].cpu().numpy().reshape(B, E, T), layers=[], need=need,
                de_all=de.cpu().numpy(), scratch=scratch.cpu().numpy())
     assert _guard_ok(de, 0, B * E * T), "de: guard overwritten"

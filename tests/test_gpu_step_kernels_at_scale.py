@@ -229,9 +229,8 @@ def test_spec_loss_at_scale(dev, case):
     lens_d = lens.to(dev) if wm > 0 else None
     modes = (1, 0) if tiled and wbd > 0 else (1,)
     refs = {}
-    try:
-        for fast in modes:
-            _lib.lib().dv3_debug_set(57, fast)
+    for fast in modes:
+        with _lib.switches({"DV3_SW_LOSS_FAST_LOG": fast}):
             if fast not in refs:
                 refs[fast] = _spec_reference(yh32, y32, lens, r, wm, wbd, tv, fast_log=bool(fast) and tiled)
             out4, g = ops.spec_loss_with_grad(yh, y, lens_d, r, wm, wbd, t_valid=tv_t)
@@ -241,8 +240,6 @@ def test_spec_loss_at_scale(dev, case):
             # determinism: a second identical call returns the same bits (no float atomics)
             out4b, gb = ops.spec_loss_with_grad(yh, y, lens_d, r, wm, wbd, t_valid=tv_t)
             assert _bits_equal(out4, out4b) and _bits_equal(g, gb), name
-    finally:
-        _lib.lib().dv3_debug_set(57, 1)
 
 
 def test_spec_loss_autograd_gscale(dev):

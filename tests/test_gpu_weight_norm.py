@@ -441,12 +441,9 @@ def _bwd_run(dev, c, seed, both_gathers=True):
     outs = []
     for sw in ((1, 0) if both_gathers else (1,)):
         k = _bwd_setup(dev, c, seed)
-        L.dv3_debug_set(51, sw)
-        try:
+        with ops._lib.switches({"DV3_SW_WN_BWD_VEC4": sw}):
             ops._lib.call("dv3_weight_norm_bwd_f32", ctypes.byref(k["d"]), ops._stream())
             outs.append(_bwd_outputs(k))
-        finally:
-            L.dv3_debug_set(51, 1)
     if both_gathers:
         for name in outs[0]:
             assert np.array_equal(outs[0][name].view(np.int32), outs[1][name].view(np.int32)), name + ": gathers differ"
