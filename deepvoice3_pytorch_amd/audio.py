@@ -14,7 +14,9 @@ Conventions (AudioConfig.convention):
            fft_size - hop zeros of padding on both sides -- T frames <-> (T + 1) * hop - fft_size samples (1024 / 256:
            L = 256 k -> k + 3 frames).
            Restated from the package's published source in oracle/audio_oracle.py (lws_windows / lws_stft / lws_istft).
-           Phase reconstruction is Griffin-Lim on that framing (north_star), not lws's own run_lws iterations.
+           Phase reconstruction is Griffin-Lim on that framing (north_star), not lws's own run_lws iterations; like
+           run_lws it can start from a single-pass phase estimate instead of zero phase (spsi_phasor, csrc/spsi.hip;
+           AudioConfig(griffin_lim_init="spsi"), opt-in).
   "torch"  torch.stft / torch.istft conventions (periodic Hann, center=True reflect padding, L = hop * (T - 1)): rounds
            1-3's form, kept for A/B runs and for callers that pair it with torch-made features.
 
@@ -60,6 +62,17 @@ def check_momentum(momentum):
     return float(momentum)
 
 
+GRIFFIN_LIM_INITS = ("zero", "spsi")
+
+
+def check_init(init):
+    """-> the Griffin-Lim starting phase's name when it is one of GRIFFIN_LIM_INITS, else ValueError naming both"""
+    if not isinstance(init, str) or init not in GRIFFIN_LIM_INITS:
+        raise ValueError("griffin_lim_init=%r must be 'zero' (zero phase) or 'spsi' (single pass spectrogram inversion)"
+                         % (init,))
+    return init
+
+
 def resolve_window_scale(window_scale, hop, fft_size=N_FFT):
     """None / "hop_normalized" -> sqrt(2 hop / fft_size) (the default, see AudioConfig); else the positive number given"""
     if window_scale is None or window_scale == "hop_normalized":
@@ -74,8 +87,13 @@ class AudioConfig(object):
 
     def __init__(self, fft_size=1024, hop_size=256, sample_rate=22050, preemphasis=0.97,
                  min_level_db=-100, ref_level_db=20, power=1.4, griffin_lim_iters=60, convention="lws",
-                 window_scale="hop_normalized", griffin_lim_momentum=0.0):
-        """griffin_lim_momentum: the momentum of the fast Griffin-Lim algorithm (see griffin_lim), in [0, 1); 0.0 (default)
+                 window_scale="hop_normalized", griffin_lim_momentum=0.0, griffin_lim_init="zero"):
+        """griffin_lim_init: the phase Griffin-Lim starts from when the caller gives no init_phasor -- "zero" (default:
+        zero phase, the path every call has run) or "spsi" (spsi_phasor: a single-pass estimate from the spectral peaks;
+        AudioConfig(griffin_lim_init="spsi", griffin_lim_iters=10, griffin_lim_momentum=0.99) ends below the 60 plain
+        iterations from zero on speech-like magnitudes).  It is an option of the inverse, not a property
+        of stored features.
+        griffin_lim_momentum: the momentum of the fast Griffin-Lim algorithm (see griffin_lim), in [0, 1); 0.0 (default)
         is the plain alternation, 0.99 what librosa and torchaudio default to -- AudioConfig(griffin_lim_iters=30,
         griffin_lim_momentum=0.99) ends below the spectral convergence of the 60 plain iterations on speech-like magnitudes
         in half the projections ("Fast Griffin-Lim").
@@ -100,6 +118,7 @@ class AudioConfig(object):
         self.power, self.griffin_lim_iters = power, griffin_lim_iters
         self.convention = convention
         self.griffin_lim_momentum = check_momentum(griffin_lim_momentum)
+        self.griffin_lim_init = check_init(griffin_lim_init)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -354,6 +373,37 @@ def griffin_lim(mag, hop, n_iter, init_phasor=None, convention="torch", window_s
     return y
 
 
+def spsi_phasor(mag, hop, tlen=None, fft_size=N_FFT):
+    """Single Pass Spectrogram Inversion (Beauregard, Harish & Wyse 2015): mag (B, T, fft_size // 2 + 1) on the device ->
+    unit phasors (B, T, bins, 2), what istft and griffin_lim take as init_phasor -- a starting phase built from the
+    magnitudes alone in one pass over the frames.  Per frame every spectral peak's phase advances by hop x the peak's
+    instantaneous frequency (the vertex of the parabola through its three bins) and is given to the bins of its lobe;
+    include/dv3hip.h (dv3_spsi_phasor_f32) states every step, tests/spsi_ref.py restates it in numpy.  tlen (device
+    int32[B]): item b has only its first tlen[b] frames; the rows past them are (1, 0), and its own rows are those of
+    its B = 1 call bit for bit."""
+    fft_size = check_fft_size(fft_size)
+    mag = _c(_chk(mag, "mag"))
+    if mag.dim() != 3 or min(mag.shape) < 1:
+        raise ValueError("spsi_phasor: non-empty (B, T, bins) magnitudes expected, got %s" % (tuple(mag.shape),))
+    B, T, F = mag.shape
+    check_bins(F, fft_size, "spsi_phasor")
+    if isinstance(hop, bool) or int(hop) != hop or not 0 < hop <= fft_size:
+        raise ValueError("spsi_phasor: hop=%r must be an integer in [1, fft_size=%d]" % (hop, fft_size))
+    if tlen is not None and (tlen.dtype != torch.int32 or tuple(tlen.shape) != (B,) or tlen.device != mag.device):
+        raise ValueError("spsi_phasor: tlen must be int32[%d] on the device of mag" % B)
+    phasor = torch.empty((B, T, F, 2), dtype=torch.float32, device=mag.device)
+    _lib.call("dv3_spsi_phasor_f32", mag.data_ptr(), phasor.data_ptr(), B, T, int(hop),
+              _c(tlen).data_ptr() if tlen is not None else None, fft_size, _stream())
+    return phasor
+
+
+def _start_phasor(mag, cfg, init_phasor, tlen=None):
+    """the phasor Griffin-Lim starts from: the caller's, else cfg.griffin_lim_init's ("zero": None, no launch)"""
+    if init_phasor is None and cfg.griffin_lim_init == "spsi":
+        return spsi_phasor(mag, cfg.hop_size, tlen, cfg.fft_size)
+    return init_phasor
+
+
 def inv_preemphasis_(y, coef):
     """de-emphasis filter (audio.py:26-28) of (B, L) waveforms -> a new tensor"""
     out = torch.empty_like(y)
@@ -365,6 +415,8 @@ def inv_spectrogram_batch(linear_outputs, cfg=None, init_phasor=None, frame_leng
     """(B, T, fft_size // 2 + 1) device tensor (model linear_outputs) -> waveforms on the device: (B, (T+1)*hop -
     fft_size) on the lws framing (what the reference's processor.istft returns for T frames), (B, hop*(T-1)) on the torch
     framing.  A spectrogram of another width than cfg.fft_size // 2 + 1 is refused (ValueError).
+    init_phasor (B, T, bins, 2): the phase Griffin-Lim starts from; None: cfg.griffin_lim_init -- zero phase, or
+    spsi_phasor of the magnitudes made here (per item with frame_lengths).  An explicit init_phasor wins.
     frame_lengths (B host ints): a batch of utterances padded to T frames; item b is inverted from its own first
     frame_lengths[b] frames exactly as its B = 1 call on the trimmed spectrogram, its samples past its own length are
     zero.  -> (waveforms, sample lengths (int64[B], host)) in that case."""
@@ -375,8 +427,8 @@ def inv_spectrogram_batch(linear_outputs, cfg=None, init_phasor=None, frame_leng
     if frame_lengths is not None:
         return _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths)
     mag = magnitudes(linear_outputs, cfg)
-    y = griffin_lim(mag, cfg.hop_size, cfg.griffin_lim_iters, init_phasor, cfg.convention, cfg.window_scale,
-                    fft_size=cfg.fft_size, momentum=cfg.griffin_lim_momentum)
+    y = griffin_lim(mag, cfg.hop_size, cfg.griffin_lim_iters, _start_phasor(mag, cfg, init_phasor), cfg.convention,
+                    cfg.window_scale, fft_size=cfg.fft_size, momentum=cfg.griffin_lim_momentum)
     return inv_preemphasis_(y, cfg.preemphasis)
 
 
@@ -397,8 +449,8 @@ def _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths):
             B, tmin, T, fl.tolist()))
     tlen = fl.to(torch.int32).to(linear_outputs.device)
     mag = magnitudes(linear_outputs, cfg)
-    y = griffin_lim(mag, hop, cfg.griffin_lim_iters, init_phasor, cfg.convention, cfg.window_scale, tlen, n_fft,
-                    cfg.griffin_lim_momentum)
+    y = griffin_lim(mag, hop, cfg.griffin_lim_iters, _start_phasor(mag, cfg, init_phasor, tlen), cfg.convention,
+                    cfg.window_scale, tlen, n_fft, cfg.griffin_lim_momentum)
     lengths = torch.tensor([num_samples(int(n), hop, cfg.convention, n_fft) for n in fl], dtype=torch.int64)
     out = torch.empty_like(y)
     _lib.call("dv3_deemphasis_items_f32", y.data_ptr(), out.data_ptr(), B, y.shape[1],

@@ -1387,6 +1387,36 @@ int dv3_mel_to_linear_f32(const float* mel, const int32_t* tlen, const float* ba
                           int32_t n_bins, int32_t upsample, int32_t iters, float min_level_db, float ref_level_db,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Single Pass Spectrogram Inversion (Beauregard, Harish & Wyse 2015): a starting phase for Griffin-Lim built from the
+ * magnitudes alone, in one pass over the frames (audio.spsi_phasor, AudioConfig(griffin_lim_init="spsi")).
+ * The reference's inv_spectrogram (audio.py:37-43) hands the spectrogram to lws.run_lws, which estimates an initial phase
+ * before it iterates; the Griffin-Lim here started from zero phase.  An entry point added under ABI 50: no struct
+ * changed, so the version stays 50.
+ *
+ * mag [B][T][F] fp32, F = fft_size / 2 + 1; phasor [B][T][F][2] fp32 (re, im), 8-byte aligned: the layout the inverse
+ * entry points take as `phasor`; tlen device int32[B] (item b has tlen[b] frames, clamped into [0, T]) or NULL (all T).
+ * Per item an accumulator acc[F] in TURNS, zero before frame 0.  For frame t < tlen[b], m = mag[b][t], all in fp64:
+ *
+ *   peak(k)   1 <= k <= F - 2 and m[k] > m[k-1] and m[k] >= m[k+1]
+ *   d         0.5 (m[k-1] - m[k+1]) / (m[k-1] - 2 m[k] + m[k+1])             |d| <= 0.5 at a peak
+ *   new[k]    frac(acc[k] + ((hop k) mod fft_size) / fft_size + hop d / fft_size)            in [0, 1)
+ *   owner(j)  of a non-peak bin: owner(j+1) if m[j+1] > m[j], else owner(j-1) if m[j-1] > m[j], else none; a climb
+ *             that ends on a non-peak (a plateau, bin 0, bin F - 1) has none
+ *   new[j]    new[owner(j)], 0 without an owner;   acc <- new (the whole row)
+ *   phasor[b][t][k] = (-1)^k (cos, sin)(2 pi new[k])
+ *
+ * the sums in the order written, frac(x) = x - floor(x) with 1.0 taken to 0; new[k] is rounded to fp32 once, for the
+ * accurate sincospif.  The (-1)^k: every framing here references a frame's transform to its first sample with the window
+ * centred at fft_size / 2, so the bins of one component alternate in sign.  Frames t >= tlen[b] are written as (1, 0):
+ * every element of phasor is written, nothing outside it.  One workgroup per item (time is a recurrence), every loop
+ * bounded by F, no atomics: two calls give bit-equal output, and an item's rows depend on its own frames alone.
+ * Refused (DV3_EINVAL, nothing launched): fft_size other than 512, 1024, 2048; a null mag or phasor; a misaligned
+ * phasor; B outside [1, 65535]; T < 1; hop outside [1, fft_size].  tests/spsi_ref.py restates it in numpy.
+ * ------------------------------------------------------------------------------------ */
+int dv3_spsi_phasor_f32(const float* mag, float* phasor, int B, int T, int hop, const int32_t* tlen /* or NULL */,
+                        int fft_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
