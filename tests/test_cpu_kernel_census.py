@@ -17,12 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 VIA = {
-    "dv3_amp_to_db_norm_f32": ("audio.spectrogram_batch", "audio._db_norm"),
-    "dv3_preemphasis_f32": ("audio.spectrogram_batch", "audio._analysis_mag"),
-    "dv3_deemphasis_f32": ("audio.inv_preemphasis_",),
-    "dv3_deemphasis_items_f32": ("audio.inv_spectrogram_batch", "audio._inv_spectrogram_items"),
     "dv3_gather_spans_f32": ("audio.gather_spans",),
-    "dv3_gl_prepare_f32": ("audio.magnitudes",),
     "dv3_item_gain_f32": ("audio.item_gains",),
     "dv3_attn_softmax_f32": ("ops.attention_core", "ops.AttnCoreFn"),
     "dv3_attn_softmax_bwd_f32": ("ops.attention_core", "ops.AttnCoreFn"),
