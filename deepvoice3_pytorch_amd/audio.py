@@ -26,6 +26,9 @@ instead of a config take the size as `fft_size=` (default 1024).
 
 A mel spectrogram is vocoded through the same path: mel_to_linear inverts the filterbank per frame (csrc/mel_inverse.hip),
 inv_melspectrogram_batch / inv_melspectrogram put its result through inv_spectrogram_batch.
+
+Pitch: yin_items tracks F0 per frame of the packed waveforms features_items takes (csrc/pitch.hip), voiced() decides
+which frames to believe (PitchConfig); synthesis.waveform_distortion builds the F0 and voicing error of an evaluation on it.
 """
 import numpy as np
 import torch
@@ -712,6 +715,95 @@ def features_from_arrays(wavs, cfg=None, device="cuda:0", **kw):
     """features_items for a list of 1-D host waveforms: one pinned staging buffer, one host-to-device copy."""
     flat, lengths = pack_waveforms(wavs)
     return features_items(flat.to(device, non_blocking=True), lengths, cfg, **kw)
+
+
+# ---------------------------------------------------------------------------------------------
+# pitch tracking: YIN per frame of the packed waveforms (csrc/pitch.hip; include/dv3hip.h: dv3_yin_items_f32)
+# ---------------------------------------------------------------------------------------------
+class PitchConfig(object):
+    """Options of the pitch tracker (yin_items): fmin, fmax in Hz bound the search -- lags tau_min = max(2,
+    floor(sample_rate / fmax)) up to tau_max = floor(sample_rate / fmin) -- and fmin=None means max(60.0, 2 * sample_rate
+    / fft_size) of the audio config, the lowest pitch whose period fits the kernel's limit tau_max <= fft_size / 2;
+    threshold in (0, 1]: YIN's absolute threshold on the normalised difference (0.1 - 0.15 in the paper); silence_db:
+    frames whose mean square is at or below 10 ** (silence_db / 10) count as unvoiced (voiced()).  Refused by value."""
+
+    def __init__(self, fmin=None, fmax=500.0, threshold=0.15, silence_db=-60.0):
+        number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and \
+            np.isfinite(float(v))
+        if fmin is not None and not (number(fmin) and float(fmin) > 0.0):
+            raise ValueError("PitchConfig: fmin=%r must be None or a positive number of Hz" % (fmin,))
+        if not (number(fmax) and float(fmax) > 0.0) or (fmin is not None and not float(fmin) < float(fmax)):
+            raise ValueError("PitchConfig: fmax=%r must be a positive number of Hz above fmin=%r" % (fmax, fmin))
+        if not (number(threshold) and 0.0 < float(threshold) <= 1.0):
+            raise ValueError("PitchConfig: threshold=%r must lie in (0, 1]" % (threshold,))
+        if not number(silence_db):
+            raise ValueError("PitchConfig: silence_db=%r must be a finite number of dB" % (silence_db,))
+        self.fmin = None if fmin is None else float(fmin)
+        self.fmax, self.threshold, self.silence_db = float(fmax), float(threshold), float(silence_db)
+
+    def resolved_fmin(self, cfg=None):
+        cfg = cfg or AudioConfig()
+        return self.fmin if self.fmin is not None else max(60.0, 2.0 * float(cfg.sample_rate) / cfg.fft_size)
+
+    def lags(self, cfg=None):
+        """-> (tau_min, tau_max) at cfg's sample rate and frame size; ValueError for a pair the kernel refuses"""
+        cfg = cfg or AudioConfig()
+        sr, n_fft, fmin = float(cfg.sample_rate), int(cfg.fft_size), self.resolved_fmin(cfg)
+        tau_min, tau_max = max(2, int(sr // self.fmax)), int(sr // fmin)
+        if tau_max > n_fft // 2 or tau_min + 1 >= tau_max:
+            raise ValueError("PitchConfig: fmin=%g Hz at sample_rate=%g and fft_size=%d searches lags [%d, %d): the longest "
+                             "must not exceed fft_size / 2 = %d (fmin >= %g Hz) and the range must hold two lags (fmax=%g)"
+                             % (fmin, sr, n_fft, tau_min, tau_max, n_fft // 2, 2.0 * sr / n_fft, self.fmax))
+        return tau_min, tau_max
+
+
+def yin_items(wav_flat, lengths, cfg=None, pitch=None, want_lag=False):
+    """YIN pitch estimates for every frame of B utterances packed back to back in `wav_flat` (packed exactly as
+    features_items takes them: a 1-D float32 device tensor, item b the next lengths[b] samples) -> (f0 (sum T_b,) in Hz,
+    ap (sum T_b,), power (sum T_b,), frames int64[B] on the host), and with want_lag a fifth element, the chosen lag
+    (sum T_b,) int32: (f0, ap, power, frames, lag).  Row t of item b describes the samples of that item's
+    features_items row t (the lws framing, no pre-emphasis, no window).  ap is the normalised difference d' at the
+    chosen lag (small = periodic), power the frame's mean square; an estimate is given for every frame and voiced(ap,
+    power, pitch) decides which to believe.  include/dv3hip.h (dv3_yin_items_f32) states every step and the bounds."""
+    cfg = cfg or AudioConfig()
+    pitch = pitch if pitch is not None else PitchConfig()
+    if not isinstance(pitch, PitchConfig):
+        raise ValueError("yin_items: pitch must be a PitchConfig, got %r" % (pitch,))
+    _check_lws(cfg, "yin_items")
+    tau_min, tau_max = pitch.lags(cfg)
+    wav_flat = _c(_chk(wav_flat, "wav_flat"))
+    if wav_flat.dim() != 1:
+        raise ValueError("yin_items: wav_flat must be 1-D (the items back to back)")
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    B = lengths.size
+    if B == 0 or int(lengths.min()) < 1 or int(lengths.sum()) != wav_flat.numel():
+        raise ValueError("yin_items: %d samples do not split into items of lengths %s (each >= 1)"
+                         % (wav_flat.numel(), lengths.tolist()))
+    hop, n_fft = cfg.hop_size, cfg.fft_size
+    frames = np.array([lws_num_frames(int(n), hop, n_fft) for n in lengths], dtype=np.int64)
+    nf = int(frames.sum())
+    if nf >= 2 ** 31 or int(lengths.max()) >= 2 ** 31 - n_fft:
+        raise ValueError("yin_items: batch too large for one launch (%d frames)" % nf)
+    dev = wav_flat.device
+    soff = _sample_offsets(lengths, dev)
+    foff = torch.from_numpy(np.concatenate([[0], np.cumsum(frames)]).astype(np.int32)).to(dev, non_blocking=True)
+    f0, ap, power = (torch.empty(nf, dtype=torch.float32, device=dev) for _ in range(3))
+    lag = torch.empty(nf, dtype=torch.int32, device=dev) if want_lag else None
+    _lib.call("dv3_yin_items_f32", wav_flat.data_ptr(), soff.data_ptr(), foff.data_ptr(), B, nf, hop, n_fft, tau_min,
+              tau_max, pitch.threshold, float(cfg.sample_rate), f0.data_ptr(), ap.data_ptr(), power.data_ptr(),
+              lag.data_ptr() if lag is not None else None, _stream())
+    return (f0, ap, power, frames, lag) if want_lag else (f0, ap, power, frames)
+
+
+def f0_from_arrays(wavs, cfg=None, device="cuda:0", pitch=None):
+    """yin_items for a list of 1-D host waveforms: one pinned staging buffer, one host-to-device copy."""
+    flat, lengths = pack_waveforms(wavs)
+    return yin_items(flat.to(device, non_blocking=True), lengths, cfg, pitch)
+
+
+def voiced(ap, power, pitch):
+    """-> bool tensor: (ap < pitch.threshold) & (power > 10 ** (pitch.silence_db / 10)); any device, no kernel"""
+    return (ap < pitch.threshold) & (power > 10.0 ** (pitch.silence_db / 10.0))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -56,9 +56,20 @@ the rows of a set into its MCD (dB per aligned frame pair) and duration ratio.
     for ids, seqs, mels in held_out_batches:
         totals.add(synthesis.evaluate_synthesis(model, seqs, mels, downsample_step=4), ids)
     print(totals.result()["mcd"], totals.result()["duration_ratio"])
+
+The same at the waveform: evaluate_synthesis_audio synthesises with tts_batch under the AudioConfig
+being judged and compares each waveform with its recording -- both analysed alike, the distortion along the DTW path and,
+from audio.yin_items' pitch tracks along that same path, the F0 error in cents and the voicing disagreement
+(waveform_distortion, pitch_distortion); WaveEvalTotals folds a set.
+
+    totals = synthesis.WaveEvalTotals()
+    for ids, seqs, recordings in held_out_batches:
+        totals.add(synthesis.evaluate_synthesis_audio(model, seqs, recordings, audio_cfg=cfg), ids)
+    r = totals.result(); print(r["mcd"], r["f0_rmse_cents"], r["vuv_error"], r["duration_ratio"])
 """
 import collections
 
+import numpy as np
 import torch
 
 from . import audio
@@ -615,6 +626,166 @@ class SynthEvalTotals(object):
             it = {k: (v if k == "mcd_sum" else int(v)) for k, v in zip(SYNTH_EVAL_COLUMNS, vals)}
             it["mcd"] = it["mcd_sum"] / it["path_len"] if it["path_len"] > 0 else float("nan")
             it["duration_ratio"] = it["frames_synth"] / it["frames_target"] if it["frames_target"] > 0 else float("nan")
+            if self.ids is not None:
+                it["id"] = self.ids[b]
+            items.append(it)
+        out["items"] = items
+        return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# waveform-level evaluation: F0 and voicing error along the same DTW path as the distortion
+# ----------------------------------------------------------------------------------------------------------------------
+PITCH_EVAL_COLUMNS = ("f0_sqcents_sum", "n_both_voiced", "n_voicing_errors", "pitch_path_len", "n_voiced_a", "n_voiced_b")
+WAVE_EVAL_COLUMNS = SYNTH_EVAL_COLUMNS + PITCH_EVAL_COLUMNS
+
+
+def pitch_distortion(f0_a, voiced_a, f0_b, voiced_b, path):
+    """F0 and voicing disagreement of two padded batches of pitch tracks along given alignment paths.
+    f0_a (B, Ta), f0_b (B, Tb): Hz (audio.yin_items, padded); voiced_a, voiced_b: bool, same shapes (audio.voiced; False
+    in the padding); path (B, Ta + Tb - 1, 2) int32 as ops.dtw / mel_distortion(want_path=True) return it: rows (frame
+    of a, frame of b), rows of -1 past the path's end are skipped.  -> (B, 6) fp32, columns PITCH_EVAL_COLUMNS, over the
+    path's pairs: f0_sqcents_sum = sum of (1200 log2(f0_a / f0_b))^2 over the pairs voiced on both sides and
+    n_both_voiced their count (so sqrt of the ratio is the RMSE in cents); n_voicing_errors the pairs voiced on one side
+    only; pitch_path_len the pairs; n_voiced_a / n_voiced_b each side's voiced frames inside its length (the path's last
+    row + 1).  The squares are summed in float64 and rounded once.  Any device; no host synchronisation."""
+    if f0_a.dim() != 2 or f0_b.dim() != 2 or f0_a.shape != voiced_a.shape or f0_b.shape != voiced_b.shape or \
+            path.dim() != 3 or path.shape[0] != f0_a.shape[0] or f0_b.shape[0] != f0_a.shape[0] or path.shape[2] != 2:
+        raise ValueError("pitch_distortion: (B, Ta), (B, Tb) tracks with flags of the same shapes and a (B, P, 2) path, got "
+                         "%s / %s, %s / %s and %s" % (tuple(f0_a.shape), tuple(voiced_a.shape), tuple(f0_b.shape),
+                                                      tuple(voiced_b.shape), tuple(path.shape)))
+    (B, Ta), Tb = f0_a.shape, f0_b.shape[1]
+    pi, pj = path[..., 0].long(), path[..., 1].long()
+    on = (pi >= 0) & (pj >= 0)
+    ia, ib = pi.clamp(0, Ta - 1), pj.clamp(0, Tb - 1)
+    va, vb = voiced_a.bool().gather(1, ia) & on, voiced_b.bool().gather(1, ib) & on
+    both = va & vb
+    fa = torch.where(both, f0_a.gather(1, ia), torch.ones_like(ia, dtype=f0_a.dtype)).double()
+    fb = torch.where(both, f0_b.gather(1, ib), torch.ones_like(ib, dtype=f0_b.dtype)).double()
+    cents = 1200.0 * torch.log2(fa / fb)
+    la, lb = pi.max(dim=1).values + 1, pj.max(dim=1).values + 1
+    inside = lambda v, n: (v.bool() & (torch.arange(v.shape[1], device=v.device)[None, :] < n[:, None])).sum(1)
+    cols = [(cents * cents).sum(1), both.sum(1), (va != vb).sum(1), on.sum(1), inside(voiced_a, la), inside(voiced_b, lb)]
+    return torch.stack([c.double() for c in cols], dim=1).to(torch.float32)
+
+
+def _pack_any(wavs, device, what):
+    """a list of 1-D waveforms (host arrays, or tensors on any device) -> (flat float32 tensor on `device`, lengths)"""
+    if len(wavs) == 0:
+        raise ValueError("%s: no waveforms" % what)
+    if all(isinstance(w, torch.Tensor) for w in wavs):
+        lengths = np.array([int(w.numel()) for w in wavs], dtype=np.int64)
+        return torch.cat([w.detach().reshape(-1).to(device=device, dtype=torch.float32) for w in wavs]), lengths
+    flat, lengths = audio.pack_waveforms([np.asarray(w.detach().cpu() if isinstance(w, torch.Tensor) else w,
+                                                     dtype=np.float32).reshape(-1) for w in wavs])
+    return flat.to(device, non_blocking=True), lengths
+
+
+def _pad_rows(rows, frames, fill=0):
+    """packed rows (sum T_b, ...) -> (B, max T_b, ...), item b's rows first, `fill` behind them"""
+    out = rows.new_full((len(frames), int(max(frames))) + tuple(rows.shape[1:]), fill)
+    o = 0
+    for b, n in enumerate(int(n) for n in frames):
+        out[b, :n] = rows[o:o + n]
+        o += n
+    return out
+
+
+def waveform_distortion(wavs_a, wavs_b, cfg=None, pitch=None, order=13, device="cuda:0", num_mels=80, fmin=125, fmax=7600):
+    """Objective comparison of two lists of waveforms, utterance b of one against utterance b of the other (lists of 1-D
+    host arrays or tensors): both sides go through audio.features_items -- the same analysis for both --, the mel rows
+    through mel_distortion at the full frame rate, and audio.yin_items' pitch tracks through pitch_distortion along that
+    same DTW path.  -> (B, 13) fp32 on the device, columns WAVE_EVAL_COLUMNS (feed it to WaveEvalTotals); "synth" in the
+    column names is side a, "target" side b.  cfg: the AudioConfig of the analysis; pitch: an audio.PitchConfig; num_mels,
+    fmin, fmax: the mel filterbank.  An item of more than DV3_DTW_MAX_T frames is refused."""
+    from . import _lib
+    cfg = cfg or audio.AudioConfig()
+    pitch = pitch if pitch is not None else audio.PitchConfig()
+    if len(wavs_a) != len(wavs_b) or len(wavs_a) == 0:
+        raise ValueError("waveform_distortion: %d and %d waveforms" % (len(wavs_a), len(wavs_b)))
+    top = _lib.CONSTS["DV3_DTW_MAX_T"]
+    sides = []
+    for name, wavs in (("a", wavs_a), ("b", wavs_b)):
+        flat, lengths = _pack_any(wavs, device, "waveform_distortion")
+        if int(lengths.min()) < 1:
+            raise ValueError("waveform_distortion: side %s holds an empty waveform (lengths %s)" % (name, lengths.tolist()))
+        frames = [audio.lws_num_frames(int(n), cfg.hop_size, cfg.fft_size) for n in lengths]
+        if max(frames) > top:
+            b = int(np.argmax(frames))
+            raise ValueError("waveform_distortion: item %d of side %s has %d frames (%d samples at hop %d), at most %d "
+                             "(DV3_DTW_MAX_T)" % (b, name, frames[b], int(lengths[b]), cfg.hop_size, top))
+        with torch.no_grad():
+            _, mel, frames = audio.features_items(flat, lengths, cfg, num_mels, fmin, fmax)
+            f0, ap, power, _ = audio.yin_items(flat, lengths, cfg, pitch)
+            sides.append((_pad_rows(mel, frames), _pad_rows(f0, frames, 1.0),
+                          _pad_rows(audio.voiced(ap, power, pitch), frames, False), [int(n) for n in frames]))
+    (mel_a, f0_a, v_a, n_a), (mel_b, f0_b, v_b, n_b) = sides
+    with torch.no_grad():
+        table, path = mel_distortion(mel_a, n_a, mel_b, n_b, cfg, order, want_path=True)
+        return torch.cat([table, pitch_distortion(f0_a, v_a, f0_b, v_b, path)], dim=1)
+
+
+def evaluate_synthesis_audio(model, sequences, target_wavs, speaker_ids=None, audio_cfg=None, pitch=None, order=13):
+    """evaluate_synthesis at the waveform: synthesises `sequences` with tts_batch under audio_cfg -- so the vocoder options
+    under test (iterations, momentum, starting phase) apply -- and compares each waveform with its recording in
+    target_wavs (1-D arrays or tensors at audio_cfg.sample_rate) by waveform_distortion(synthesised, target).
+    -> the (B, 13) table, columns WAVE_EVAL_COLUMNS."""
+    B = len(sequences)
+    if B == 0 or len(target_wavs) != B:
+        raise ValueError("evaluate_synthesis_audio: %d sequences and %d targets" % (B, len(target_wavs)))
+    dev = next(model.parameters()).device
+    res = tts_batch(model, sequences, speaker_ids, audio_cfg)
+    return waveform_distortion([r[3] for r in res], list(target_wavs), audio_cfg, pitch, order, device=dev)
+
+
+class WaveEvalTotals(object):
+    """Accumulates waveform_distortion / evaluate_synthesis_audio tables over a held-out set, as SynthEvalTotals does for
+    the mel tables: add() keeps tensors and does not synchronise; result() makes one transfer and sums in float64 in the
+    order the rows were added, so every figure is the same however the set was cut into batches:
+        mcd             sum mcd_sum / sum path_len                        (dB per aligned frame pair)
+        duration_ratio  sum frames_synth / sum frames_target
+        f0_rmse_cents   sqrt(sum f0_sqcents_sum / sum n_both_voiced)      (NaN when no pair is voiced on both sides)
+        vuv_error       sum n_voicing_errors / sum pitch_path_len
+        n_items, and items: one dict per utterance in the order added -- its columns, the four figures of its own, and
+        "id" when ids were given."""
+
+    def __init__(self):
+        self._tables, self.ids = [], None
+
+    def add(self, table, ids=None):
+        table = table.detach()
+        if table.dim() != 2 or table.shape[1] != len(WAVE_EVAL_COLUMNS):
+            raise ValueError("WaveEvalTotals.add: a table of shape %s, expected (B, %d)" % (
+                tuple(table.shape), len(WAVE_EVAL_COLUMNS)))
+        n = int(table.shape[0])
+        if (ids is not None) != (self.ids is not None) and self._tables:
+            raise ValueError("WaveEvalTotals.add: ids for every batch or for none")
+        if ids is not None:
+            ids = list(ids)
+            if len(ids) != n:
+                raise ValueError("WaveEvalTotals.add: %d ids for %d items" % (len(ids), n))
+            self.ids = (self.ids or []) + ids
+        self._tables.append(table.to(torch.float32))
+
+    @staticmethod
+    def _figures(v):
+        ratio = lambda a, b: v[a] / v[b] if v[b] > 0 else float("nan")
+        return {"mcd": ratio("mcd_sum", "path_len"), "duration_ratio": ratio("frames_synth", "frames_target"),
+                "f0_rmse_cents": ratio("f0_sqcents_sum", "n_both_voiced") ** 0.5,
+                "vuv_error": ratio("n_voicing_errors", "pitch_path_len")}
+
+    def result(self):
+        if not self._tables:
+            raise ValueError("WaveEvalTotals.result: nothing was added")
+        rows = torch.cat([t.cpu() for t in self._tables]).double()
+        tot = {name: float(sum(rows[:, i].tolist())) for i, name in enumerate(WAVE_EVAL_COLUMNS)}   # the rows' own order
+        out = {"n_items": int(rows.shape[0])}
+        out.update(tot)
+        out.update(self._figures(tot))
+        items = []
+        for b, vals in enumerate(rows.tolist()):
+            it = {k: (v if k in ("mcd_sum", "f0_sqcents_sum") else int(v)) for k, v in zip(WAVE_EVAL_COLUMNS, vals)}
+            it.update(self._figures(it))
             if self.ids is not None:
                 it["id"] = self.ids[b]
             items.append(it)

@@ -1417,6 +1417,57 @@ int dv3_mel_to_linear_f32(const float* mel, const int32_t* tlen, const float* ba
 int dv3_spsi_phasor_f32(const float* mag, float* phasor, int B, int T, int hop, const int32_t* tlen /* or NULL */,
                         int fft_size, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Pitch tracking: YIN (de Cheveigne & Kawahara 2002, steps 2-5) per frame of B utterances packed back to back, for F0 and
+ * voicing error in evaluation.  One new entry point with plain arguments, no struct added or changed, so
+ * the version stays 50.
+ *
+ * x, soff (device int64[B+1]) and foff (device int32[B+1]) are those of dv3_analysis_items_f32_n, and so is the framing:
+ * row t of item b describes the samples of that item's linear / mel row t.  With N = n_fft, s[0 .. N) is item b's signal
+ * with N - hop zeros in front and zeros past its end, from sample t hop of that padded signal on; a frame never reads
+ * another item.  No pre-emphasis, no window, no gain.  With W = N - tau_max:
+ *
+ *   d(tau)   sum over j < W of (s[j] - s[j + tau])^2,  tau = 1 .. tau_max, fp32, from the differences themselves
+ *   c(tau)   sum over k = 1 .. tau of d(k)
+ *   d'(0) = 1;  d'(tau) = d(tau) tau / c(tau), evaluated (d(tau) * float(tau)) / c(tau);  d'(tau) = 1 where c(tau) = 0
+ *   lag      search tau ascending over [tau_min, tau_max): at the first tau with d'(tau) < threshold, descend while
+ *            d'(tau + 1) < d'(tau) (strictly) and tau + 1 < tau_max; that tau.  If there is none: the smallest tau of the
+ *            range that attains the minimum of d'.  An estimate is always given; voicing is the caller's decision from ap.
+ *   delta    with a, b, c = d'(lag - 1), d'(lag), d'(lag + 1) and D = (a - 2 b) + c:
+ *            clamp(0.5 (a - c) / D, -1, 1) if D > 0, else 0
+ *   f0 = sample_rate / (float(lag) + delta);   ap = b;   power = (1 / N) sum over j < N of s[j]^2
+ *
+ * An all-zero frame gives, exactly, lag = tau_min, f0 = sample_rate / tau_min, ap = 1, power = 0.
+ * f0, ap, power: [n_frames] fp32 each; lag: [n_frames] int32 or NULL (the other outputs are the same without it).
+ *
+ * Summation orders (fixed, no atomics: two calls give bit-equal output, and a row is a function of its own item alone --
+ * not of B, the order or the neighbours).  Every term is one rounded difference squared into an fmaf.
+ *   d(tau)   the j range is cut into S = max(1, 256 / (tau_max / 4 + 1)) (integer divisions) slices of
+ *            4 ceil(ceil(W / S) / 4) consecutive j; per slice a chain over ascending j; the slices added in ascending order
+ *   c(tau)   lane l of one wave owns the CH = ceil(tau_max / 64) | 1 consecutive lags from 1 + l CH: its total (a chain
+ *            from 0), an inclusive Hillis-Steele scan of the 64 totals, then from the total of the lanes before it a chain
+ *            over its own lags
+ *   power    thread i of 256 chains s[i], s[i + 256], ...; a wave's 64 sums meet in the xor butterfly (32, 16, .. 1);
+ *            the four waves are added in order; one multiplication by 1 / N (exact)
+ * Each is a summation tree of non-negative terms, so against exact arithmetic on the same fp32 samples the relative
+ * error of a sum is at most (number of terms + 2) 2^-24: a tree of n fmaf / additions errs by at most n 2^-24 of the sum
+ * of its terms whatever its order, with no second-order term (Jeannerod & Rump 2013), and the rounded difference
+ * squared is within 2 * 2^-24 of the exact one:
+ *   power    (N + 2) 2^-24
+ *   d(tau)   (W + 2) 2^-24;   c(tau)  (W + tau + 2) 2^-24  (tau - 1 additions of d on top of d's own error)
+ *   d'(tau)  (2 W + tau + 8) 2^-24  (d, c, the product with tau, the quotient; the second-order remainder of the
+ *            quotient is below 2 * 2^-24 at every size taken)
+ * These hold while no square underflows; tests/pitch_ref.py restates the definition in float64.
+ *
+ * Refused (DV3_EINVAL, dv3_last_error starts "yin_items:" and names the numbers, nothing launched): a null x, soff, foff,
+ * f0, ap or power; B < 1; n_frames < 1; n_fft other than 512, 1024, 2048; hop outside [1, n_fft]; tau_min < 2; tau_max above
+ * n_fft / 2 (at most DV3_YIN_MAX_LAG); tau_min + 1 >= tau_max; threshold outside (0, 1]; sample_rate not finite and positive.
+ * ------------------------------------------------------------------------------------ */
+#define DV3_YIN_MAX_LAG 1024
+int dv3_yin_items_f32(const float* x, const int64_t* soff, const int32_t* foff, int32_t B, int32_t n_frames, int32_t hop,
+                      int32_t n_fft, int32_t tau_min, int32_t tau_max, float threshold, float sample_rate,
+                      float* f0, float* ap, float* power, int32_t* lag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
