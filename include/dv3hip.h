@@ -511,6 +511,12 @@ int dv3_gate_bwd_f32(const dv3_gate_bwd_desc* d, void* stream);
  * 75,80,165,290,321).  Philox4x32-10, counter = (word index, site), key = seed.
  * bits[w] bit i == 1  <=>  element 32*w+i of the row is kept; p quantised to 1/65536.
  * dev_seed_offset: a device-resident step counter, so a replayed hipGraph draws new masks.
+ * In full (tests/philox_ref.py states it in integers, tests/test_gpu_dropout_masks.py holds every form to it bit for
+ * bit): word w is four calls q = 0..3 with the 128-bit counter (4w + q, site), each a 64-bit half, low word first, and
+ * the key s = (seed + *dev_seed_offset) mod 2^64; output e of call q gives two 16-bit uniforms, the low half (h = 0)
+ * first; bit 8q + 2e + h is set when the uniform is >= thr, thr = (uint32_t)(p * 65536.0f + 0.5f).  The drop rate is
+ * thr / 65536 (within 2^-17 of p); from p >= 1 - 2^-17 on thr is 65536 and NOTHING is kept, though every p < 1 is
+ * accepted.
  * ------------------------------------------------------------------------------------ */
 int dv3_dropout_bits(uint32_t* bits, int64_t n_words, float p, uint64_t seed,
                      uint64_t site, const uint64_t* dev_seed_offset /* added to seed; NULL = 0 */,
