@@ -19,8 +19,6 @@ sys.path.insert(0, ROOT)
 VIA = {
     "dv3_gather_spans_f32": ("audio.gather_spans",),
     "dv3_item_gain_f32": ("audio.item_gains",),
-    "dv3_attn_softmax_f32": ("ops.attention_core", "ops.AttnCoreFn"),
-    "dv3_attn_softmax_bwd_f32": ("ops.attention_core", "ops.AttnCoreFn"),
     "dv3_bce_loss_items_f32": ("ops.bce_loss_items",),
     "dv3_spec_loss_items_f32": ("ops.spec_loss_items",),
     "dv3_guided_attn_loss_items_f32": ("ops.guided_attention_loss_items",),
