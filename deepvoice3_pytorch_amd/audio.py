@@ -27,6 +27,10 @@ instead of a config take the size as `fft_size=` (default 1024).
 A mel spectrogram is vocoded through the same path: mel_to_linear inverts the filterbank per frame (csrc/mel_inverse.hip),
 inv_melspectrogram_batch / inv_melspectrogram put its result through inv_spectrogram_batch.
 
+Speaking rate and pitch: inv_spectrogram_batch(..., prosody=Prosody(rate, semitones)) puts the
+magnitudes through warp_magnitudes (csrc/prosody.hip) before the phase is built: the frames resampled in time, the
+harmonics moved along the frequency axis under the spectral envelope.  Off by default: without the keyword nothing runs.
+
 Pitch: yin_items tracks F0 per frame of the packed waveforms features_items takes (csrc/pitch.hip), voiced() decides
 which frames to believe (PitchConfig); synthesis.waveform_distortion builds the F0 and voicing error of an evaluation on it.
 """
@@ -407,6 +411,117 @@ def _start_phasor(mag, cfg, init_phasor, tlen=None):
     return init_phasor
 
 
+# ---------------------------------------------------------------------------------------------
+# speaking rate and pitch at vocoding: a warp of the magnitudes Griffin-Lim starts from (csrc/prosody.hip)
+# ---------------------------------------------------------------------------------------------
+def _numbers(v, what, lo, hi):
+    """a scalar or a sequence of numbers in [lo, hi] -> (is_scalar, [floats]); ValueError naming the offending value"""
+    scalar = not isinstance(v, (list, tuple, np.ndarray, torch.Tensor))
+    vals = [v] if scalar else (v.tolist() if isinstance(v, (np.ndarray, torch.Tensor)) else list(v))
+    if not scalar and (len(vals) == 0 or isinstance(vals[0], list)):
+        raise ValueError("Prosody: %s=%r must be a number or a flat, non-empty sequence of numbers" % (what, v))
+    out = []
+    for x in vals:
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not lo <= float(x) <= hi:
+            raise ValueError("Prosody: %s=%r must be a number in [%g, %g]" % (what, x, lo, hi))      # (nan fails the test)
+        out.append(float(x))
+    return scalar, out
+
+
+class Prosody(object):
+    """How an utterance is spoken, applied where it is vocoded (warp_magnitudes): rate, the speaking-rate
+    multiplier in [0.25, 4] (above 1 is faster: T frames become about T / rate); semitones in [-24, 24], the pitch shift
+    (every frequency times 2 ** (semitones / 12)) -- each a scalar for every item or one value per item;
+    preserve_envelope (True): shift the harmonics under the spectral envelope so that formants stay where they are, else
+    the whole frame moves along the frequency axis; envelope_hz (400): the half width of the triangular smoother that
+    defines the envelope, in Hz -- half_width(cfg) bins, which must lie in [1, DV3_PROSODY_MAX_HALF_WIDTH].
+    Refused by value (ValueError naming it)."""
+
+    def __init__(self, rate=1.0, semitones=0.0, preserve_envelope=True, envelope_hz=400.0):
+        self._scalar_rate, self.rate = _numbers(rate, "rate", 0.25, 4.0)
+        self._scalar_semitones, self.semitones = _numbers(semitones, "semitones", -24.0, 24.0)
+        if not self._scalar_rate and not self._scalar_semitones and len(self.rate) != len(self.semitones):
+            raise ValueError("Prosody: %d rates and %d semitones" % (len(self.rate), len(self.semitones)))
+        if isinstance(envelope_hz, bool) or not isinstance(envelope_hz, (int, float, np.integer, np.floating)) or \
+                not 0.0 < float(envelope_hz) < float("inf"):
+            raise ValueError("Prosody: envelope_hz=%r must be a positive number of Hz" % (envelope_hz,))
+        self.preserve_envelope, self.envelope_hz = bool(preserve_envelope), float(envelope_hz)
+
+    def half_width(self, cfg=None):
+        """W = round(envelope_hz * fft_size / sample_rate) (halves up) bins; ValueError outside [1, 64]"""
+        cfg = cfg or AudioConfig()
+        W = int(np.floor(self.envelope_hz * cfg.fft_size / float(cfg.sample_rate) + 0.5))
+        top = _lib.CONSTS["DV3_PROSODY_MAX_HALF_WIDTH"]
+        if not 1 <= W <= top:
+            raise ValueError("Prosody: envelope_hz=%r is %d bins at fft_size=%d and sample_rate=%r: outside [1, %d]"
+                             % (self.envelope_hz, W, cfg.fft_size, cfg.sample_rate, top))
+        return W
+
+    def per_item(self, B):
+        """-> (rates, semitones), B floats each; a per-item list of another length is refused"""
+        out = []
+        for scalar, vals, what in ((self._scalar_rate, self.rate, "rate"),
+                                   (self._scalar_semitones, self.semitones, "semitones")):
+            if not scalar and len(vals) != B:
+                raise ValueError("Prosody: %d values of %s=%r for %d items" % (len(vals), what, vals, B))
+            out.append(vals * B if scalar else list(vals))
+        return out[0], out[1]
+
+    def neutral(self):
+        """every rate is 1 and every shift 0: nothing to do"""
+        return all(r == 1.0 for r in self.rate) and all(s == 0.0 for s in self.semitones)
+
+
+def _active(prosody, what):
+    """the `prosody=` keyword -> the Prosody to apply, or None when there is none or it changes nothing"""
+    if prosody is None:
+        return None
+    if not isinstance(prosody, Prosody):
+        raise ValueError("%s: prosody must be an audio.Prosody, got %r" % (what, prosody))
+    return None if prosody.neutral() else prosody
+
+
+def warped_frames(T, rate, cfg=None):
+    """T' = max(min_frames, floor((T - 1) / rate + 0.5) + 1): the frames an item of T frames has at speaking rate `rate`
+    (host float64, like every other length here)"""
+    cfg = cfg or AudioConfig()
+    return max(min_frames(cfg.hop_size, cfg.convention, cfg.fft_size),
+               int(np.floor((int(T) - 1) / float(rate) + 0.5)) + 1)
+
+
+def warp_magnitudes(mag, frame_lengths, cfg, prosody):
+    """Change rate and pitch of magnitudes on their way into Griffin-Lim: mag (B, T, fft_size // 2 + 1) on the device, what
+    magnitudes() made; frame_lengths: B host ints (item b has only its first frame_lengths[b] frames; the rest is never
+    read) or None (all T); prosody: a Prosody.  -> (out (B, max T'_b, bins), T' int64[B] on the host), T'_b =
+    warped_frames(T_b, rate_b, cfg); item b's rows past T'_b are zero.  Output frame j of item b is the item's source at
+    frame j * rate_b (linear interpolation, the last frame held), read along the frequency axis at k / ratio_b -- under
+    the envelope when prosody.preserve_envelope; include/dv3hip.h (dv3_prosody_warp_f32) states every step,
+    tests/prosody_ref.py restates it.  An item at rate 1 and 0 semitones comes back bit for bit, and every item's rows
+    depend on that item alone.  One launch, whatever the settings."""
+    cfg = cfg or AudioConfig()
+    if not isinstance(prosody, Prosody):
+        raise ValueError("warp_magnitudes: prosody must be an audio.Prosody, got %r" % (prosody,))
+    mag = _c(_chk(mag, "mag"))
+    if mag.dim() != 3 or min(mag.shape) < 1:
+        raise ValueError("warp_magnitudes: non-empty (B, T, bins) magnitudes expected, got %s" % (tuple(mag.shape),))
+    B, T, F = mag.shape
+    check_bins(F, cfg.fft_size, "warp_magnitudes")
+    fl = torch.full((B,), T, dtype=torch.int64) if frame_lengths is None else \
+        _host_lengths(frame_lengths, B, 1, T, "warp_magnitudes")
+    rates, semis = prosody.per_item(B)
+    W = prosody.half_width(cfg)
+    out_len = torch.tensor([warped_frames(int(n), r, cfg) for n, r in zip(fl, rates)], dtype=torch.int64)
+    T_out = int(out_len.max())
+    dev = mag.device
+    rate = torch.tensor(rates, dtype=torch.float64).to(dev)
+    ratio = torch.tensor([2.0 ** (s / 12.0) for s in semis], dtype=torch.float64).to(dev)
+    tlen_in, tlen_out = fl.to(torch.int32).to(dev), out_len.to(torch.int32).to(dev)      # (named: both live through the call)
+    out = torch.empty((B, T_out, F), dtype=torch.float32, device=dev)
+    _lib.call("dv3_prosody_warp_f32", mag.data_ptr(), out.data_ptr(), B, T, T_out, F, tlen_in.data_ptr(),
+              tlen_out.data_ptr(), rate.data_ptr(), ratio.data_ptr(), W, int(prosody.preserve_envelope), _stream())
+    return out, out_len
+
+
 def inv_preemphasis_(y, coef):
     """de-emphasis filter (audio.py:26-28) of (B, L) waveforms -> a new tensor"""
     out = torch.empty_like(y)
@@ -414,7 +529,7 @@ def inv_preemphasis_(y, coef):
     return out
 
 
-def inv_spectrogram_batch(linear_outputs, cfg=None, init_phasor=None, frame_lengths=None):
+def inv_spectrogram_batch(linear_outputs, cfg=None, init_phasor=None, frame_lengths=None, prosody=None):
     """(B, T, fft_size // 2 + 1) device tensor (model linear_outputs) -> waveforms on the device: (B, (T+1)*hop -
     fft_size) on the lws framing (what the reference's processor.istft returns for T frames), (B, hop*(T-1)) on the torch
     framing.  A spectrogram of another width than cfg.fft_size // 2 + 1 is refused (ValueError).
@@ -422,11 +537,24 @@ def inv_spectrogram_batch(linear_outputs, cfg=None, init_phasor=None, frame_leng
     spsi_phasor of the magnitudes made here (per item with frame_lengths).  An explicit init_phasor wins.
     frame_lengths (B host ints): a batch of utterances padded to T frames; item b is inverted from its own first
     frame_lengths[b] frames exactly as its B = 1 call on the trimmed spectrogram, its samples past its own length are
-    zero.  -> (waveforms, sample lengths (int64[B], host)) in that case."""
+    zero.  -> (waveforms, sample lengths (int64[B], host)) in that case.
+    prosody (an audio.Prosody): speaking rate and pitch -- the magnitudes go through warp_magnitudes before the phase
+    is built, item b is inverted from its T'_b = warped_frames(T_b, rate_b) frames (T_b = T without frame_lengths) and the
+    return is (waveforms, sample lengths) either way, the lengths num_samples(T'_b).  An init_phasor cannot be given
+    with it (it would describe the frames before the warp).  None, or one whose every rate is 1 and shift 0: nothing is
+    launched for it and the call is the one without the keyword."""
     cfg = cfg or AudioConfig()
     if linear_outputs.dim() != 3:
         raise ValueError("inv_spectrogram_batch: a (B, T, bins) spectrogram expected, got %s" % (tuple(linear_outputs.shape),))
     check_bins(linear_outputs.shape[-1], cfg.fft_size, "inv_spectrogram_batch")
+    prosody = _active(prosody, "inv_spectrogram_batch")
+    if prosody is not None:
+        if init_phasor is not None:
+            raise ValueError("inv_spectrogram_batch: init_phasor describes the frames before the warp; it cannot be "
+                             "combined with prosody")
+        if frame_lengths is None:
+            frame_lengths = [linear_outputs.shape[1]] * linear_outputs.shape[0]
+        return _inv_spectrogram_items(linear_outputs, cfg, None, frame_lengths, prosody)
     if frame_lengths is not None:
         return _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths)
     mag = magnitudes(linear_outputs, cfg)
@@ -442,7 +570,7 @@ def inv_spectrogram(spectrogram, cfg=None, device="cuda:0"):
     return y[0].cpu().numpy()
 
 
-def _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths):
+def _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths, prosody=None):
     B, T = linear_outputs.shape[0], linear_outputs.shape[1]
     fl = torch.as_tensor(frame_lengths).reshape(-1).to(torch.int64).cpu()
     hop, n_fft = cfg.hop_size, cfg.fft_size
@@ -450,8 +578,10 @@ def _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths):
     if fl.numel() != B or int(fl.min()) < tmin or int(fl.max()) > T:
         raise ValueError("inv_spectrogram_batch: %d frame lengths in [%d, %d] expected, got %s" % (
             B, tmin, T, fl.tolist()))
-    tlen = fl.to(torch.int32).to(linear_outputs.device)
     mag = magnitudes(linear_outputs, cfg)
+    if prosody is not None:            # from here on the items have their warped frame counts
+        mag, fl = warp_magnitudes(mag, fl, cfg, prosody)
+    tlen = fl.to(torch.int32).to(linear_outputs.device)
     y = griffin_lim(mag, hop, cfg.griffin_lim_iters, _start_phasor(mag, cfg, init_phasor, tlen), cfg.convention,
                     cfg.window_scale, tlen, n_fft, cfg.griffin_lim_momentum)
     lengths = torch.tensor([num_samples(int(n), hop, cfg.convention, n_fft) for n in fl], dtype=torch.int64)
@@ -621,7 +751,8 @@ def mel_to_linear(mel, cfg=None, frame_lengths=None, upsample=1, options=None):
 def inv_melspectrogram_batch(mel, cfg=None, frame_lengths=None, upsample=1, options=None, init_phasor=None):
     """(B, T, num_mels) normalised mel on the device -> waveforms: exactly inv_spectrogram_batch(mel_to_linear(mel, cfg,
     frame_lengths, upsample, options), cfg, init_phasor, frame_lengths * upsample), with its return forms (the waveforms;
-    with frame_lengths, in mel frames: (waveforms, sample lengths))."""
+    with frame_lengths, in mel frames: (waveforms, sample lengths)).  For speaking rate and pitch write that composition
+    out and give inv_spectrogram_batch the prosody= keyword (synthesis.tts_batch(from_mel=True, rate=...) does)."""
     cfg = cfg or AudioConfig()
     lin = mel_to_linear(mel, cfg, frame_lengths, upsample, options)
     if frame_lengths is None:

@@ -47,6 +47,13 @@ floor.
 
     for mel, linear, alignment, wav in synthesis.tts_batch(model, seqs, from_mel=True): ...
 
+Speaking rate and pitch, opt-in on all three entry points (per ticket on RollingSynthesizer.submit):
+rate= (above 1: faster) and semitones=, a scalar or one value per utterance, and prosody= (an audio.Prosody: the envelope
+settings) are applied where the utterance is vocoded -- audio.warp_magnitudes between the magnitudes and Griffin-Lim --,
+so `wav` changes and mel, linear and alignment stay what the model made; token spans follow the new time axis.
+
+    for mel, linear, alignment, wav in synthesis.tts_batch(model, seqs, rate=[0.8, 1.0], semitones=[0, 3]): ...
+
 Free-running evaluation: how far is the model's own synthesis of a held-out sentence from its
 recording?  evaluate_synthesis decodes (no Griffin-Lim), aligns each utterance with its target by dynamic time warping
 (ops.dtw) under the mel-cepstral distance (audio.mel_cepstra) and returns one row per utterance; SynthEvalTotals folds
@@ -196,8 +203,63 @@ def mel_options(from_mel):
     return from_mel
 
 
+def utterance_prosody(rate, semitones, prosody, B, what):
+    """the `rate=`, `semitones=`, `prosody=` keywords of the entry points -> None (nothing asked for, or nothing that
+    changes anything), or an audio.Prosody with what applies to the B utterances: rate and semitones (a scalar or one
+    value per utterance) where given, else the prosody's own; the envelope settings are the prosody's (default: an
+    audio.Prosody()).  Values and lengths are refused as audio.Prosody refuses them."""
+    if rate is None and semitones is None and prosody is None:
+        return None
+    if prosody is not None and not isinstance(prosody, audio.Prosody):
+        raise ValueError("%s: prosody must be an audio.Prosody, got %r" % (what, prosody))
+    base = prosody if prosody is not None else audio.Prosody()
+    own = lambda scalar, vals: vals[0] if scalar else vals
+    p = audio.Prosody(own(base._scalar_rate, base.rate) if rate is None else rate,
+                      own(base._scalar_semitones, base.semitones) if semitones is None else semitones,
+                      base.preserve_envelope, base.envelope_hz)
+    p.per_item(B)
+    return None if p.neutral() else p
+
+
+def _spans_at_rate(span, rate):
+    """a timing dict on the time axis of an utterance spoken at `rate`: start and end in seconds divided by it (the
+    summary's columns are counts of steps and keys and a score, none in seconds: they stay)"""
+    if rate == 1.0:
+        return span
+    out = dict(span)
+    out["start"], out["end"] = span["start"] / rate, span["end"] / rate
+    return out
+
+
+def _vocode(linear, audio_cfg, frame_lengths, settings):
+    """one retiring group's Griffin-Lim: settings holds per item None or that ticket's scalar audio.Prosody.  Items whose
+    envelope settings agree (and those without any) share ONE inv_spectrogram_batch call with per-item rates and shifts;
+    a group that mixes envelope settings is vocoded in one call per setting -- every item's waveform depends on the
+    item alone, so the split changes no result.  -> (waveforms (G, L), sample lengths int64[G])"""
+    keys = sorted({(p.preserve_envelope, p.envelope_hz) for p in settings if p is not None})
+    if not keys:
+        return audio.inv_spectrogram_batch(linear, audio_cfg, frame_lengths=frame_lengths)
+    fl = torch.as_tensor(frame_lengths).reshape(-1).to(torch.int64)
+    parts = []
+    for n, key in enumerate(keys):
+        idx = [g for g, p in enumerate(settings)
+               if (p is None and n == 0) or (p is not None and (p.preserve_envelope, p.envelope_hz) == key)]
+        pros = audio.Prosody([1.0 if settings[g] is None else settings[g].rate[0] for g in idx],
+                             [0.0 if settings[g] is None else settings[g].semitones[0] for g in idx], key[0], key[1])
+        sub = linear if len(idx) == len(settings) else linear[torch.tensor(idx, device=linear.device)]
+        parts.append((idx,) + tuple(audio.inv_spectrogram_batch(sub, audio_cfg, frame_lengths=fl[idx], prosody=pros)))
+    if len(parts) == 1:
+        return parts[0][1], parts[0][2]
+    wavs = linear.new_zeros((len(settings), max(w.size(1) for _, w, _ in parts)))
+    samples = torch.zeros(len(settings), dtype=torch.int64)
+    for idx, w, s in parts:
+        wavs[torch.tensor(idx, device=linear.device), :w.size(1)] = w
+        samples[idx] = s
+    return wavs, samples
+
+
 def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=False, stall_limit=None, timings=False,
-              timing_advance=1, from_mel=False):
+              timing_advance=1, rate=None, semitones=None, prosody=None, from_mel=False):
     """sequences: a list of int id sequences (one per utterance); speaker_ids: None or one id per utterance.
     -> a list of (mel (T_b, mel_dim), linear (T_b * upsampling, linear_dim), alignment (steps_b, Tt_b), wav (L_b,)),
     device tensors, each trimmed to its own utterance.  diagnostics: a fifth element, the utterance's alignment
@@ -208,9 +270,15 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=Fa
     from_mel (False; True or an audio.MelInverse): vocode the decoder's MEL instead of the post-net's output -- the
     post-net is not run (a model trained without it has a random one), `linear` is audio.mel_to_linear of the
     utterance's own mel frames at the post-net's upsampling (postnet_upsampling; audio_cfg's bins, not the model's
-    linear_dim) and `wav` its inversion.  A preview of the seq2seq half, not the post-net's quality."""
+    linear_dim) and `wav` its inversion.  A preview of the seq2seq half, not the post-net's quality.
+    rate, semitones (a scalar or one value per utterance), prosody (an audio.Prosody: the envelope settings, and the
+    rates and shifts where the two keywords do not give them): how each utterance is spoken -- applied
+    to the magnitudes on their way into Griffin-Lim (audio.warp_magnitudes), so only `wav` changes, to
+    audio.num_samples(audio.warped_frames(frames, rate)) samples; mel, linear and alignment stay what the model made,
+    and with timings every token's start and end are divided by the utterance's rate."""
     if len(sequences) == 0:
         return []
+    pros = utterance_prosody(rate, semitones, prosody, len(sequences), "tts_batch")
     mel_opt = mel_options(from_mel)
     if mel_opt is None:
         check_linear_dim(model, audio_cfg, "tts_batch")
@@ -235,7 +303,7 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=Fa
     with torch.no_grad():
         if mel_opt is not None:
             linear = audio.mel_to_linear(mel, audio_cfg, frames, up, mel_opt)
-        wavs, samples = audio.inv_spectrogram_batch(linear, audio_cfg, frame_lengths=frames * up)
+        wavs, samples = audio.inv_spectrogram_batch(linear, audio_cfg, frame_lengths=frames * up, prosody=pros)
     stats = None
     if diagnostics:
         steps = [int(n) // steps_per_frame for n in frames]
@@ -244,6 +312,8 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=Fa
     if timings:
         spans = token_timings(alignments, [int(n) // steps_per_frame for n in frames], lengths,
                               seconds_per_step(audio_cfg, steps_per_frame, up), "btk", timing_advance)
+        if pros is not None:
+            spans = [_spans_at_rate(s, r) for s, r in zip(spans, pros.per_item(B)[0])]
     out = []
     for b in range(B):
         n = int(frames[b])
@@ -302,10 +372,18 @@ class RollingSynthesizer(object):
         self._req = {}
         self._next = 0
 
-    def submit(self, ids, speaker_id=None, max_decoder_steps=None):
+    def submit(self, ids, speaker_id=None, max_decoder_steps=None, rate=None, semitones=None, prosody=None):
         """queue one utterance (a sequence of int ids) -> its ticket (0, 1, 2, ... in submission order).
-        max_decoder_steps: this request's own cap (default and upper limit: the decoder's)"""
+        max_decoder_steps: this request's own cap (default and upper limit: the decoder's); rate, semitones (scalars),
+        prosody (an audio.Prosody): how THIS utterance is spoken, as tts_batch takes them -- retirement gathers the
+        group's values into its one Griffin-Lim call"""
         ids = [int(i) for i in ids]
+        for name, v in (("rate", rate), ("semitones", semitones)):
+            if v is not None and isinstance(v, (list, tuple, np.ndarray, torch.Tensor)):
+                raise ValueError("RollingSynthesizer.submit: %s=%r must be one number: a ticket is one utterance" % (name, v))
+        pros = utterance_prosody(rate, semitones, prosody, 1, "RollingSynthesizer.submit")
+        if pros is not None:
+            pros.half_width(self.audio_cfg)          # refused here, not when the utterance retires
         if len(ids) < 1:
             raise ValueError("RollingSynthesizer.submit: empty sequence")
         if len(ids) > self.max_text_len:
@@ -321,7 +399,7 @@ class RollingSynthesizer(object):
                 "missing" if multi else "given", getattr(self.model, "n_speakers", 1)))
         ticket = self._next
         self._next += 1
-        self._req[ticket] = (ids, speaker_id, cap)
+        self._req[ticket] = (ids, speaker_id, cap, pros)
         self.schedule.submit(ticket)
         return ticket
 
@@ -388,13 +466,15 @@ class RollingSynthesizer(object):
                 finally:
                     ops.valid = prev
                 up = linear.size(1) // mel.size(1)
-            wavs, samples = audio.inv_spectrogram_batch(linear, self.audio_cfg, frame_lengths=frames * up)
+            settings = [self._req[t][3] for t in tickets]
+            wavs, samples = _vocode(linear, self.audio_cfg, frames * up, settings)
         stats = None
         if self.diagnostics:
             stats = _diagnose(alignments, steps, lengths, [self._req[t][2] for t in tickets])
         spans = None
         if self.timings:            # a released slot's stacked rows stay as they are until it is admitted again
             spans = self._timings(retired, lengths, alignments, seconds_per_step(self.audio_cfg, r, up))
+            spans = [s if p is None else _spans_at_rate(s, p.rate[0]) for s, p in zip(spans, settings)]
         out = []
         for b, t in enumerate(tickets):
             n = int(frames[b])
@@ -464,7 +544,7 @@ class RollingSynthesizer(object):
 
 def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, audio_cfg=None, chunk=8,
                max_decoder_steps=None, diagnostics=False, stall_limit=None, timings=False, timing_advance=1,
-               from_mel=False):
+               rate=None, semitones=None, prosody=None, from_mel=False):
     """Rolling-admission counterpart of tts_batch, as a generator: sequences (any iterable of id lists; speaker_ids an
     iterable alongside, or None; max_decoder_steps None, one cap, or an iterable of per-utterance caps) are submitted
     in order as slots free -- at most `slots` are queued ahead -- and every utterance is yielded when it retires, in
@@ -472,7 +552,8 @@ def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, 
     max_text_len None: the longest sequence (the iterable is then read up front).  diagnostics, stall_limit: as
     RollingSynthesizer takes them (a last element per result; the end-of-text stop); timings, timing_advance: as there
     (one more element per result, the utterance's timing dict); from_mel: as tts_batch takes it (the mel is vocoded, the
-    post-net is not run)."""
+    post-net is not run); rate, semitones: None, one number, or an iterable of per-utterance values alongside
+    `sequences`; prosody: an audio.Prosody carrying the envelope settings (RollingSynthesizer.submit takes all three)."""
     if max_text_len is None:
         sequences = [list(s) for s in sequences]
         if not sequences:
@@ -486,6 +567,9 @@ def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, 
     caps = None
     if max_decoder_steps is not None and not isinstance(max_decoder_steps, int):
         caps = iter(max_decoder_steps)
+    number = lambda v: v is None or isinstance(v, (int, float, np.integer, np.floating))
+    rates = None if number(rate) else iter(rate)
+    shifts = None if number(semitones) else iter(semitones)
     more = True
     while more or rs.pending():
         while more and len(rs.schedule.queue) < slots:
@@ -495,7 +579,9 @@ def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, 
                 more = False
                 break
             rs.submit(ids, next(spk) if spk is not None else None,
-                      next(caps) if caps is not None else max_decoder_steps)
+                      next(caps) if caps is not None else max_decoder_steps,
+                      rate=float(next(rates)) if rates is not None else rate,
+                      semitones=float(next(shifts)) if shifts is not None else semitones, prosody=prosody)
         for res in rs.poll():
             yield res
 

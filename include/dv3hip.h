@@ -1474,6 +1474,49 @@ int dv3_yin_items_f32(const float* x, const int64_t* soff, const int32_t* foff, 
                       int32_t n_fft, int32_t tau_min, int32_t tau_max, float threshold, float sample_rate,
                       float* f0, float* ap, float* power, int32_t* lag, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Speaking rate and pitch at vocoding: a time-and-frequency warp of the magnitudes Griffin-Lim starts from, with the
+ * spectral envelope kept in place so that formants do not move with the pitch (audio.warp_magnitudes, audio.Prosody;
+ * DESIGN.md 3.6i).  The reference has no counterpart: its model gives one rate and one pitch per text.  One new entry
+ * point with plain arguments, no struct added or changed, so the version stays 50.
+ *
+ * mag [B][T_in][bins] fp32: the magnitudes dv3_gl_prepare_f32 makes (of the model's linear output, or of
+ * dv3_mel_to_linear_f32's); out [B][T_out][bins] fp32, another buffer than mag.  tlen_in device int32[B] or NULL (all
+ * T_in), tlen_out device int32[B], both clamped into [0, T_in] / [0, T_out]; rate, ratio device double[B]: rate[b] source
+ * frames per output frame (above 1: faster), ratio[b] the factor every frequency is multiplied by (2^(semitones / 12)).
+ * With n = tlen_in[b], item b's output frame j < tlen_out[b] (n >= 1) is, in fp32 unless said otherwise, every product
+ * and sum rounded once and none contracted:
+ *
+ *   lerp(a, x, y)  x itself if a == 0, else (1 - a) x + a y
+ *   time      u = min(j rate[b], n - 1) in fp64 (a u that is not >= 0 counts as 0);  i0 = floor(u);  a = u - i0 in fp64,
+ *             rounded once to fp32;  i1 = min(i0 + 1, n - 1);  m[k] = lerp(a, mag[b][i0][k], mag[b][i1][k]).
+ *             Frames at or beyond n are never read.
+ *   ratio[b] == 1 (or no positive number):  out[k] = m[k] -- with a == 0 a copy, bit for bit.
+ *   otherwise s = k / ratio[b] in fp64.  Where s <= bins - 1:  s0 = floor(s), fa = s - s0 rounded once to fp32,
+ *             s1 = min(s0 + 1, bins - 1), and read(v)[k] = lerp(fa, v[s0], v[s1]).
+ *   plain (preserve_envelope == 0):   out[k] = read(m)[k] where s <= bins - 1, else m[bins - 1]
+ *   envelope-preserving, W = env_half_width:
+ *             l[k] = logf(max(m[k], 1e-10f))
+ *             E[k] = (sum over kk = max(k - W, 0) .. min(k + W, bins - 1), ascending, of (W + 1 - |kk - k|) l[kk], each
+ *                    term one fmaf into the running sum from 0) / (the sum of those integer weights, exact)
+ *             X[k] = l[k] - E[k];   X'[k] = read(X)[k] where s <= bins - 1, else 0;   out[k] = expf(E[k] + X'[k])
+ *             (the triangular moving average truncated at the edges and renormalised by the weights that remain; logf and
+ *             expf are the accurate ones, not the hardware approximations)
+ *
+ * Rows j >= tlen_out[b] (and every row of an item with n < 1) are written as zeros: every element of out is written,
+ * nothing outside it.  One workgroup per output frame, fixed summation order, no atomics: two calls give bit-equal
+ * output, and an item's rows depend on its own frames alone -- not on B, its neighbours or the padding.  The caller
+ * chooses tlen_out (audio.warp_magnitudes: floor((n - 1) / rate + 0.5) + 1, at least the inverse's shortest signal).
+ * Refused (DV3_EINVAL, dv3_last_error starts "prosody_warp:", nothing launched): a null mag, out, tlen_out, rate or ratio;
+ * out == mag; misaligned pointers; B outside [1, 65535]; T_in < 1; T_out < 1; bins outside [1, 1025]; preserve_envelope
+ * other than 0 or 1; env_half_width outside [1, DV3_PROSODY_MAX_HALF_WIDTH] (in either mode).
+ * tests/prosody_ref.py restates the definition in float64.
+ * ------------------------------------------------------------------------------------ */
+#define DV3_PROSODY_MAX_HALF_WIDTH 64
+int dv3_prosody_warp_f32(const float* mag, float* out, int32_t B, int32_t T_in, int32_t T_out, int32_t bins,
+                         const int32_t* tlen_in /* or NULL */, const int32_t* tlen_out, const double* rate,
+                         const double* ratio, int32_t env_half_width, int32_t preserve_envelope, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
