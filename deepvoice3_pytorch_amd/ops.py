@@ -695,7 +695,8 @@ class GateFuse(object):
     and of the saved pre-gate pair, a write of the pre-gate gradient, on the queue of backward that has no slack) becomes
     part of its tail.  Request: the producer's saved pair `ab`, its mode / residual flag, its input `x` (highway), `pair`
     = write the pre-gate gradient as pair words (the producer's two gradient GEMMs then stage it without conversion).
-    Result (after conv_gemm): dab (B, 2C, T), dres (highway) and the bias partial sums part [2C][n_part]."""
+    Result (after conv_gemm): dab (B, 2C, T), dres (highway) and the bias partial sums part [2C][n_part].  A caller may set
+    dab / dres / part beforehand (contiguous fp32 tensors of exactly those shapes): attach then writes into them."""
     __slots__ = ("ab", "mode", "residual", "x", "pair", "dab", "dres", "part", "n_part")
 
     def __init__(self, ab, mode, residual, x=None, pair=False):
@@ -703,20 +704,28 @@ class GateFuse(object):
         self.dab = self.dres = self.part = None
         self.n_part = 0
 
+    def _out(self, name, shape, device):
+        t = getattr(self, name)
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=device)
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != device:
+            raise RuntimeError("GateFuse: a caller-provided %s must be a contiguous fp32 %s tensor on %s" % (name, shape, device))
+        return t
+
     def attach(self, d, B, C, T, device):
         ab = self.ab
         if ab.dtype != torch.float32 or tuple(ab.shape) != (B, 2 * C, T) or not ab.is_contiguous():
             raise RuntimeError("GateFuse: the producer's pre-gate pair must be a contiguous fp32 (B, 2C, T) tensor")
         self.n_part = (B * T + 31) // 32
-        self.dab = torch.empty((B, 2 * C, T), dtype=torch.float32, device=device)
-        self.part = torch.empty((2 * C, self.n_part), dtype=torch.float32, device=device)
+        self.dab = self._out("dab", (B, 2 * C, T), device)
+        self.part = self._out("part", (2 * C, self.n_part), device)
         d.pg, d.dpg, d.pg_part = ab.data_ptr(), self.dab.data_ptr(), self.part.data_ptr()
         d.pg_mode, d.pg_residual, d.pg_pair = self.mode, self.residual, int(self.pair)
         if self.mode == EPI_HIGHWAY:
             x = self.x
             if x is None or x.dtype != torch.float32 or tuple(x.shape) != (B, C, T) or x.stride(2) != 1:
                 raise RuntimeError("GateFuse: a highway producer needs its fp32 (B, C, T) input")
-            self.dres = torch.empty((B, C, T), dtype=torch.float32, device=device)
+            self.dres = self._out("dres", (B, C, T), device)
             d.pg_x, d.pg_x_bs, d.pg_x_rs, d.dpg_res = x.data_ptr(), x.stride(0), x.stride(1), self.dres.data_ptr()
 
 
@@ -738,7 +747,7 @@ def conv_gemm(x, a, lda, a_half, *, B, Cin, Tin, M, Tout, J=1, dil=1, padL=0, mo
                              mode=mode, Cg=Cg, bias=bias, spk=spk, spk_strides=spk_strides, r=r, r2=r2,
                              residual=residual, ab=ab, xmask=xmask, xmask_rs=xmask_rs, ymask=ymask,
                              ymask_rs=ymask_rs, drop_scale=drop_scale, a_split=a_split, r_scale=r_scale, x_c8=x_c8,
-                             out_c8=out_c8, xmask_c8=xmask_c8, ymask_c8=ymask_c8, Cout=Cout)
+                             out_c8=out_c8, xmask_c8=xmask_c8, ymask_c8=ymask_c8, Cout=Cout, y=y)
     # bf16 storage (single-term bf16 kernels): x / r / r2 may be bf16 tensors (all three alike), y / ab are written in
     # out_dtype
     in_bf16 = x is not None and x.dtype == torch.bfloat16
@@ -838,13 +847,20 @@ def prepare_streamk_ws(device, stream):
 
 def _conv_gemm_c8(x, a, lda, a_half, *, B, Cin, Tin, M, Tout, J, dil, padL, mode, Cg, bias, spk, spk_strides, r, r2,
                   residual, ab, xmask, xmask_rs, ymask, ymask_rs, drop_scale, a_split, r_scale, x_c8, out_c8, xmask_c8,
-                  ymask_c8, Cout):
-    """the bf16-storage forms of dv3_conv_gemm_f32 (single-term bf16 kernels): c8 in and / or c8 out"""
+                  ymask_c8, Cout, y=None):
+    """the bf16-storage forms of dv3_conv_gemm_f32 (single-term bf16 kernels): c8 in and / or c8 out.  y: a caller-provided
+    output -- a contiguous c8 tensor whose padding channels are zero (the kernels keep them), or a dense fp32 (B, Cout, Tout)"""
     if _gemm_mode != "bf16" or a_split is None:
         raise RuntimeError("c8 activations need the bf16 GEMM mode and a split weight image")
     dev = (x_c8 if x_c8 is not None else x).device
+    if y is not None:
+        want = (B, c8_groups(Cout), Tout, 8) if out_c8 else (B, Cout, Tout)
+        if y.dtype != (torch.bfloat16 if out_c8 else torch.float32) or tuple(y.shape) != want or not y.is_contiguous():
+            raise RuntimeError("conv_gemm: a caller-provided output of a c8 launch must be a contiguous %s %s tensor" %
+                               ("c8 bf16" if out_c8 else "fp32", want))
     if out_c8:
-        y = _c8_empty(B, Cout, Tout, dev)
+        if y is None:
+            y = _c8_empty(B, Cout, Tout, dev)
         for t_ in (r, r2):
             if t_ is not None and not is_c8(t_):
                 raise RuntimeError("conv_gemm: a c8 output reads its residual inputs in c8")
@@ -853,7 +869,8 @@ def _conv_gemm_c8(x, a, lda, a_half, *, B, Cin, Tin, M, Tout, J, dil, padL, mode
     else:
         if r is not None or r2 is not None or ab is not None:
             raise RuntimeError("conv_gemm: c8 input with an fp32 output takes no residual / pre-gate save")
-        y = torch.empty((B, Cout, Tout), dtype=torch.float32, device=dev)
+        if y is None:
+            y = torch.empty((B, Cout, Tout), dtype=torch.float32, device=dev)
     d = _conv_desc()
     if x_c8 is not None:
         if x_c8.shape[1] != c8_groups(Cin) or x_c8.shape[2] != Tin or not x_c8.is_contiguous():
@@ -892,17 +909,21 @@ def pair_words_of(x):
     return w.view(torch.float32)
 
 
-def wgrad_gemm_c8(g8, x8, *, B, M, Cin, T, J, dil, padL, n_slabs, xmask_c8=None, drop_scale=1.0, rows_of_slabs=False):
+def wgrad_gemm_c8(g8, x8, *, B, M, Cin, T, J, dil, padL, n_slabs, xmask_c8=None, drop_scale=1.0, rows_of_slabs=False,
+                  out=None):
     """dv3_wgrad_gemm_f32, c8 form: g8 (B, M/8.., T, 8), x8 (B, Cin/8.., T, 8) -> out [S][J][M][Cin]
-    (rows_of_slabs: [J][M][S][Cin], see wgrad_gemm)"""
+    (rows_of_slabs: [J][M][S][Cin], see wgrad_gemm); out: a caller-provided contiguous fp32 tensor of that shape"""
+    shape = (J, M, n_slabs, Cin) if rows_of_slabs else (n_slabs, J, M, Cin)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=g8.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise RuntimeError("wgrad_gemm_c8: a caller-provided output must be a contiguous fp32 %s tensor" % (shape,))
     d = _wgrad_desc()
     d.g, d.x = g8.data_ptr(), x8.data_ptr()
     d.xmask_c8, d.drop_scale = _ptr(xmask_c8), drop_scale
     if rows_of_slabs:
-        out = torch.empty((J, M, n_slabs, Cin), dtype=torch.float32, device=g8.device)
         d.out, d.out_ss, d.ldo = out.data_ptr(), Cin, n_slabs * Cin
     else:
-        out = torch.empty((n_slabs, J, M, Cin), dtype=torch.float32, device=g8.device)
         d.out, d.out_ss, d.ldo = out.data_ptr(), J * M * Cin, Cin
     d.B, d.M, d.Cin, d.T, d.Tin, d.J, d.dil, d.padL, d.n_slabs = B, M, Cin, T, T, J, dil, padL, n_slabs
     d.split_bf16, d.k_split, d.c8 = 2, 1, 1

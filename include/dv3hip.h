@@ -151,6 +151,22 @@ enum {
  * A is the PACKED weight: [J][Cin][lda], m contiguous, produced by dv3_weight_norm_pack_f32.
  * For GLU/HIGHWAY the m axis holds the `a` half in [0,Cg) and the gate half at [a_half,
  * a_half+Cg); M must equal 2*Cg and the output has Cg channels.
+ *
+ * PLACEMENT of the tensors (tests/test_gpu_gemm_footprint.py pins every line; strides are in elements):
+ *   fp32 x, r, r2, y     any 4-byte aligned base, any row stride rs >= the row length (T; 2 T for y of the interleaved
+ *                        store), any batch stride bs that keeps the rows apart: views into larger buffers are fine.
+ *                        The kernels WRITE the logical elements only -- never a row gap, a batch gap or a word before /
+ *                        behind the tensor -- and nothing that lies outside the logical elements of an input reaches
+ *                        a value (loads past a tensor's edge are clamped into it).  The 16-byte epilogues are taken
+ *                        when base % 16 == 0, rs % 4 == 0, bs % 4 == 0 (and Tout % 4 == 0); they give the same bits as
+ *                        the 4-byte ones, except in the summation order of pg_part.
+ *   a with a_bs != 0     (an activation as the packed operand) any 4-byte aligned base and lda; staged element by
+ *                        element unless base % 16 == 0 and lda, a_half, a_bs are multiples of 4
+ *   ab, pg, dpg, dpg_res, pg_part    DENSE: [B][M][Tout] / [B][2M][Tout] / [2M][n_part] contiguous, no stride fields;
+ *                        pg_x has strides like x
+ *   xmask, ymask         rows of xmask_rs / ymask_rs >= ceil(T / 32) words, the row index dense ([B * Cin] / [B * M]);
+ *                        words beyond ceil(T / 32) of a row are never used
+ *   c8 tensors           16-byte aligned and contiguous; padding channels zero on entry, kept zero
  */
 typedef struct dv3_conv_desc {
   const float* x;  int64_t x_bs, x_rs;      /* input  [B][Cin][Tin]                         */
@@ -358,6 +374,13 @@ int dv3_split_pack_bf16(const float* packed, uint16_t* out, int32_t J, int32_t K
  *
  * slab s covers batches {s, s+S, s+2S, ...}; S = n_slabs (S == B gives a per-batch
  * result, S == 1 a full reduction).  The slabs are summed by dv3_weight_norm_bwd_f32.
+ *
+ * PLACEMENT (tests/test_gpu_gemm_footprint.py; strides in elements): fp32 g and x take any 4-byte aligned base, any
+ * row stride >= T / Tin and any batch stride.  The split kernels load 8 frames at a time from offsets clamped into
+ * [base, base + (B-1) bs + (rows-1) rs + T): a unit that crosses a row end may READ the gap behind it (or the next row)
+ * and removes those frames by a select, so what lies there never reaches a sum; nothing outside that span is read.
+ * out: any 4-byte aligned base, ldo >= Cin, out_ss as the layout demands; only the first Cin floats of a row are written.
+ * xmask as in dv3_conv_desc.  c8 g / x: 16-byte aligned and contiguous.
  */
 typedef struct dv3_wgrad_desc {
   const float* g;  int64_t g_bs, g_rs;       /* [B][M][T]                                    */
