@@ -6,7 +6,18 @@ flat list of descriptors built ONCE per utterance batch -- one dv3_conv_step_f32
 buffer on a device step counter, k-tap GEMV, the whole layer tail) and one dv3_attn_step_f32 per attention read --
 that the host replays launch by launch (optionally as one hipGraph per step), or that ONE persistent launch walks for
 the whole utterance (dv3_decode_program_run: the loop, the ring buffers, the stop rule and the layer-to-layer
-hand-over all stay on the device; opt-in, see StepProgram.decode).  `StepProgram` owns the buffers the descriptors point at.
+hand-over all stay on the device; opt-in, see StepProgram.decode).  `StepProgram` owns the buffers the descriptors point
+at, the stacked per-step outputs among them (`stack`, read back through `results` / `read_slot` / `read_slots`).
+
+How a decoder builds its program: ONE walk over its layers, `Decoder._step_entries`, appends the entries; the walk over a
+"Conv1d (+ReLU)" stack is modules.conv_relu_layers, shared with the module-by-module path.  `Decoder._slot_entries` runs
+that walk on per-slot operand buffers; `Decoder._fast_decode_eligible(Tk)` is the same call against a DRY program
+(StepProgram(1, "meta", ...): meta-device buffers, nothing packed, launched or allocated), which records why the step
+kernels would not take an entry (`refuse`: a layer the walk has no entry for, a window `ops.conv_step_fits` rejects,
+attention scores beyond the LDS) -- so the predicate can not drift from the builder.  `incremental_forward` does not
+ask the predicate first: it builds its program once, and a build that was refused (nothing is packed or laid out for
+a program from its first refusal on) hands the call to the module-by-module loop.  The frames around the walk, the
+same for both decoder families, are `incremental_decode` and `slot_program_frame` below.
 
 Slot mode (StepProgram(B, device, t_cap=...)): the program is built ONCE for B batch slots and lives
 across utterances.  Every slot runs at its own step t - t_off[b] (the kernels' slot mode, include/dv3hip.h), so a slot
@@ -14,6 +25,7 @@ whose utterance has ended is handed to the next one (`admit`) while its neighbou
 the host-side book of which ticket sits in which slot since which global step.
 """
 import ctypes
+import functools
 
 import torch
 
@@ -91,18 +103,70 @@ def item_results(stops, outputs, alignments, dones, states):
     return outputs, alignments, dones, states, lengths.long()
 
 
-SLOT_IDLE = 2 ** 31 - 1          # t_off of a slot nobody sits in: its step t - t_off is negative for every t >= 0
+def item_key_len(text_lengths, B, Tk, device):
+    """Decoder.incremental_forward(text_lengths=...): each item's key count as a device int32[B] (None: reference mode)"""
+    if text_lengths is None:
+        return None
+    tl = torch.as_tensor(text_lengths).reshape(-1).to(torch.int64).cpu()
+    if tl.numel() != B or int(tl.min()) < 1 or int(tl.max()) > Tk:
+        raise ValueError("text_lengths: %d lengths in [1, %d] expected for a batch of %d, got %s" % (
+            B, Tk, B, tl.tolist()))
+    return tl.to(torch.int32).to(device)
+
+
+def incremental_decode(dec, encoder_out, text_lengths, *args):
+    """The frame of Decoder.incremental_forward, both families: the per-utterance key lengths and stop list, the fused
+    step program (dec._incremental_fast), the module-by-module loop (dec._incremental_modules) where the step kernels
+    do not take the decoder or the key count, and the zero tails of a per-utterance result.  The program is built ONCE
+    per call: _incremental_fast returns None if its own build was refused (StepProgram.refuse: nothing of a refused
+    program is packed or launched), which is the answer _fast_decode_eligible gives from a dry build.  args: the
+    family's own arguments, handed to either."""
+    keys = encoder_out[0]
+    B = keys.size(0)
+    key_len = item_key_len(text_lengths, B, keys.size(1), keys.device)
+    stops = [0] * B if key_len is not None else None
+    res = None
+    if getattr(dec, "fast_decode", False) and keys.is_cuda:
+        res = dec._incremental_fast(encoder_out, *args, key_len=key_len, stops=stops)
+    if res is None:
+        res = dec._incremental_modules(encoder_out, *args, key_len=key_len, stops=stops)
+    return res if stops is None else item_results(stops, *res)
+
+
+def slot_program_frame(dec, slots, max_text_len, dev):
+    """The frame of Decoder.slot_program, both families: the checks -> an empty slot-mode StepProgram of
+    max_decoder_steps + 1 rows per slot"""
+    if dec.training:
+        raise RuntimeError("slot_program: eval mode only")
+    if dev.type != "cuda" or not getattr(dec, "fast_decode", False) or not dec._fast_decode_eligible(int(max_text_len)):
+        raise RuntimeError("slot_program: rolling admission runs on the fused decode-step kernels only, and this "
+                           "decoder (or %d keys) is not eligible for them (_fast_decode_eligible); there is no "
+                           "module-by-module fallback in slot mode" % int(max_text_len))
+    t_cap = dec.max_decoder_steps + 1
+    if t_cap >= dec.embed_query_positions.weight.size(0):
+        raise RuntimeError("slot_program: decoder steps exceed max_positions")
+    return StepProgram(int(slots), dev, t_cap=t_cap)
+
+
+# ops.conv_step_fits (the library's own answer for a (taps, input channels) pair), asked once per pair
+_conv_step_fits = functools.lru_cache(maxsize=None)(ops.conv_step_fits)
+SLOT_IDLE = 2 ** 31 - 1         # t_off of a slot nobody sits in: its step t - t_off is negative for every t >= 0
 
 
 class StepProgram(object):
     def __init__(self, B, device, t_cap=None):
         """t_cap: slot mode -- the rows every stacked output and step-indexed table holds per slot (the decoder's
-        max_decoder_steps + 1); the program then owns t_off and key_len (int32[B] on the device)"""
+        max_decoder_steps + 1); the program then owns t_off and key_len (int32[B] on the device).
+        device "meta": a dry program -- the entries are recorded with every scalar field set and checked (`refused`),
+        but its buffers are meta tensors and nothing is packed, launched or allocated"""
         self.B, self.dev = B, device
+        self.dry = torch.device(device).type == "meta"
+        self.refused = None           # why the step kernels do not take this program (the first reason), see refuse()
         self.f32 = dict(dtype=torch.float32, device=device)
         self.t_dev = torch.zeros(1, dtype=torch.int32, device=device)      # the step counter every launch reads
         self.keep, self.prog = [self.t_dev], []
         self.per_item = False         # an attention entry reads per-utterance key lengths (attn_step(key_len=...))
+        self.n_attn, self.align_scale = 0, 1.0      # attention entries so far; what results() scales the alignments by
         self.t_cap = None if t_cap is None else int(t_cap)
         if self.t_cap is not None:
             if self.t_cap < 1:
@@ -116,19 +180,45 @@ class StepProgram(object):
     def slot_mode(self):
         return self.t_cap is not None
 
+    @property
+    def live(self):
+        """weights are packed and operands laid out for the entries: not in a dry program, and no more once one was refused"""
+        return not self.dry and self.refused is None
+
     def buffer(self, *shape):
-        t = torch.zeros(*shape, **self.f32)
+        t = (torch.empty if self.dry else torch.zeros)(*shape, **self.f32)      # (zeros on "meta" is a slow Python path)
         self.keep.append(t)
         return t
+
+    def stack(self, n, D, Cs, Tk):
+        """the stacked per-step outputs, n rows each (slot mode: n = t_cap), for the entries' out_seq / attn_seq:
+        outs (n, B, D), dones_seq (n, B, 1), states (n, B, Cs), aligns (n, B, Tk)"""
+        self.outs, self.dones_seq = self.buffer(n, self.B, D), self.buffer(n, self.B, 1)
+        self.states, self.aligns = self.buffer(n, self.B, Cs), self.buffer(n, self.B, Tk)
+
+    def refuse(self, why):
+        """the step kernels do not take what the builder was about to append: the decoder is not eligible"""
+        self.refused = self.refused or why
+
+    def _step_tiles(self, pk, K, M, Cg):
+        """the weights of a packed image in step-tile order, built once per image"""
+        tiles = getattr(pk, "step_tiles", None)
+        if tiles is None:
+            tiles = torch.empty(ops._lib.lib().dv3_conv_step_pack_floats(K, M, Cg), **self.f32)
+            ops._lib.call("dv3_conv_step_pack_f32", pk.fwd.data_ptr(), pk.lda, pk.a_half, K, M, Cg, tiles.data_ptr(),
+                          ops._stream())
+            pk.step_tiles = tiles
+        return tiles
 
     def conv_step(self, layer, x, mode, Cout, k=1, dil=1, gated=False, residual=False, spk=None, r=None, r2=None,
                   post_add=None, y=None, y_act=None, y_pre=None, out_seq=None):
         """one incremental conv layer (conv.py:17-46) with its tail; x (B, Cin) view (row stride free) -> y (B, Cout)"""
         B = self.B
-        pk = layer.packed(glu_cg=Cout if gated else 0)
         if y is None:
             y = torch.empty(B, Cout, **self.f32)
         Cin = x.size(1)
+        if not _conv_step_fits(k, Cin):         # dv3_conv_step_f32 stages the k-tap window of a batch group in LDS
+            self.refuse("a %d-tap layer of %d input channels does not fit the conv-step kernel's LDS" % (k, Cin))
         d = STRUCTS["dv3_conv_step_desc"]()
         d.x, d.x_bs = x.data_ptr(), x.stride(0)
         if k > 1:
@@ -136,15 +226,11 @@ class StepProgram(object):
             ring = self.buffer(L, B, Cin)
             d.ring, d.L = ring.data_ptr(), L
         d.t = self.t_dev.data_ptr()
-        tiles = getattr(pk, "step_tiles", None)         # the weights in step-tile order, built once per packed image
-        if tiles is None:
-            Cg, M = (Cout if gated else 0), (2 * Cout if gated else Cout)
-            n = ops._lib.lib().dv3_conv_step_pack_floats(k * Cin, M, Cg)
-            tiles = torch.empty(n, **self.f32)
-            ops._lib.call("dv3_conv_step_pack_f32", pk.fwd.data_ptr(), pk.lda, pk.a_half, k * Cin, M, Cg,
-                          tiles.data_ptr(), ops._stream())
-            pk.step_tiles = tiles
-        d.a, d.lda, d.a_half = tiles.data_ptr(), pk.lda, pk.a_half
+        pk = None
+        if self.live:
+            pk = layer.packed(glu_cg=Cout if gated else 0)
+            tiles = self._step_tiles(pk, k * Cin, 2 * Cout if gated else Cout, Cout if gated else 0)
+            d.a, d.lda, d.a_half = tiles.data_ptr(), pk.lda, pk.a_half
         d.bias = layer.bias.data_ptr() if layer.bias is not None else None
         if spk is not None:
             d.spk, d.spk_bs = spk.data_ptr(), spk.stride(0)
@@ -180,6 +266,12 @@ class StepProgram(object):
                 raise RuntimeError("decode program: slot mode reads per-slot key / value rows and its own key_len")
             key_len = self.key_len
         E, Tk = (k.size(2), k.size(1)) if rows else (k.size(1), k.size(2))
+        if (E + Tk) * 4 > 64 * 1024:            # dv3_attn_step_f32 keeps the query and the scores of all keys in LDS
+            self.refuse("the attention scores of %d keys do not fit the attention-step kernel's LDS" % Tk)
+        # the stacked alignment is the FIRST attention layer's; over n layers the reference's running `ave + ave`
+        # followed by / n (deepvoice3.py:449-461) makes of it that alignment * 2^(n-1) / n
+        self.n_attn += 1
+        self.align_scale = float(2 ** (self.n_attn - 1)) / self.n_attn
         ctx = torch.empty(B, E, **self.f32)
         la = self.buffer(2 * B if key_len is not None else 2).to(torch.int32) if monotonic else None
         if la is not None:
@@ -190,7 +282,7 @@ class StepProgram(object):
                 raise RuntimeError("decode program: key / value rows must be contiguous")
             kt, vt = k, v
         else:
-            kt, vt = ops.transpose(k.contiguous()), ops.transpose(v.contiguous())
+            kt, vt = (ops.transpose(k.contiguous()), ops.transpose(v.contiguous())) if self.live else (k, v)
         self.keep.extend([kt, vt])
         a = STRUCTS["dv3_attn_step_desc"]()
         a.q, a.q_bs, a.k, a.v, a.kv_tke = q.data_ptr(), q.stride(0), kt.data_ptr(), vt.data_ptr(), 1
@@ -245,17 +337,16 @@ class StepProgram(object):
         return arr, ti
 
     # ---- slot mode -------------------------------------------------------------------------------------------------
-    def seal(self, cur_in, outs, dones_seq, states, aligns, write_operands, align_scale=1.0):
-        """slot mode: the program is complete.  cur_in: the decoder-input buffer (the x of entry 0); outs / dones_seq /
-        states / aligns: the stacked (t_cap, B, .) outputs; write_operands(slot_index int64[n] on the device, memory,
-        text_positions, speaker_embed): the decoder family's writer of the per-slot operands (projected keys and values,
-        position codes, speaker biases) for a group of admitted utterances."""
-        if not self.slot_mode:
-            raise RuntimeError("decode program: seal() is the slot mode's")
+    def seal(self, cur_in, write_operands):
+        """slot mode: the program is complete.  cur_in: the decoder-input buffer (the x of entry 0);
+        write_operands(slot_index int64[n] on the device, memory, text_positions, speaker_embed): the decoder family's
+        writer of the per-slot operands (projected keys and values, position codes, speaker biases) for a group of
+        admitted utterances."""
+        if not self.slot_mode or self.dry or self.refused:
+            raise RuntimeError("decode program: seal() is the slot mode's, of a program the step kernels take (%s)" %
+                               self.refused)
         if not self.prog or self.prog[0][0] != "dv3_conv_step_f32" or self.prog[0][1].x != cur_in.data_ptr():
             raise RuntimeError("decode program: entry 0 must read the decoder input buffer")
-        self.outs, self.dones_seq, self.states, self.aligns = outs, dones_seq, states, aligns
-        self.align_scale = float(align_scale)
         self._write_operands = write_operands
         self._arr, _ = self._entries(cur_in, None)
         p = STRUCTS["dv3_decode_program"]()
@@ -307,21 +398,39 @@ class StepProgram(object):
         """the stacked done flags > 0.5 as host rows [t_b][slot] (one device read per chunk of steps)"""
         return (self.dones_seq.reshape(self.t_cap, self.B) > 0.5).tolist()
 
-    def read_slot(self, slot, n):
-        """copies of slot's first n stacked rows -> (outputs (n, D), alignments (n, Tk_cap), dones (n,), states (n, Cs))"""
-        ali = self.aligns[:n, slot].clone()
+    def _stacked(self, n, items=slice(None)):
+        """the first n stacked rows of `items` (an index, a slice or an index tensor over the batch), the alignments
+        scaled -> (outputs, alignments, states), each (n, items, .)"""
+        outs, ali, states = (x[:n].index_select(1, items) if torch.is_tensor(items) else x[:n, items]
+                             for x in (self.outs, self.aligns, self.states))
         if self.align_scale != 1.0:
             ali = ali * self.align_scale
-        return (self.outs[:n, slot].clone(), ali, self.dones_seq[:n, slot, 0].clone(), self.states[:n, slot].clone())
+        return outs, ali, states
+
+    def results(self, t):
+        """what Decoder.incremental_forward returns after t steps -> (outputs (B, t, D), alignments (B, t, Tk),
+        dones: t tensors (B, 1, 1), decoder_states (B, t, Cs))"""
+        outs, ali, states = self._stacked(t)
+        return (outs.transpose(0, 1).contiguous(), ali.transpose(0, 1),
+                [self.dones_seq[i].view(self.B, 1, 1) for i in range(t)], states.transpose(0, 1).contiguous())
+
+    def decode_for(self, dec, cur_in, test_inputs, stops):
+        """decode() with the decoder's step limits and its choice of loop -> results() of the steps taken"""
+        t = self.decode(cur_in, test_inputs, self.dones_seq, dec.min_decoder_steps, dec.max_decoder_steps,
+                        getattr(dec, "use_step_graph", False), getattr(dec, "persistent_decode", None),
+                        getattr(dec, "launched_decode", None), stops=stops)
+        return self.results(t)
+
+    def read_slot(self, slot, n):
+        """copies of slot's first n stacked rows -> (outputs (n, D), alignments (n, Tk_cap), dones (n,), states (n, Cs))"""
+        outs, ali, states = self._stacked(n, slot)
+        return outs.clone(), ali.clone(), self.dones_seq[:n, slot, 0].clone(), states.clone()
 
     def read_slots(self, slots, steps):
         """the stacked results of several slots as one zero-tailed batch (item_results): slots[i] ran steps[i] steps
         -> (outputs (n, max steps, D), alignments (n, max steps, Tk_cap), states (n, max steps, Cs))"""
         idx = torch.tensor([int(s) for s in slots], dtype=torch.int64).to(self.dev)
-        m = max(steps)
-        outputs, alignments, states = (x[:m].index_select(1, idx).transpose(0, 1) for x in (self.outs, self.aligns, self.states))
-        if self.align_scale != 1.0:
-            alignments = alignments * self.align_scale
+        outputs, alignments, states = (x.transpose(0, 1) for x in self._stacked(max(steps), idx))
         outputs, alignments, _, states, _ = item_results(list(steps), outputs, alignments, [], states)
         return outputs, alignments, states
 
@@ -410,6 +519,8 @@ class StepProgram(object):
                 raise RuntimeError("decode program: the persistent program does not take slot mode (its loop is one "
                                    "step index for the batch); slots run through admit() / run_steps()")
             raise RuntimeError("decode program: a slot-mode program runs through admit() / run_steps(), not decode()")
+        if self.dry or self.refused:
+            raise RuntimeError("decode program: the step kernels do not take this program (%s)" % (self.refused or "dry"))
         if self.per_item and stops is None:
             raise RuntimeError("decode program: per-utterance attention entries need the per-item stop rule (stops=)")
         if persistent is None:

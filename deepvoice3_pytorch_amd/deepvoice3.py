@@ -19,8 +19,9 @@ from torch import nn
 from . import ops
 from .modules import Conv1d, ConvTranspose1d, Embedding, Linear
 from .modules import key_lengths_i32, get_mask_from_lengths, SinusoidalEncoding, Conv1dGLU
+from .modules import conv_relu_layers, incremental_stack
 from . import conv as _conv
-from .decode_program import StepTrace, item_results
+from .decode_program import StepProgram, StepTrace, incremental_decode, slot_program_frame
 
 
 def expand_speaker_embed(inputs_btc, speaker_embed=None, tdim=1):
@@ -322,7 +323,7 @@ class Decoder(nn.Module):
         self.max_decoder_steps = 200
         self.min_decoder_steps = 10
         self.use_step_graph = False     # free-running decode: replay one hipGraph per step
-        self.fast_decode = True         # incremental_forward on the fused decode-step kernels (17 launches per step)
+        self.fast_decode = True         # incremental_forward on the fused decode-step kernels (16 launches per step)
         self.use_memory_mask = use_memory_mask
         if isinstance(force_monotonic_attention, bool):
             self.force_monotonic_attention = [force_monotonic_attention] * len(convolutions)
@@ -413,23 +414,19 @@ class Decoder(nn.Module):
         text_lengths (B,) ints: per-utterance mode -- item b decodes as if it were alone (its own keys, window,
         context scale and stop, as the reference at B = 1); the result then carries a fifth entry, each item's
         number of decoder steps, and every frame past it is zero."""
-        keys, values = encoder_out
-        B = keys.size(0)
-        dev = keys.device
         if self.training:
             raise RuntimeError('incremental_forward only supports eval mode')
-        key_len = _item_key_len(text_lengths, B, keys.size(1), dev)
-        stops = [0] * B if key_len is not None else None
-        if getattr(self, "fast_decode", False) and keys.is_cuda and self._fast_decode_eligible(keys.size(1)):
-            res = self._incremental_fast(encoder_out, text_positions, speaker_embed, initial_input, test_inputs,
-                                         key_len, stops)
-            return res if stops is None else item_results(stops, *res)
+        return incremental_decode(self, encoder_out, text_lengths, text_positions, speaker_embed, initial_input,
+                                  test_inputs)
+
+    def _memory_projections(self, encoder_out, text_positions, speaker_embed):
+        """What a decode reads of the encoder memory; none of it depends on the step -> the position-coded keys
+        (B, C, Tk) and, per entry of self.attention (None where there is no attention), the projected (keys, values)
+        as contiguous (B, E, Tk) tensors"""
+        keys, values = encoder_out
         w = self._rate(self.key_position_rate, self.speaker_proj1, speaker_embed)
-        keys_bct = self.embed_keys_positions.forward_bct(text_positions, w,
-                                                         base=keys.transpose(1, 2).contiguous())
+        keys_bct = self.embed_keys_positions.forward_bct(text_positions, w, base=keys.transpose(1, 2).contiguous())
         values_bct = values.transpose(1, 2).contiguous()
-        Tk = keys_bct.size(-1)
-        # key / value projections do not depend on the step: hoist them out of the loop
         proj = []
         for att in self.attention:
             if att is None:
@@ -437,8 +434,15 @@ class Decoder(nn.Module):
                 continue
             k = att.key_projection.forward_bct(keys_bct) if att.key_projection is not None else keys_bct
             v = att.value_projection.forward_bct(values_bct) if att.value_projection is not None else values_bct
-            proj.append((k, v))
+            proj.append((k.contiguous(), v.contiguous()))
+        return keys_bct, proj
 
+    def _incremental_modules(self, encoder_out, text_positions, speaker_embed=None, initial_input=None,
+                             test_inputs=None, key_len=None, stops=None):
+        """incremental_forward module by module: every configuration the reference handles"""
+        keys = encoder_out[0]
+        B, Tk, dev = keys.size(0), keys.size(1), keys.device
+        proj = self._memory_projections(encoder_out, text_positions, speaker_embed)[1]
         trace = StepTrace(self.min_decoder_steps, self.max_decoder_steps, test_inputs is not None, stops)
         last_attended = [torch.zeros(1 if key_len is None else 2 * B, dtype=torch.int32, device=dev) if v else None
                          for v in self.force_monotonic_attention]
@@ -451,7 +455,7 @@ class Decoder(nn.Module):
         def step(x, frame_pos):
             """one decoder step (deepvoice3.py:397-461): x (B,1,in_dim*r), frame_pos (B,1) long"""
             frame_pos_embed = self.embed_query_positions.forward_bct(frame_pos, wq)   # (B, C, 1)
-            x = self._incremental_stack(self.preattention, x, speaker_embed)
+            x = incremental_stack(self.preattention, x, Conv1dGLU, speaker_embed)
             ave_alignment = None
             for idx, (f, attention) in enumerate(zip(self.convolutions, self.attention)):
                 residual = x
@@ -522,60 +526,29 @@ class Decoder(nn.Module):
             t += 1
             if trace.stop(done):
                 break
-        return trace.result() if stops is None else item_results(stops, *trace.result())
+        return trace.result()
 
     def _fast_decode_eligible(self, Tk):
-        """What the fused step program (csrc/decode_step.hip) takes; anything else runs the module-by-module
-        path below, which handles every configuration the reference does."""
-        def fits(conv):      # dv3_conv_step_f32 stages the k-tap window of a batch group + its reduction stages in LDS
-            return ops.conv_step_fits(conv.kernel_size[0], conv.in_channels)
-        mods, i = list(self.preattention), 0
-        while i < len(mods):
-            f = mods[i]
-            if isinstance(f, Conv1dGLU):
-                if not fits(f.conv):
-                    return False
-            elif isinstance(f, _conv.Conv1d):
-                if f.kernel_size[0] != 1 or not fits(f):
-                    return False
-                i += int(i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU))
-            else:
-                return False
-            i += 1
-        for f, att in zip(self.convolutions, self.attention):
-            if not isinstance(f, Conv1dGLU) or not fits(f.conv):
-                return False
-            if att is not None:
-                E = att.query_projection.out_features
-                if (E + Tk) * 4 > 64 * 1024:
-                    return False
-        return True
+        """What the fused step program (csrc/decode_step.hip) takes; anything else runs the module-by-module path
+        above, which handles every configuration the reference does.  Asked of the builder itself: the walk that
+        appends the entries (_step_entries, through _slot_entries) runs against a dry program of one slot."""
+        P = StepProgram(1, "meta", t_cap=1)
+        self._slot_entries(P, int(Tk))
+        return P.refused is None
 
     # -- the same decode on the fused step kernels (csrc/decode_step.hip) -------------------------------
     def _incremental_fast(self, encoder_out, text_positions, speaker_embed=None, initial_input=None,
                           test_inputs=None, key_len=None, stops=None):
         """incremental_forward as a flat per-step program (decode_program.StepProgram): one conv-step entry per conv /
-        projection layer and one attention-step entry per attention read (17 per step for the ljspeech preset instead
+        projection layer and one attention-step entry per attention read (16 per step for the ljspeech preset instead
         of ~100 module calls), walked by ONE persistent launch for the whole utterance (or launch by launch):
         ring buffers indexed by the step counter (no window shifting), every layer tail fused, the per-step
         outputs written straight into the stacked result tensors.  Same quirks as the module-by-module path
         (last_attended from batch item 0, no padding mask, `ave_alignment + ave_alignment`)."""
-        from .decode_program import StepProgram
-        keys, values = encoder_out
+        keys = encoder_out[0]
         B, dev = keys.size(0), keys.device
         with torch.no_grad():
-            w = self._rate(self.key_position_rate, self.speaker_proj1, speaker_embed)
-            keys_bct = self.embed_keys_positions.forward_bct(text_positions, w, base=keys.transpose(1, 2).contiguous())
-            values_bct = values.transpose(1, 2).contiguous()
-            Tk = keys_bct.size(-1)
-            proj = []
-            for att in self.attention:
-                if att is None:
-                    proj.append(None)
-                    continue
-                k = att.key_projection.forward_bct(keys_bct) if att.key_projection is not None else keys_bct
-                v = att.value_projection.forward_bct(values_bct) if att.value_projection is not None else values_bct
-                proj.append((k.contiguous(), v.contiguous()))
+            memory = self._memory_projections(encoder_out, text_positions, speaker_embed)
             D = self.in_dim * self.r
             n_max = test_inputs.size(1) if test_inputs is not None else self.max_decoder_steps + 1
             wq = self._rate(self.query_position_rate, self.speaker_proj2, speaker_embed)
@@ -583,36 +556,24 @@ class Decoder(nn.Module):
             pe_all = self.embed_query_positions.forward_bct(pos, wq).permute(2, 0, 1).contiguous()   # (n_max, B, C)
             P = StepProgram(B, dev)
             cur_in = (initial_input.reshape(B, D).clone().float() if initial_input is not None else P.buffer(B, D))
-            free_running = test_inputs is None
-            nxt_in = cur_in if free_running else P.buffer(B, D)
-            n_att = sum(1 for a in self.attention if a is not None)
-            Cs = self.convolutions[-1].conv.out_channels // 2
-            outs, dones_seq = P.buffer(n_max, B, D), P.buffer(n_max, B, 1)
-            states, aligns = P.buffer(n_max, B, Cs), P.buffer(n_max, B, Tk)
-            P.keep.extend([keys_bct, values_bct, proj, pe_all, cur_in, nxt_in])
+            nxt_in = cur_in if test_inputs is None else P.buffer(B, D)
+            P.keep.extend([memory, pe_all, cur_in, nxt_in])
 
             def spk_of(f):
                 se = speaker_embed if speaker_embed.dim() == 2 else speaker_embed[:, 0, :]
                 return f.speaker_bias(se).contiguous()
 
-            self._step_entries(P, cur_in, nxt_in, pe_all, proj, spk_of, key_len, outs, dones_seq, states, aligns)
-            t = P.decode(cur_in, test_inputs, dones_seq, self.min_decoder_steps, self.max_decoder_steps,
-                         getattr(self, "use_step_graph", False), getattr(self, "persistent_decode", None),
-                         getattr(self, "launched_decode", None), stops=stops)
-            scale = float(2 ** (n_att - 1)) / n_att if n_att else 1.0
-            alignments = aligns[:t].transpose(0, 1)
-            if scale != 1.0:
-                alignments = alignments * scale
-            decoder_states = states[:t].transpose(0, 1).contiguous()
-            outputs = outs[:t].transpose(0, 1).contiguous()
-            dones = [dones_seq[i].view(B, 1, 1) for i in range(t)]
-        return outputs, alignments, dones, decoder_states
+            self._step_entries(P, n_max, keys.size(1), cur_in, nxt_in, pe_all, memory[1], spk_of, key_len)
+            return None if P.refused else P.decode_for(self, cur_in, test_inputs, stops)
 
-    def _step_entries(self, P, cur_in, nxt_in, pe_all, proj, spk_of, key_len, outs, dones_seq, states, aligns, rows=False):
-        """the step program (deepvoice3.py:397-461) appended to P.  proj[idx]: attention layer idx's projected (keys,
-        values) -- (B, E, Tk), or the (B, Tk, E) row images with rows=True; spk_of(f): the (B, C) speaker bias of GLU
-        layer f (called only for layers that have one)"""
+    def _step_entries(self, P, n, Tk, cur_in, nxt_in, pe_all, proj, spk_of, key_len, rows=False):
+        """The step program (deepvoice3.py:397-461) appended to P, with its stacked outputs of n rows over Tk keys: the
+        one walk over this decoder's layers, for the per-batch program, the slot program and the eligibility check
+        alike.  A layer it has no entry for is refused (P.refuse) and ends the walk.  proj[idx]: attention layer
+        idx's projected (keys, values) -- (B, E, Tk), or the (B, Tk, E) row images with rows=True; spk_of(f): the
+        (B, C) speaker bias of GLU layer f (called only for layers that have one)"""
         D = self.in_dim * self.r
+        P.stack(n, D, self.last_conv.in_channels, Tk)
 
         def glu_step(f, x, residual, **kw):
             spk = spk_of(f) if f.speaker_proj is not None else None
@@ -620,40 +581,51 @@ class Decoder(nn.Module):
                                dil=f.conv.dilation[0], gated=True, residual=residual, spk=spk, **kw)
 
         x = cur_in
-        mods, i = list(self.preattention), 0
-        while i < len(mods):
-            f = mods[i]
+        for f, relu in conv_relu_layers(self.preattention):
             if isinstance(f, Conv1dGLU):
                 x = glu_step(f, x, f.residual)
-            elif isinstance(f, _conv.Conv1d):
-                relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-                if f.kernel_size[0] != 1:
-                    raise RuntimeError("fast decode: only 1x1 plain convolutions in the pre-attention stack")
+            elif isinstance(f, _conv.Conv1d) and f.kernel_size[0] == 1:
                 x = P.conv_step(f, x, ops.EPI_RELU if relu else ops.EPI_LINEAR, f.out_channels)
-                i += int(relu)
             else:
-                raise RuntimeError("fast decode: unsupported pre-attention module %r" % type(f))
-            i += 1
-        first_att = True
+                return P.refuse("pre-attention module %r (a Conv1dGLU or a 1x1 Conv1d is taken)" % f)
         n_conv = len(self.convolutions)
         for idx, (f, attention) in enumerate(zip(self.convolutions, self.attention)):
+            if not isinstance(f, Conv1dGLU):
+                return P.refuse("convolution module %r (a Conv1dGLU is taken)" % f)
             residual = x
-            st = states if idx == n_conv - 1 else None
+            st = P.states if idx == n_conv - 1 else None
             if attention is None:
                 x = glu_step(f, x, f.residual, r2=residual, out_seq=st)   # (glu + residual) * sqrt(.5)
                 continue
             xq = glu_step(f, x, f.residual, post_add=pe_all)              # conv output + the step's position code
             kp, vp = proj[idx]
             q = P.conv_step(attention.query_projection, xq, ops.EPI_LINEAR, attention.query_projection.out_features)
-            # ave_alignment = the FIRST layer's alignment * 2^(n-1)/n (the reference's `ave + ave`)
+            # ave_alignment = the FIRST layer's alignment * 2^(n-1)/n (the reference's `ave + ave`): P.align_scale
             ctx = P.attn_step(q, kp, vp, attention.window_backward, attention.window_ahead,
-                              self.force_monotonic_attention[idx], attn_seq=aligns if first_att else None,
+                              self.force_monotonic_attention[idx], attn_seq=P.aligns if P.n_attn == 0 else None,
                               key_len=key_len, rows=rows)
-            first_att = False
             x = P.conv_step(attention.out_projection, ctx, ops.EPI_LINEAR, attention.out_projection.out_features,
                             r=xq, r2=residual, out_seq=st)
-        pre = P.conv_step(self.last_conv, x, ops.EPI_LINEAR, D, y_act=nxt_in, out_seq=outs)
-        P.conv_step(self.fc, pre, ops.EPI_SIGMOID, 1, out_seq=dones_seq)
+        pre = P.conv_step(self.last_conv, x, ops.EPI_LINEAR, D, y_act=nxt_in, out_seq=P.outs)
+        P.conv_step(self.fc, pre, ops.EPI_SIGMOID, 1, out_seq=P.dones_seq)
+
+    def _slot_entries(self, P, Tk):
+        """the step program on per-slot operand buffers of P's own, filled at admission (slot_program) or never (the dry
+        program of _fast_decode_eligible) -> (decoder-input buffer, position codes (t_cap, B, C), per attention layer
+        the (keys, values) rows (B, Tk, E), [(GLU layer, its speaker-bias rows (B, C))])"""
+        B = P.B
+        cur_in = P.buffer(B, self.in_dim * self.r)
+        pe_all = P.buffer(P.t_cap, B, self.embed_query_positions.weight.size(1))
+        rows = [None if att is None else tuple(P.buffer(B, Tk, att.query_projection.out_features) for _ in range(2))
+                for att in self.attention]
+        spk_rows = []
+
+        def spk_of(f):
+            spk_rows.append((f, P.buffer(B, f.conv.out_channels // 2)))
+            return spk_rows[-1][1]
+
+        self._step_entries(P, P.t_cap, Tk, cur_in, cur_in, pe_all, rows, spk_of, None, rows=True)
+        return cur_in, pe_all, rows, spk_rows
 
     def slot_program(self, slots, max_text_len):
         """The step program in slot mode (decode_program.StepProgram), built ONCE for `slots` batch
@@ -661,107 +633,38 @@ class Decoder(nn.Module):
         speaker-bias rows, position-code columns and stacked outputs of max_decoder_steps + 1 rows per slot.
         P.admit(slot list, memory, text_positions, text_lengths, speaker_embed) hands slots to new utterances,
         P.run_steps(n) decodes.  Only configurations the fused step kernels take: no module-by-module fallback."""
-        from .decode_program import StepProgram
-        B, Tk = int(slots), int(max_text_len)
+        Tk = int(max_text_len)
         dev = self.last_conv.bias.device if self.last_conv.bias is not None else next(self.parameters()).device
-        if self.training:
-            raise RuntimeError("slot_program: eval mode only")
-        if dev.type != "cuda" or not getattr(self, "fast_decode", False) or not self._fast_decode_eligible(Tk):
-            raise RuntimeError("slot_program: rolling admission runs on the fused decode-step kernels only, and this "
-                               "decoder (or %d keys) is not eligible for them (_fast_decode_eligible); there is no "
-                               "module-by-module fallback in slot mode" % Tk)
-        D = self.in_dim * self.r
-        t_cap = self.max_decoder_steps + 1
-        if t_cap >= self.embed_query_positions.weight.size(0):
-            raise RuntimeError("slot_program: decoder steps exceed max_positions")
+        P = slot_program_frame(self, slots, Tk, dev)
+        t_cap = P.t_cap
         multi = self.speaker_proj1 is not None
         with torch.no_grad():
-            P = StepProgram(B, dev, t_cap=t_cap)
-            cur_in = P.buffer(B, D)
-            n_att = sum(1 for a in self.attention if a is not None)
-            Cs = self.convolutions[-1].conv.out_channels // 2
-            Cq = self.embed_query_positions.weight.size(1)
-            outs, dones_seq = P.buffer(t_cap, B, D), P.buffer(t_cap, B, 1)
-            states, aligns = P.buffer(t_cap, B, Cs), P.buffer(t_cap, B, Tk)
-            pe_all = P.buffer(t_cap, B, Cq)
-            rows = []
-            for att in self.attention:
-                if att is None:
-                    rows.append(None)
-                    continue
-                E = att.query_projection.out_features
-                rows.append((P.buffer(B, Tk, E), P.buffer(B, Tk, E)))
-            spk_rows = {}
-
-            def spk_of(f):
-                spk_rows[id(f)] = (f, P.buffer(B, f.conv.out_channels // 2))
-                return spk_rows[id(f)][1]
-
-            self._step_entries(P, cur_in, cur_in, pe_all, rows, spk_of, None, outs, dones_seq, states, aligns, rows=True)
+            cur_in, pe_all, rows, spk_rows = self._slot_entries(P, Tk)
             pos = torch.arange(1, t_cap + 1, device=dev, dtype=torch.long)[None]
 
             def write_operands(idx, memory, text_positions, speaker_embed):
-                keys, values = memory
-                n, Tt = keys.size(0), keys.size(1)
+                n, Tt = memory[0].size(0), memory[0].size(1)
                 if Tt > Tk:
                     raise ValueError("slot_program: %d keys, the slots hold %d" % (Tt, Tk))
                 if multi and speaker_embed is None:
                     raise ValueError("slot_program: a multi-speaker decoder needs speaker_embed at admission")
-                w = self._rate(self.key_position_rate, self.speaker_proj1, speaker_embed)
-                keys_bct = self.embed_keys_positions.forward_bct(text_positions, w, base=keys.transpose(1, 2).contiguous())
-                values_bct = values.transpose(1, 2).contiguous()
-                for att, kv in zip(self.attention, rows):
-                    if att is None:
-                        continue
-                    k = att.key_projection.forward_bct(keys_bct) if att.key_projection is not None else keys_bct
-                    v = att.value_projection.forward_bct(values_bct) if att.value_projection is not None else values_bct
-                    kv[0][idx, :Tt] = ops.transpose(k.contiguous())
-                    kv[1][idx, :Tt] = ops.transpose(v.contiguous())
+                for kv, p in zip(rows, self._memory_projections(memory, text_positions, speaker_embed)[1]):
+                    if p is not None:
+                        kv[0][idx, :Tt], kv[1][idx, :Tt] = ops.transpose(p[0]), ops.transpose(p[1])
                 wq = self._rate(self.query_position_rate, self.speaker_proj2, speaker_embed)
                 pe = self.embed_query_positions.forward_bct(pos.expand(n, t_cap).contiguous(), wq)      # (n, C, t_cap)
                 pe_all[:, idx] = pe.permute(2, 0, 1)
-                for f, buf in spk_rows.values():
+                for f, buf in spk_rows:
                     se = speaker_embed if speaker_embed.dim() == 2 else speaker_embed[:, 0, :]
                     buf[idx] = f.speaker_bias(se)
 
-            scale = float(2 ** (n_att - 1)) / n_att if n_att else 1.0
-            P.seal(cur_in, outs, dones_seq, states, aligns, write_operands, align_scale=scale)
+            P.seal(cur_in, write_operands)
         return P
-
-    @staticmethod
-    def _incremental_stack(modules, x, speaker_embed):
-        n = len(modules)
-        i = 0
-        while i < n:
-            f = modules[i]
-            if isinstance(f, Conv1dGLU):
-                x = f.incremental_forward(x, speaker_embed)
-            elif isinstance(f, _conv.Conv1d):
-                if i + 1 < n and isinstance(modules[i + 1], nn.ReLU):
-                    x = f.incremental_forward(x, _gate=dict(mode=ops.EPI_RELU))
-                    i += 1
-                else:
-                    x = f.incremental_forward(x)
-            else:
-                x = f(x)
-            i += 1
-        return x
 
     def start_fresh_sequence(self):
         _clear_modules(self.preattention)
         _clear_modules(self.convolutions)
         self.last_conv.clear_buffer()
-
-
-def _item_key_len(text_lengths, B, Tk, device):
-    """Decoder.incremental_forward(text_lengths=...): each item's key count as a device int32[B] (None: reference mode)"""
-    if text_lengths is None:
-        return None
-    tl = torch.as_tensor(text_lengths).reshape(-1).to(torch.int64).cpu()
-    if tl.numel() != B or int(tl.min()) < 1 or int(tl.max()) > Tk:
-        raise ValueError("text_lengths: %d lengths in [1, %d] expected for a batch of %d, got %s" % (
-            B, Tk, B, tl.tolist()))
-    return tl.to(torch.int32).to(device)
 
 
 def _clear_modules(modules):

@@ -211,6 +211,36 @@ class HighwayConv1d(_GatedConv):
         return self.conv.incremental_forward(x, _gate=dict(mode=self.mode, r=r, residual=self.glu))
 
 
+def conv_relu_layers(modules):
+    """The eval-time walk of a "Conv1d (+ReLU)" stack (a pre-attention stack, an audio encoder / decoder sequence):
+    yields (layer, fused_relu), one pair per launch.  An nn.ReLU directly after a plain Conv1d is folded into that
+    layer (fused_relu True) and not yielded.  Every other module -- a gated layer, a ReLU that no plain Conv1d
+    precedes, anything else -- is yielded as it is with fused_relu False: the module-by-module path calls it
+    (incremental_stack), the fused step program has no entry for a module that is not a conv layer and reports the
+    decoder as not eligible."""
+    mods = list(modules)
+    i = 0
+    while i < len(mods):
+        f = mods[i]
+        relu = isinstance(f, _conv.Conv1d) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+        yield f, relu
+        i += 1 + int(relu)
+
+
+def incremental_stack(modules, x, gated, *args):
+    """one decoder step through a stack, module by module: x (B, 1, C) -> (B, 1, C').  gated: the family's gated layer
+    class (Conv1dGLU with args = (speaker_embed,), HighwayConv1d with none), stepped by its incremental_forward(x,
+    *args); a plain Conv1d likewise, with a following ReLU fused; any other module is called on x"""
+    for f, relu in conv_relu_layers(modules):
+        if isinstance(f, gated):
+            x = f.incremental_forward(x, *args)
+        elif isinstance(f, _conv.Conv1d):
+            x = f.incremental_forward(x, _gate=dict(mode=ops.EPI_RELU) if relu else None)
+        else:
+            x = f(x)
+    return x
+
+
 def key_lengths_i32(lengths, device):
     """`input_lengths` as the int32 device vector the attention kernels read.  A tensor already on
     the device is used as is (no host round trip: keeps the step hipGraph-capturable)."""

@@ -13,9 +13,9 @@ from . import ops
 from . import conv as _conv
 from .modules import Embedding, Linear, Conv1d, ConvTranspose1d
 from .modules import HighwayConv1d, get_mask_from_lengths, key_lengths_i32
-from .modules import position_encoding_init
-from .deepvoice3 import AttentionLayer, _c8_enter, _c8_leave, _conv1d_c8, _item_key_len
-from .decode_program import StepTrace, item_results
+from .modules import position_encoding_init, conv_relu_layers, incremental_stack
+from .deepvoice3 import AttentionLayer, _c8_enter, _c8_leave, _conv1d_c8
+from .decode_program import StepProgram, StepTrace, incremental_decode, slot_program_frame
 
 
 def _run_seq(mods, x, valid_axis=None):
@@ -64,26 +64,6 @@ def _run_seq(mods, x, valid_axis=None):
     return _c8_leave(x, C)
 
 
-def _run_seq_incremental(mods, x):
-    mods = list(mods)
-    n = len(mods)
-    i = 0
-    while i < n:
-        f = mods[i]
-        if isinstance(f, _conv.Conv1d):
-            if i + 1 < n and isinstance(mods[i + 1], nn.ReLU):
-                x = f.incremental_forward(x, _gate=dict(mode=ops.EPI_RELU))
-                i += 1
-            else:
-                x = f.incremental_forward(x)
-        elif isinstance(f, HighwayConv1d):
-            x = f.incremental_forward(x)
-        else:
-            x = f(x)
-        i += 1
-    return x
-
-
 class Encoder(nn.Module):
     def __init__(self, n_vocab, embed_dim, channels, kernel_size=3, n_speakers=1, speaker_embed_dim=16,
                  embedding_weight_std=0.01, padding_idx=None, dropout=0.1):
@@ -118,6 +98,8 @@ class Encoder(nn.Module):
 
 
 class Decoder(nn.Module):
+    fast_decode = True        # incremental_forward on the fused decode-step kernels (set False for the module-by-module path)
+
     def __init__(self, embed_dim, in_dim=80, r=5, channels=256, kernel_size=3, n_speakers=1,
                  speaker_embed_dim=16, max_positions=512, padding_idx=None, dropout=0.1,
                  use_memory_mask=False, force_monotonic_attention=False, query_position_rate=1.0,
@@ -211,172 +193,129 @@ class Decoder(nn.Module):
     def _fast_decode_eligible(self, Tk):
         """what the fused step program below takes (csrc/decode_step.hip stages a layer's k-tap window of 4 batch items
         and the attention scores in 64 KB of LDS); anything else runs the module-by-module path"""
-        def fits(conv):
-            return ops.conv_step_fits(conv.kernel_size[0], conv.in_channels)
-        for mods in (self.audio_encoder_modules, self.audio_decoder_modules):
-            for f in mods:
-                if isinstance(f, HighwayConv1d):
-                    if f.glu or not fits(f.conv):
-                        return False
-                elif isinstance(f, _conv.Conv1d):
-                    if f.kernel_size[0] != 1 or not fits(f):
-                        return False
-                elif not isinstance(f, nn.ReLU):
-                    return False
-        E = self.attention.query_projection.out_features
-        return (E + Tk) * 4 <= 64 * 1024 and fits(self.last_conv)
+        P = StepProgram(1, "meta", t_cap=1)      # dry: the builder's own walk, nothing packed, launched or allocated
+        self._slot_entries(P, int(Tk))
+        return P.refused is None
 
-    def _incremental_fast(self, encoder_out, text_positions, initial_input=None, test_inputs=None, key_len=None,
-                          stops=None):
-        """incremental_forward (nyanko.py:250-338) as a flat per-step launch program (decode_program.StepProgram):
-        28 conv-step launches + one attention-step launch per decoder step instead of ~150 module calls; the
-        concat [R, Q] (nyanko.py:308) is one (B, 2D) buffer both producers write into."""
-        from .decode_program import StepProgram
+    def _memory_projections(self, encoder_out, text_positions):
+        """what a decode reads of the encoder memory -> the position-coded keys (B, D, Tk) and the projected
+        (keys, values), contiguous (B, E, Tk)"""
         keys, values = encoder_out
-        B, dev = keys.size(0), keys.device
-        with torch.no_grad():
-            keys_bct = keys.transpose(1, 2).contiguous()
-            if text_positions is not None:
-                keys_bct = ops.add_position_encoding(keys_bct, text_positions, self.embed_keys_positions.weight,
-                                                     None, False)
-            values_bct = values.transpose(1, 2).contiguous()
-            att = self.attention
-            k = (att.key_projection.forward_bct(keys_bct) if att.key_projection is not None else keys_bct).contiguous()
-            v = (att.value_projection.forward_bct(values_bct) if att.value_projection is not None else values_bct).contiguous()
-            Tk = k.size(-1)
-            F = self.in_dim * self.r
-            n_max = test_inputs.size(1) if test_inputs is not None else self.max_decoder_steps + 1
-            P = StepProgram(B, dev)
-            # position code of step t = row t + 1 of the frozen table (nyanko.py:162-166), the same for every item
-            pe_all = self.embed_query_positions.weight[1:n_max + 1].detach().contiguous()      # (n_max, D)
-            if pe_all.size(0) < n_max:
-                raise RuntimeError("decoder steps exceed max_positions")
-            pe_all = pe_all[:, None, :].expand(n_max, B, pe_all.size(1))                          # batch stride 0
-            cur_in = (initial_input.reshape(B, F).clone().float() if initial_input is not None else P.buffer(B, F))
-            free_running = test_inputs is None
-            nxt_in = cur_in if free_running else P.buffer(B, F)
-            D = self.last_conv.in_channels
-            outs, dones_seq = P.buffer(n_max, B, F), P.buffer(n_max, B, 1)
-            states, aligns = P.buffer(n_max, B, D), P.buffer(n_max, B, Tk)
-            cat = P.buffer(B, 2 * D)                       # [R | Q]
-            xq = P.buffer(B, D)
-            P.keep.extend([k, v, pe_all, cur_in, nxt_in])
-
-            self._step_entries(P, cur_in, nxt_in, pe_all, k, v, key_len, outs, dones_seq, states, aligns, cat, xq)
-            t = P.decode(cur_in, test_inputs, dones_seq, self.min_decoder_steps, self.max_decoder_steps,
-                         getattr(self, "use_step_graph", False), getattr(self, "persistent_decode", None),
-                         getattr(self, "launched_decode", None), stops=stops)
-            alignments = aligns[:t].transpose(0, 1)
-            decoder_states = states[:t].transpose(0, 1).contiguous()
-            outputs = outs[:t].transpose(0, 1).contiguous()
-            dones = [dones_seq[i].view(B, 1, 1) for i in range(t)]
-        return outputs, alignments, dones, decoder_states
-
-    def _step_entries(self, P, cur_in, nxt_in, pe_all, k, v, key_len, outs, dones_seq, states, aligns, cat, xq, rows=False):
-        """the step program (nyanko.py:283-321) appended to P; k, v: the projected keys / values (B, E, Tk), or their
-        (B, Tk, E) row images with rows=True; cat (B, 2D) = [R | Q], xq (B, D) = Q + position code"""
-        att = self.attention
-        D = self.last_conv.in_channels
-        F = self.in_dim * self.r
-
-        def run(mods, x, last_kw=None):
-            """a Conv1d(+ReLU) / HighwayConv1d stack, one launch per layer; last_kw: extra outputs of the last layer"""
-            mods = list(mods)
-            i = 0
-            while i < len(mods):
-                f = mods[i]
-                relu = isinstance(f, _conv.Conv1d) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-                last = (i + int(relu)) == len(mods) - 1
-                kw = dict(last_kw) if (last and last_kw) else {}
-                if isinstance(f, HighwayConv1d):
-                    x = P.conv_step(f.conv, x, ops.EPI_HIGHWAY, f.conv.out_channels // 2, k=f.conv.kernel_size[0],
-                                    dil=f.conv.dilation[0], gated=True, **kw)
-                else:
-                    x = P.conv_step(f, x, ops.EPI_RELU if relu else ops.EPI_LINEAR, f.out_channels, **kw)
-                    i += int(relu)
-                i += 1
-            return x
-
-        # audio encoder: Q (into the concat buffer) and Q + position code (the attention query input)
-        run(self.audio_encoder_modules, cur_in, dict(y=xq, post_add=pe_all, y_pre=cat[:, D:]))
-        q = P.conv_step(att.query_projection, xq, ops.EPI_LINEAR, att.query_projection.out_features)
-        ctx = P.attn_step(q, k, v, att.window_backward, att.window_ahead, self.force_monotonic_attention,
-                          attn_seq=aligns, key_len=key_len, rows=rows)
-        P.conv_step(att.out_projection, ctx, ops.EPI_LINEAR, att.out_projection.out_features, r=xq, y=cat[:, :D])
-        x = run(self.audio_decoder_modules, cat, dict(out_seq=states))
-        pre = P.conv_step(self.last_conv, x, ops.EPI_LINEAR, F, y_act=nxt_in, out_seq=outs)
-        P.conv_step(self.fc, pre, ops.EPI_SIGMOID, 1, out_seq=dones_seq)
-
-    def slot_program(self, slots, max_text_len):
-        """The step program in slot mode (decode_program.StepProgram, DESIGN.md 3.6c): built once for `slots` batch
-        slots and texts of up to max_text_len ids; see deepvoice3.Decoder.slot_program.  (The position codes are the
-        frozen table for every item: only the keys and values are per slot.)"""
-        from .decode_program import StepProgram
-        B, Tk = int(slots), int(max_text_len)
-        dev = self.embed_query_positions.weight.device
-        if self.training:
-            raise RuntimeError("slot_program: eval mode only")
-        if dev.type != "cuda" or not getattr(self, "fast_decode", True) or not self._fast_decode_eligible(Tk):
-            raise RuntimeError("slot_program: rolling admission runs on the fused decode-step kernels only, and this "
-                               "decoder (or %d keys) is not eligible for them (_fast_decode_eligible); there is no "
-                               "module-by-module fallback in slot mode" % Tk)
-        att = self.attention
-        F, D = self.in_dim * self.r, self.last_conv.in_channels
-        E = att.query_projection.out_features
-        t_cap = self.max_decoder_steps + 1
-        with torch.no_grad():
-            P = StepProgram(B, dev, t_cap=t_cap)
-            pe_all = self.embed_query_positions.weight[1:t_cap + 1].detach().contiguous()      # (t_cap, D)
-            if pe_all.size(0) < t_cap:
-                raise RuntimeError("slot_program: decoder steps exceed max_positions")
-            pe_all = pe_all[:, None, :].expand(t_cap, B, pe_all.size(1))                         # batch stride 0
-            cur_in = P.buffer(B, F)
-            outs, dones_seq = P.buffer(t_cap, B, F), P.buffer(t_cap, B, 1)
-            states, aligns = P.buffer(t_cap, B, D), P.buffer(t_cap, B, Tk)
-            cat, xq = P.buffer(B, 2 * D), P.buffer(B, D)
-            kt, vt = P.buffer(B, Tk, E), P.buffer(B, Tk, E)
-            P.keep.append(pe_all)
-            self._step_entries(P, cur_in, cur_in, pe_all, kt, vt, None, outs, dones_seq, states, aligns, cat, xq, rows=True)
-
-            def write_operands(idx, memory, text_positions, speaker_embed):
-                keys, values = memory
-                Tt = keys.size(1)
-                if Tt > Tk:
-                    raise ValueError("slot_program: %d keys, the slots hold %d" % (Tt, Tk))
-                keys_bct = keys.transpose(1, 2).contiguous()
-                if text_positions is not None:
-                    keys_bct = ops.add_position_encoding(keys_bct, text_positions, self.embed_keys_positions.weight,
-                                                         None, False)
-                values_bct = values.transpose(1, 2).contiguous()
-                k = att.key_projection.forward_bct(keys_bct) if att.key_projection is not None else keys_bct
-                v = att.value_projection.forward_bct(values_bct) if att.value_projection is not None else values_bct
-                kt[idx, :Tt] = ops.transpose(k.contiguous())
-                vt[idx, :Tt] = ops.transpose(v.contiguous())
-
-            P.seal(cur_in, outs, dones_seq, states, aligns, write_operands)
-        return P
-
-    def incremental_forward(self, encoder_out, text_positions, initial_input=None, test_inputs=None,
-                            text_lengths=None):
-        """nyanko.py:250-338.  text_lengths: per-utterance mode, as deepvoice3.Decoder.incremental_forward."""
-        keys, values = encoder_out
-        B = keys.size(0)
-        dev = keys.device
-        key_len = _item_key_len(text_lengths, B, keys.size(1), dev)
-        stops = [0] * B if key_len is not None else None
-        if getattr(self, "fast_decode", True) and keys.is_cuda and self._fast_decode_eligible(keys.size(1)):
-            res = self._incremental_fast(encoder_out, text_positions, initial_input, test_inputs, key_len, stops)
-            return res if stops is None else item_results(stops, *res)
         keys_bct = keys.transpose(1, 2).contiguous()
         if text_positions is not None:
             keys_bct = ops.add_position_encoding(keys_bct, text_positions, self.embed_keys_positions.weight,
                                                  None, False)
         values_bct = values.transpose(1, 2).contiguous()
-        Tk = keys_bct.size(-1)
         att = self.attention
         k = att.key_projection.forward_bct(keys_bct) if att.key_projection is not None else keys_bct
         v = att.value_projection.forward_bct(values_bct) if att.value_projection is not None else values_bct
+        return keys_bct, (k.contiguous(), v.contiguous())
 
+    def _position_codes(self, n, B):
+        """position code of step t = row t + 1 of the frozen table (nyanko.py:162-166), the same for every item
+        -> (n, B, D) with batch stride 0"""
+        pe = self.embed_query_positions.weight[1:n + 1].detach().contiguous()
+        if pe.size(0) < n:
+            raise RuntimeError("decoder steps exceed max_positions")
+        return pe[:, None, :].expand(n, B, pe.size(1))
+
+    def _incremental_fast(self, encoder_out, text_positions, initial_input=None, test_inputs=None, key_len=None,
+                          stops=None):
+        """incremental_forward (nyanko.py:250-338) as a flat per-step launch program (decode_program.StepProgram):
+        27 conv-step launches + one attention-step launch per decoder step instead of ~150 module calls; the
+        concat [R, Q] (nyanko.py:308) is one (B, 2D) buffer both producers write into."""
+        keys = encoder_out[0]
+        B, F = keys.size(0), self.in_dim * self.r
+        with torch.no_grad():
+            k, v = self._memory_projections(encoder_out, text_positions)[1]
+            n_max = test_inputs.size(1) if test_inputs is not None else self.max_decoder_steps + 1
+            P = StepProgram(B, keys.device)
+            cur_in = (initial_input.reshape(B, F).clone().float() if initial_input is not None else P.buffer(B, F))
+            nxt_in = cur_in if test_inputs is None else P.buffer(B, F)
+            P.keep.extend([k, v, cur_in, nxt_in])
+            self._step_entries(P, n_max, keys.size(1), cur_in, nxt_in, k, v, key_len)
+            return None if P.refused else P.decode_for(self, cur_in, test_inputs, stops)
+
+    def _step_entries(self, P, n, Tk, cur_in, nxt_in, k, v, key_len, rows=False):
+        """The step program (nyanko.py:283-321) appended to P, with its stacked outputs of n rows over Tk keys: the one
+        walk over this decoder's layers, for the per-batch program, the slot program and the eligibility check alike.
+        A layer it has no entry for is refused (P.refuse) and ends the walk.  k, v: the projected keys / values
+        (B, E, Tk), or their (B, Tk, E) row images with rows=True"""
+        att = self.attention
+        D = self.last_conv.in_channels
+        F = self.in_dim * self.r
+        P.stack(n, F, D, Tk)
+        pe_all = self._position_codes(n, P.B)
+        cat, xq = P.buffer(P.B, 2 * D), P.buffer(P.B, D)         # [R | Q]; Q + position code
+        P.keep.append(pe_all)
+
+        def run(mods, x, last_kw):
+            """a Conv1d(+ReLU) / HighwayConv1d stack, one launch per layer; last_kw: extra outputs of the last layer
+            -> its output, None if a layer was refused"""
+            layers = list(conv_relu_layers(mods))
+            for i, (f, relu) in enumerate(layers):
+                kw = last_kw if i == len(layers) - 1 else {}
+                if isinstance(f, HighwayConv1d) and not f.glu:
+                    x = P.conv_step(f.conv, x, ops.EPI_HIGHWAY, f.conv.out_channels // 2, k=f.conv.kernel_size[0],
+                                    dil=f.conv.dilation[0], gated=True, **kw)
+                elif isinstance(f, _conv.Conv1d) and f.kernel_size[0] == 1:
+                    x = P.conv_step(f, x, ops.EPI_RELU if relu else ops.EPI_LINEAR, f.out_channels, **kw)
+                else:
+                    return P.refuse("module %r (a HighwayConv1d without glu or a 1x1 Conv1d is taken)" % f)
+            return x
+
+        # audio encoder: Q (into the concat buffer) and Q + position code (the attention query input)
+        if run(self.audio_encoder_modules, cur_in, dict(y=xq, post_add=pe_all, y_pre=cat[:, D:])) is None:
+            return
+        q = P.conv_step(att.query_projection, xq, ops.EPI_LINEAR, att.query_projection.out_features)
+        ctx = P.attn_step(q, k, v, att.window_backward, att.window_ahead, self.force_monotonic_attention,
+                          attn_seq=P.aligns, key_len=key_len, rows=rows)
+        P.conv_step(att.out_projection, ctx, ops.EPI_LINEAR, att.out_projection.out_features, r=xq, y=cat[:, :D])
+        x = run(self.audio_decoder_modules, cat, dict(out_seq=P.states))
+        if x is None:
+            return
+        pre = P.conv_step(self.last_conv, x, ops.EPI_LINEAR, F, y_act=nxt_in, out_seq=P.outs)
+        P.conv_step(self.fc, pre, ops.EPI_SIGMOID, 1, out_seq=P.dones_seq)
+
+    def _slot_entries(self, P, Tk):
+        """the step program on per-slot key / value rows of P's own, filled at admission (slot_program) or never (the
+        dry program of _fast_decode_eligible) -> (decoder-input buffer, key rows, value rows (B, Tk, E))"""
+        E = self.attention.query_projection.out_features
+        cur_in, kt, vt = P.buffer(P.B, self.in_dim * self.r), P.buffer(P.B, Tk, E), P.buffer(P.B, Tk, E)
+        self._step_entries(P, P.t_cap, Tk, cur_in, cur_in, kt, vt, None, rows=True)
+        return cur_in, kt, vt
+
+    def slot_program(self, slots, max_text_len):
+        """The step program in slot mode (decode_program.StepProgram, DESIGN.md 3.6c): built once for `slots` batch
+        slots and texts of up to max_text_len ids; see deepvoice3.Decoder.slot_program.  (The position codes are the
+        frozen table for every item: only the keys and values are per slot.)"""
+        Tk = int(max_text_len)
+        P = slot_program_frame(self, slots, Tk, self.embed_query_positions.weight.device)
+        with torch.no_grad():
+            cur_in, kt, vt = self._slot_entries(P, Tk)
+
+            def write_operands(idx, memory, text_positions, speaker_embed):
+                Tt = memory[0].size(1)
+                if Tt > Tk:
+                    raise ValueError("slot_program: %d keys, the slots hold %d" % (Tt, Tk))
+                k, v = self._memory_projections(memory, text_positions)[1]
+                kt[idx, :Tt], vt[idx, :Tt] = ops.transpose(k), ops.transpose(v)
+
+            P.seal(cur_in, write_operands)
+        return P
+
+    def incremental_forward(self, encoder_out, text_positions, initial_input=None, test_inputs=None,
+                            text_lengths=None):
+        """nyanko.py:250-338.  text_lengths: per-utterance mode, as deepvoice3.Decoder.incremental_forward."""
+        return incremental_decode(self, encoder_out, text_lengths, text_positions, initial_input, test_inputs)
+
+    def _incremental_modules(self, encoder_out, text_positions, initial_input=None, test_inputs=None, key_len=None,
+                             stops=None):
+        """incremental_forward module by module: every configuration the reference handles"""
+        keys = encoder_out[0]
+        B, Tk, dev = keys.size(0), keys.size(1), keys.device
+        att = self.attention
+        k, v = self._memory_projections(encoder_out, text_positions)[1]
         trace = StepTrace(self.min_decoder_steps, self.max_decoder_steps, test_inputs is not None, stops)
         last_attended = (torch.zeros(1 if key_len is None else 2 * B, dtype=torch.int32, device=dev)
                          if self.force_monotonic_attention else None)
@@ -391,7 +330,7 @@ class Decoder(nn.Module):
                 current_input = test_inputs[:, t:t + 1, :]
             else:
                 current_input = trace.last_output if t > 0 else initial_input
-            x = _run_seq_incremental(self.audio_encoder_modules, current_input)      # (B, 1, D)
+            x = incremental_stack(self.audio_encoder_modules, current_input, HighwayConv1d)      # (B, 1, D)
             Q = x
             xq = ops.add_position_encoding(x.transpose(1, 2).contiguous(), frame_pos,
                                            self.embed_query_positions.weight, None, False)
@@ -408,7 +347,7 @@ class Decoder(nn.Module):
                 ops._lib.call("dv3_attn_argmax_i32", alignment.data_ptr(), Tk, last_attended.data_ptr(),
                               ops._stream())
             x = torch.cat((R, Q), dim=-1)
-            x = _run_seq_incremental(self.audio_decoder_modules, x)
+            x = incremental_stack(self.audio_decoder_modules, x, HighwayConv1d)
             decoder_state = x
             x = self.last_conv.incremental_forward(x)
             done = torch.sigmoid(self.fc(x))
@@ -416,7 +355,7 @@ class Decoder(nn.Module):
             t += 1
             if trace.stop(done):
                 break
-        return trace.result() if stops is None else item_results(stops, *trace.result())
+        return trace.result()
 
     def start_fresh_sequence(self):
         """forget the incremental state of every layer that keeps one (nyanko.py:340-343)"""

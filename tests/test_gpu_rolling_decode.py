@@ -6,7 +6,9 @@ decoder families, and synthesis.tts_stream.
      batch group, one idle slot, one slot that overruns t_cap): every item bit-equal to the same item alone at B = 1 on
      the shared counter, and within the bounds of tests/decode_step_ref.py of the float64 references;
   2. decoder level: 12 utterances through 4 slots with staggered admission, every item bit-equal to
-     Decoder.incremental_forward at B = 1 on its own encoder output (slots are reused after longer utterances);
+     Decoder.incremental_forward at B = 1 on its own encoder output (slots are reused after longer utterances); the
+     per-batch and the slot program of one decoder descriptor for descriptor, and against the presets' table of
+     tests/test_cpu_decode_plan.py; a stack the program has no entry for decodes module by module;
   3. end to end: synthesis.tts_stream against synthesis.tts_batch;
   4. the refusals.
 """
@@ -375,6 +377,118 @@ def test_slot_program_items_equal_b1(dev, family):
         assert torch.equal(ali[:, :s], wa[0]), (family, b, "alignments")
         assert not ali[:, s:].any(), (family, b)
         assert torch.equal(done, torch.cat([d.reshape(1) for d in wd])), (family, b, "done flags")
+
+
+def _batch_program(dec, *args, **kw):
+    """the program one incremental_forward call builds, caught where the decoder hands it to StepProgram.decode"""
+    from deepvoice3_pytorch_amd.decode_program import StepProgram
+    caught, decode = [], StepProgram.decode
+
+    def spy(self, *a, **k):
+        caught.append(self)
+        return decode(self, *a, **k)
+
+    StepProgram.decode = spy
+    try:
+        dec.incremental_forward(*args, **kw)
+    finally:
+        StepProgram.decode = decode
+    assert len(caught) == 1
+    return caught[0]
+
+
+SLOT_FIELDS = ("t_off", "t_cap", "key_len")           # what a slot program sets and a per-batch program does not
+
+
+def _descriptor(d):
+    """every field of a step descriptor the two builders must agree in: the shape and mode fields by value, the pointers
+    as set / null; strides and the slot fields aside"""
+    shape = ("B", "Cin", "M", "Cg", "J", "dil", "mode", "residual", "L", "E", "Tk", "win_back", "win_ahead", "kv_tke")
+    out = {}
+    for f, t in d._fields_:
+        if f in SLOT_FIELDS:
+            continue
+        if t is ctypes.c_void_p:
+            out[f] = bool(getattr(d, f))
+        elif f in shape:
+            out[f] = getattr(d, f)
+    return out
+
+
+@pytest.mark.parametrize("family", ["nyanko", "deepvoice3", "multispeaker", "deepvoice3_ljspeech", "deepvoice3_vctk",
+                                    "nyanko_ljspeech"])
+def test_batch_and_slot_programs_agree(dev, family):
+    """Decoder._incremental_fast and Decoder.slot_program append the same entries (one walk, _step_entries): kind, B,
+    Cin, M, Cg, J, dil, mode, residual, L and which optional pointers are set, entry for entry; built from a preset they
+    are the table of tests/test_cpu_decode_plan.py"""
+    from tests.test_cpu_decode_plan import PLAN, plan_rows
+    model, hp = _toy(family, dev)
+    dec = model.seq2seq.decoder
+    dec.min_decoder_steps = dec.max_decoder_steps = 3
+    multi = hp.get("n_speakers", 1) > 1
+    B, Tk = 2, 16
+    g = torch.Generator().manual_seed(5)
+    text = torch.randint(2, hp["n_vocab"], (B, Tk), generator=g).to(dev)
+    tpos = torch.arange(1, Tk + 1, device=dev).repeat(B, 1)
+    with torch.no_grad():
+        se = model.embed_speakers(torch.tensor([1, 0], device=dev)) if multi else None
+        enc = model.seq2seq.encoder(text, **(dict(speaker_embed=se) if multi else {}))
+        kw = dict(speaker_embed=se) if multi else {}
+        batch = _batch_program(dec, enc, tpos, **kw)
+        per_item = _batch_program(dec, enc, tpos, text_lengths=[Tk, 9], **kw)
+        slot = dec.slot_program(B, Tk)
+    assert len(batch.prog) == len(per_item.prog) == len(slot.prog)
+    for i, ((nb, db), (ni, di), (ns, ds)) in enumerate(zip(batch.prog, per_item.prog, slot.prog)):
+        assert nb == ni == ns, (family, i)
+        assert _descriptor(db) == _descriptor(di) == _descriptor(ds), (family, i, nb, _descriptor(db), _descriptor(ds))
+        assert ds.t_cap == slot.t_cap and ds.t_off and not db.t_off and not db.t_cap, (family, i)
+        if nb == "dv3_attn_step_f32":
+            assert ds.key_len and di.key_len and not db.key_len, (family, i)
+    assert batch.align_scale == slot.align_scale
+    if family in PLAN:
+        assert plan_rows(batch) == plan_rows(slot) == PLAN[family], family
+
+
+def test_stray_relu_falls_back_to_the_module_path(dev):
+    """a nyanko stack with a ReLU directly after a HighwayConv1d: the step program has no entry for it, so the decoder
+    is not eligible and incremental_forward runs module by module -- the tensors of fast_decode = False, bit for bit"""
+    from torch import nn
+    from deepvoice3_pytorch_amd.modules import HighwayConv1d
+    model, hp = _toy("nyanko", dev)
+    dec = model.seq2seq.decoder
+    mods = list(dec.audio_decoder_modules)
+    i = next(i for i, f in enumerate(mods) if isinstance(f, HighwayConv1d))
+    dec.audio_decoder_modules = nn.ModuleList(mods[:i + 1] + [nn.ReLU()] + mods[i + 1:])
+    dec.min_decoder_steps, dec.max_decoder_steps = 4, 9
+    assert dec._fast_decode_eligible(16) is False
+    with pytest.raises(RuntimeError, match="not eligible"):
+        dec.slot_program(2, 16)
+    g = torch.Generator().manual_seed(9)
+    text = torch.randint(2, hp["n_vocab"], (2, 13), generator=g).to(dev)
+    tpos = torch.arange(1, 14, device=dev).repeat(2, 1)
+    taken = []                                        # which path answered: (name, it returned a result)
+    for name in ("_incremental_fast", "_incremental_modules"):
+        def spy(*a, _f=getattr(dec, name), _n=name, **k):
+            out = _f(*a, **k)
+            taken.append((_n, out is not None))
+            return out
+        setattr(dec, name, spy)
+    with torch.no_grad():
+        enc = model.seq2seq.encoder(text)
+        for tl in (None, [13, 6]):
+            res = {}
+            for fast in (True, False):
+                dec.fast_decode = fast
+                dec.start_fresh_sequence()
+                del taken[:]
+                res[fast] = dec.incremental_forward(enc, tpos, text_lengths=tl)
+                # fast: the program's build was refused and the module path took the call; else the module path alone
+                assert taken == ([("_incremental_fast", False)] if fast else []) + [("_incremental_modules", True)], taken
+            a, b = res[True], res[False]
+            assert 5 <= a[0].size(1) <= 10 and bool(torch.isfinite(a[0]).all())
+            assert len(a) == len(b) == (4 if tl is None else 5) and len(a[2]) == len(b[2])
+            for x, y in zip((a[0], a[1], a[3]) + tuple(a[2]) + tuple(a[4:]), (b[0], b[1], b[3]) + tuple(b[2]) + tuple(b[4:])):
+                assert torch.equal(x, y), tl
 
 
 # ----------------------------------------------------------------------------------------------------------------------
