@@ -43,6 +43,7 @@ if not os.path.isabs(_LIBPATH):
 
 _CTYPES = {
     "float": ctypes.c_float,
+    "double": ctypes.c_double,
     "int32_t": ctypes.c_int32,
     "int64_t": ctypes.c_int64,
     "uint32_t": ctypes.c_uint32,

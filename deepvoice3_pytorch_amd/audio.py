@@ -33,6 +33,11 @@ harmonics moved along the frequency axis under the spectral envelope.  Off by de
 
 Pitch: yin_items tracks F0 per frame of the packed waveforms features_items takes (csrc/pitch.hip), voiced() decides
 which frames to believe (PitchConfig); synthesis.waveform_distortion builds the F0 and voicing error of an evaluation on it.
+
+Deliverable audio (csrc/master.hip): the reference ends at save_wav (audio.py:16-18: peak-normalise, int16, a file).
+wave_levels measures every utterance, wave_gains turns levels into gains under a Mastering, wave_master places, scales,
+fades and quantises in one launch; master_items / to_pcm16 apply them to a padded batch, save_wav writes the file.
+synthesis.join_utterances builds a document of several utterances on them.  Off by default: nothing runs unasked.
 """
 import numpy as np
 import torch
@@ -1122,3 +1127,281 @@ def prepare_items(wavs, source_rate, cfg=None, spans=None, top_db=15.0, device="
             lens[b] = hi - lo
     t_starts, t_lens = trim_items(res, starts, lens, top_db)
     return gather_spans(res, t_starts, t_lens)
+
+
+# ---------------------------------------------------------------------------------------------
+# deliverable audio: levels, gains, and one launch that places, scales, fades and quantises (csrc/master.hip)
+# ---------------------------------------------------------------------------------------------
+LEVEL_COLUMNS = ("peak", "sumsq", "sum", "over", "nonfinite")      # the columns of a level row (dv3_wave_levels_f32)
+_MASTER_MODES = {"float32": "DV3_MASTER_F32", "int16": "DV3_MASTER_I16"}
+_GAIN_POLICIES = {"peak": "DV3_GAIN_PEAK", "rms": "DV3_GAIN_RMS", "reference": "DV3_GAIN_REFERENCE"}
+
+
+def _span_tables(wav_flat, starts, lengths, max_len, what):
+    """host integers or int64 device tensors -> (starts_d, lengths_d, B, max_len): device tensors need max_len, a bound
+    on every length (the kernel clamps at it), because nothing is read back here"""
+    dev = wav_flat.device
+    if torch.is_tensor(starts) and torch.is_tensor(lengths) and starts.is_cuda and lengths.is_cuda:
+        if max_len is None:
+            raise ValueError("%s: spans on the device need max_len= (a bound on the lengths; nothing is read back)" % what)
+        return _c(starts.to(torch.int64)), _c(lengths.to(torch.int64)), int(starts.numel()), int(max_len)
+    starts_h, lengths_h = _spans(wav_flat, starts, lengths, what)
+    sl = torch.from_numpy(np.concatenate([starts_h, lengths_h])).to(dev, non_blocking=True)
+    return sl[:starts_h.size], sl[starts_h.size:], int(starts_h.size), int(lengths_h.max())
+
+
+def wave_levels(wav_flat, starts, lengths, max_len=None):
+    """The level of B spans of a flat float32 device tensor, span b = wav_flat[starts[b] : starts[b] + lengths[b]] (host
+    integers, or int64 device tensors together with max_len=, a bound on the lengths) -> float64 (B, 5) on the device,
+    columns LEVEL_COLUMNS: peak = max |x| and sumsq, sum over the finite samples (fp64 accumulation in a fixed order),
+    over = samples with |x| >= 1, nonfinite = NaN or infinite samples.  A padded (B, L) batch is B spans at b * L of its
+    flattened view, nothing repacked.  Row b is a function of item b's samples alone (include/dv3hip.h:
+    dv3_wave_levels_f32).  No host read."""
+    wav_flat = _c(_chk(wav_flat, "wav_flat")).reshape(-1)
+    starts_d, lengths_d, B, max_len = _span_tables(wav_flat, starts, lengths, max_len, "wave_levels")
+    if not 1 <= B <= 65535:
+        raise ValueError("wave_levels: %d spans, at most 65535 per call" % B)
+    dev = wav_flat.device
+    nchunk = -(-max_len // _lib.CONSTS["DV3_LEVELS_CHUNK"])
+    scratch = torch.empty(max(B * nchunk * len(LEVEL_COLUMNS), 1), dtype=torch.float64, device=dev)
+    levels = torch.empty((B, len(LEVEL_COLUMNS)), dtype=torch.float64, device=dev)
+    _lib.call("dv3_wave_levels_f32", wav_flat.data_ptr(), starts_d.data_ptr(), lengths_d.data_ptr(), B, max_len,
+              scratch.data_ptr(), levels.data_ptr(), _stream())
+    return levels
+
+
+def _db(v, what, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not lo <= float(v) <= hi:
+        raise ValueError("Mastering: %s=%r must be a number in [%g, %g]" % (what, v, lo, hi))
+    return float(v)
+
+
+class Mastering(object):
+    """How synthesised waveforms become deliverable audio (master_items, synthesis.join_utterances).
+    level: None (gain 1), "peak" (the largest |x| goes to target_db dBFS), "rms" (the RMS goes to target_db dBFS, but
+    no peak above ceiling_db) or "reference" (the reference's save_wav, audio.py:16-18: x * 32767 / max(0.01, peak)
+    truncated to int16 -- it takes dtype "int16", no dither and no fades); scope: "item" (every utterance its own gain)
+    or "document" (one gain from the combined levels of all of them); target_db: default -1 for "peak", -20 for "rms";
+    max_gain_db caps the gain of "peak" and "rms" (a near-silent item is not blown up); fade_ms: the raised-cosine fade
+    at a document's joins and edges (join_utterances; master_items fades nothing); dither, seed: TPDF dither of +-1 LSB
+    before the int16 rounding, a function of (seed, sample index); dtype: "int16" or "float32".
+    The defaults are starting points, not measurements: nothing here was heard on a trained voice.
+    Refused by value (ValueError naming it)."""
+
+    def __init__(self, level=None, scope="item", target_db=None, ceiling_db=-1.0, max_gain_db=30.0, fade_ms=5.0,
+                 dither=False, seed=0, dtype="int16"):
+        if level is not None and level not in _GAIN_POLICIES:
+            raise ValueError("Mastering: level=%r must be None, 'peak', 'rms' or 'reference'" % (level,))
+        if scope not in ("item", "document"):
+            raise ValueError("Mastering: scope=%r must be 'item' or 'document'" % (scope,))
+        if dtype not in _MASTER_MODES:
+            raise ValueError("Mastering: dtype=%r must be 'int16' or 'float32'" % (dtype,))
+        if not isinstance(dither, (bool, np.bool_)):
+            raise ValueError("Mastering: dither=%r must be True or False" % (dither,))
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("Mastering: seed=%r must be an integer in [0, 2^64)" % (seed,))
+        if target_db is None:
+            target_db = -20.0 if level == "rms" else -1.0
+        self.level, self.scope, self.dtype = level, scope, dtype
+        self.target_db = _db(target_db, "target_db", -120.0, 0.0)
+        self.ceiling_db = _db(ceiling_db, "ceiling_db", -120.0, 0.0)
+        self.max_gain_db = _db(max_gain_db, "max_gain_db", 0.0, 120.0)
+        self.fade_ms = _db(fade_ms, "fade_ms", 0.0, 1000.0)
+        self.dither, self.seed = bool(dither), int(seed)
+        if self.dither and dtype != "int16":
+            raise ValueError("Mastering: dither=True needs dtype='int16'")
+        if level == "reference" and (dtype != "int16" or self.dither):
+            raise ValueError("Mastering: level='reference' is the reference's save_wav: dtype='int16' and no dither")
+
+    def mode(self):
+        """the DV3_MASTER_* output mode"""
+        return _lib.CONSTS["DV3_MASTER_I16_REFERENCE" if self.level == "reference" else _MASTER_MODES[self.dtype]]
+
+    def fade_samples(self, sample_rate):
+        """F = round(fade_ms * sample_rate / 1000) (halves up), 0 under the "reference" level; ValueError above
+        DV3_MASTER_MAX_FADE"""
+        if self.level == "reference":
+            return 0
+        F = int(np.floor(self.fade_ms * float(sample_rate) / 1000.0 + 0.5))
+        if F > _lib.CONSTS["DV3_MASTER_MAX_FADE"]:
+            raise ValueError("Mastering: fade_ms=%r is %d samples at %r Hz, at most %d" % (
+                self.fade_ms, F, sample_rate, _lib.CONSTS["DV3_MASTER_MAX_FADE"]))
+        return F
+
+
+def check_mastering(mastering, what):
+    """the `mastering=` keyword -> None or the Mastering; anything else is refused"""
+    if mastering is not None and not isinstance(mastering, Mastering):
+        raise ValueError("%s: mastering must be an audio.Mastering, got %r" % (what, mastering))
+    return mastering
+
+
+def wave_gains(levels, lengths, mastering, groups=None):
+    """Levels -> the per-item values the master launch takes, float32 (B,) on the device: levels (B, 5) from wave_levels,
+    lengths int64 (B,) on the device, mastering.level the policy ("peak", "rms": a multiplier; "reference": the divisor
+    max(0.01, peak)), groups: None (mastering.scope decides: every item alone, or all of them one group) or the group
+    offsets, ascending host ints from 0 to B.  fp64 on the device, rounded once (include/dv3hip.h: dv3_wave_gains_f32)."""
+    if mastering.level is None:
+        raise ValueError("wave_gains: mastering.level is None (the gain is 1: nothing to compute)")
+    B = int(levels.shape[0])
+    if tuple(levels.shape) != (B, len(LEVEL_COLUMNS)) or levels.dtype != torch.float64 or not levels.is_cuda:
+        raise ValueError("wave_gains: levels must be wave_levels' float64 (B, 5) device table")
+    if lengths.numel() != B or lengths.dtype != torch.int64 or not lengths.is_cuda:
+        raise ValueError("wave_gains: lengths must be an int64 device tensor of %d items" % B)
+    if groups is None:
+        groups = list(range(B + 1)) if mastering.scope == "item" else [0, B]
+    goff = np.asarray(groups, dtype=np.int64).reshape(-1)
+    if goff.size < 2 or goff[0] != 0 or goff[-1] != B or np.any(np.diff(goff) < 0):
+        raise ValueError("wave_gains: groups must ascend from 0 to %d, got %s" % (B, goff.tolist()))
+    dev = levels.device
+    goff_d = torch.from_numpy(goff.astype(np.int32)).to(dev, non_blocking=True)
+    gain = torch.empty(B, dtype=torch.float32, device=dev)
+    lin = lambda db: 10.0 ** (db / 20.0)
+    _lib.call("dv3_wave_gains_f32", _c(levels).data_ptr(), _c(lengths).data_ptr(), goff_d.data_ptr(), B, goff.size - 1,
+              _lib.CONSTS[_GAIN_POLICIES[mastering.level]], lin(mastering.target_db), lin(mastering.ceiling_db),
+              lin(mastering.max_gain_db), gain.data_ptr(), _stream())
+    return gain
+
+
+_FADE_CACHE = {}
+
+
+def fade_table_np(F):
+    """the rising half of a raised cosine sampled at the half-sample points: fade[i] = 0.5 - 0.5 cos(pi (i + 0.5) / F) in
+    float64, rounded once to float32; fade[i] + fade[F - 1 - i] is 1 within one ulp"""
+    i = np.arange(int(F), dtype=np.float64)
+    return (0.5 - 0.5 * np.cos(np.pi * (i + 0.5) / float(F))).astype(np.float32) if F else np.zeros(0, np.float32)
+
+
+def fade_table(device, F):
+    key = (str(device), int(F))
+    if key not in _FADE_CACHE:
+        _FADE_CACHE[key] = torch.from_numpy(fade_table_np(F)).to(device)
+    return _FADE_CACHE[key]
+
+
+def check_segments(src, length, dst, total, N, reference=False):
+    """the layout rules of dv3_wave_master_f32 on host integers -> (src, len, dst) int64 arrays; ValueError on a span
+    outside the `total` source samples or the N output samples, on starts or ends that do not ascend, on an output sample
+    under three segments, and in the reference mode on any overlap"""
+    src, length, dst = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (src, length, dst))
+    S = src.size
+    if S < 1 or length.size != S or dst.size != S or S > _lib.CONSTS["DV3_MASTER_MAX_SEGMENTS"]:
+        raise ValueError("wave_master: %d / %d / %d entries of src / len / dst (1 .. %d segments)" % (
+            src.size, length.size, dst.size, _lib.CONSTS["DV3_MASTER_MAX_SEGMENTS"]))
+    if int(length.min()) < 0 or int(src.min()) < 0 or int((src + length).max()) > int(total):
+        raise ValueError("wave_master: a segment's span lies outside the %d source samples" % int(total))
+    end = dst + length
+    if int(dst.min()) < 0 or int(end.max()) > int(N):
+        raise ValueError("wave_master: a segment lies outside the %d output samples" % int(N))
+    if np.any(np.diff(dst) < 0) or np.any(np.diff(end) < 0):
+        raise ValueError("wave_master: segments are not sorted (dst and dst + len must both ascend)")
+    live = np.flatnonzero(length > 0)                     # an empty segment covers nothing
+    if reference and live.size > 1 and np.any(dst[live][1:] < end[live][:-1]):
+        raise ValueError("wave_master: the reference mode takes no overlapping segments")
+    if live.size > 2 and np.any(dst[live][2:] < end[live][:-2]):
+        raise ValueError("wave_master: an output sample is covered by three segments (at most two: a crossfade)")
+    return src, length, dst
+
+
+def wave_master(wav_flat, src, length, dst, gain, flags, N, fade_samples=0, dtype="int16", reference=False, dither=False,
+                seed=0):
+    """ONE launch that builds N output samples from S segments of a flat float32 device tensor: segment s =
+    wav_flat[src[s] : src[s] + length[s]] goes to out[dst[s] : dst[s] + length[s]] times gain[s] (a float32 device
+    tensor, or None: 1), faded in over its first / out over its last fade_samples samples where flags[s] has bit 0 / bit
+    1; two segments laid over each other are added (a crossfade), samples under no segment are zero.  src, length, dst,
+    flags: host integers, checked here (check_segments).  dtype "float32", or "int16" (round to nearest even of y *
+    32767, saturating; dither=True adds TPDF dither from (seed, sample index) first); reference=True: int16 as the
+    reference's save_wav makes it, gain[s] the DIVISOR max(0.01, peak).  include/dv3hip.h (dv3_wave_master_f32) states
+    every step; tests/master_ref.py restates it.  -> the (N,) output; no host read."""
+    wav_flat = _c(_chk(wav_flat, "wav_flat")).reshape(-1)
+    N, F = int(N), int(fade_samples)
+    src, length, dst = check_segments(src, length, dst, wav_flat.numel(), N, reference)
+    S = src.size
+    flags = np.array(np.broadcast_to(np.asarray(flags, dtype=np.int32), (S,)))        # (a writable copy)
+    if dtype not in _MASTER_MODES or (reference and dtype != "int16"):
+        raise ValueError("wave_master: dtype=%r (reference=%r)" % (dtype, reference))
+    if not 0 <= F <= _lib.CONSTS["DV3_MASTER_MAX_FADE"]:
+        raise ValueError("wave_master: fade_samples=%d outside [0, %d]" % (F, _lib.CONSTS["DV3_MASTER_MAX_FADE"]))
+    dev = wav_flat.device
+    tab = torch.from_numpy(np.concatenate([src, length, dst])).to(dev, non_blocking=True)
+    flags_d = torch.from_numpy(flags).to(dev, non_blocking=True)
+    if gain is None:
+        gain = torch.ones(S, dtype=torch.float32, device=dev)
+    if gain.numel() != S or gain.dtype != torch.float32 or not gain.is_cuda:
+        raise ValueError("wave_master: gain must be a float32 device tensor of %d values" % S)
+    gain = _c(gain)
+    fade = fade_table(dev, F) if F else None
+    mode = _lib.CONSTS["DV3_MASTER_I16_REFERENCE" if reference else _MASTER_MODES[dtype]]
+    out = torch.empty(N, dtype=torch.int16 if dtype == "int16" else torch.float32, device=dev)
+    if N == 0:                                            # (every segment empty: nothing to launch)
+        return out
+    _lib.call("dv3_wave_master_f32", wav_flat.data_ptr(), tab[:S].data_ptr(), tab[S:2 * S].data_ptr(), tab[2 * S:].data_ptr(),
+              gain.data_ptr(), flags_d.data_ptr(), S, fade.data_ptr() if F else None, F, mode, int(bool(dither)), int(seed),
+              out.data_ptr(), N, _stream())
+    return out
+
+
+def master_items(wavs, samples, mastering):
+    """Every utterance of a padded batch mastered ALONE: wavs (B, L) float32 on the device (tts_batch's Griffin-Lim
+    output), samples: B host ints (item b is its first samples[b] samples; the lengths are already on the host, so
+    nothing is read back), mastering: a Mastering.  -> (B, L) of mastering.dtype, item b's samples first and zeros behind
+    them (a view of a buffer whose rows are padded to 16 bytes).  Levels, gains (they stay on the device) and one master
+    launch; with dither one master launch per item, each counting its samples from 0, so that an item's bits do not
+    depend on what shares its batch.  No fades: fade_ms is for join_utterances."""
+    mastering = check_mastering(mastering, "master_items")
+    if mastering is None:
+        raise ValueError("master_items: mastering is None")
+    wavs = _c(_chk(wavs, "wavs"))
+    if wavs.dim() != 2 or min(wavs.shape) < 1:
+        raise ValueError("master_items: a non-empty (B, L) batch expected, got %s" % (tuple(wavs.shape),))
+    B, L = wavs.shape
+    samples = np.asarray(torch.as_tensor(samples).cpu() if torch.is_tensor(samples) else samples, dtype=np.int64).reshape(-1)
+    if samples.size != B or int(samples.min()) < 0 or int(samples.max()) > L:
+        raise ValueError("master_items: %d lengths in [0, %d] expected, got %s" % (B, L, samples.tolist()))
+    flat = wavs.reshape(-1)
+    starts = np.arange(B, dtype=np.int64) * L
+    gain = None
+    if mastering.level is not None:
+        starts_d, lengths_d, _, max_len = _span_tables(flat, starts, samples, None, "master_items")
+        gain = wave_gains(wave_levels(flat, starts_d, lengths_d, max_len), lengths_d, mastering)
+    Lp = -(-L // 8) * 8
+    kw = dict(dtype=mastering.dtype, reference=mastering.level == "reference", seed=mastering.seed)
+    if not mastering.dither:
+        out = wave_master(flat, starts, samples, np.arange(B, dtype=np.int64) * Lp, gain, 0, B * Lp, **kw)
+        return out.view(B, Lp)[:, :L]
+    out = torch.empty((B, Lp), dtype=torch.int16, device=wavs.device)
+    for b in range(B):
+        out[b] = wave_master(flat, starts[b:b + 1], samples[b:b + 1], [0], None if gain is None else gain[b:b + 1], 0, Lp,
+                             dither=True, **kw)
+    return out[:, :L]
+
+
+def to_pcm16(wavs, samples):
+    """the reference's save_wav samples (audio.py:16-18) of a padded batch, on the device: item b becomes
+    (x * 32767 / max(0.01, max |x|)).astype(int16) over its own samples[b] samples, bit for bit numpy's float32
+    evaluation -> int16 (B, L)"""
+    return master_items(wavs, samples, Mastering(level="reference"))
+
+
+def save_wav(path, pcm, sample_rate):
+    """write mono 16-bit PCM with the standard library's `wave`: pcm a 1-D int16 tensor (any device) or array -- what
+    master_items, to_pcm16 or synthesis.join_utterances return under dtype "int16"; float data is refused, not scaled"""
+    import wave
+    if torch.is_tensor(pcm):
+        pcm = pcm.detach().cpu().numpy()
+    pcm = np.asarray(pcm)
+    if pcm.dtype != np.int16 or pcm.ndim != 1:
+        raise ValueError("save_wav: 1-D int16 samples expected, got %s of shape %s (master with dtype='int16' first)"
+                         % (pcm.dtype, pcm.shape))
+    sr = int(sample_rate)
+    if sr < 1 or sr != sample_rate:
+        raise ValueError("save_wav: sample_rate=%r must be a positive integer" % (sample_rate,))
+    w = wave.open(path, "wb")
+    try:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(sr)
+        w.writeframes(np.ascontiguousarray(pcm.astype("<i2")).tobytes())
+    finally:
+        w.close()

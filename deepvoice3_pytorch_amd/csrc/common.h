@@ -154,6 +154,22 @@ __device__ __forceinline__ float dv3_wave_max(float v) {
   return v;
 }
 
+// Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> four 32-bit words.  ONE definition for the
+// dropout masks (elementwise.hip) and the mastering dither (master.hip); tests/philox_ref.py restates it.
+__device__ __forceinline__ void dv3_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                              uint32_t k0, uint32_t k1, uint32_t out[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
 // keep-bit lookup: bits laid out [row][row_stride words], bit t&31 of word t>>5
 __device__ __forceinline__ bool dv3_keep(const uint32_t* __restrict__ bits, int64_t row,
                                          int rs, int t) {

@@ -275,29 +275,15 @@ __global__ __launch_bounds__(256) void gate_bwd_c8_kernel(const dv3_gate_bwd_des
 
 // ------------------------------------------------------------------------------------------
 // Philox4x32-10 keep-bit generator (replaces F.dropout's bernoulli_: modules.py:147,210).
-// One thread per 32-bit mask word = 4 Philox calls x 8 sixteen-bit uniforms.
+// One thread per 32-bit mask word = 4 Philox calls x 8 sixteen-bit uniforms (dv3_philox4x32_10: common.h).
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 __device__ __forceinline__ uint32_t philox_keep_word(int64_t w, uint32_t thr, uint64_t seed, uint64_t site) {
   uint32_t word = 0;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const uint64_t ci = (uint64_t)w * 4 + q;
     uint32_t o[4];
-    philox4x32_10((uint32_t)ci, (uint32_t)(ci >> 32), (uint32_t)site, (uint32_t)(site >> 32),
+    dv3_philox4x32_10((uint32_t)ci, (uint32_t)(ci >> 32), (uint32_t)site, (uint32_t)(site >> 32),
                   (uint32_t)seed, (uint32_t)(seed >> 32), o);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {

@@ -54,6 +54,15 @@ so `wav` changes and mel, linear and alignment stay what the model made; token s
 
     for mel, linear, alignment, wav in synthesis.tts_batch(model, seqs, rate=[0.8, 1.0], semitones=[0, 3]): ...
 
+Deliverable audio, opt-in: mastering= (an audio.Mastering) on all three entry points turns every `wav`
+into the mastered one (audio.master_items: each utterance alone, so the three agree); join_utterances joins any list of
+device waveforms into one document -- silence trimmed, levelled, sentences crossfaded or separated by faded pauses,
+quantised, in one launch after one host read --, and tts_document speaks a text longer than one utterance, sentence by
+sentence, with every token's span on the document's time axis.
+
+    wav, spans = synthesis.tts_document(model, [seq0, seq1, ...], mastering=audio.Mastering("rms", "document"))
+    audio.save_wav("document.wav", wav, 22050)
+
 Free-running evaluation: how far is the model's own synthesis of a held-out sentence from its
 recording?  evaluate_synthesis decodes (no Griffin-Lim), aligns each utterance with its target by dynamic time warping
 (ops.dtw) under the mel-cepstral distance (audio.mel_cepstra) and returns one row per utterance; SynthEvalTotals folds
@@ -259,7 +268,7 @@ def _vocode(linear, audio_cfg, frame_lengths, settings):
 
 
 def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=False, stall_limit=None, timings=False,
-              timing_advance=1, rate=None, semitones=None, prosody=None, from_mel=False):
+              timing_advance=1, rate=None, semitones=None, prosody=None, mastering=None, from_mel=False):
     """sequences: a list of int id sequences (one per utterance); speaker_ids: None or one id per utterance.
     -> a list of (mel (T_b, mel_dim), linear (T_b * upsampling, linear_dim), alignment (steps_b, Tt_b), wav (L_b,)),
     device tensors, each trimmed to its own utterance.  diagnostics: a fifth element, the utterance's alignment
@@ -275,9 +284,12 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=Fa
     rates and shifts where the two keywords do not give them): how each utterance is spoken -- applied
     to the magnitudes on their way into Griffin-Lim (audio.warp_magnitudes), so only `wav` changes, to
     audio.num_samples(audio.warped_frames(frames, rate)) samples; mel, linear and alignment stay what the model made,
-    and with timings every token's start and end are divided by the utterance's rate."""
+    and with timings every token's start and end are divided by the utterance's rate.
+    mastering (an audio.Mastering): `wav` becomes audio.master_items of the batch's waveforms -- every utterance levelled
+    and quantised alone; nothing else in the result changes."""
     if len(sequences) == 0:
         return []
+    audio.check_mastering(mastering, "tts_batch")
     pros = utterance_prosody(rate, semitones, prosody, len(sequences), "tts_batch")
     mel_opt = mel_options(from_mel)
     if mel_opt is None:
@@ -304,6 +316,8 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=Fa
         if mel_opt is not None:
             linear = audio.mel_to_linear(mel, audio_cfg, frames, up, mel_opt)
         wavs, samples = audio.inv_spectrogram_batch(linear, audio_cfg, frame_lengths=frames * up, prosody=pros)
+        if mastering is not None:
+            wavs = audio.master_items(wavs, samples, mastering)
     stats = None
     if diagnostics:
         steps = [int(n) // steps_per_frame for n in frames]
@@ -340,7 +354,7 @@ class RollingSynthesizer(object):
     step kernels do not take is refused (no module-by-module fallback)."""
 
     def __init__(self, model, slots=64, max_text_len=256, audio_cfg=None, chunk=8, diagnostics=False, stall_limit=None,
-                 timings=False, timing_advance=1, from_mel=False):
+                 timings=False, timing_advance=1, mastering=None, from_mel=False):
         """diagnostics: every retired result gains a last element, the utterance's alignment statistics (one device
         read per retired group); stall_limit: the end-of-text stop -- after every chunk one statistics call runs in
         place on the program's stacked alignment buffer over the busy slots, and a slot whose attention reached its
@@ -349,7 +363,9 @@ class RollingSynthesizer(object):
         if they are there: the utterance's timing dict (token_timings with max_advance = timing_advance), searched in
         place on the program's stacked alignment buffer over the retiring slots.  from_mel (True or an
         audio.MelInverse): retirement vocodes the group's mel instead of running the post-net, as tts_batch does.
+        mastering (an audio.Mastering): every retired `wav` is the mastered one, as tts_batch makes it.
         All off by default: no launch and no result changes."""
+        self.mastering = audio.check_mastering(mastering, "RollingSynthesizer")
         if slots < 1 or max_text_len < 1 or chunk < 1:
             raise ValueError("RollingSynthesizer: slots, max_text_len and chunk must be positive")
         if stall_limit is not None and int(stall_limit) < 0:
@@ -468,6 +484,8 @@ class RollingSynthesizer(object):
                 up = linear.size(1) // mel.size(1)
             settings = [self._req[t][3] for t in tickets]
             wavs, samples = _vocode(linear, self.audio_cfg, frames * up, settings)
+            if self.mastering is not None:
+                wavs = audio.master_items(wavs, samples, self.mastering)
         stats = None
         if self.diagnostics:
             stats = _diagnose(alignments, steps, lengths, [self._req[t][2] for t in tickets])
@@ -544,7 +562,7 @@ class RollingSynthesizer(object):
 
 def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, audio_cfg=None, chunk=8,
                max_decoder_steps=None, diagnostics=False, stall_limit=None, timings=False, timing_advance=1,
-               rate=None, semitones=None, prosody=None, from_mel=False):
+               rate=None, semitones=None, prosody=None, mastering=None, from_mel=False):
     """Rolling-admission counterpart of tts_batch, as a generator: sequences (any iterable of id lists; speaker_ids an
     iterable alongside, or None; max_decoder_steps None, one cap, or an iterable of per-utterance caps) are submitted
     in order as slots free -- at most `slots` are queued ahead -- and every utterance is yielded when it retires, in
@@ -553,7 +571,8 @@ def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, 
     RollingSynthesizer takes them (a last element per result; the end-of-text stop); timings, timing_advance: as there
     (one more element per result, the utterance's timing dict); from_mel: as tts_batch takes it (the mel is vocoded, the
     post-net is not run); rate, semitones: None, one number, or an iterable of per-utterance values alongside
-    `sequences`; prosody: an audio.Prosody carrying the envelope settings (RollingSynthesizer.submit takes all three)."""
+    `sequences`; prosody: an audio.Prosody carrying the envelope settings (RollingSynthesizer.submit takes all three);
+    mastering: an audio.Mastering, as tts_batch takes it."""
     if max_text_len is None:
         sequences = [list(s) for s in sequences]
         if not sequences:
@@ -561,7 +580,7 @@ def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, 
         max_text_len = max(len(s) for s in sequences)
     rs = RollingSynthesizer(model, slots=slots, max_text_len=max_text_len, audio_cfg=audio_cfg, chunk=chunk,
                             diagnostics=diagnostics, stall_limit=stall_limit, timings=timings,
-                            timing_advance=timing_advance, from_mel=from_mel)
+                            timing_advance=timing_advance, from_mel=from_mel, mastering=mastering)
     it = iter(sequences)
     spk = iter(speaker_ids) if speaker_ids is not None else None
     caps = None
@@ -584,6 +603,131 @@ def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, 
                       semitones=float(next(shifts)) if shifts is not None else semitones, prosody=prosody)
         for res in rs.poll():
             yield res
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# deliverable audio: a document of several utterances
+# ----------------------------------------------------------------------------------------------------------------------
+def plan_document(lengths, sample_rate, pauses=0.25, fade_samples=0, starts=None, lead=0.0, tail=0.0):
+    """Where every sentence of a document goes -- a pure host function.  lengths: the S sentences' samples; pauses: seconds
+    of silence between neighbours, one number or S - 1 of them (rounded to samples, halves up); fade_samples: F; starts:
+    each sentence's first sample in the source buffer (None: back to back); lead, tail: seconds of silence before the
+    first and after the last sentence.  -> (table, N): table a dict of arrays "src", "len", "dst" (int64) and "flags"
+    (int32: bit 0 fade-in, bit 1 fade-out), what audio.wave_master takes, and N the document's samples.
+      * a sentence of at least F samples fades in and out (flags 3): at the document's edges, into and out of every
+        pause, and across a pause of 0, where the next sentence starts F samples before this one ends -- the crossfade;
+      * a sentence shorter than F gets no fade (flags 0), and a join it takes part in is a plain butt join;
+      * a pause of 0 is also a butt join (both fades kept, no overlap) where the crossfade would put a third sentence
+        over a sample: the next sentence never starts before the one before this one has ended."""
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    S, F, sr = lengths.size, int(fade_samples), float(sample_rate)
+    if S < 1 or int(lengths.min()) < 0:
+        raise ValueError("plan_document: at least one sentence of >= 0 samples expected, got %s" % (lengths.tolist(),))
+    if not sr > 0 or F < 0 or F != fade_samples:
+        raise ValueError("plan_document: sample_rate=%r must be positive and fade_samples=%r a non-negative integer"
+                         % (sample_rate, fade_samples))
+    gaps = np.broadcast_to(np.asarray(pauses, dtype=np.float64), (S - 1,)) if np.ndim(pauses) == 0 else \
+        np.asarray(pauses, dtype=np.float64).reshape(-1)
+    if gaps.size != S - 1 or not np.all(gaps >= 0) or not np.all(np.isfinite(gaps)):
+        raise ValueError("plan_document: pauses=%r must be one number or %d of them, each >= 0 seconds" % (pauses, S - 1))
+    if not (0 <= float(lead) < float("inf") and 0 <= float(tail) < float("inf")):
+        raise ValueError("plan_document: lead=%r and tail=%r must be >= 0 seconds" % (lead, tail))
+    to_samples = lambda sec: int(np.floor(float(sec) * sr + 0.5))
+    if starts is None:
+        src = np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64)
+    else:
+        src = np.asarray(starts, dtype=np.int64).reshape(-1)
+        if src.size != S or (S and int(src.min()) < 0):
+            raise ValueError("plan_document: %d starts for %d sentences" % (src.size, S))
+    faded = (lengths >= F) & (lengths > 0) & (F > 0)
+    dst = np.zeros(S, dtype=np.int64)
+    dst[0] = to_samples(lead)
+    for k in range(1, S):
+        end, gap = int(dst[k - 1] + lengths[k - 1]), to_samples(gaps[k - 1])
+        before = int(dst[k - 2] + lengths[k - 2]) if k >= 2 else 0
+        cross = gap == 0 and faded[k - 1] and faded[k] and end - F >= before
+        dst[k] = end - F if cross else end + gap
+    N = int(dst[-1] + lengths[-1]) + to_samples(tail)
+    return {"src": src, "len": lengths.copy(), "dst": dst, "flags": np.where(faded, 3, 0).astype(np.int32)}, N
+
+
+def join_utterances(wavs, sample_rate, pauses=0.25, trim_db=40.0, mastering=None, lead=0.0, tail=0.0, return_plan=False):
+    """One document from a list of 1-D float32 device waveforms (tts_batch's `wav` elements, say).  trim_db: silence at
+    each utterance's edges is cut by audio.trim_items at that threshold (None: nothing is cut; an utterance under 1025
+    samples comes back untrimmed, as trim_items leaves it); mastering: an audio.Mastering (None:
+    Mastering("peak", scope="document")) -- its level and scope give every utterance's gain from audio.wave_levels of
+    the TRIMMED spans, its fade_ms the fades, its dtype and dither the output; pauses, lead, tail: plan_document's.
+    Trim, levels, gains, the plan and ONE master launch (audio.wave_master); exactly one host read -- the trimmed spans,
+    which size the output (none when trim_db is None).  -> (the document (N,), [(start, end) of every utterance in
+    seconds]); return_plan: a third element, plan_document's table with "N" and "starts" (each utterance's first sample
+    in the packed source, before trimming) added.  The defaults of trim_db, pauses and the Mastering are starting
+    points, not measurements: nothing here was heard on a trained voice."""
+    mastering = audio.check_mastering(mastering, "join_utterances") or audio.Mastering("peak", scope="document")
+    if len(wavs) == 0:
+        raise ValueError("join_utterances: no waveforms")
+    for w in wavs:
+        if not torch.is_tensor(w) or not w.is_cuda or w.dim() != 1 or w.dtype != torch.float32:
+            raise ValueError("join_utterances: 1-D float32 device tensors expected")
+    lengths = np.array([int(w.numel()) for w in wavs], dtype=np.int64)
+    starts = np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64)
+    if int(lengths.sum()) == 0:
+        raise ValueError("join_utterances: every waveform is empty")
+    flat = torch.cat(list(wavs))
+    if trim_db is not None:
+        t_starts, t_lens = audio.trim_items(flat, starts, lengths, trim_db)
+        host = torch.stack([t_starts, t_lens]).cpu().numpy()                  # the one host read
+        src, lens = host[0].astype(np.int64), host[1].astype(np.int64)
+    else:
+        src, lens = starts.copy(), lengths.copy()
+    F = mastering.fade_samples(sample_rate)
+    table, N = plan_document(lens, sample_rate, pauses, F, starts=src, lead=lead, tail=tail)
+    gain = None
+    if mastering.level is not None:
+        sl = torch.from_numpy(np.concatenate([src, lens])).to(flat.device, non_blocking=True)
+        S = src.size
+        gain = audio.wave_gains(audio.wave_levels(flat, sl[:S], sl[S:], int(lens.max())), sl[S:], mastering)
+    doc = audio.wave_master(flat, table["src"], table["len"], table["dst"], gain, table["flags"], N, F, mastering.dtype,
+                            mastering.level == "reference", mastering.dither, mastering.seed)
+    sr = float(sample_rate)
+    spans = [(float(d) / sr, float(d + n) / sr) for d, n in zip(table["dst"], table["len"])]
+    if return_plan:
+        table = dict(table, N=N, starts=starts)
+        return doc, spans, table
+    return doc, spans
+
+
+def tts_document(model, sentences, speaker_id=None, batch=64, timings=False, audio_cfg=None, timing_advance=1,
+                 stall_limit=None, **join_options):
+    """Speak a text longer than one utterance: sentences (a list of int id sequences, each within the model's
+    max_positions) go through tts_batch in groups of at most `batch` (speaker_id: None or one id for the whole
+    document), then through join_utterances(wavs, audio_cfg.sample_rate, **join_options) -- pauses, trim_db, mastering,
+    lead, tail.  -> (document (N,), [(start, end) of every sentence in seconds]); timings=True: a third element, per
+    sentence its timing dict (token_timings) with "start" and "end" moved onto the document's time axis: plus the
+    sentence's first output sample minus the samples trimmed off its front, over the sample rate."""
+    sentences = [list(s) for s in sentences]
+    if len(sentences) == 0:
+        raise ValueError("tts_document: no sentences")
+    if int(batch) < 1:
+        raise ValueError("tts_document: batch=%r must be positive" % (batch,))
+    cfg = audio_cfg or audio.AudioConfig()
+    wavs, spans = [], []
+    for i in range(0, len(sentences), int(batch)):
+        group = sentences[i:i + int(batch)]
+        res = tts_batch(model, group, None if speaker_id is None else [speaker_id] * len(group), audio_cfg,
+                        stall_limit=stall_limit, timings=timings, timing_advance=timing_advance)
+        wavs += [r[3] for r in res]
+        spans += [r[4] for r in res] if timings else []
+    doc, where, plan = join_utterances(wavs, cfg.sample_rate, return_plan=True, **join_options)
+    if not timings:
+        return doc, where
+    sr = float(cfg.sample_rate)
+    out = []
+    for k, span in enumerate(spans):
+        shift = float(int(plan["dst"][k]) - (int(plan["src"][k]) - int(plan["starts"][k]))) / sr
+        moved = dict(span)
+        moved["start"], moved["end"] = span["start"] + shift, span["end"] + shift
+        out.append(moved)
+    return doc, where, out
 
 
 # ----------------------------------------------------------------------------------------------------------------------

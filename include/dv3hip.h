@@ -1540,6 +1540,98 @@ int dv3_prosody_warp_f32(const float* mag, float* out, int32_t B, int32_t T_in, 
                          const int32_t* tlen_in /* or NULL */, const int32_t* tlen_out, const double* rate,
                          const double* ratio, int32_t env_half_width, int32_t preserve_envelope, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Deliverable audio: the last stage of synthesis -- measure every utterance's level, turn the levels into gains, and
+ * place, scale, fade and quantise the utterances into one output in ONE launch (audio.wave_levels, audio.master_items,
+ * audio.to_pcm16, synthesis.join_utterances).  The reference's counterpart is audio.save_wav
+ * (audio.py:16-18): wav * 32767 / max(0.01, max|wav|) as int16, one file per line of text (synthesis.py:133-147); it joins
+ * nothing.  Three new entry points with plain arguments, no struct added or changed, so the version stays 50.
+ *
+ * dv3_wave_levels_f32: x a flat fp32 buffer; item b is the span x[starts[b] .. starts[b] + n_b), starts / lengths device
+ * int64[B] as dv3_gather_spans_f32 takes them, n_b = lengths[b] clamped into [0, max_len].  levels double[B][5]
+ * (DV3_LEVEL_COLUMNS), row b:
+ *   peak       max |x| over the item's finite samples (exact; 0 when there is none)
+ *   sumsq      sum of x^2 over the finite samples: every square exact in fp64, the sum accumulated in fp64
+ *   sum        sum of x over the finite samples, accumulated in fp64
+ *   over       the number of samples with |x| >= 1 (an infinity counts, a NaN does not)
+ *   nonfinite  the number of samples that are NaN or infinite
+ * Summation order: the item is cut into chunks of DV3_LEVELS_CHUNK samples counted from ITS OWN first sample; in a chunk
+ * lane t of 256 adds samples t, t + 256, ... in that order, the 256 partial results are added in a fixed binary tree, and
+ * the chunks' results in ascending order.  No atomics.  Samples are read as single dwords, so the row is the same
+ * wherever the span starts (any 4-byte alignment), whatever B is and whatever its neighbours hold: it is a function of
+ * the item's samples alone.  A zero-length item gives a row of zeros.  Every row is written; nothing outside the table
+ * and the scratch is.  scratch: B * ceil(max_len / DV3_LEVELS_CHUNK) * 5 doubles the call may overwrite (NULL allowed
+ * when max_len is 0).  Refused (DV3_EINVAL, "wave_levels:", nothing launched): a null x, starts, lengths or levels; a null
+ * scratch with max_len > 0; B outside [1, 65535]; max_len outside [0, 2^40]; levels or scratch not 8-byte aligned.
+ *
+ * dv3_wave_gains_f32: levels as above, lengths the same int64[B] (each clamped at 0), goff device int32[G + 1] ascending
+ * from 0 to B: items goff[g] .. goff[g + 1] - 1 form group g and share one value computed from their combined levels
+ * P = the largest peak, Q = the sum of sumsq (ascending item order), n = the sum of the lengths; goff = 0, 1, .., B gives
+ * per-item gains.  gain float[B]; all arithmetic in fp64 (division and square root correctly rounded), rounded ONCE to
+ * fp32 at the end:
+ *   DV3_GAIN_PEAK       g = target / P
+ *   DV3_GAIN_RMS        g = min(target / sqrt(Q / n), ceiling / P)
+ *   DV3_GAIN_REFERENCE  the value written is the DIVISOR fmaxf(P, 0.01f) of audio.py:17 (P is an fp32 value), not a
+ *                       multiplier; target, ceiling and max_gain are not read
+ * Under PEAK and RMS g is then capped, g = min(g, max_gain), and g = 1 for a silent or empty group (P == 0 or n == 0, and
+ * under RMS Q == 0).  target, ceiling and max_gain are LINEAR values (10^(dB / 20)), positive and finite.  Item indices
+ * read from goff are clamped into [0, B].  Refused ("wave_gains:"): null pointers; B outside [1, 65535]; G outside [1, B];
+ * a policy that is none of the three; under PEAK and RMS a target, ceiling or max_gain that is no positive finite number.
+ *
+ * dv3_wave_master_f32: x the flat fp32 source; S segments as device arrays -- src, len, dst int64[S], gain float[S],
+ * flags int32[S] (DV3_MASTER_FADE_IN = 1, DV3_MASTER_FADE_OUT = 2): segment s is x[src[s] .. src[s] + len[s]) placed at
+ * output samples dst[s] .. dst[s] + len[s]; fade float[F], 0 <= F <= DV3_MASTER_MAX_FADE (NULL allowed when F is 0), which
+ * the caller makes as 0.5 - 0.5 cos(pi (i + 0.5) / F) in fp64 rounded once.  Layout rules, which the CALLER guarantees
+ * (the arrays live on the device; audio.wave_master checks them on the host and refuses violations): dst ascending; the
+ * ends dst[s] + len[s] ascending too; no output sample covered by more than two segments; every span inside x.  The
+ * kernel reads x[src[s] + i] only for 0 <= i < len[s], whatever the table holds.  Output sample n, for every covering
+ * segment s in segment order, i = n - dst[s], every product and sum in fp32 rounded once, none contracted into an
+ * fma (fmul, fadd and fdiv below are the IEEE operations, what numpy's float32 operators are):
+ *     w = 1
+ *     if fade-in  and i < F:            w = fade[i]
+ *     if fade-out and i >= len[s] - F:  w = fmul(w, fade[len[s] - 1 - i])
+ *     t = fmul(fmul(gain[s], w), x[src[s] + i])
+ *     y = t (one covering segment);  y = fadd(t_a, t_b) (two, a before b);  y = 0 (none)
+ * so that a fade-out over the last F samples of one segment laid over the fade-in of the next sums to weight 1 within
+ * one ulp: the crossfade.  Output modes (out is 16-byte aligned):
+ *   DV3_MASTER_F32            out float[N]:    out[n] = y
+ *   DV3_MASTER_I16            out int16_t[N]:  v = fmul(y, 32767.f); with dither v = fadd(v, d(n)); q = rintf(v) (ties to
+ *                             even) clamped into [-32768, 32767]; a NaN gives 0
+ *   DV3_MASTER_I16_REFERENCE  out int16_t[N]:  no fades (F == 0, flags ignored), no dither, and the caller lays no two
+ *                             segments over each other; gain[s] is the DIVISOR: t = fdiv(fmul(x, 32767.f), gain[s])
+ *                             (correctly rounded), q = (int16) truncf(t), saturating, NaN gives 0 -- numpy's
+ *                             (wav * 32767 / max(0.01, peak)).astype(int16) of audio.py:17-18
+ * Dither: d(n) is triangular (TPDF, +-1 LSB) from Philox4x32-10 as the dropout masks use it: key (lo32(seed),
+ * hi32(seed)), counter (lo32(n), hi32(n), 0, 0) -- a function of the output index, not of the launch geometry --,
+ * u1 = (r0 >> 8) 2^-24, u2 = (r1 >> 8) 2^-24, d = u1 - u2 (exact in fp32).
+ * Every one of the N outputs is written (gaps between segments are zeros: the caller need not clear out), nothing beyond
+ * N.  No atomics, no cross-lane sums: two calls give bit-equal output.  N == 0 launches nothing.  Refused
+ * ("wave_master:", nothing launched): a null x, src, len, dst, gain, flags or out; a null fade with F > 0; S outside
+ * [1, DV3_MASTER_MAX_SEGMENTS]; F outside [0, DV3_MASTER_MAX_FADE]; N outside [0, 2^40]; a mode that is none of the
+ * three; dither other than 0 or 1; the reference mode with F > 0 or with dither; dither in the F32 mode; out not 16-byte
+ * aligned; out == x.
+ * tests/master_ref.py restates the three definitions in numpy float32 and in float64.
+ * ------------------------------------------------------------------------------------ */
+#define DV3_LEVEL_COLUMNS 5
+#define DV3_LEVELS_CHUNK 16384
+#define DV3_GAIN_PEAK 0
+#define DV3_GAIN_RMS 1
+#define DV3_GAIN_REFERENCE 2
+#define DV3_MASTER_F32 0
+#define DV3_MASTER_I16 1
+#define DV3_MASTER_I16_REFERENCE 2
+#define DV3_MASTER_FADE_IN 1
+#define DV3_MASTER_FADE_OUT 2
+#define DV3_MASTER_MAX_FADE 8192
+#define DV3_MASTER_MAX_SEGMENTS 1048576
+int dv3_wave_levels_f32(const float* x, const int64_t* starts, const int64_t* lengths, int32_t B, int64_t max_len,
+                        double* scratch, double* levels, void* stream);
+int dv3_wave_gains_f32(const double* levels, const int64_t* lengths, const int32_t* goff, int32_t B, int32_t G,
+                       int32_t policy, double target, double ceiling, double max_gain, float* gain, void* stream);
+int dv3_wave_master_f32(const float* x, const int64_t* src, const int64_t* len, const int64_t* dst, const float* gain,
+                        const int32_t* flags, int32_t S, const float* fade /* or NULL when F is 0 */, int32_t F,
+                        int32_t mode, int32_t dither, uint64_t seed, void* out, int64_t N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
