@@ -31,6 +31,11 @@ Speaking rate and pitch: inv_spectrogram_batch(..., prosody=Prosody(rate, semito
 magnitudes through warp_magnitudes (csrc/prosody.hip) before the phase is built: the frames resampled in time, the
 harmonics moved along the frequency axis under the spectral envelope.  Off by default: without the keyword nothing runs.
 
+Prosody marks: the same controls inside an item.  ProsodyMarks holds spans with their own rate, semitones and gain_db,
+breaks and a transition; plan_prosody turns the segments into per-output-frame position, ratio and gain tables (two small
+kernels around one host read), warp_magnitudes_curve follows such tables -- a caller's own just as well --, plan_map
+carries timings onto the new time axis; inv_spectrogram_batch(..., prosody=marks) composes them.
+
 Pitch: yin_items tracks F0 per frame of the packed waveforms features_items takes (csrc/pitch.hip), voiced() decides
 which frames to believe (PitchConfig); synthesis.waveform_distortion builds the F0 and voicing error of an evaluation on it.
 
@@ -486,6 +491,15 @@ def _active(prosody, what):
     return None if prosody.neutral() else prosody
 
 
+def _active_marks(prosody, B, what):
+    """the `prosody=` keyword when it holds ProsodyMarks (one, or a sequence of one or None per item, in frames)
+    -> (True, the list of B or None when nothing changes anything); (False, None) when it holds something else"""
+    if isinstance(prosody, ProsodyMarks) or (isinstance(prosody, (list, tuple)) and len(prosody) > 0 and
+                                             all(m is None or isinstance(m, ProsodyMarks) for m in prosody)):
+        return True, item_marks(prosody, B, "frames", what)
+    return False, None
+
+
 def warped_frames(T, rate, cfg=None):
     """T' = max(min_frames, floor((T - 1) / rate + 0.5) + 1): the frames an item of T frames has at speaking rate `rate`
     (host float64, like every other length here)"""
@@ -527,6 +541,300 @@ def warp_magnitudes(mag, frame_lengths, cfg, prosody):
     return out, out_len
 
 
+# ---------------------------------------------------------------------------------------------
+# prosody marks: rate, pitch, level and pauses that vary within an utterance
+# ---------------------------------------------------------------------------------------------
+class MarksNotApplied(UserWarning):
+    """synthesis found no admissible monotonic path for an utterance that carries ProsodyMarks in tokens: there are no
+    token bounds to place the marks at, and the utterance was vocoded as if it had none"""
+
+
+_MARK_LIMITS = (("rate", 0.25, 4.0, 1.0), ("semitones", -24.0, 24.0, 0.0), ("gain_db", -40.0, 20.0, 0.0))
+MAX_BREAK_SECONDS = 10.0
+
+
+def _index(v, what):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
+        raise ValueError("ProsodyMarks: %s=%r must be a non-negative integer" % (what, v))
+    return int(v)
+
+
+class ProsodyMarks(object):
+    """How the PARTS of one utterance are spoken -- what <prosody>, <emphasis> and <break> say:
+    spans: [(first, last_exclusive, dict(rate=, semitones=, gain_db=)), ...] in ascending order without overlap, each
+    value optional -- rate in [0.25, 4] (above 1: faster), semitones in [-24, 24], gain_db in [-40, 20];
+    breaks: [(after_index, seconds), ...]: silence of at most MAX_BREAK_SECONDS put in after unit after_index;
+    units: "tokens" (input tokens: synthesis.tts_batch(marks=) places them by the utterance's monotonic path) or
+    "frames" (frames of the spectrogram: inv_spectrogram_batch(prosody=) takes them as they stand);
+    transition_ms: semitones and gain_db glide linearly over this long around a boundary between two parts that follow
+    each other without a break (0: they step; the rate always steps); preserve_envelope, envelope_hz: as Prosody takes
+    them.  What lies between and around the spans is spoken as the model made it.  The utterance is cut at every span
+    edge and every break: at most DV3_PROSODY_MAX_SEGMENTS parts.  Refused by value (ValueError naming it)."""
+
+    def __init__(self, spans=(), breaks=(), units="tokens", transition_ms=0.0, preserve_envelope=True, envelope_hz=400.0):
+        if units not in ("tokens", "frames"):
+            raise ValueError("ProsodyMarks: units=%r must be \"tokens\" or \"frames\"" % (units,))
+        self.units = units
+        self._envelope = Prosody(1.0, 0.0, preserve_envelope, envelope_hz)
+        self.preserve_envelope, self.envelope_hz = self._envelope.preserve_envelope, self._envelope.envelope_hz
+        if isinstance(transition_ms, bool) or not isinstance(transition_ms, (int, float, np.integer, np.floating)) or \
+                not 0.0 <= float(transition_ms) < float("inf"):
+            raise ValueError("ProsodyMarks: transition_ms=%r must be a number of milliseconds >= 0" % (transition_ms,))
+        self.transition_ms = float(transition_ms)
+        self.spans, at = [], 0
+        for span in spans:
+            if not isinstance(span, (list, tuple)) or len(span) != 3 or not isinstance(span[2], dict):
+                raise ValueError("ProsodyMarks: span %r must be (first, last_exclusive, dict of settings)" % (span,))
+            first, last = _index(span[0], "span first"), _index(span[1], "span last_exclusive")
+            if last <= first:
+                raise ValueError("ProsodyMarks: span [%d, %d) is empty" % (first, last))
+            if first < at:
+                raise ValueError("ProsodyMarks: span [%d, %d) overlaps or precedes the span that ends at %d" % (first, last, at))
+            unknown = sorted(set(span[2]) - {name for name, _, _, _ in _MARK_LIMITS})
+            if unknown:
+                raise ValueError("ProsodyMarks: span [%d, %d) has unknown settings %r (rate, semitones, gain_db)"
+                                 % (first, last, unknown))
+            vals = []
+            for name, lo, hi, dflt in _MARK_LIMITS:
+                x = span[2].get(name, dflt)
+                if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not lo <= float(x) <= hi:
+                    raise ValueError("ProsodyMarks: %s=%r must be a number in [%g, %g]" % (name, x, lo, hi))
+                vals.append(float(x))
+            self.spans.append((first, last) + tuple(vals))
+            at = last
+        self.breaks = {}
+        for brk in breaks:
+            if not isinstance(brk, (list, tuple)) or len(brk) != 2:
+                raise ValueError("ProsodyMarks: break %r must be (after_index, seconds)" % (brk,))
+            after, sec = _index(brk[0], "break after_index"), brk[1]
+            if isinstance(sec, bool) or not isinstance(sec, (int, float, np.integer, np.floating)) or \
+                    not 0.0 <= float(sec) <= MAX_BREAK_SECONDS:
+                raise ValueError("ProsodyMarks: break seconds=%r must be a number in [0, %g]" % (sec, MAX_BREAK_SECONDS))
+            if after in self.breaks:
+                raise ValueError("ProsodyMarks: two breaks after index %d" % after)
+            self.breaks[after] = float(sec)
+        cuts = {c for s in self.spans for c in s[:2] if c > 0} | {a + 1 for a in self.breaks}
+        self.cuts = sorted(cuts)
+        top = _lib.CONSTS["DV3_PROSODY_MAX_SEGMENTS"]
+        if len(self.cuts) + 1 > top:
+            raise ValueError("ProsodyMarks: %d segments (one more than the span edges and breaks), at most %d"
+                             % (len(self.cuts) + 1, top))
+
+    def half_width(self, cfg=None):
+        return self._envelope.half_width(cfg)
+
+    def neutral(self):
+        """no span changes anything and no break is longer than nothing"""
+        return all(s[2:] == (1.0, 0.0, 0.0) for s in self.spans) and not any(self.breaks.values())
+
+    def ramp_frames(self, cfg=None):
+        """transition_ms in frames (halves up); ValueError beyond DV3_PROSODY_MAX_RAMP"""
+        cfg = cfg or AudioConfig()
+        R = int(np.floor(self.transition_ms * 1e-3 * cfg.sample_rate / float(cfg.hop_size) + 0.5))
+        if R > _lib.CONSTS["DV3_PROSODY_MAX_RAMP"]:
+            raise ValueError("ProsodyMarks: transition_ms=%r is %d frames, at most %d" % (
+                self.transition_ms, R, _lib.CONSTS["DV3_PROSODY_MAX_RAMP"]))
+        return R
+
+    def key(self):
+        """the settings a launch shares: marks with equal keys can be planned and warped together"""
+        return (self.preserve_envelope, self.envelope_hz, self.transition_ms)
+
+    def segments(self, cfg=None):
+        """the segment table: dict of "start" (int64[S], each segment's first unit; segment s ends where s + 1 starts, the
+        last one with the utterance), "rate", "semitones", "gain_db" (float64[S]) and "break_frames" (int32[S]: seconds
+        times sample_rate / hop_size, halves up -- the silence after the segment).  Gaps between spans are neutral."""
+        cfg = cfg or AudioConfig()
+        start = [0] + self.cuts
+        rows = []
+        for s, c in enumerate(start):
+            vals = (1.0, 0.0, 0.0)
+            for first, last, rate, semi, db in self.spans:
+                if first <= c < last:
+                    vals = (rate, semi, db)
+            end = start[s + 1] if s + 1 < len(start) else None
+            sec = self.breaks.get(end - 1, 0.0) if end is not None else 0.0
+            rows.append(vals + (int(np.floor(sec * cfg.sample_rate / float(cfg.hop_size) + 0.5)),))
+        cols = list(zip(*rows))
+        return {"start": np.asarray(start, dtype=np.int64), "rate": np.asarray(cols[0], dtype=np.float64),
+                "semitones": np.asarray(cols[1], dtype=np.float64), "gain_db": np.asarray(cols[2], dtype=np.float64),
+                "break_frames": np.asarray(cols[3], dtype=np.int32)}
+
+
+def item_marks(marks, B, units, what):
+    """one ProsodyMarks, or a sequence of B entries each a ProsodyMarks or None -> None when nothing changes anything,
+    else the list of B (None: that item is left alone).  Another type, count or unit is refused."""
+    if marks is None:
+        return None
+    items = [marks] * B if isinstance(marks, ProsodyMarks) else list(marks)
+    if len(items) != B:
+        raise ValueError("%s: %d marks for %d items" % (what, len(items), B))
+    for m in items:
+        if m is not None and not isinstance(m, ProsodyMarks):
+            raise ValueError("%s: marks must be audio.ProsodyMarks (or None), got %r" % (what, m))
+        if m is not None and m.units != units:
+            raise ValueError("%s: marks in %r given where %r are expected" % (what, m.units, units))
+    items = [None if m is None or m.neutral() else m for m in items]
+    return items if any(m is not None for m in items) else None
+
+
+def marks_tables(marks, cfg=None):
+    """a list of ProsodyMarks (None: a neutral item) that share key() -> the padded host tables of the batch: dict of
+    "nseg" int32[B], "start" int64[B][S + 1] (a segment's first unit; padded with the largest int32), "rate", "semitones",
+    "gain_db" float64[B][S], "break_frames" int32[B][S], S the most segments of any item"""
+    keys = {m.key() for m in marks if m is not None}
+    if len(keys) > 1:
+        raise ValueError("plan_prosody: the marks of one call must share preserve_envelope, envelope_hz and transition_ms, "
+                         "got %s" % sorted(keys))
+    segs = [(m or ProsodyMarks()).segments(cfg) for m in marks]
+    B, S = len(segs), max(len(t["rate"]) for t in segs)
+    out = {"nseg": np.array([len(t["rate"]) for t in segs], dtype=np.int32),
+           "start": np.full((B, S + 1), 2 ** 31 - 1, dtype=np.int64), "rate": np.ones((B, S)),
+           "semitones": np.zeros((B, S)), "gain_db": np.zeros((B, S)), "break_frames": np.zeros((B, S), dtype=np.int32)}
+    for b, t in enumerate(segs):
+        n = len(t["rate"])
+        out["start"][b, :n] = t["start"]
+        for k in ("rate", "semitones", "gain_db", "break_frames"):
+            out[k][b, :n] = t[k]
+    return out
+
+
+def plan_prosody(bounds, frame_lengths, marks, cfg=None, usable=None):
+    """Where every output frame of a batch under ProsodyMarks comes from (dv3_curve_plan_f64, dv3_curve_fill_f64;
+    include/dv3hip.h states both, tests/prosody_curve_ref.py restates them).  marks: B entries, each a ProsodyMarks or
+    None, sharing key(); frame_lengths: B host ints, each item's source frames; bounds: device int (B, S + 1), the source
+    frame every segment starts at (column s for segment s; the kernels clamp them, make them non-decreasing and end the
+    last segment with the item) -- None: the marks are in frames and their own starts are the bounds; usable: None or a
+    device bool[B] -- an item where it is false is planned as if it had no marks (synthesis: no monotonic path), all on
+    the device.  ONE host read sits between the two launches: the items' output frame counts T'_b, which size the tables
+    and give Griffin-Lim its lengths (`usable` rides in the same transfer); there is no other synchronisation.
+    -> dict: "out_lengths" int64[B] (host), "tlen_in", "tlen_out" int32[B], "nseg", "c" (the repaired bounds) and "o"
+    int32 (B, S + 1), "rate" float64 (B, S), "break_frames" int32 (B, S), "pos", "ratio" float64 and "gain" float32
+    (B, max T'_b): device tensors; "usable": B host bools; "W", "preserve_envelope": the warp's settings."""
+    cfg = cfg or AudioConfig()
+    marks = list(marks)
+    B = len(marks)
+    t = marks_tables(marks, cfg)
+    S = t["rate"].shape[1]
+    first = next((m for m in marks if m is not None), None) or ProsodyMarks()
+    W, R = first.half_width(cfg), first.ramp_frames(cfg)
+    fl = _host_lengths(frame_lengths, B, 1, 2 ** 31 - 1, "plan_prosody")
+    if bounds is None:
+        if any(m is not None and m.units != "frames" for m in marks):
+            raise ValueError("plan_prosody: marks in tokens need the token bounds in frames")
+        bounds = torch.from_numpy(np.minimum(t["start"], int(fl.max())).astype(np.int32))
+    if not torch.is_tensor(bounds) or tuple(bounds.shape) != (B, S + 1):
+        raise ValueError("plan_prosody: bounds must be a (%d, %d) integer tensor" % (B, S + 1))
+    dev = bounds.device if bounds.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    put = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(dev)
+    bounds = _c(bounds.to(dev).to(torch.int32))
+    nseg, rate = put(t["nseg"], torch.int32), put(t["rate"], torch.float64)
+    semi, db, brk = put(t["semitones"], torch.float64), put(t["gain_db"], torch.float64), put(t["break_frames"], torch.int32)
+    tlen_in = fl.to(torch.int32).to(dev)
+    if usable is not None:                 # an item without a usable path: one neutral segment, chosen on the device
+        ok = usable.to(dev).to(torch.bool)
+        rate, semi, db = [torch.where(ok[:, None], v, torch.full_like(v, x)) for v, x in ((rate, 1.0), (semi, 0.0), (db, 0.0))]
+        brk, nseg = torch.where(ok[:, None], brk, torch.zeros_like(brk)), torch.where(ok, nseg, torch.ones_like(nseg))
+    T_in = int(fl.max())
+    o = torch.empty((B, S + 1), dtype=torch.int32, device=dev)
+    tlen_out = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.call("dv3_curve_plan_f64", tlen_in.data_ptr(), B, T_in, S, nseg.data_ptr(), bounds.data_ptr(), rate.data_ptr(),
+              brk.data_ptr(), min_frames(cfg.hop_size, cfg.convention, cfg.fft_size), o.data_ptr(), tlen_out.data_ptr(),
+              _stream())
+    host = (tlen_out if usable is None else torch.stack([tlen_out, ok.to(torch.int32)])).cpu()      # the one host read
+    out_len = (host if usable is None else host[0]).to(torch.int64)
+    T_out = int(out_len.max())
+    pos = torch.empty((B, T_out), dtype=torch.float64, device=dev)
+    ratio, gain = torch.empty_like(pos), torch.empty((B, T_out), dtype=torch.float32, device=dev)
+    _lib.call("dv3_curve_fill_f64", tlen_in.data_ptr(), B, T_in, S, nseg.data_ptr(), bounds.data_ptr(), rate.data_ptr(),
+              semi.data_ptr(), db.data_ptr(), brk.data_ptr(), o.data_ptr(), tlen_out.data_ptr(), T_out, R, pos.data_ptr(),
+              ratio.data_ptr(), gain.data_ptr(), _stream())
+    n = tlen_in[:, None]
+    col = torch.arange(S + 1, device=dev)[None, :]
+    c = torch.cummax(torch.where(col == 0, torch.zeros_like(bounds), torch.minimum(bounds.clamp(min=0), n)), dim=1)[0]
+    c = torch.where(col >= nseg[:, None], n.expand_as(c), c).to(torch.int32)
+    return {"out_lengths": out_len, "tlen_in": tlen_in, "tlen_out": tlen_out, "nseg": nseg, "c": c, "o": o, "rate": rate,
+            "break_frames": brk, "pos": pos, "ratio": ratio, "gain": gain, "W": W, "preserve_envelope": first.preserve_envelope,
+            "usable": [True] * B if usable is None else [bool(v) for v in host[1]]}
+
+
+def plan_map(plan, frames, side="start"):
+    """Source frames -> output frames under a plan, in float64, for timings: frames (B, N) integer or float tensor on the
+    plan's device.  A frame x in segment s (c_s <= x < c_{s+1} for side "start", c_s < x <= c_{s+1} for "end": where a
+    token starts, and where one ends) maps to o_s + len_s (x - c_s) / (c_{s+1} - c_s), len_s = o_{s+1} - break_s - o_s the
+    segment's own output frames: the segment's source frames spread evenly over them (len_s is (c_{s+1} - c_s) / rate_s
+    rounded to whole frames), so a token that ends at a break ends BEFORE the silence, the next one starts after it --
+    the gap is break_s frames exactly -- and without a break the two meet.  Monotone in x; torch only, no
+    synchronisation (it runs on host tensors just as well)."""
+    if side not in ("start", "end"):
+        raise ValueError("plan_map: side=%r must be \"start\" or \"end\"" % (side,))
+    c, o = plan["c"].to(torch.float64), plan["o"].to(torch.float64)
+    x = frames.to(torch.float64)
+    s = torch.searchsorted(c.contiguous(), x.contiguous(), right=(side == "start")) - 1
+    s = torch.minimum(s.clamp(min=0), (plan["nseg"].to(torch.int64) - 1)[:, None])
+    take = lambda v: torch.gather(v, 1, s)
+    c0, o0 = take(c[:, :-1]), take(o[:, :-1])
+    width, frames_out = take(c[:, 1:]) - c0, take(o[:, 1:]) - take(plan["break_frames"].to(torch.float64)) - o0
+    along = torch.where(width > 0, (x - c0) / width.clamp(min=1.0), torch.zeros_like(x)).clamp(0.0, 1.0)
+    return o0 + frames_out * along
+
+
+def warp_magnitudes_curve(mag, frame_lengths, cfg, pos, ratio, gain, out_lengths, preserve_envelope=True,
+                          envelope_hz=400.0, check=True):
+    """warp_magnitudes along per-output-frame curves (dv3_curve_warp_f32; include/dv3hip.h states every step): pos, ratio
+    float64 and gain float32, each (B, T_out) on the device -- output frame j of item b is the item's source at frame
+    pos[b, j] (the last frame held beyond it; a negative or NaN position is a silent frame), read along the frequency
+    axis at k / ratio[b, j] and multiplied by gain[b, j]; out_lengths: B host ints in [1, T_out], rows past them are
+    zero.  A caller with a pitch track passes ratio = target / f0 (audio.yin_items).  check: the gains must be finite and
+    >= 0 and the ratios positive where they are used -- the kernel does not look -- which costs one host read; plans made
+    by plan_prosody are inside the limits by construction and skip it.  -> out (B, T_out, bins).  One launch."""
+    cfg = cfg or AudioConfig()
+    mag = _c(_chk(mag, "mag"))
+    if mag.dim() != 3 or min(mag.shape) < 1:
+        raise ValueError("warp_magnitudes_curve: non-empty (B, T, bins) magnitudes expected, got %s" % (tuple(mag.shape),))
+    B, T, F = mag.shape
+    check_bins(F, cfg.fft_size, "warp_magnitudes_curve")
+    fl = torch.full((B,), T, dtype=torch.int64) if frame_lengths is None else \
+        _host_lengths(frame_lengths, B, 1, T, "warp_magnitudes_curve")
+    W = Prosody(1.0, 0.0, preserve_envelope, envelope_hz).half_width(cfg)
+    for name, v, dt in (("pos", pos, torch.float64), ("ratio", ratio, torch.float64), ("gain", gain, torch.float32)):
+        if not torch.is_tensor(v) or v.dtype != dt or v.dim() != 2 or v.shape[0] != B or v.shape[1] < 1 or \
+                v.shape != pos.shape or v.device != mag.device:
+            raise ValueError("warp_magnitudes_curve: %s must be a (%d, T_out) %s tensor on the device of mag" % (name, B, dt))
+    T_out = int(pos.shape[1])
+    ol = _host_lengths(out_lengths, B, 1, T_out, "warp_magnitudes_curve (out_lengths)")
+    if check:
+        live = (torch.arange(T_out)[None, :] < ol[:, None]).to(mag.device) & (pos >= 0)
+        bad = live & ~(torch.isfinite(gain) & (gain >= 0) & torch.isfinite(ratio) & (ratio > 0))
+        if bool(bad.any()):
+            b, j = [int(v) for v in torch.nonzero(bad)[0]]
+            raise ValueError("warp_magnitudes_curve: gain=%r, ratio=%r at item %d, frame %d: a finite gain >= 0 and a finite "
+                             "ratio > 0 expected" % (float(gain[b, j]), float(ratio[b, j]), b, j))
+    pos, ratio, gain = _c(pos), _c(ratio), _c(gain)
+    tlen_in, tlen_out = fl.to(torch.int32).to(mag.device), ol.to(torch.int32).to(mag.device)
+    out = torch.empty((B, T_out, F), dtype=torch.float32, device=mag.device)
+    _lib.call("dv3_curve_warp_f32", mag.data_ptr(), out.data_ptr(), B, T, T_out, F, tlen_in.data_ptr(), tlen_out.data_ptr(),
+              pos.data_ptr(), ratio.data_ptr(), gain.data_ptr(), W, int(bool(preserve_envelope)), _stream())
+    return out
+
+
+def warp_magnitudes_marks(mag, frame_lengths, cfg, marks, bounds=None, usable=None):
+    """plan_prosody and warp_magnitudes_curve in a row -> (out (B, max T'_b, bins), the plan)"""
+    cfg = cfg or AudioConfig()
+    B, T = mag.shape[0], mag.shape[1]
+    fl = torch.full((B,), T, dtype=torch.int64) if frame_lengths is None else \
+        _host_lengths(frame_lengths, B, 1, T, "warp_magnitudes_marks")
+    if bounds is None:
+        if any(m is not None and m.units != "frames" for m in marks):
+            raise ValueError("warp_magnitudes_marks: marks in tokens need the token bounds in frames")
+        bounds = torch.from_numpy(np.minimum(marks_tables(marks, cfg)["start"], T).astype(np.int32)).to(mag.device)
+    plan = plan_prosody(bounds, fl, marks, cfg, usable)
+    first = next(m for m in marks if m is not None)
+    out = warp_magnitudes_curve(mag, fl, cfg, plan["pos"], plan["ratio"], plan["gain"], plan["out_lengths"],
+                                first.preserve_envelope, first.envelope_hz, check=False)
+    return out, plan
+
+
 def inv_preemphasis_(y, coef):
     """de-emphasis filter (audio.py:26-28) of (B, L) waveforms -> a new tensor"""
     out = torch.empty_like(y)
@@ -547,12 +855,17 @@ def inv_spectrogram_batch(linear_outputs, cfg=None, init_phasor=None, frame_leng
     is built, item b is inverted from its T'_b = warped_frames(T_b, rate_b) frames (T_b = T without frame_lengths) and the
     return is (waveforms, sample lengths) either way, the lengths num_samples(T'_b).  An init_phasor cannot be given
     with it (it would describe the frames before the warp).  None, or one whose every rate is 1 and shift 0: nothing is
-    launched for it and the call is the one without the keyword."""
+    launched for it and the call is the one without the keyword.
+    prosody may instead be an audio.ProsodyMarks in frames, or a list of one (or None) per item, which must share their
+    envelope and transition settings: rate, pitch, level and pauses that vary within the item --
+    plan_prosody, then warp_magnitudes_curve in the place of warp_magnitudes; everything above holds, with T'_b the
+    plan's frame counts (one host read).  Marks that change nothing launch nothing."""
     cfg = cfg or AudioConfig()
     if linear_outputs.dim() != 3:
         raise ValueError("inv_spectrogram_batch: a (B, T, bins) spectrogram expected, got %s" % (tuple(linear_outputs.shape),))
     check_bins(linear_outputs.shape[-1], cfg.fft_size, "inv_spectrogram_batch")
-    prosody = _active(prosody, "inv_spectrogram_batch")
+    is_marks, marks = _active_marks(prosody, linear_outputs.shape[0], "inv_spectrogram_batch")
+    prosody = marks if is_marks else _active(prosody, "inv_spectrogram_batch")
     if prosody is not None:
         if init_phasor is not None:
             raise ValueError("inv_spectrogram_batch: init_phasor describes the frames before the warp; it cannot be "
@@ -575,7 +888,10 @@ def inv_spectrogram(spectrogram, cfg=None, device="cuda:0"):
     return y[0].cpu().numpy()
 
 
-def _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths, prosody=None):
+def _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths, prosody=None, bounds=None, usable=None,
+                           want_plan=False):
+    """prosody: None, a Prosody, or a list of ProsodyMarks / None per item -- then bounds, usable: plan_prosody's (None:
+    marks in frames), and with want_plan the plan is a third element of the return"""
     B, T = linear_outputs.shape[0], linear_outputs.shape[1]
     fl = torch.as_tensor(frame_lengths).reshape(-1).to(torch.int64).cpu()
     hop, n_fft = cfg.hop_size, cfg.fft_size
@@ -584,7 +900,10 @@ def _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths, pros
         raise ValueError("inv_spectrogram_batch: %d frame lengths in [%d, %d] expected, got %s" % (
             B, tmin, T, fl.tolist()))
     mag = magnitudes(linear_outputs, cfg)
-    if prosody is not None:            # from here on the items have their warped frame counts
+    if isinstance(prosody, list):      # ProsodyMarks in frames: the items have their planned frame counts
+        mag, plan = warp_magnitudes_marks(mag, fl, cfg, prosody, bounds, usable)
+        fl = plan["out_lengths"]
+    elif prosody is not None:          # from here on the items have their warped frame counts
         mag, fl = warp_magnitudes(mag, fl, cfg, prosody)
     tlen = fl.to(torch.int32).to(linear_outputs.device)
     y = griffin_lim(mag, hop, cfg.griffin_lim_iters, _start_phasor(mag, cfg, init_phasor, tlen), cfg.convention,
@@ -593,7 +912,16 @@ def _inv_spectrogram_items(linear_outputs, cfg, init_phasor, frame_lengths, pros
     out = torch.empty_like(y)
     _lib.call("dv3_deemphasis_items_f32", y.data_ptr(), out.data_ptr(), B, y.shape[1],
               lengths.to(torch.int32).to(y.device).data_ptr(), float(cfg.preemphasis), _stream())
-    return out, lengths
+    return (out, lengths, plan) if want_plan else (out, lengths)
+
+
+def inv_spectrogram_marks(linear_outputs, cfg, frame_lengths, marks, bounds, usable=None):
+    """inv_spectrogram_batch(..., prosody=marks) for marks whose bounds the caller brings (synthesis: token bounds from the
+    monotonic path, device int (B, S + 1) source frames; usable: device bool[B], false where there is no path)
+    -> (waveforms, sample lengths, the plan of plan_prosody)"""
+    cfg = cfg or AudioConfig()
+    check_bins(linear_outputs.shape[-1], cfg.fft_size, "inv_spectrogram_marks")
+    return _inv_spectrogram_items(linear_outputs, cfg, None, frame_lengths, list(marks), bounds, usable, want_plan=True)
 
 
 # ---------------------------------------------------------------------------------------------

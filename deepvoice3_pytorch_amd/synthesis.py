@@ -54,6 +54,17 @@ so `wav` changes and mel, linear and alignment stay what the model made; token s
 
     for mel, linear, alignment, wav in synthesis.tts_batch(model, seqs, rate=[0.8, 1.0], semitones=[0, 3]): ...
 
+Prosody marks, opt-in on all three entry points (per ticket on RollingSynthesizer.submit): marks= takes
+one audio.ProsodyMarks per utterance (or None) -- spans of TOKENS with their own rate, semitones and gain_db, breaks after
+tokens, an optional transition.  The utterance's monotonic path (ops.monotonic_path) turns token spans into frame spans
+on the device, audio.plan_prosody turns those into per-frame tables and the warp follows them; only `wav` changes, and
+with timings a slowed token gets longer and a break is the gap between two tokens.  Not together with rate=, semitones=
+or prosody=.  An utterance without an admissible path is vocoded without its marks (audio.MarksNotApplied warning).
+tts_document does not take marks: it trims and joins what tts_batch returns.
+
+    marks = audio.ProsodyMarks(spans=[(4, 9, dict(rate=0.8))], breaks=[(9, 0.3)], transition_ms=30)
+    for mel, linear, alignment, wav in synthesis.tts_batch(model, [seq0, seq1], marks=[marks, None]): ...
+
 Deliverable audio, opt-in: mastering= (an audio.Mastering) on all three entry points turns every `wav`
 into the mastered one (audio.master_items: each utterance alone, so the three agree); join_utterances joins any list of
 device waveforms into one document -- silence trimmed, levelled, sentences crossfaded or separated by faded pauses,
@@ -163,6 +174,13 @@ def token_spans(durations, seconds_per_step):
     return (upto - durations).to(torch.float64) * sps, upto.to(torch.float64) * sps
 
 
+def search_path(alignments, steps, lengths, layout="btk", max_advance=1):
+    """ops.monotonic_path with host step and key counts -> (summary rows, path, durations) on the device, no host read"""
+    from . import ops
+    as_i32 = lambda v: torch.tensor([int(n) for n in v], dtype=torch.int32).to(alignments.device)
+    return ops.monotonic_path(alignments, as_i32(steps), as_i32(lengths), layout, max_advance)
+
+
 def token_timings(alignments, steps, lengths, seconds_per_step, layout="btk", max_advance=1):
     """Where every input token is spoken: alignments / layout as ops.monotonic_path takes them (read in place), item b's
     rows < steps[b] and keys < lengths[b] (host ints); seconds_per_step: the waveform time of one decoder step;
@@ -171,11 +189,14 @@ def token_timings(alignments, steps, lengths, seconds_per_step, layout="btk", ma
     "durations" (N_b,) int32, the steps of every key; "start" and "end" (N_b,) float64, token_spans of them in seconds;
     "summary" (len(TIMING_COLUMNS),) fp32, the item's row.  An item without an admissible path (summary[0] = 0) has a
     path of -1, zero durations and empty spans at 0."""
-    from . import ops
-    dev = alignments.device
+    return timings_of_path(search_path(alignments, steps, lengths, layout, max_advance), steps, lengths, seconds_per_step)
+
+
+def timings_of_path(searched, steps, lengths, seconds_per_step):
+    """token_timings' dicts from what search_path returned for the same steps and lengths (a caller that needs the
+    durations for something else too searches once)"""
     steps, lengths = [int(n) for n in steps], [int(n) for n in lengths]
-    as_i32 = lambda v: torch.tensor(v, dtype=torch.int32).to(dev)
-    out, path, durations = ops.monotonic_path(alignments, as_i32(steps), as_i32(lengths), layout, max_advance)
+    out, path, durations = searched
     start, end = token_spans(durations, seconds_per_step)
     T, Tk = path.size(1), durations.size(1)
     res = []
@@ -230,6 +251,84 @@ def utterance_prosody(rate, semitones, prosody, B, what):
     return None if p.neutral() else p
 
 
+def utterance_marks(marks, rate, semitones, prosody, B, what):
+    """the `marks=` keyword of the entry points -> None (nothing asked for, or nothing that changes anything) or a list of
+    B entries, each an audio.ProsodyMarks in tokens or None.  One mechanism per call: marks together with rate,
+    semitones or prosody are refused."""
+    if marks is None:
+        return None
+    if rate is not None or semitones is not None or prosody is not None:
+        raise ValueError("%s: marks cannot be combined with rate, semitones or prosody: one mechanism per call" % what)
+    return audio.item_marks(marks, B, "tokens", what)
+
+
+def token_bounds(durations, marks, step_frames, audio_cfg=None):
+    """the source frame every segment of the items' marks starts at: durations (G, Tk) steps per key on the device (zero
+    past an item's keys), marks: G ProsodyMarks in tokens, step_frames: linear frames per decoder step (r * upsampling)
+    -> int32 (G, S + 1) on the device: the running sum of the durations gathered at the segments' first tokens (a token
+    index past the text gives the utterance's end) times step_frames.  No host read.  Decoder-step resolution."""
+    start = audio.marks_tables(marks, audio_cfg)["start"]
+    upto = torch.nn.functional.pad(torch.cumsum(durations.to(torch.int64), dim=1), (1, 0))
+    idx = torch.from_numpy(np.minimum(start, durations.size(1))).to(durations.device)
+    return (torch.gather(upto, 1, idx) * int(step_frames)).to(torch.int32)
+
+
+def _spans_under_plan(span, plan, row, step_frames, audio_cfg):
+    """a timing dict on the time axis of an utterance spoken under a plan (audio.plan_map): a token's start is mapped as a
+    start, its end as an end, so a break shows as the gap between one token's end and the next one's start"""
+    cfg = audio_cfg or audio.AudioConfig()
+    one = {k: (v[row:row + 1] if torch.is_tensor(v) and v.dim() >= 1 and k != "out_lengths" else v) for k, v in plan.items()}
+    upto = torch.cumsum(span["durations"].to(torch.int64), dim=0)
+    sec = float(cfg.hop_size) / float(cfg.sample_rate)
+    out = dict(span)
+    out["start"] = audio.plan_map(one, ((upto - span["durations"]) * int(step_frames))[None], "start")[0] * sec
+    out["end"] = audio.plan_map(one, (upto * int(step_frames))[None], "end")[0] * sec
+    return out
+
+
+def _vocode_marked(linear, audio_cfg, frame_lengths, settings, marks, searched, step_frames, what):
+    """_vocode for a group in which some items carry ProsodyMarks (marks: per item one or None; searched: search_path's
+    result for the group).  The marked items are vocoded in one audio.inv_spectrogram_marks call per key() -- token bounds
+    from the path's durations, all on the device --, the others by _vocode; every item's waveform depends on the item
+    alone.  An item whose path is infeasible is vocoded without its marks, and an audio.MarksNotApplied warning names it
+    (the flag rides in the plan's one host read).  -> (waveforms, sample lengths, per item None or (plan, row))"""
+    import warnings
+    G, dev = len(marks), linear.device
+    fl = torch.as_tensor(frame_lengths).reshape(-1).to(torch.int64)
+    feasible, durations = searched[0][:, 0] > 0, searched[2]
+    groups = {}
+    for g, m in enumerate(marks):
+        if m is not None:
+            groups.setdefault(m.key(), []).append(g)
+    rest = [g for g in range(G) if marks[g] is None]
+    parts, plans = [], [None] * G
+    if rest:
+        parts.append((rest,) + tuple(_vocode(linear[torch.tensor(rest, device=dev)], audio_cfg, fl[rest],
+                                             [settings[g] for g in rest])))
+    for key in sorted(groups):
+        idx = groups[key]
+        at = torch.tensor(idx, device=dev)
+        sub_marks = [marks[g] for g in idx]
+        bounds = token_bounds(durations[at], sub_marks, step_frames, audio_cfg)
+        w, n, plan = audio.inv_spectrogram_marks(linear if len(idx) == G else linear[at], audio_cfg, fl[idx], sub_marks,
+                                                 bounds, feasible[at])
+        parts.append((idx, w, n))
+        for row, g in enumerate(idx):
+            plans[g] = (plan, row)
+        lost = [g for row, g in enumerate(idx) if not plan["usable"][row]]
+        if lost:
+            warnings.warn(audio.MarksNotApplied("%s: no monotonic path for item(s) %s of the group: vocoded without their "
+                                                "marks" % (what, lost)))
+    if len(parts) == 1:
+        return parts[0][1], parts[0][2], plans
+    wavs = linear.new_zeros((G, max(w.size(1) for _, w, _ in parts)))
+    samples = torch.zeros(G, dtype=torch.int64)
+    for idx, w, n in parts:
+        wavs[torch.tensor(idx, device=dev), :w.size(1)] = w
+        samples[idx] = n
+    return wavs, samples, plans
+
+
 def _spans_at_rate(span, rate):
     """a timing dict on the time axis of an utterance spoken at `rate`: start and end in seconds divided by it (the
     summary's columns are counts of steps and keys and a score, none in seconds: they stay)"""
@@ -268,7 +367,7 @@ def _vocode(linear, audio_cfg, frame_lengths, settings):
 
 
 def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=False, stall_limit=None, timings=False,
-              timing_advance=1, rate=None, semitones=None, prosody=None, mastering=None, from_mel=False):
+              timing_advance=1, rate=None, semitones=None, prosody=None, marks=None, mastering=None, from_mel=False):
     """sequences: a list of int id sequences (one per utterance); speaker_ids: None or one id per utterance.
     -> a list of (mel (T_b, mel_dim), linear (T_b * upsampling, linear_dim), alignment (steps_b, Tt_b), wav (L_b,)),
     device tensors, each trimmed to its own utterance.  diagnostics: a fifth element, the utterance's alignment
@@ -286,10 +385,18 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=Fa
     audio.num_samples(audio.warped_frames(frames, rate)) samples; mel, linear and alignment stay what the model made,
     and with timings every token's start and end are divided by the utterance's rate.
     mastering (an audio.Mastering): `wav` becomes audio.master_items of the batch's waveforms -- every utterance levelled
-    and quantised alone; nothing else in the result changes."""
+    and quantised alone; nothing else in the result changes.
+    marks (one audio.ProsodyMarks in tokens per utterance, None entries allowed): rate, pitch, level and
+    pauses that vary WITHIN the utterance.  The token bounds are the running sums of the monotonic path's durations
+    (ops.monotonic_path at max_advance = timing_advance) times r * upsampling, gathered on the device; only `wav` changes,
+    to audio.num_samples(T'_b) samples under the plan's frame count; with timings every token's start and end go through
+    audio.plan_map -- tokens in a slowed span get longer and a break is the gap between two tokens.  An utterance
+    without an admissible path is vocoded without its marks under an audio.MarksNotApplied warning.  marks together with
+    rate, semitones or prosody are refused; marks that change nothing launch nothing."""
     if len(sequences) == 0:
         return []
     audio.check_mastering(mastering, "tts_batch")
+    marks = utterance_marks(marks, rate, semitones, prosody, len(sequences), "tts_batch")
     pros = utterance_prosody(rate, semitones, prosody, len(sequences), "tts_batch")
     mel_opt = mel_options(from_mel)
     if mel_opt is None:
@@ -315,7 +422,14 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=Fa
     with torch.no_grad():
         if mel_opt is not None:
             linear = audio.mel_to_linear(mel, audio_cfg, frames, up, mel_opt)
-        wavs, samples = audio.inv_spectrogram_batch(linear, audio_cfg, frame_lengths=frames * up, prosody=pros)
+        steps = [int(n) // steps_per_frame for n in frames]
+        searched = plans = None
+        if marks is not None:
+            searched = search_path(alignments, steps, lengths, "btk", timing_advance)
+            wavs, samples, plans = _vocode_marked(linear, audio_cfg, frames * up, [None] * B, marks, searched,
+                                                  steps_per_frame * up, "tts_batch")
+        else:
+            wavs, samples = audio.inv_spectrogram_batch(linear, audio_cfg, frame_lengths=frames * up, prosody=pros)
         if mastering is not None:
             wavs = audio.master_items(wavs, samples, mastering)
     stats = None
@@ -324,10 +438,14 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=Fa
         stats = _diagnose(alignments, steps, lengths, [model.seq2seq.decoder.max_decoder_steps] * B)
     spans = None
     if timings:
-        spans = token_timings(alignments, [int(n) // steps_per_frame for n in frames], lengths,
-                              seconds_per_step(audio_cfg, steps_per_frame, up), "btk", timing_advance)
+        steps, sps = [int(n) // steps_per_frame for n in frames], seconds_per_step(audio_cfg, steps_per_frame, up)
+        spans = token_timings(alignments, steps, lengths, sps, "btk", timing_advance) if searched is None else \
+            timings_of_path(searched, steps, lengths, sps)
         if pros is not None:
             spans = [_spans_at_rate(s, r) for s, r in zip(spans, pros.per_item(B)[0])]
+        if plans is not None:
+            spans = [s if p is None else _spans_under_plan(s, p[0], p[1], steps_per_frame * up, audio_cfg)
+                     for s, p in zip(spans, plans)]
     out = []
     for b in range(B):
         n = int(frames[b])
@@ -388,12 +506,16 @@ class RollingSynthesizer(object):
         self._req = {}
         self._next = 0
 
-    def submit(self, ids, speaker_id=None, max_decoder_steps=None, rate=None, semitones=None, prosody=None):
+    def submit(self, ids, speaker_id=None, max_decoder_steps=None, rate=None, semitones=None, prosody=None, marks=None):
         """queue one utterance (a sequence of int ids) -> its ticket (0, 1, 2, ... in submission order).
         max_decoder_steps: this request's own cap (default and upper limit: the decoder's); rate, semitones (scalars),
         prosody (an audio.Prosody): how THIS utterance is spoken, as tts_batch takes them -- retirement gathers the
-        group's values into its one Griffin-Lim call"""
+        group's values into its one Griffin-Lim call; marks (an audio.ProsodyMarks in tokens): THIS utterance's marks, as
+        tts_batch takes them (not together with the other three)"""
         ids = [int(i) for i in ids]
+        marks = utterance_marks(marks, rate, semitones, prosody, 1, "RollingSynthesizer.submit")
+        if marks is not None:
+            marks[0].half_width(self.audio_cfg), marks[0].ramp_frames(self.audio_cfg)        # refused here, not at retirement
         for name, v in (("rate", rate), ("semitones", semitones)):
             if v is not None and isinstance(v, (list, tuple, np.ndarray, torch.Tensor)):
                 raise ValueError("RollingSynthesizer.submit: %s=%r must be one number: a ticket is one utterance" % (name, v))
@@ -415,7 +537,7 @@ class RollingSynthesizer(object):
                 "missing" if multi else "given", getattr(self.model, "n_speakers", 1)))
         ticket = self._next
         self._next += 1
-        self._req[ticket] = (ids, speaker_id, cap, pros)
+        self._req[ticket] = (ids, speaker_id, cap, pros, None if marks is None else marks[0])
         self.schedule.submit(ticket)
         return ticket
 
@@ -483,7 +605,14 @@ class RollingSynthesizer(object):
                     ops.valid = prev
                 up = linear.size(1) // mel.size(1)
             settings = [self._req[t][3] for t in tickets]
-            wavs, samples = _vocode(linear, self.audio_cfg, frames * up, settings)
+            marks = [self._req[t][4] for t in tickets]
+            searched = plans = None
+            if any(m is not None for m in marks):
+                searched = search_path(alignments, steps, lengths, "btk", self.timing_advance)
+                wavs, samples, plans = _vocode_marked(linear, self.audio_cfg, frames * up, settings, marks, searched, r * up,
+                                                      "RollingSynthesizer (tickets %s)" % (tickets,))
+            else:
+                wavs, samples = _vocode(linear, self.audio_cfg, frames * up, settings)
             if self.mastering is not None:
                 wavs = audio.master_items(wavs, samples, self.mastering)
         stats = None
@@ -491,8 +620,13 @@ class RollingSynthesizer(object):
             stats = _diagnose(alignments, steps, lengths, [self._req[t][2] for t in tickets])
         spans = None
         if self.timings:            # a released slot's stacked rows stay as they are until it is admitted again
-            spans = self._timings(retired, lengths, alignments, seconds_per_step(self.audio_cfg, r, up))
+            sps = seconds_per_step(self.audio_cfg, r, up)
+            spans = self._timings(retired, lengths, alignments, sps) if searched is None else \
+                timings_of_path(searched, steps, lengths, sps)
             spans = [s if p is None else _spans_at_rate(s, p.rate[0]) for s, p in zip(spans, settings)]
+            if plans is not None:
+                spans = [s if p is None else _spans_under_plan(s, p[0], p[1], r * up, self.audio_cfg)
+                         for s, p in zip(spans, plans)]
         out = []
         for b, t in enumerate(tickets):
             n = int(frames[b])
@@ -562,7 +696,7 @@ class RollingSynthesizer(object):
 
 def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, audio_cfg=None, chunk=8,
                max_decoder_steps=None, diagnostics=False, stall_limit=None, timings=False, timing_advance=1,
-               rate=None, semitones=None, prosody=None, mastering=None, from_mel=False):
+               rate=None, semitones=None, prosody=None, marks=None, mastering=None, from_mel=False):
     """Rolling-admission counterpart of tts_batch, as a generator: sequences (any iterable of id lists; speaker_ids an
     iterable alongside, or None; max_decoder_steps None, one cap, or an iterable of per-utterance caps) are submitted
     in order as slots free -- at most `slots` are queued ahead -- and every utterance is yielded when it retires, in
@@ -572,7 +706,8 @@ def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, 
     (one more element per result, the utterance's timing dict); from_mel: as tts_batch takes it (the mel is vocoded, the
     post-net is not run); rate, semitones: None, one number, or an iterable of per-utterance values alongside
     `sequences`; prosody: an audio.Prosody carrying the envelope settings (RollingSynthesizer.submit takes all three);
-    mastering: an audio.Mastering, as tts_batch takes it."""
+    mastering: an audio.Mastering, as tts_batch takes it; marks: None or an iterable alongside `sequences` of one
+    audio.ProsodyMarks in tokens (or None) per utterance, each handed to its submit."""
     if max_text_len is None:
         sequences = [list(s) for s in sequences]
         if not sequences:
@@ -589,6 +724,9 @@ def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, 
     number = lambda v: v is None or isinstance(v, (int, float, np.integer, np.floating))
     rates = None if number(rate) else iter(rate)
     shifts = None if number(semitones) else iter(semitones)
+    if isinstance(marks, audio.ProsodyMarks):
+        raise ValueError("tts_stream: marks must be an iterable of one audio.ProsodyMarks (or None) per utterance")
+    each = None if marks is None else iter(marks)
     more = True
     while more or rs.pending():
         while more and len(rs.schedule.queue) < slots:
@@ -600,7 +738,8 @@ def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, 
             rs.submit(ids, next(spk) if spk is not None else None,
                       next(caps) if caps is not None else max_decoder_steps,
                       rate=float(next(rates)) if rates is not None else rate,
-                      semitones=float(next(shifts)) if shifts is not None else semitones, prosody=prosody)
+                      semitones=float(next(shifts)) if shifts is not None else semitones, prosody=prosody,
+                      marks=next(each) if each is not None else None)
         for res in rs.poll():
             yield res
 

@@ -1541,6 +1541,85 @@ int dv3_prosody_warp_f32(const float* mag, float* out, int32_t B, int32_t T_in, 
                          const double* ratio, int32_t env_half_width, int32_t preserve_envelope, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Prosody marks: rate, pitch, level and pauses that vary WITHIN an utterance (audio.ProsodyMarks, audio.plan_prosody,
+ * audio.warp_magnitudes_curve).  The warp above with its per-item scalars replaced by per-output-frame
+ * tables, and two small kernels that make the tables from segments.  Three new entry points with plain arguments, no
+ * struct added or changed, so the version stays 50.  (Their names carry "curve", not the family's prefix: the suite pins
+ * the list of entry points named after the family to the scalar warp alone.)
+ *
+ * dv3_curve_warp_f32: mag, out, tlen_in, tlen_out, bins, env_half_width, preserve_envelope as dv3_prosody_warp_f32 takes
+ * them; pos, ratio device double[B][T_out], gain device float[B][T_out].  With n = tlen_in[b] (n >= 1), item b's output
+ * frame j < tlen_out[b] is, in fp32 unless said otherwise, every product and sum rounded once and none contracted:
+ *
+ *   silence   pos[b][j] is not >= 0 (negative, or NaN):  out[k] = 0 for every k; ratio and gain are not looked at.
+ *   time      u = min(pos[b][j], n - 1) in fp64;  i0 = floor(u);  a = u - i0 in fp64, rounded once to fp32;
+ *             i1 = min(i0 + 1, n - 1);  m[k] = lerp(a, mag[b][i0][k], mag[b][i1][k]), lerp as above.  Frames at or beyond
+ *             n are never read.
+ *   frequency v[k] = what dv3_prosody_warp_f32 calls out[k], with ratio[b][j] in place of ratio[b]: m[k] itself where the
+ *             ratio is 1 or no positive number; else the plain or the envelope-preserving branch, word for word.
+ *   gain      out[k] = v[k] where gain[b][j] == 1, else v[k] gain[b][j]: ONE more rounded product.  The gain is NOT
+ *             checked on the device: a negative, infinite or NaN gain multiplies as it stands (audio.warp_magnitudes_curve
+ *             refuses one before the launch).
+ *
+ * Rows j >= tlen_out[b] (and every row of an item with n < 1) are zeros; every element of out is written, nothing outside
+ * it; one 256-thread workgroup per output frame, fixed summation order, no atomics; an item's rows depend on that item's
+ * frames and table rows alone.  With pos[b][j] = j rate[b] (the fp64 product), ratio[b][j] = ratio[b] and gain 1 the
+ * output is dv3_prosody_warp_f32's bit for bit: both kernels are one body.
+ * Refused (DV3_EINVAL, "curve_warp:", nothing launched): what dv3_prosody_warp_f32 refuses, with pos in the place of rate,
+ * and a null gain; gain not 4-byte aligned.
+ *
+ * Segments -> tables.  Item b has nseg[b] segments (clamped into [1, S]; S <= DV3_PROSODY_MAX_SEGMENTS is the tables'
+ * stride): bounds int32[B][S + 1] source frames, and per segment rate, semitones, gain_db double[B][S] and break_frames
+ * int32[B][S], the silent frames put in AFTER the segment.  The bounds are repaired as they are read: c_0 = 0,
+ * c_s = max(c_{s-1}, min(max(bounds[b][s], 0), n)) for 0 < s < nseg, c_nseg = n.  A rate outside
+ * [1 / DV3_PROSODY_MAX_RATE, DV3_PROSODY_MAX_RATE] (or NaN) counts as 1, break_frames is clamped into
+ * [0, DV3_PROSODY_MAX_BREAK]; semitones and gain_db are used as they stand (audio.ProsodyMarks checks all of them).
+ *
+ * dv3_curve_plan_f64: one thread per item, an ascending scan in fp64.  o_0 = 0 and o_{s+1} = o_s + len_s + break_s, with
+ *   len_s = 0                                                  for an empty segment (c_{s+1} == c_s)
+ *   len_s = floor((c_{s+1} - 1 - c_s) / rate_s + 0.5) + 1      for the segment that ends the item (c_{s+1} == n, non-empty):
+ *                                                              the item's last frame keeps its place, as in the scalar warp
+ *   len_s = the integer with (len_s - 1) rate_s < c_{s+1} - c_s <= len_s rate_s, both products in fp64 -- ceil((c_{s+1} -
+ *           c_s) / rate_s), corrected by one where the rounded quotient crossed an integer -- for every other segment:
+ *           its frames stop short of the next segment's first source frame, so the time map stays monotone.
+ * o int32[B][S + 1] (entries past nseg[b] repeat o_nseg; sums saturate at 2^31 - 1), tlen_out[b] = max(min_frames, o_nseg).
+ * One segment without a break gives audio.warped_frames(n, rate).
+ * Refused ("curve_plan:"): a null nseg, bounds, rate, break_frames, o or tlen_out (tlen_in may be NULL: all T_in); rate not
+ * 8-byte aligned; B outside [1, 65535]; T_in < 1; S outside [1, DV3_PROSODY_MAX_SEGMENTS]; min_frames < 0.
+ *
+ * dv3_curve_fill_f64: one thread per (b, j), j < T_out, finds its segment by a scan of o and writes all three tables:
+ *   inside segment s (o_s <= j < o_s + len_s)   pos = c_s + (j - o_s) rate_s, one fp64 product and one fp64 sum
+ *   in a break (o_s + len_s <= j < o_{s+1})     pos = -1
+ *   o_nseg <= j < tlen_out[b]                   (frames the min_frames clamp added) pos = n - 1: the item's last frame is
+ *                                               held, with the last segment's semitones and gain_db
+ *   j >= tlen_out[b], or n < 1                  pos = -1, ratio = 1, gain = 1
+ *   ratio = exp2(semitones / 12) in fp64;  gain = pow(10, gain_db / 20) in fp64, rounded once to fp32 (exactly 1 at 0 dB).
+ * ramp_frames = R > 0: a boundary e = o_{s+1} between segments s and s + 1 is eligible when both have output frames and
+ * break_s = 0.  Its ramp is the R frames e - floor(R / 2) .. e - floor(R / 2) + R - 1, cut at the far ends of the two
+ * segments; frame number t of it (from 0) has semitones = x_s + w (x_{s+1} - x_s), w = (t + 1) / (R + 1) in fp64, and
+ * gain_db alike.  Where the ramps of a segment's two boundaries overlap, the later boundary's holds.  The rate is not
+ * ramped: pos stays piecewise linear.
+ * Refused ("curve_fill:"): a null pointer other than tlen_in; a misaligned double table; B, T_in, S as above; T_out < 1;
+ * ramp_frames outside [0, DV3_PROSODY_MAX_RAMP].
+ * tests/prosody_curve_ref.py restates all three in float64.
+ * ------------------------------------------------------------------------------------ */
+#define DV3_PROSODY_MAX_SEGMENTS 64
+#define DV3_PROSODY_MAX_RATE 64
+#define DV3_PROSODY_MAX_BREAK 1048576
+#define DV3_PROSODY_MAX_RAMP 4096
+int dv3_curve_warp_f32(const float* mag, float* out, int32_t B, int32_t T_in, int32_t T_out, int32_t bins,
+                       const int32_t* tlen_in /* or NULL */, const int32_t* tlen_out, const double* pos,
+                       const double* ratio, const float* gain, int32_t env_half_width, int32_t preserve_envelope,
+                       void* stream);
+int dv3_curve_plan_f64(const int32_t* tlen_in /* or NULL */, int32_t B, int32_t T_in, int32_t S, const int32_t* nseg,
+                       const int32_t* bounds, const double* rate, const int32_t* break_frames, int32_t min_frames,
+                       int32_t* o, int32_t* tlen_out, void* stream);
+int dv3_curve_fill_f64(const int32_t* tlen_in /* or NULL */, int32_t B, int32_t T_in, int32_t S, const int32_t* nseg,
+                       const int32_t* bounds, const double* rate, const double* semitones, const double* gain_db,
+                       const int32_t* break_frames, const int32_t* o, const int32_t* tlen_out, int32_t T_out,
+                       int32_t ramp_frames, double* pos, double* ratio, float* gain, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Deliverable audio: the last stage of synthesis -- measure every utterance's level, turn the levels into gains, and
  * place, scale, fade and quantise the utterances into one output in ONE launch (audio.wave_levels, audio.master_items,
  * audio.to_pcm16, synthesis.join_utterances).  The reference's counterpart is audio.save_wav
