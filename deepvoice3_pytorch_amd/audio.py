@@ -43,6 +43,11 @@ Deliverable audio (csrc/master.hip): the reference ends at save_wav (audio.py:16
 wave_levels measures every utterance, wave_gains turns levels into gains under a Mastering, wave_master places, scales,
 fades and quantises in one launch; master_items / to_pcm16 apply them to a padded batch, save_wav writes the file.
 synthesis.join_utterances builds a document of several utterances on them.  Off by default: nothing runs unasked.
+
+Loudness (csrc/loudness.hip): Mastering(level="lufs") levels to a LUFS target under a sample-peak or
+true-peak ceiling.  wave_loudness measures ITU-R BS.1770 integrated loudness and the 4x true peak of spans or groups of
+spans on the device (k_weighting and true_peak_table make its float64 coefficients and its interpolator on the host),
+loudness_gains turns its rows into gains.
 """
 import numpy as np
 import torch
@@ -1507,19 +1512,26 @@ def _db(v, what, lo, hi):
 class Mastering(object):
     """How synthesised waveforms become deliverable audio (master_items, synthesis.join_utterances).
     level: None (gain 1), "peak" (the largest |x| goes to target_db dBFS), "rms" (the RMS goes to target_db dBFS, but
-    no peak above ceiling_db) or "reference" (the reference's save_wav, audio.py:16-18: x * 32767 / max(0.01, peak)
+    no peak above ceiling_db), "lufs" (the BS.1770 integrated loudness goes to target_db LUFS, but no peak above
+    ceiling_db; true_peak=True makes that a dBTP ceiling on the 4x oversampled true peak; it needs a sample rate:
+    wave_loudness) or "reference" (the reference's save_wav, audio.py:16-18: x * 32767 / max(0.01, peak)
     truncated to int16 -- it takes dtype "int16", no dither and no fades); scope: "item" (every utterance its own gain)
-    or "document" (one gain from the combined levels of all of them); target_db: default -1 for "peak", -20 for "rms";
-    max_gain_db caps the gain of "peak" and "rms" (a near-silent item is not blown up); fade_ms: the raised-cosine fade
+    or "document" (one gain from the combined levels of all of them; under "lufs" the items' blocks are pooled, the
+    standard's integrated loudness of the whole programme); target_db: default -1 for "peak", -20 for "rms", -23 for
+    "lufs" (EBU R 128); max_gain_db caps the gain of "peak", "rms" and "lufs" (a near-silent item is not blown up); fade_ms: the raised-cosine fade
     at a document's joins and edges (join_utterances; master_items fades nothing); dither, seed: TPDF dither of +-1 LSB
     before the int16 rounding, a function of (seed, sample index); dtype: "int16" or "float32".
     The defaults are starting points, not measurements: nothing here was heard on a trained voice.
     Refused by value (ValueError naming it)."""
 
     def __init__(self, level=None, scope="item", target_db=None, ceiling_db=-1.0, max_gain_db=30.0, fade_ms=5.0,
-                 dither=False, seed=0, dtype="int16"):
-        if level is not None and level not in _GAIN_POLICIES:
-            raise ValueError("Mastering: level=%r must be None, 'peak', 'rms' or 'reference'" % (level,))
+                 dither=False, seed=0, dtype="int16", true_peak=False):
+        if level is not None and level != "lufs" and level not in _GAIN_POLICIES:
+            raise ValueError("Mastering: level=%r must be None, 'peak', 'rms', 'lufs' or 'reference'" % (level,))
+        if not isinstance(true_peak, (bool, np.bool_)):
+            raise ValueError("Mastering: true_peak=%r must be True or False" % (true_peak,))
+        if true_peak and level != "lufs":
+            raise ValueError("Mastering: true_peak=True needs level='lufs' (the other levels' ceiling is a sample peak)")
         if scope not in ("item", "document"):
             raise ValueError("Mastering: scope=%r must be 'item' or 'document'" % (scope,))
         if dtype not in _MASTER_MODES:
@@ -1529,8 +1541,8 @@ class Mastering(object):
         if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
             raise ValueError("Mastering: seed=%r must be an integer in [0, 2^64)" % (seed,))
         if target_db is None:
-            target_db = -20.0 if level == "rms" else -1.0
-        self.level, self.scope, self.dtype = level, scope, dtype
+            target_db = {"rms": -20.0, "lufs": -23.0}.get(level, -1.0)
+        self.level, self.scope, self.dtype, self.true_peak = level, scope, dtype, bool(true_peak)
         self.target_db = _db(target_db, "target_db", -120.0, 0.0)
         self.ceiling_db = _db(ceiling_db, "ceiling_db", -120.0, 0.0)
         self.max_gain_db = _db(max_gain_db, "max_gain_db", 0.0, 120.0)
@@ -1571,6 +1583,8 @@ def wave_gains(levels, lengths, mastering, groups=None):
     offsets, ascending host ints from 0 to B.  fp64 on the device, rounded once (include/dv3hip.h: dv3_wave_gains_f32)."""
     if mastering.level is None:
         raise ValueError("wave_gains: mastering.level is None (the gain is 1: nothing to compute)")
+    if mastering.level == "lufs":
+        raise ValueError("wave_gains: level='lufs' is measured by wave_loudness and turned into gains by loudness_gains")
     B = int(levels.shape[0])
     if tuple(levels.shape) != (B, len(LEVEL_COLUMNS)) or levels.dtype != torch.float64 or not levels.is_cuda:
         raise ValueError("wave_gains: levels must be wave_levels' float64 (B, 5) device table")
@@ -1589,6 +1603,160 @@ def wave_gains(levels, lengths, mastering, groups=None):
               _lib.CONSTS[_GAIN_POLICIES[mastering.level]], lin(mastering.target_db), lin(mastering.ceiling_db),
               lin(mastering.max_gain_db), gain.data_ptr(), _stream())
     return gain
+
+
+# ---- loudness: BS.1770 integrated loudness and true peak (csrc/loudness.hip) --------------------------
+LOUDNESS_COLUMNS = ("lufs", "blocks", "gated_abs", "gated_rel", "momentary_max", "true_peak", "flags")
+_K_SHELF = (1681.974450955533, 3.999843853973347, 0.7071752369554196, 0.4996667741545416)     # f0, G dB, Q, Vb exponent
+_K_HIGHPASS = (38.13547087602444, 0.5003270373238773)                                        # f0, Q
+_KW_CACHE = {}
+_TP_CACHE = []
+
+
+def loudness_step(sample_rate):
+    """h = floor(0.1 fs + 0.5): the step of the gating blocks (a block is 4 h samples); ValueError outside 8000 .. 192000"""
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float, np.integer, np.floating)) or \
+            not 8000 <= float(sample_rate) <= 192000:
+        raise ValueError("loudness: sample_rate=%r must be a number in [8000, 192000]" % (sample_rate,))
+    return int(np.floor(0.1 * float(sample_rate) + 0.5))
+
+
+def k_weighting(sample_rate):
+    """The K-weighting of BS.1770 at `sample_rate`, in float64 by the bilinear transform of the analogue prototypes
+    (include/dv3hip.h states the formulas) -> {"shelf": (b, a), "highpass": (b, a), "coef": the 10 doubles
+    dv3_wave_loudness_f64 takes, "A": the 4x4 zero-input transition of the cascade's state, "h": the step, "Ah": A^h}"""
+    h = loudness_step(sample_rate)
+    key = float(sample_rate)
+    if key in _KW_CACHE:
+        return _KW_CACHE[key]
+    f0, G, Q, e = _K_SHELF
+    K = np.tan(np.pi * f0 / key)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** e
+    a0 = 1.0 + K / Q + K * K
+    sb = np.array([Vh + Vb * K / Q + K * K, 2.0 * (K * K - Vh), Vh - Vb * K / Q + K * K], dtype=np.float64) / a0
+    sa = np.array([1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0], dtype=np.float64)
+    f0, Q = _K_HIGHPASS
+    K = np.tan(np.pi * f0 / key)
+    a0 = 1.0 + K / Q + K * K
+    pb = np.array([1.0, -2.0, 1.0], dtype=np.float64)
+    pa = np.array([1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0], dtype=np.float64)
+    A = np.array([[-sa[1], 1.0, 0.0, 0.0],
+                  [-sa[2], 0.0, 0.0, 0.0],
+                  [pb[1] - pa[1] * pb[0], 0.0, -pa[1], 1.0],
+                  [pb[2] - pa[2] * pb[0], 0.0, -pa[2], 0.0]], dtype=np.float64)
+    out = {"shelf": (sb, sa), "highpass": (pb, pa), "coef": np.concatenate([sb, sa[1:], pb, pa[1:]]), "A": A, "h": h,
+           "Ah": np.ascontiguousarray(np.linalg.matrix_power(A, h))}
+    _KW_CACHE[key] = out
+    return out
+
+
+def true_peak_table():
+    """The 4x interpolator of the true-peak estimate: g[i] = sinc(i / 4) kaiser(49, beta=8)[i + 24], i = -24 .. 24, in
+    float64, cut into its phases 1 .. 3 of 12 taps (phase 0 is the identity) and rounded once -> float32 (3, 12),
+    table[p - 1][j] = g[p + 4 (j - 6)], the tap of x[m + 6 - j] in y[4 m + p]"""
+    if not _TP_CACHE:
+        i = np.arange(-24, 25, dtype=np.float64)
+        g = np.sinc(i / 4.0) * np.kaiser(49, 8.0)
+        _TP_CACHE.append(np.array([[g[24 + p + 4 * (j - 6)] for j in range(12)] for p in (1, 2, 3)]).astype(np.float32))
+    return _TP_CACHE[0].copy()
+
+
+def _group_offsets(groups, B, what):
+    goff = np.asarray(groups, dtype=np.int64).reshape(-1)
+    if goff.size < 2 or goff[0] != 0 or goff[-1] != B or np.any(np.diff(goff) < 0) or goff.size - 1 > B:
+        raise ValueError("%s: groups must ascend from 0 to %d in at most %d groups, got %s" % (what, B, B, goff.tolist()))
+    return goff.astype(np.int32)
+
+
+def wave_loudness(wav_flat, starts, lengths, sample_rate, groups=None, true_peak=False, max_len=None, levels=None,
+                  want_tables=False):
+    """BS.1770 integrated loudness of B spans of a flat float32 device tensor (spans as wave_levels takes them: host
+    integers, or int64 device tensors with max_len=), mono: K-weighting in float64 from a zero state at every span's own
+    first sample, 400 ms blocks every 100 ms, the absolute gate at -70 and the relative gate 10 below the gated mean.
+    groups: None (every span its own row) or group offsets, ascending host ints from 0 to B: a group's blocks are
+    pooled.  -> float64 (G, 7) on the device, columns LOUDNESS_COLUMNS: lufs, blocks, gated_abs, gated_rel,
+    momentary_max, true_peak, flags (bit 0: no complete block, measured ungated; bit 1: silent, lufs is -inf).
+    true_peak=True: the peak column is the 4x oversampled true peak (true_peak_table), else the sample peak (from
+    `levels`, wave_levels' table of the same spans, measured here when None).  want_tables: -> (rows, energy (B, K),
+    states (B, K, 4)), the sub-block energies and every chunk's start state.  include/dv3hip.h states every step
+    (dv3_wave_loudness_f64, dv3_loudness_gate_f64); tests/loudness_ref.py restates them.  No host read."""
+    import ctypes
+    wav_flat = _c(_chk(wav_flat, "wav_flat")).reshape(-1)
+    kw = k_weighting(sample_rate)
+    h = kw["h"]
+    starts_d, lengths_d, B, max_len = _span_tables(wav_flat, starts, lengths, max_len, "wave_loudness")
+    if not 1 <= B <= 65535:
+        raise ValueError("wave_loudness: %d spans, at most 65535 per call" % B)
+    if max_len > 2 ** 30:
+        raise ValueError("wave_loudness: max_len=%d, at most 2^30 samples per span" % max_len)
+    goff = _group_offsets(list(range(B + 1)) if groups is None else groups, B, "wave_loudness")
+    G = goff.size - 1
+    dev = wav_flat.device
+    K = -(-max_len // h)
+    f64 = dict(dtype=torch.float64, device=dev)
+    states = torch.empty((B, max(K, 1), 4), **f64)
+    energy = torch.empty((B, max(K, 1)), **f64)
+    coef = (ctypes.c_double * 10)(*kw["coef"].tolist())
+    Ah = (ctypes.c_double * 16)(*kw["Ah"].reshape(-1).tolist())
+    if true_peak:
+        table = (ctypes.c_float * 36)(*true_peak_table().reshape(-1).tolist())
+        peak = torch.empty(B, **f64)
+        scratch = torch.empty(max(B * -(-max_len // _lib.CONSTS["DV3_TRUE_PEAK_CHUNK"]), 1), **f64)
+        stride = 1
+    else:
+        table = scratch = None
+        peak = wave_levels(wav_flat, starts_d, lengths_d, max_len) if levels is None else _c(levels)
+        if tuple(peak.shape) != (B, len(LEVEL_COLUMNS)) or peak.dtype != torch.float64 or not peak.is_cuda:
+            raise ValueError("wave_loudness: levels must be wave_levels' float64 (B, 5) device table")
+        stride = len(LEVEL_COLUMNS)
+    _lib.call("dv3_wave_loudness_f64", wav_flat.data_ptr(), starts_d.data_ptr(), lengths_d.data_ptr(), B, max_len, h,
+              ctypes.addressof(coef), ctypes.addressof(Ah), ctypes.addressof(table) if true_peak else None,
+              states.data_ptr(), energy.data_ptr(), scratch.data_ptr() if true_peak else None,
+              peak.data_ptr() if true_peak else None, _stream())
+    goff_d = torch.from_numpy(goff).to(dev, non_blocking=True)
+    rows = torch.empty((G, len(LOUDNESS_COLUMNS)), **f64)
+    _lib.call("dv3_loudness_gate_f64", energy.data_ptr(), lengths_d.data_ptr(), goff_d.data_ptr(), peak.data_ptr(), stride,
+              B, G, max_len, h, rows.data_ptr(), _stream())
+    if want_tables:
+        return rows, energy[:, :K], states[:, :K]
+    return rows
+
+
+def loudness_gains(rows, groups, mastering):
+    """wave_loudness' rows -> float32 (B,) gains on the device, B = groups[-1]: group g (items groups[g] ..
+    groups[g + 1] - 1) gets g = min(10^((target_db - lufs) / 20), ceiling / peak, max_gain), 1 when it is silent; float64
+    on the device, rounded once (include/dv3hip.h: dv3_loudness_gains_f32).  mastering: a Mastering("lufs")."""
+    if not isinstance(mastering, Mastering) or mastering.level != "lufs":
+        raise ValueError("loudness_gains: a Mastering with level='lufs' expected")
+    G = int(rows.shape[0]) if torch.is_tensor(rows) and rows.dim() == 2 else -1
+    if G < 1 or tuple(rows.shape) != (G, len(LOUDNESS_COLUMNS)) or rows.dtype != torch.float64 or not rows.is_cuda:
+        raise ValueError("loudness_gains: rows must be wave_loudness' float64 (G, 7) device table")
+    B = int(np.asarray(groups).reshape(-1)[-1]) if len(groups) else 0
+    goff = _group_offsets(groups, B, "loudness_gains")
+    if goff.size - 1 != G:
+        raise ValueError("loudness_gains: %d rows for %d groups" % (G, goff.size - 1))
+    dev = rows.device
+    goff_d = torch.from_numpy(goff).to(dev, non_blocking=True)
+    gain = torch.empty(B, dtype=torch.float32, device=dev)
+    lin = lambda db: 10.0 ** (db / 20.0)
+    _lib.call("dv3_loudness_gains_f32", _c(rows).data_ptr(), goff_d.data_ptr(), B, G, float(mastering.target_db),
+              lin(mastering.ceiling_db), lin(mastering.max_gain_db), gain.data_ptr(), _stream())
+    return gain
+
+
+def span_gains(wav_flat, starts_d, lengths_d, max_len, mastering, sample_rate=None):
+    """the gains of B spans (int64 device tensors and a bound on the lengths) under a Mastering with a level: wave_levels
+    and wave_gains, or under "lufs" wave_levels (the ceiling's sample peak), wave_loudness and loudness_gains"""
+    if mastering.level != "lufs":
+        return wave_gains(wave_levels(wav_flat, starts_d, lengths_d, max_len), lengths_d, mastering)
+    levels = None if mastering.true_peak else wave_levels(wav_flat, starts_d, lengths_d, max_len)
+    if sample_rate is None:
+        raise ValueError("Mastering: level='lufs' needs a sample rate")
+    B = int(starts_d.numel())
+    groups = list(range(B + 1)) if mastering.scope == "item" else [0, B]
+    rows = wave_loudness(wav_flat, starts_d, lengths_d, sample_rate, groups, mastering.true_peak, max_len, levels)
+    return loudness_gains(rows, groups, mastering)
 
 
 _FADE_CACHE = {}
@@ -1670,13 +1838,14 @@ def wave_master(wav_flat, src, length, dst, gain, flags, N, fade_samples=0, dtyp
     return out
 
 
-def master_items(wavs, samples, mastering):
+def master_items(wavs, samples, mastering, sample_rate=None):
     """Every utterance of a padded batch mastered ALONE: wavs (B, L) float32 on the device (tts_batch's Griffin-Lim
     output), samples: B host ints (item b is its first samples[b] samples; the lengths are already on the host, so
     nothing is read back), mastering: a Mastering.  -> (B, L) of mastering.dtype, item b's samples first and zeros behind
     them (a view of a buffer whose rows are padded to 16 bytes).  Levels, gains (they stay on the device) and one master
     launch; with dither one master launch per item, each counting its samples from 0, so that an item's bits do not
-    depend on what shares its batch.  No fades: fade_ms is for join_utterances."""
+    depend on what shares its batch.  No fades: fade_ms is for join_utterances.  sample_rate: needed by level "lufs"
+    alone (span_gains)."""
     mastering = check_mastering(mastering, "master_items")
     if mastering is None:
         raise ValueError("master_items: mastering is None")
@@ -1690,9 +1859,11 @@ def master_items(wavs, samples, mastering):
     flat = wavs.reshape(-1)
     starts = np.arange(B, dtype=np.int64) * L
     gain = None
+    if mastering.level == "lufs" and sample_rate is None:
+        raise ValueError("master_items: level='lufs' needs sample_rate= (the loudness measure is defined per sample rate)")
     if mastering.level is not None:
         starts_d, lengths_d, _, max_len = _span_tables(flat, starts, samples, None, "master_items")
-        gain = wave_gains(wave_levels(flat, starts_d, lengths_d, max_len), lengths_d, mastering)
+        gain = span_gains(flat, starts_d, lengths_d, max_len, mastering, sample_rate)
     Lp = -(-L // 8) * 8
     kw = dict(dtype=mastering.dtype, reference=mastering.level == "reference", seed=mastering.seed)
     if not mastering.dither:

@@ -69,7 +69,9 @@ Deliverable audio, opt-in: mastering= (an audio.Mastering) on a
 into the mastered one (audio.master_items: each utterance alone, so the three agree); join_utterances joins any list of
 device waveforms into one document -- silence trimmed, levelled, sentences crossfaded or separated by faded pauses,
 quantised, in one launch after one host read --, and tts_document speaks a text longer than one utterance, sentence by
-sentence, with every token's span on the document's time axis.
+sentence, with every token's span on the document's time axis.  Mastering("lufs") levels to a BS.1770 loudness target
+(DESIGN.md 3.6l): per utterance, or with scope="document" from the pooled blocks of all sentences; the entry points
+pass their audio_cfg.sample_rate.
 
     wav, spans = synthesis.tts_document(model, [seq0, seq1, ...], mastering=audio.Mastering("rms", "document"))
     audio.save_wav("document.wav", wav, 22050)
@@ -431,7 +433,7 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=Fa
         else:
             wavs, samples = audio.inv_spectrogram_batch(linear, audio_cfg, frame_lengths=frames * up, prosody=pros)
         if mastering is not None:
-            wavs = audio.master_items(wavs, samples, mastering)
+            wavs = audio.master_items(wavs, samples, mastering, (audio_cfg or audio.AudioConfig()).sample_rate)
     stats = None
     if diagnostics:
         steps = [int(n) // steps_per_frame for n in frames]
@@ -614,7 +616,8 @@ class RollingSynthesizer(object):
             else:
                 wavs, samples = _vocode(linear, self.audio_cfg, frames * up, settings)
             if self.mastering is not None:
-                wavs = audio.master_items(wavs, samples, self.mastering)
+                wavs = audio.master_items(wavs, samples, self.mastering,
+                                          (self.audio_cfg or audio.AudioConfig()).sample_rate)
         stats = None
         if self.diagnostics:
             stats = _diagnose(alignments, steps, lengths, [self._req[t][2] for t in tickets])
@@ -824,7 +827,7 @@ def join_utterances(wavs, sample_rate, pauses=0.25, trim_db=40.0, mastering=None
     if mastering.level is not None:
         sl = torch.from_numpy(np.concatenate([src, lens])).to(flat.device, non_blocking=True)
         S = src.size
-        gain = audio.wave_gains(audio.wave_levels(flat, sl[:S], sl[S:], int(lens.max())), sl[S:], mastering)
+        gain = audio.span_gains(flat, sl[:S], sl[S:], int(lens.max()), mastering, sample_rate)
     doc = audio.wave_master(flat, table["src"], table["len"], table["dst"], gain, table["flags"], N, F, mastering.dtype,
                             mastering.level == "reference", mastering.dither, mastering.seed)
     sr = float(sample_rate)

@@ -1711,6 +1711,113 @@ int dv3_wave_master_f32(const float* x, const int64_t* src, const int64_t* len, 
                         const int32_t* flags, int32_t S, const float* fade /* or NULL when F is 0 */, int32_t F,
                         int32_t mode, int32_t dither, uint64_t seed, void* out, int64_t N, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Loudness mastering: ITU-R BS.1770 integrated loudness and true peak, mono, channel weight 1 (audio.wave_loudness,
+ * audio.loudness_gains, Mastering(level="lufs"); csrc/loudness.hip).  The reference has no counterpart.
+ * Three new entry points with plain arguments, no struct added or changed, so the version stays 50.
+ *
+ * The measure.  fs the sample rate, 8000 <= fs <= 192000.  Step h = floor(0.1 fs + 0.5) samples (DV3_LOUDNESS_MIN_STEP
+ * <= h <= DV3_LOUDNESS_MAX_STEP); a block is 4 h samples.
+ *   K-weighting: two biquads in cascade, fp64, from a zero state at the item's own first sample.  The caller computes
+ *   the coefficients in fp64 by the bilinear transform of the analogue prototypes (audio.k_weighting):
+ *     shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / fs),
+ *                Vh = 10^(G / 20), Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2;
+ *                b = [Vh + Vb K / Q + K^2, 2 (K^2 - Vh), Vh - Vb K / Q + K^2] / a0
+ *                a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0]
+ *     high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773; b = [1, -2, 1] (NOT divided by a0), a as above
+ *   At 48 kHz these are the standard's table.  coef (a HOST array of 10 doubles) = shelf b0 b1 b2 a1 a2, high-pass
+ *   b0 b1 b2 a1 a2.  Each biquad runs in transposed direct form II, state (s1, s2) for the shelf and (t1, t2) for the
+ *   high-pass, per input sample x (an fp32 value widened exactly):
+ *     u  = b0 x + s1;   s1 = (b1 x - a1 u) + s2;   s2 = b2 x - a2 u         (the shelf's b, a)
+ *     y  = b0 u + t1;   t1 = (b1 u - a1 y) + t2;   t2 = b2 u - a2 y         (the high-pass's b, a)
+ *   in fp64; the compiler may contract a product and a sum into one fma.  The zero-input transition of the state vector
+ *   s = (s1, s2, t1, t2) is the matrix
+ *     A = [ -a1           1   0    0 ]      (row 0, 1: the shelf's a; c = the high-pass's b, d = the high-pass's a)
+ *         [ -a2           0   0    0 ]
+ *         [ c1 - d1 c0    0  -d1   1 ]
+ *         [ c2 - d2 c0    0  -d2   0 ]
+ *   and Ah (a HOST array of 16 doubles, row-major) is A^h, built by the caller in fp64 (numpy.linalg.matrix_power).
+ *   Sub-block energies: E[b][k] = sum of y^2 over samples [k h, (k + 1) h) of item b, accumulated in fp64 in ascending
+ *   sample order; the last, partial sub-block is kept.  Block j of item b covers [j h, j h + 4 h): an item of n samples
+ *   has J = (n - 4 h) / h + 1 (integer division) blocks when n >= 4 h, else none; blocks never straddle items.
+ *     z_j = (((E[j] + E[j+1]) + E[j+2]) + E[j+3]) * (1 / (4 h));   l_j = -0.691 + 10 log10 z_j
+ *   Gating over a group (items goff[g] .. goff[g + 1] - 1, the offsets dv3_wave_gains_f32 takes), its blocks pooled:
+ *     1. the absolute gate keeps l_j > -70;
+ *     2. Gr = -0.691 + 10 log10(mean z over the absolute-gated blocks) - 10;
+ *     3. L  = -0.691 + 10 log10(mean z over the blocks with l_j > -70 and l_j > Gr).
+ *   Two edge rules that are NOT in the standard: a group with no complete block is measured ungated,
+ *   L = -0.691 + 10 log10(sum of E / sum of n) over its items' sub-blocks, and flagged DV3_LOUDNESS_SHORT; a group with
+ *   blocks none of which passes the absolute gate has L = -inf and is flagged DV3_LOUDNESS_SILENT (so is a short group
+ *   whose energy or length is 0: the flag says "L is -inf", and such a group takes gain 1).
+ *   True peak: the largest |v| over the item's samples x[m] and the interpolants y[4 m + p], p = 1, 2, 3, m = 0 .. n - 1,
+ *   of the 4x oversampled signal, samples outside the item's span counting as zero.  Interpolator
+ *   g[i] = sinc(i / 4) kaiser(49, beta = 8)[i + 24], i = -24 .. 24 (phase 0 is the identity), each phase
+ *   DV3_TRUE_PEAK_TAPS = 12 taps: y[4 m + p] = sum over j = 0 .. 11 of table[p - 1][j] x[m + 6 - j], table[p - 1][j] =
+ *   g[p + 4 (j - 6)], built in fp64 and rounded once to fp32 (audio.true_peak_table); the sum runs in fp32 from 0 in
+ *   ascending j, each step one fmaf.  4x oversampling under-reads content near Nyquist.
+ *
+ * dv3_wave_loudness_f64: x, starts, lengths, B, max_len as dv3_wave_levels_f32 takes them (n_b = lengths[b] clamped into
+ * [0, max_len]; max_len <= 2^30); K = ceil(max_len / h).  Three launches (csrc/loudness.hip says why no warm-up overlap
+ * can replace them: the high-pass pole has radius 0.989 at 22.05 kHz):
+ *   pass 1  every chunk [k h, (k + 1) h) of every item is filtered from a zero state; its end state e_k is stored;
+ *   pass 2  per item, s_0 = 0, s_{k+1}[r] = ((((Ah[r][0] s_k[0] + Ah[r][1] s_k[1]) + Ah[r][2] s_k[2]) + Ah[r][3] s_k[3])
+ *           + e_k[r]) for k ascending: every chunk's true start state;
+ *   pass 3  every chunk is filtered again from s_k, and E[b][k] is summed.
+ * Outputs: states double[B][K][4], 16-byte aligned: states[b][k] = s_k = (s1, s2, t1, t2) before sample k h of item b
+ * (for k > 0 that is the filter's state after sample k h - 1), zeros for chunks at or past the item's end; energy
+ * double[B][K]: E[b][k], zeros past the item's end.  With peak_table (a HOST array of 3 x 12 floats) and true_peak
+ * double[B] non-NULL (both or neither), a fourth and fifth launch write true_peak[b] (0 for an empty item); peak_scratch:
+ * B * ceil(max_len / DV3_TRUE_PEAK_CHUNK) doubles the call may overwrite.  A row is a function of the item's samples
+ * alone: it does not depend on B, on the neighbours or on where the span lies (any 4-byte alignment).  No atomics.
+ * Nothing outside the named tables is written; max_len == 0 launches no filter pass.  Refused (DV3_EINVAL,
+ * "wave_loudness:", nothing launched): a null x, starts, lengths, coef or Ah; null states or energy with max_len > 0;
+ * peak_table without true_peak or the reverse; a null peak_scratch with a peak_table and max_len > 0; B outside
+ * [1, 65535]; max_len outside [0, 2^30]; h outside [DV3_LOUDNESS_MIN_STEP, DV3_LOUDNESS_MAX_STEP]; a coefficient, an
+ * entry of Ah or of peak_table that is not finite; states not 16-byte aligned, energy, peak_scratch or true_peak not
+ * 8-byte aligned.
+ *
+ * dv3_loudness_gate_f64: energy, lengths, max_len and h as above, goff device int32[G + 1] ascending from 0 to B (indices
+ * clamped into [0, B]), peak: item b's peak is peak[b * peak_stride] (true_peak with stride 1, or the level table of
+ * dv3_wave_levels_f32 with stride DV3_LEVEL_COLUMNS: its sample peak).  rows double[G][DV3_LOUDNESS_COLUMNS], row g:
+ *   lufs           L of the group (-inf when silent)
+ *   blocks         the number of blocks of its items
+ *   gated_abs      blocks that pass the absolute gate
+ *   gated_rel      blocks that pass both gates (0 for a short group)
+ *   momentary_max  the largest l_j over all its blocks (-inf when there is none)
+ *   peak           the largest of its items' peaks
+ *   flags          DV3_LOUDNESS_SHORT | DV3_LOUDNESS_SILENT
+ * One wave per group.  Summation order of every mean: the items in ascending order, lane t of 64 adding blocks t,
+ * t + 64, ... of each item to its own fp64 partial; the 64 partials are added in a fixed butterfly (xor 32, 16, .., 1).
+ * The gates compare l_j as computed on the device (fp64 log10).  goff = 0, 1, .., B gives a per-item table.  Refused
+ * ("loudness_gate:"): a null lengths, goff, peak or rows; a null energy with max_len > 0; B outside [1, 65535]; G outside
+ * [1, B]; max_len or h outside their ranges; peak_stride outside [1, 64]; a table not 8-byte aligned.
+ *
+ * dv3_loudness_gains_f32: rows as above, gain float[B]; per group, in fp64 (pow and division as the device's library
+ * rounds them), rounded ONCE to fp32:
+ *     g = 10^((target_lufs - L) / 20);  if peak > 0: g = min(g, ceiling / peak);  g = min(g, max_gain)
+ * and g = 1 for a group flagged DV3_LOUDNESS_SILENT; every item of the group gets g.  target_lufs in LUFS (dB),
+ * ceiling and max_gain LINEAR (10^(dB / 20)).  Refused ("loudness_gains:"): null pointers; B outside [1, 65535]; G
+ * outside [1, B]; target_lufs outside [-120, 0]; a ceiling or max_gain that is no positive finite number; rows not
+ * 8-byte aligned.
+ * tests/loudness_ref.py restates all of it in numpy float64.
+ * ------------------------------------------------------------------------------------ */
+#define DV3_LOUDNESS_COLUMNS 7
+#define DV3_LOUDNESS_SHORT 1
+#define DV3_LOUDNESS_SILENT 2
+#define DV3_LOUDNESS_MIN_STEP 800
+#define DV3_LOUDNESS_MAX_STEP 19200
+#define DV3_TRUE_PEAK_TAPS 12
+#define DV3_TRUE_PEAK_CHUNK 1024
+int dv3_wave_loudness_f64(const float* x, const int64_t* starts, const int64_t* lengths, int32_t B, int64_t max_len,
+                          int32_t h, const double* coef, const double* Ah, const float* peak_table /* or NULL */,
+                          double* states, double* energy, double* peak_scratch /* or NULL */,
+                          double* true_peak /* or NULL */, void* stream);
+int dv3_loudness_gate_f64(const double* energy, const int64_t* lengths, const int32_t* goff, const double* peak,
+                          int32_t peak_stride, int32_t B, int32_t G, int64_t max_len, int32_t h, double* rows,
+                          void* stream);
+int dv3_loudness_gains_f32(const double* rows, const int32_t* goff, int32_t B, int32_t G, double target_lufs,
+                           double ceiling, double max_gain, float* gain, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
