@@ -83,7 +83,35 @@ class MultiSpeakerTTSModel(nn.Module):
         return mel, linear, alignments, done
 
 
-    def synthesize_batch(self, text_sequences, text_lengths, speaker_ids=None, stall_limit=None, postnet=True):
+    def _guide_of(self, durations, tl, Tt, dev):
+        """synthesize_batch(durations=...) -> (guide table, steps) on the device, or ValueError naming the item"""
+        from . import ops
+        B, T = tl.numel(), self.seq2seq.decoder.max_decoder_steps + 1
+        if torch.is_tensor(durations):
+            if durations.dtype != torch.int32 or not durations.is_cuda or tuple(durations.shape) != (B, Tt):
+                raise ValueError("synthesize_batch: durations as a tensor are int32 (%d, %d) on the device (what "
+                                 "ops.monotonic_path returns), got %s %s" % (B, Tt, durations.dtype, tuple(durations.shape)))
+            dur = durations
+        else:
+            rows = [[int(v) for v in d] for d in durations]
+            if len(rows) != B:
+                raise ValueError("synthesize_batch: %d duration lists for %d utterances" % (len(rows), B))
+            host = torch.zeros(B, Tt, dtype=torch.int32)
+            for b, d in enumerate(rows):
+                if len(d) != int(tl[b]):
+                    raise ValueError("synthesize_batch: item %d has %d durations for its %d tokens" % (b, len(d), int(tl[b])))
+                host[b, :len(d)] = torch.tensor(d, dtype=torch.int32)
+            dur = host.to(dev)
+        guide, steps, flags = ops.guide_from_durations(dur, tl.to(torch.int32).to(dev), T)
+        for b, f in enumerate(flags.tolist()):
+            if f:
+                raise ValueError("synthesize_batch: durations of item %d are flagged %s (negative: a duration below 0; "
+                                 "empty: they sum to 0; over: they sum to more than max_decoder_steps + 1 = %d)" % (
+                                     b, "+".join(ops.guide_flag_names(f)), T))
+        return guide, steps
+
+    def synthesize_batch(self, text_sequences, text_lengths, speaker_ids=None, durations=None, guide_window=None,
+                         stall_limit=None, postnet=True):
         """Per-utterance batched synthesis: every item of a ragged batch comes back as if it had been synthesised alone
         (the reference's synthesis.tts at B = 1, synthesis.py:42-73, model part).  text_sequences (B, Tt) int ids on
         the device, padded past each item's text_lengths[b]; positions are 1..text_lengths[b].  The encoder and the
@@ -95,10 +123,23 @@ class MultiSpeakerTTSModel(nn.Module):
         decode_program.stall_stop(...) steps if its done flag has not fired by then.  Applied after the decode and before
         the post-net; the decode loop itself still runs until the slowest item's done flag (or the cap).
         postnet=False: the post-net is not run and linear comes back None (a model trained without its post-net has
-        nothing to say there; synthesis.tts_batch(from_mel=...) vocodes the mel instead); nothing else differs."""
+        nothing to say there; synthesis.tts_batch(from_mel=...) vocodes the mel instead); nothing else differs.
+        durations (None: off): decoder steps per token -- an int32 (B, Tt) device tensor, as
+        ops.monotonic_path and train_step.align_batch return them, or one list of text_lengths[b] ints per utterance.
+        The decode is guided: every attention layer's window of step t is centred on the token that owns step t
+        (ops.guide_from_durations), a token of duration 0 is skipped, and item b stops after sum(durations[b]) steps:
+        frame_lengths = that sum x r.  done is what the model computed; the stop is the guide's end.  guide_window
+        (backward, ahead): the window around the guided token instead of the attention layers' own.  A negative
+        duration, a sum of 0 or a sum above max_decoder_steps + 1 raises ValueError naming the item.  Not together with
+        stall_limit.  Runs on the fused step kernels only."""
         from . import ops
         if self.training:
             raise RuntimeError("synthesize_batch: eval mode only")
+        if durations is not None and stall_limit is not None:
+            raise ValueError("synthesize_batch: durations prescribe every item's stop; stall_limit cannot be combined "
+                             "with them")
+        if durations is None and guide_window is not None:
+            raise ValueError("synthesize_batch: guide_window is the window of a guided decode (durations=)")
         dev = text_sequences.device
         B, Tt = text_sequences.shape
         tl = torch.as_tensor(text_lengths).reshape(-1).to(torch.int64).cpu()
@@ -119,6 +160,8 @@ class MultiSpeakerTTSModel(nn.Module):
                 memory = enc(text_sequences, lengths=None, speaker_embed=speaker_embed)
                 dec.start_fresh_sequence()
                 kw = dict(speaker_embed=speaker_embed) if speaker_embed is not None else {}
+                if durations is not None:
+                    kw.update(guide=self._guide_of(durations, tl, Tt, dev), guide_window=guide_window)
                 mel, alignments, done, states, steps = dec.incremental_forward(memory, text_positions,
                                                                                text_lengths=tl, **kw)
                 if stall_limit is not None:

@@ -343,19 +343,30 @@ __global__ __launch_bounds__(256) void conv_step_slots_kernel(const dv3_conv_ste
 
 // one attention read of batch item b at step t; all 256 threads of the workgroup take part
 // (slot mode: the caller passes the item's own step; the stacked row and the window's two sides follow from it)
+// GUIDED (dv3_attn_step_guided_f32): the window's centre is the guide table's entry of this step, row b of `guide`
+// (stride guide_bs) at min(t, steps[b] - 1), instead of the previous step's argmax; last_attended is neither read nor
+// written and the argmax reduction is skipped.  The unguided instantiation is the code as it was.
+template <bool GUIDED = false>
 __device__ __forceinline__ void attn_step_item(const dv3_attn_step_desc& p, const int t, const int b, float* lds,
-                                               float* red, int* redi) {
+                                               float* red, int* redi, const int32_t* __restrict__ guide = nullptr,
+                                               const int64_t guide_bs = 0, const int32_t* __restrict__ steps = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int E = p.E, Tk = p.Tk;
   // per-utterance mode: this item's own key count s (the stride stays Tk); keys n >= s never enter the window, so
   // their probabilities come out as exact zeros and every partial sum / max is the one of a B = 1 call at Tk = s
   const bool items = p.key_len != nullptr;
   const int s = items ? min(max(p.key_len[b], 1), Tk) : Tk;
-  int32_t* const la_rd = p.last_attended ? p.last_attended + (items ? (t & 1) * p.B + b : (t & 1)) : nullptr;
+  int32_t* const la_rd = (!GUIDED && p.last_attended) ? p.last_attended + (items ? (t & 1) * p.B + b : (t & 1)) : nullptr;
   float* q = lds;
   float* sc = lds + E;
   int lo = 0, hi = s;
-  if (la_rd) {                 // deepvoice3.py:150-156
+  if constexpr (GUIDED) {      // the same two-sided rule around the guide's key (clamped to the item's own keys)
+    const int row = max((int)min((int64_t)min(t, steps[b] - 1), guide_bs - 1), 0);      // never past the row's stride
+    const int la = min(max(guide[(int64_t)b * guide_bs + row], 0), s - 1);
+    const int back = la - p.win_back, ahead = la + p.win_ahead;
+    if (back > 0) lo = back;
+    if (ahead < s) hi = ahead;
+  } else if (la_rd) {          // deepvoice3.py:150-156
     const int la = *la_rd;
     const int back = la - p.win_back, ahead = la + p.win_ahead;
     if (back > 0) lo = back;
@@ -407,7 +418,9 @@ __device__ __forceinline__ void attn_step_item(const dv3_attn_step_desc& p, cons
     sc[n] = pr;
     if (p.attn) p.attn[(int64_t)b * Tk + n] = pr;
     if (p.attn_seq) p.attn_seq[(int64_t)t * p.attn_seq_ts + (int64_t)b * Tk + n] = pr;
-    if (pr > best) { best = pr; bi = n; }
+    if constexpr (!GUIDED) {
+      if (pr > best) { best = pr; bi = n; }
+    }
   }
   __syncthreads();
   // context (deepvoice3.py:167-171): sum_n p[n] v[e][n] * (Tk * sqrt(1/Tk))
@@ -427,7 +440,7 @@ __device__ __forceinline__ void attn_step_item(const dv3_attn_step_desc& p, cons
     p.ctx[(int64_t)b * p.ctx_bs + e] = c * scale;
   }
   // next step's window: argmax of batch item 0 (deepvoice3.py:445) -- of every item in per-utterance mode --, first maximum
-  if ((b == 0 || items) && p.last_attended) {
+  if (!GUIDED && (b == 0 || items) && p.last_attended) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
       const float ov = __shfl_xor(best, off, 64);
@@ -459,6 +472,15 @@ __global__ __launch_bounds__(256) void attn_step_slots_kernel(const dv3_attn_ste
   const int tb = (p.t ? p.t[0] : p.t_value) - p.t_off[blockIdx.x];
   if (tb < 0 || tb >= p.t_cap) return;             // workgroup-uniform
   attn_step_item(p, tb, blockIdx.x, lds, red, redi);
+}
+
+// guided decode (per-utterance mode only): the item's window sits on its guide row's key of this step
+__global__ __launch_bounds__(256) void attn_step_guided_kernel(const dv3_attn_step_desc p, const int32_t* __restrict__ guide,
+                                                               const int64_t guide_bs, const int32_t* __restrict__ steps) {
+  extern __shared__ float lds[];
+  __shared__ float red[4];
+  __shared__ int redi[4];
+  attn_step_item<true>(p, p.t ? p.t[0] : p.t_value, blockIdx.x, lds, red, redi, guide, guide_bs, steps);
 }
 
 // fwd_pack [Ktot][lda] -> step-tile order, window elements zero-padded to kpad (include/dv3hip.h: dv3_conv_step_pack_f32)
@@ -705,7 +727,34 @@ extern "C" int dv3_decode_program_run(const dv3_decode_program* d, void* stream)
   return dv3_check_launch("decode_program");
 }
 
+// the guided forms' own conditions on an attention entry (include/dv3hip.h: dv3_attn_step_guided_f32)
+static int attn_guided_check(const dv3_attn_step_desc* a, const int32_t* guide, int64_t guide_bs, const int32_t* steps,
+                             int64_t rows) {
+  DV3_REQUIRE(guide && steps, "attn_step_guided: guide or steps is null");
+  DV3_REQUIRE(!a->t_off, "attn_step_guided: slot mode (t_off) is not taken: a slot's step is t - t_off[b], and the guide "
+                         "table is indexed by one step counter for the batch");
+  DV3_REQUIRE(a->key_len, "attn_step_guided: per-utterance mode only (key_len is null)");
+  DV3_REQUIRE(a->win_back >= 0 && a->win_ahead >= 1, "attn_step_guided: window (%d, %d): win_back >= 0 and win_ahead >= 1",
+              (int)a->win_back, (int)a->win_ahead);
+  DV3_REQUIRE(guide_bs >= rows, "attn_step_guided: guide_bs = %lld below the %lld steps of the call", (long long)guide_bs,
+              (long long)rows);
+  return DV3_OK;
+}
+
+static int decode_program_launch(const dv3_decode_program* d, const int32_t* guide, int64_t guide_bs, const int32_t* steps,
+                                 bool guided, void* stream);
+
 extern "C" int dv3_decode_program_launch(const dv3_decode_program* d, void* stream) {
+  return decode_program_launch(d, nullptr, 0, nullptr, false, stream);
+}
+
+extern "C" int dv3_decode_program_launch_guided(const dv3_decode_program* d, const int32_t* guide, int64_t guide_bs,
+                                                const int32_t* steps, void* stream) {
+  return decode_program_launch(d, guide, guide_bs, steps, true, stream);
+}
+
+static int decode_program_launch(const dv3_decode_program* d, const int32_t* guide, int64_t guide_bs, const int32_t* steps,
+                                 bool guided, void* stream) {
   DV3_REQUIRE(d && d->entries_host, "decode_program_launch: null pointer");
   DV3_REQUIRE(d->n_entries > 0 && d->B > 0 && d->n_steps > 0 && d->t0 >= 0, "decode_program_launch: bad dims");
   hipStream_t st = (hipStream_t)stream;
@@ -717,6 +766,11 @@ extern "C" int dv3_decode_program_launch(const dv3_decode_program* d, void* stre
     DV3_REQUIRE(en.kind == 0 || en.kind == 1, "decode_program_launch: entry %d has kind %d", e, en.kind);
     const int rc = en.kind == 0 ? conv_step_check(&en.conv, false, &lds[e]) : attn_step_check(&en.attn, false, &lds[e]);
     if (rc != DV3_OK) return rc;
+    if (guided) {
+      DV3_REQUIRE(!(en.kind == 0 && en.conv.t_off), "decode_program_launch_guided: slot mode (t_off) is not taken");
+      if (en.kind == 1 && attn_guided_check(&en.attn, guide, guide_bs, steps, (int64_t)d->t0 + d->n_steps) != DV3_OK)
+        return DV3_EINVAL;
+    }
   }
   for (int s = 0; s < d->n_steps; ++s) {
     const int t = d->t0 + s;
@@ -733,7 +787,10 @@ extern "C" int dv3_decode_program_launch(const dv3_decode_program* d, void* stre
         dv3_attn_step_desc a = en.attn;
         a.t = nullptr;
         a.t_value = t;
-        hipLaunchKernelGGL(a.t_off ? attn_step_slots_kernel : attn_step_kernel, dim3(a.B), dim3(256), lds[e], st, a);
+        if (guided)
+          hipLaunchKernelGGL(attn_step_guided_kernel, dim3(a.B), dim3(256), lds[e], st, a, guide, guide_bs, steps);
+        else
+          hipLaunchKernelGGL(a.t_off ? attn_step_slots_kernel : attn_step_kernel, dim3(a.B), dim3(256), lds[e], st, a);
       }
     }
   }
@@ -805,4 +862,16 @@ extern "C" int dv3_attn_step_f32(const dv3_attn_step_desc* d, void* stream) {
   if (rc != DV3_OK) return rc;
   hipLaunchKernelGGL(d->t_off ? attn_step_slots_kernel : attn_step_kernel, dim3(d->B), dim3(256), lds, (hipStream_t)stream, *d);
   return dv3_check_launch("attn_step");
+}
+
+// the step index is the device counter `t` (or t_value): what the host can check of guide_bs is t_value alone
+extern "C" int dv3_attn_step_guided_f32(const dv3_attn_step_desc* d, const int32_t* guide, int64_t guide_bs,
+                                        const int32_t* steps, void* stream) {
+  size_t lds = 0;
+  const int rc = attn_step_check(d, false, &lds);    // (the step may travel in t_value: last_attended is not used)
+  if (rc != DV3_OK) return rc;
+  DV3_REQUIRE(d->t || d->t_value >= 0, "attn_step_guided: negative step");
+  if (attn_guided_check(d, guide, guide_bs, steps, d->t ? 1 : (int64_t)d->t_value + 1) != DV3_OK) return DV3_EINVAL;
+  hipLaunchKernelGGL(attn_step_guided_kernel, dim3(d->B), dim3(256), lds, (hipStream_t)stream, *d, guide, guide_bs, steps);
+  return dv3_check_launch("attn_step_guided");
 }

@@ -114,23 +114,76 @@ def item_key_len(text_lengths, B, Tk, device):
     return tl.to(torch.int32).to(device)
 
 
-def incremental_decode(dec, encoder_out, text_lengths, *args):
+def incremental_decode(dec, encoder_out, text_lengths, *args, **guided):
     """The frame of Decoder.incremental_forward, both families: the per-utterance key lengths and stop list, the fused
     step program (dec._incremental_fast), the module-by-module loop (dec._incremental_modules) where the step kernels
     do not take the decoder or the key count, and the zero tails of a per-utterance result.  The program is built ONCE
     per call: _incremental_fast returns None if its own build was refused (StepProgram.refuse: nothing of a refused
     program is packed or launched), which is the answer _fast_decode_eligible gives from a dry build.  args: the
-    family's own arguments, handed to either."""
+    family's own arguments, handed to either.
+    guided: guide=(guide int32 (B, T) on the device, steps int32[B]) -- a guided decode: every
+    attention layer centres item b's window of step t on guide[b, min(t, steps[b] - 1)] and item b stops after
+    steps[b] steps -- and guide_window=(backward, ahead), the window used instead of the layers' own.  Guided decoding
+    runs on the fused step kernels only: it needs text_lengths, and a decoder they do not take is refused."""
     keys = encoder_out[0]
     B = keys.size(0)
     key_len = item_key_len(text_lengths, B, keys.size(1), keys.device)
     stops = [0] * B if key_len is not None else None
+    guide, guide_window = guided.pop("guide", None), guided.pop("guide_window", None)
+    if guided:
+        raise TypeError("incremental_forward: unexpected keyword(s) %s" % sorted(guided))
+    if guide is not None:
+        return guided_decode(dec, encoder_out, key_len, stops, args, guide, guide_window)
+    if guide_window is not None:
+        raise ValueError("incremental_forward: guide_window is the window of a guided decode (guide=)")
     res = None
     if getattr(dec, "fast_decode", False) and keys.is_cuda:
         res = dec._incremental_fast(encoder_out, *args, key_len=key_len, stops=stops)
     if res is None:
         res = dec._incremental_modules(encoder_out, *args, key_len=key_len, stops=stops)
     return res if stops is None else item_results(stops, *res)
+
+
+def guide_window_of(guide_window):
+    """the guide_window= keyword -> None or (backward >= 0, ahead >= 1) as ints"""
+    if guide_window is None:
+        return None
+    try:
+        back, ahead = (int(w) for w in guide_window)
+    except (TypeError, ValueError):
+        raise ValueError("guide_window: a pair (backward, ahead) expected, got %r" % (guide_window,))
+    if back < 0 or ahead < 1:
+        raise ValueError("guide_window: backward >= 0 and ahead >= 1 expected, got (%d, %d)" % (back, ahead))
+    return back, ahead
+
+
+def guided_decode(dec, encoder_out, key_len, stops, args, guide, guide_window):
+    """incremental_decode under a guide: the checks, then the fused step program alone"""
+    keys = encoder_out[0]
+    if key_len is None:
+        raise ValueError("incremental_forward: a guide needs text_lengths (guided decoding is per utterance)")
+    try:
+        table, steps = guide
+    except (TypeError, ValueError):
+        raise ValueError("incremental_forward: guide=(guide table, steps) expected")
+    B = keys.size(0)
+    for t, name in ((table, "guide table"), (steps, "steps")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32):
+            raise ValueError("incremental_forward: the %s must be an int32 tensor on the device" % name)
+    if table.dim() != 2 or table.size(0) != B or steps.numel() != B or (table.size(1) > 1 and table.stride(1) != 1):
+        raise ValueError("incremental_forward: a guide table (B, T) with a dense step axis and B steps expected for a "
+                         "batch of %d, got %s and %d steps" % (B, tuple(table.shape), steps.numel()))
+    window = guide_window_of(guide_window)
+    if not (getattr(dec, "fast_decode", False) and keys.is_cuda):
+        raise RuntimeError("guided decode: runs on the fused decode-step kernels only (fast_decode on a GPU); there is "
+                           "no module-by-module fallback under a guide")
+    res = dec._incremental_fast(encoder_out, *args, key_len=key_len, stops=stops, guide=(table, steps),
+                                guide_window=window)
+    if res is None:
+        raise RuntimeError("guided decode: runs on the fused decode-step kernels only, and this decoder (or %d keys) is "
+                           "not eligible for them (_fast_decode_eligible); there is no module-by-module fallback under "
+                           "a guide" % keys.size(1))
+    return item_results(stops, *res)
 
 
 def slot_program_frame(dec, slots, max_text_len, dev):
@@ -255,12 +308,16 @@ class StepProgram(object):
         self.prog.append(("dv3_conv_step_f32", d))
         return y
 
-    def attn_step(self, q, k, v, window_backward, window_ahead, monotonic, attn_seq=None, key_len=None, rows=False):
+    def attn_step(self, q, k, v, window_backward, window_ahead, monotonic, attn_seq=None, key_len=None, rows=False,
+                  guide_window=None):
         """one attention read over (B, E, Tk) keys / values (deepvoice3.py:143-171 at Tq = 1, no padding mask);
         key_len (device int32[B]): per-utterance mode -- item b reads its own keys n < key_len[b] with its own window.
         rows: k and v are already the contiguous-row (B, Tk, E) images the kernel reads (slot mode: the slots' rows,
-        rewritten at every admission)"""
+        rewritten at every admission); guide_window (backward, ahead): the window of a guided decode, instead of the
+        layer's own"""
         B = self.B
+        if guide_window is not None:
+            window_backward, window_ahead = guide_window
         if self.slot_mode:
             if not rows or key_len is not None:
                 raise RuntimeError("decode program: slot mode reads per-slot key / value rows and its own key_len")
@@ -302,11 +359,19 @@ class StepProgram(object):
         self.prog.append(("dv3_attn_step_f32", a))
         return ctx
 
-    def run_step(self):
+    def run_step(self, guide=None):
+        """guide (table, steps): the attention entries run the guided kernel on it"""
         s = ops._stream()
         for name, d in self.prog:
-            ops._lib.call(name, ctypes.byref(d), s)
+            if guide is not None and name == "dv3_attn_step_f32":
+                ops._lib.call("dv3_attn_step_guided_f32", ctypes.byref(d), guide[0].data_ptr(), self._guide_bs(guide[0]),
+                              guide[1].data_ptr(), s)
+            else:
+                ops._lib.call(name, ctypes.byref(d), s)
         self.t_dev.add_(1)
+
+    def _guide_bs(self, table):
+        return table.stride(0) if self.B > 1 else table.size(1)
 
     def _entries(self, cur_in, test_inputs):
         """the program as a host array of dv3_decode_entry (teacher forcing: the entries that read the decoder input
@@ -414,11 +479,11 @@ class StepProgram(object):
         return (outs.transpose(0, 1).contiguous(), ali.transpose(0, 1),
                 [self.dones_seq[i].view(self.B, 1, 1) for i in range(t)], states.transpose(0, 1).contiguous())
 
-    def decode_for(self, dec, cur_in, test_inputs, stops):
+    def decode_for(self, dec, cur_in, test_inputs, stops, guide=None):
         """decode() with the decoder's step limits and its choice of loop -> results() of the steps taken"""
         t = self.decode(cur_in, test_inputs, self.dones_seq, dec.min_decoder_steps, dec.max_decoder_steps,
                         getattr(dec, "use_step_graph", False), getattr(dec, "persistent_decode", None),
-                        getattr(dec, "launched_decode", None), stops=stops)
+                        getattr(dec, "launched_decode", None), stops=stops, guide=guide)
         return self.results(t)
 
     def read_slot(self, slot, n):
@@ -500,8 +565,39 @@ class StepProgram(object):
             if t >= limit:
                 return t
 
+    def decode_guided(self, cur_in, guide, stops, launched):
+        """the loop under a guide: free running on the model's own outputs, item b's attention windows
+        centred on guide[b, min(t, steps[b] - 1)], max(steps) steps -- one host read of steps, no done flag is read;
+        stops[:] = steps.  launched: the whole utterance in ONE dv3_decode_program_launch_guided call; else one
+        dv3_attn_step_guided_f32 / dv3_conv_step_f32 call per entry per step from here.  -> number of steps taken"""
+        table, steps = guide
+        counts = [int(n) for n in steps.tolist()]
+        n = max(counts)
+        if len(counts) != self.B or min(counts) < 1:
+            raise ValueError("decode program: a guide gives every one of the %d items at least one step, got %s" % (
+                self.B, counts))
+        if n > table.size(1) or n > self.outs.size(0):
+            raise ValueError("decode program: the guide asks for %d steps; its table holds %d rows and the program's "
+                             "stacked outputs %d" % (n, table.size(1), self.outs.size(0)))
+        steps = steps.contiguous()
+        self.keep.extend([table, steps])
+        if launched:
+            arr, _ = self._entries(cur_in, None)
+            p = STRUCTS["dv3_decode_program"]()
+            p.entries_host = ctypes.addressof(arr)
+            p.n_entries, p.B = len(self.prog), self.B
+            p.t0, p.n_steps = 0, n
+            ops._lib.call("dv3_decode_program_launch_guided", ctypes.byref(p), table.data_ptr(), self._guide_bs(table),
+                          steps.data_ptr(), ops._stream())
+            self.t_dev.fill_(n)
+        else:
+            for _ in range(n):
+                self.run_step((table, steps))
+        stops[:] = counts
+        return n
+
     def decode(self, cur_in, test_inputs, dones_seq, min_steps, max_steps, use_graph, persistent=None, launched=None,
-               stops=None):
+               stops=None, guide=None):
         """the decoder loop (deepvoice3.py:397-473 / nyanko.py:277-331): teacher-forced over test_inputs (B, n, D), or
         free running until every item's done flag passed 0.5 after min_steps, at most max_steps + 1 steps.
         -> number of steps taken.  Default (launched): one launch per program entry per step, issued by the library in
@@ -513,7 +609,11 @@ class StepProgram(object):
         invalidate across the 8 XCDs, ~3.5 us) costs more than a kernel boundary does (scripts/decode_time.py), so
         it is opt-in.  Per-utterance mode (attention entries with key_len): pass stops = [0] * B; every item stops by
         its own done flag (item_stops), the loop runs until all have, and stops holds each item's step count; the
-        persistent program does not take this mode."""
+        persistent program does not take this mode.  guide=(table, steps): decode_guided (per-utterance mode only; not
+        the persistent program, not a slot-mode program)."""
+        if guide is not None and self.slot_mode:
+            raise RuntimeError("decode program: a slot-mode program does not take a guide (a slot runs at its own step "
+                               "t - t_off[b]; the guide table has one step axis for the batch)")
         if self.slot_mode:
             if persistent or (persistent is None and persistent_default):
                 raise RuntimeError("decode program: the persistent program does not take slot mode (its loop is one "
@@ -525,6 +625,15 @@ class StepProgram(object):
             raise RuntimeError("decode program: per-utterance attention entries need the per-item stop rule (stops=)")
         if persistent is None:
             persistent = persistent_default
+        if guide is not None:
+            if persistent:
+                raise RuntimeError("decode program: persistent=True does not take a guide (dv3_decode_program_run has no "
+                                   "guided form); use the launched or Python-driven loop")
+            if test_inputs is not None:
+                raise RuntimeError("decode program: a guide and test_inputs (teacher forcing) are not combined")
+            if not self.per_item or stops is None:
+                raise RuntimeError("decode program: a guide needs per-utterance attention entries (key_len) and stops=")
+            return self.decode_guided(cur_in, guide, stops, launched_default if launched is None else launched)
         if persistent:
             if stops is not None:
                 raise RuntimeError("decode program: the persistent program does not take per-utterance decoding "

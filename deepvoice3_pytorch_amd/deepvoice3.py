@@ -406,18 +406,23 @@ class Decoder(nn.Module):
         return outputs, torch.stack(alignments), done, decoder_states
 
     def incremental_forward(self, encoder_out, text_positions, speaker_embed=None, initial_input=None,
-                            test_inputs=None, text_lengths=None):
+                            test_inputs=None, text_lengths=None, guide=None, guide_window=None):
         """Greedy autoregressive decode (deepvoice3.py:367-485).  The reference's quirks are
         kept: last_attended comes from batch item 0 (:445), no padding mask, and the running
         `ave_alignment + ave_alignment` (:449).  last_attended stays on the device (no host sync
         per attention layer); the stop rule is checked on the host like the reference does.
         text_lengths (B,) ints: per-utterance mode -- item b decodes as if it were alone (its own keys, window,
         context scale and stop, as the reference at B = 1); the result then carries a fifth entry, each item's
-        number of decoder steps, and every frame past it is zero."""
+        number of decoder steps, and every frame past it is zero.
+        guide=(guide table int32 (B, T), steps int32[B]), both on the device (ops.guide_from_durations): a guided decode
+         -- every attention layer centres item b's window of step t on guide[b, min(t, steps[b] - 1)]
+        instead of on its previous argmax, and item b stops after steps[b] steps, whatever its done flag says (the
+        flags are returned as computed).  guide_window=(backward, ahead): that window instead of the layers' own.
+        Needs text_lengths and the fused step kernels; a decoder they do not take is refused."""
         if self.training:
             raise RuntimeError('incremental_forward only supports eval mode')
         return incremental_decode(self, encoder_out, text_lengths, text_positions, speaker_embed, initial_input,
-                                  test_inputs)
+                                  test_inputs, guide=guide, guide_window=guide_window)
 
     def _memory_projections(self, encoder_out, text_positions, speaker_embed):
         """What a decode reads of the encoder memory; none of it depends on the step -> the position-coded keys
@@ -538,7 +543,7 @@ class Decoder(nn.Module):
 
     # -- the same decode on the fused step kernels (csrc/decode_step.hip) -------------------------------
     def _incremental_fast(self, encoder_out, text_positions, speaker_embed=None, initial_input=None,
-                          test_inputs=None, key_len=None, stops=None):
+                          test_inputs=None, key_len=None, stops=None, guide=None, guide_window=None):
         """incremental_forward as a flat per-step program (decode_program.StepProgram): one conv-step entry per conv /
         projection layer and one attention-step entry per attention read (16 per step for the ljspeech preset instead
         of ~100 module calls), walked by ONE persistent launch for the whole utterance (or launch by launch):
@@ -563,10 +568,11 @@ class Decoder(nn.Module):
                 se = speaker_embed if speaker_embed.dim() == 2 else speaker_embed[:, 0, :]
                 return f.speaker_bias(se).contiguous()
 
-            self._step_entries(P, n_max, keys.size(1), cur_in, nxt_in, pe_all, memory[1], spk_of, key_len)
-            return None if P.refused else P.decode_for(self, cur_in, test_inputs, stops)
+            self._step_entries(P, n_max, keys.size(1), cur_in, nxt_in, pe_all, memory[1], spk_of, key_len,
+                               guide_window=guide_window)
+            return None if P.refused else P.decode_for(self, cur_in, test_inputs, stops, guide=guide)
 
-    def _step_entries(self, P, n, Tk, cur_in, nxt_in, pe_all, proj, spk_of, key_len, rows=False):
+    def _step_entries(self, P, n, Tk, cur_in, nxt_in, pe_all, proj, spk_of, key_len, rows=False, guide_window=None):
         """The step program (deepvoice3.py:397-461) appended to P, with its stacked outputs of n rows over Tk keys: the
         one walk over this decoder's layers, for the per-batch program, the slot program and the eligibility check
         alike.  A layer it has no entry for is refused (P.refuse) and ends the walk.  proj[idx]: attention layer
@@ -603,7 +609,7 @@ class Decoder(nn.Module):
             # ave_alignment = the FIRST layer's alignment * 2^(n-1)/n (the reference's `ave + ave`): P.align_scale
             ctx = P.attn_step(q, kp, vp, attention.window_backward, attention.window_ahead,
                               self.force_monotonic_attention[idx], attn_seq=P.aligns if P.n_attn == 0 else None,
-                              key_len=key_len, rows=rows)
+                              key_len=key_len, rows=rows, guide_window=guide_window)
             x = P.conv_step(attention.out_projection, ctx, ops.EPI_LINEAR, attention.out_projection.out_features,
                             r=xq, r2=residual, out_seq=st)
         pre = P.conv_step(self.last_conv, x, ops.EPI_LINEAR, D, y_act=nxt_in, out_seq=P.outs)

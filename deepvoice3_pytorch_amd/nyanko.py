@@ -220,7 +220,7 @@ class Decoder(nn.Module):
         return pe[:, None, :].expand(n, B, pe.size(1))
 
     def _incremental_fast(self, encoder_out, text_positions, initial_input=None, test_inputs=None, key_len=None,
-                          stops=None):
+                          stops=None, guide=None, guide_window=None):
         """incremental_forward (nyanko.py:250-338) as a flat per-step launch program (decode_program.StepProgram):
         27 conv-step launches + one attention-step launch per decoder step instead of ~150 module calls; the
         concat [R, Q] (nyanko.py:308) is one (B, 2D) buffer both producers write into."""
@@ -233,10 +233,10 @@ class Decoder(nn.Module):
             cur_in = (initial_input.reshape(B, F).clone().float() if initial_input is not None else P.buffer(B, F))
             nxt_in = cur_in if test_inputs is None else P.buffer(B, F)
             P.keep.extend([k, v, cur_in, nxt_in])
-            self._step_entries(P, n_max, keys.size(1), cur_in, nxt_in, k, v, key_len)
-            return None if P.refused else P.decode_for(self, cur_in, test_inputs, stops)
+            self._step_entries(P, n_max, keys.size(1), cur_in, nxt_in, k, v, key_len, guide_window=guide_window)
+            return None if P.refused else P.decode_for(self, cur_in, test_inputs, stops, guide=guide)
 
-    def _step_entries(self, P, n, Tk, cur_in, nxt_in, k, v, key_len, rows=False):
+    def _step_entries(self, P, n, Tk, cur_in, nxt_in, k, v, key_len, rows=False, guide_window=None):
         """The step program (nyanko.py:283-321) appended to P, with its stacked outputs of n rows over Tk keys: the one
         walk over this decoder's layers, for the per-batch program, the slot program and the eligibility check alike.
         A layer it has no entry for is refused (P.refuse) and ends the walk.  k, v: the projected keys / values
@@ -269,7 +269,7 @@ class Decoder(nn.Module):
             return
         q = P.conv_step(att.query_projection, xq, ops.EPI_LINEAR, att.query_projection.out_features)
         ctx = P.attn_step(q, k, v, att.window_backward, att.window_ahead, self.force_monotonic_attention,
-                          attn_seq=P.aligns, key_len=key_len, rows=rows)
+                          attn_seq=P.aligns, key_len=key_len, rows=rows, guide_window=guide_window)
         P.conv_step(att.out_projection, ctx, ops.EPI_LINEAR, att.out_projection.out_features, r=xq, y=cat[:, :D])
         x = run(self.audio_decoder_modules, cat, dict(out_seq=P.states))
         if x is None:
@@ -305,9 +305,11 @@ class Decoder(nn.Module):
         return P
 
     def incremental_forward(self, encoder_out, text_positions, initial_input=None, test_inputs=None,
-                            text_lengths=None):
-        """nyanko.py:250-338.  text_lengths: per-utterance mode, as deepvoice3.Decoder.incremental_forward."""
-        return incremental_decode(self, encoder_out, text_lengths, text_positions, initial_input, test_inputs)
+                            text_lengths=None, guide=None, guide_window=None):
+        """nyanko.py:250-338.  text_lengths: per-utterance mode; guide, guide_window: a guided decode; all as
+        deepvoice3.Decoder.incremental_forward."""
+        return incremental_decode(self, encoder_out, text_lengths, text_positions, initial_input, test_inputs,
+                                  guide=guide, guide_window=guide_window)
 
     def _incremental_modules(self, encoder_out, text_positions, initial_input=None, test_inputs=None, key_len=None,
                              stops=None):

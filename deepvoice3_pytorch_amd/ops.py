@@ -2415,6 +2415,85 @@ def attn_step_items(q, k, v, key_len, last_attended, t, win_back, win_ahead):
     return ctx, attn
 
 
+GUIDE_FLAGS = (("negative", "DV3_GUIDE_NEGATIVE"), ("empty", "DV3_GUIDE_EMPTY"), ("over", "DV3_GUIDE_OVER"))
+
+
+def guide_flag_names(flags):
+    """a flags word of guide_from_durations -> the names of its bits: "negative" (a duration below 0), "empty" (the
+    durations sum to 0), "over" (they sum to more than T)"""
+    return tuple(name for name, const in GUIDE_FLAGS if int(flags) & CONSTS[const])
+
+
+def guide_from_durations(durations, key_len, T, guide=None):
+    """The guide table of a guided decode (dv3_guide_from_durations_i32, include/dv3hip.h): durations
+    (B, Tk) int32 on the device (rows may be strided, the key axis dense), key_len int32[B]: item b's first key_len[b]
+    step counts are read; T: the rows of the table.  guide: an int32 (B, >= T) tensor to fill (a strided view with a
+    dense step axis), or None: a fresh (B, T) one.
+    -> (guide: the key every step t < T is centred on -- np.repeat(np.arange(key_len[b]), durations[b])[:T], continued
+    by its last entry --, steps int32[B] = min(sum, T), flags int32[B]: bits DV3_GUIDE_*, see guide_flag_names).
+    Runs on the current stream; no host synchronisation."""
+    _chk(durations, "durations", torch.int32)
+    _chk(key_len, "key_len", torch.int32)
+    if durations.dim() != 2 or (durations.size(1) > 1 and durations.stride(1) != 1):
+        raise RuntimeError("guide_from_durations: durations (B, Tk) with a dense key axis, got %s strides %s" % (
+            tuple(durations.shape), durations.stride()))
+    B, Tk = durations.shape
+    T = int(T)
+    key_len = _c(key_len)
+    if key_len.numel() != B:
+        raise RuntimeError("guide_from_durations: %d key lengths for %d items" % (key_len.numel(), B))
+    if guide is None:
+        guide = torch.empty(B, T, dtype=torch.int32, device=durations.device)
+    else:
+        _chk(guide, "guide", torch.int32)
+        if guide.dim() != 2 or guide.size(0) != B or guide.size(1) < T or (guide.size(1) > 1 and guide.stride(1) != 1):
+            raise RuntimeError("guide_from_durations: guide (B, >= T) with a dense step axis, got %s strides %s" % (
+                tuple(guide.shape), guide.stride()))
+    steps = torch.empty(B, dtype=torch.int32, device=durations.device)
+    flags = torch.empty(B, dtype=torch.int32, device=durations.device)
+    _lib.call("dv3_guide_from_durations_i32", durations.data_ptr(), durations.stride(0) if B > 1 else max(Tk, durations.stride(0)),
+              key_len.data_ptr(), B, Tk, T, guide.data_ptr(), guide.stride(0) if B > 1 else max(T, guide.stride(0)),
+              steps.data_ptr(), flags.data_ptr(), _stream())
+    return guide, steps, flags
+
+
+def attn_step_guided(q, k, v, key_len, guide, steps, t, win_back, win_ahead, last_attended=None, kv_tke=False):
+    """one guided per-utterance attention read at step t (dv3_attn_step_guided_f32, include/dv3hip.h): attn_step_items
+    with item b's window centred on guide[b, min(t, steps[b] - 1)] instead of on the previous argmax.  q (B, E, 1); k
+    and v (B, E, Tk), or (B, Tk, E) with kv_tke; key_len, steps int32[B]; guide int32 (B, >= t + 1), step axis dense; t:
+    the device int32[1] step counter or a host int.  last_attended (int32[2, B] or None) is handed to the kernel in the
+    descriptor, which neither reads nor writes it.  A host step is checked against the table's rows; with a device
+    counter the host cannot see the step, and the kernel clamps the row index into [0, guide_bs): a counter or a
+    steps[b] past the table reads the row's last entry (of its stride), never past it.
+    -> ctx (B, E, 1), attn (B, 1, Tk) with exact zeros outside the window"""
+    B, E, Tk = (k.size(0), k.size(2), k.size(1)) if kv_tke else k.shape
+    q, k, v = _c(q), _c(k), _c(v)
+    _chk(guide, "guide", torch.int32)
+    _chk(steps, "steps", torch.int32)
+    if guide.dim() != 2 or guide.size(0) != B or (guide.size(1) > 1 and guide.stride(1) != 1) or steps.numel() != B:
+        raise RuntimeError("attn_step_guided: guide (B, T) with a dense step axis and B steps, got %s strides %s, %d steps"
+                           % (tuple(guide.shape), guide.stride(), steps.numel()))
+    steps = _c(steps)
+    ctx = torch.empty(B, E, 1, dtype=torch.float32, device=q.device)
+    attn = torch.empty(B, 1, Tk, dtype=torch.float32, device=q.device)
+    d = STRUCTS["dv3_attn_step_desc"]()
+    d.q, d.q_bs, d.k, d.v, d.kv_tke = q.data_ptr(), E, k.data_ptr(), v.data_ptr(), int(bool(kv_tke))
+    d.last_attended = _ptr(last_attended)
+    d.win_back, d.win_ahead = win_back, win_ahead
+    if torch.is_tensor(t):
+        d.t = t.data_ptr()
+    else:
+        if not 0 <= int(t) < guide.size(1):
+            raise RuntimeError("attn_step_guided: step %d outside the guide's %d rows" % (int(t), guide.size(1)))
+        d.t_value = int(t)
+    d.ctx, d.ctx_bs, d.attn = ctx.data_ptr(), E, attn.data_ptr()
+    d.B, d.E, d.Tk = B, E, Tk
+    d.key_len = key_len.data_ptr()
+    _lib.call("dv3_attn_step_guided_f32", ctypes.byref(d), guide.data_ptr(), guide.stride(0) if B > 1 else guide.size(1),
+              steps.data_ptr(), _stream())
+    return ctx, attn
+
+
 # ----------------------------------------------------------------------------------------------
 # losses (fused value + gradient; train.py:537-601,704-740)
 # ----------------------------------------------------------------------------------------------

@@ -176,6 +176,38 @@ def token_spans(durations, seconds_per_step):
     return (upto - durations).to(torch.float64) * sps, upto.to(torch.float64) * sps
 
 
+def fit_durations(durations, total_steps, min_steps=0):
+    """One utterance's per-token step counts scaled to an exact total, on the host: the "exact length"
+    and "rate at the model" helper in front of tts_batch(durations=...).  durations: N non-negative ints (a list, an
+    array or a tensor); total_steps: what the result sums to; min_steps: what every token gets at least.
+    Token n's weight is w[n] = max(durations[n] - min_steps, 0); it gets min_steps + w[n] * R / sum(w) of the
+    R = total_steps - N * min_steps steps left, rounded by largest remainder in exact integer arithmetic (ties: the
+    earlier token).  So with min_steps = 0 a token of duration 0 stays 0; a token with the larger duration never gets
+    fewer steps; and total_steps = sum(durations) with every duration >= min_steps gives the durations back.  Weights
+    that are all zero under a min_steps > 0 share R evenly.  -> a list of N ints.
+    ValueError: a negative duration, min_steps < 0, total_steps < N * min_steps, or nothing to scale (all durations 0
+    at min_steps = 0 and total_steps > 0)."""
+    d = [int(v) for v in (durations.tolist() if hasattr(durations, "tolist") else durations)]
+    total, m, N = int(total_steps), int(min_steps), len(d)
+    if N == 0 or min(d) < 0 or m < 0:
+        raise ValueError("fit_durations: at least one duration, none negative, and min_steps >= 0 expected")
+    R = total - N * m
+    if R < 0:
+        raise ValueError("fit_durations: %d steps do not hold %d tokens of at least %d steps" % (total, N, m))
+    w = [max(v - m, 0) for v in d]
+    S = sum(w)
+    if S == 0:
+        if m == 0 and R > 0:
+            raise ValueError("fit_durations: all durations are 0: there is nothing to scale to %d steps" % total)
+        w, S = [1] * N, N
+    out = [m + v * R // S for v in w]
+    left = total - sum(out)                          # < N: one more step each, by remainder, the earlier token first
+    order = sorted(range(N), key=lambda n: (-(w[n] * R % S), n))
+    for n in order[:left]:
+        out[n] += 1
+    return out
+
+
 def search_path(alignments, steps, lengths, layout="btk", max_advance=1):
     """ops.monotonic_path with host step and key counts -> (summary rows, path, durations) on the device, no host read"""
     from . import ops
@@ -369,7 +401,8 @@ def _vocode(linear, audio_cfg, frame_lengths, settings):
 
 
 def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=False, stall_limit=None, timings=False,
-              timing_advance=1, rate=None, semitones=None, prosody=None, marks=None, mastering=None, from_mel=False):
+              timing_advance=1, rate=None, semitones=None, prosody=None, marks=None, mastering=None, durations=None,
+              guide_window=None, from_mel=False):
     """sequences: a list of int id sequences (one per utterance); speaker_ids: None or one id per utterance.
     -> a list of (mel (T_b, mel_dim), linear (T_b * upsampling, linear_dim), alignment (steps_b, Tt_b), wav (L_b,)),
     device tensors, each trimmed to its own utterance.  diagnostics: a fifth element, the utterance's alignment
@@ -394,9 +427,17 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=Fa
     to audio.num_samples(T'_b) samples under the plan's frame count; with timings every token's start and end go through
     audio.plan_map -- tokens in a slowed span get longer and a break is the gap between two tokens.  An utterance
     without an admissible path is vocoded without its marks under an audio.MarksNotApplied warning.  marks together with
-    rate, semitones or prosody are refused; marks that change nothing launch nothing."""
+    rate, semitones or prosody are refused; marks that change nothing launch nothing.
+    durations: decoder steps per token, one list of len(sequence) ints per utterance or an int32
+    (B, longest sequence) device tensor -- the decode is guided (synthesize_batch(durations=...)): utterance b has
+    exactly sum(durations[b]) decoder steps and every step attends around the token that owns it; guide_window
+    (backward, ahead) replaces the attention layers' own window.  Not together with stall_limit (the stop is
+    prescribed).  Everything else -- diagnostics, timings, from_mel, rate / semitones / marks, mastering -- works on
+    what the guided decode stored."""
     if len(sequences) == 0:
         return []
+    if durations is not None and stall_limit is not None:
+        raise ValueError("tts_batch: durations prescribe every utterance's stop; stall_limit cannot be combined with them")
     audio.check_mastering(mastering, "tts_batch")
     marks = utterance_marks(marks, rate, semitones, prosody, len(sequences), "tts_batch")
     pros = utterance_prosody(rate, semitones, prosody, len(sequences), "tts_batch")
@@ -417,8 +458,9 @@ def tts_batch(model, sequences, speaker_ids=None, audio_cfg=None, diagnostics=Fa
     if speaker_ids is not None:
         spk = torch.as_tensor(speaker_ids, dtype=torch.long).reshape(-1).to(dev)
     model.eval()
+    guided = {} if durations is None and guide_window is None else dict(durations=durations, guide_window=guide_window)
     mel, linear, alignments, _, frames = model.synthesize_batch(text, lengths, spk, stall_limit=stall_limit,
-                                                                postnet=mel_opt is None)
+                                                                postnet=mel_opt is None, **guided)
     up = linear.size(1) // mel.size(1) if mel_opt is None else postnet_upsampling(model)
     steps_per_frame = mel.size(1) // alignments.size(1)        # r
     with torch.no_grad():
@@ -699,7 +741,7 @@ class RollingSynthesizer(object):
 
 def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, audio_cfg=None, chunk=8,
                max_decoder_steps=None, diagnostics=False, stall_limit=None, timings=False, timing_advance=1,
-               rate=None, semitones=None, prosody=None, marks=None, mastering=None, from_mel=False):
+               rate=None, semitones=None, prosody=None, marks=None, mastering=None, durations=None, from_mel=False):
     """Rolling-admission counterpart of tts_batch, as a generator: sequences (any iterable of id lists; speaker_ids an
     iterable alongside, or None; max_decoder_steps None, one cap, or an iterable of per-utterance caps) are submitted
     in order as slots free -- at most `slots` are queued ahead -- and every utterance is yielded when it retires, in
@@ -710,7 +752,12 @@ def tts_stream(model, sequences, speaker_ids=None, slots=64, max_text_len=None, 
     post-net is not run); rate, semitones: None, one number, or an iterable of per-utterance values alongside
     `sequences`; prosody: an audio.Prosody carrying the envelope settings (RollingSynthesizer.submit takes all three);
     mastering: an audio.Mastering, as tts_batch takes it; marks: None or an iterable alongside `sequences` of one
-    audio.ProsodyMarks in tokens (or None) per utterance, each handed to its submit."""
+    audio.ProsodyMarks in tokens (or None) per utterance, each handed to its submit.  durations: refused -- a guided
+    decode (tts_batch(durations=...)) does not run in slot mode."""
+    if durations is not None:
+        raise ValueError("tts_stream: durations are not taken: rolling admission decodes in slot mode, where every slot "
+                         "runs at its own step, and the guided attention kernel has one step axis for the batch; use "
+                         "tts_batch(durations=...)")
     if max_text_len is None:
         sequences = [list(s) for s in sequences]
         if not sequences:

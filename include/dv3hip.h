@@ -999,6 +999,40 @@ int dv3_decode_program_launch(const dv3_decode_program* prog, void* stream);
  * the decoder input (the x of entry 0, Cin floats).  At most 128 rings + windows per program. */
 int dv3_decode_slots_reset(const dv3_decode_program* prog, const int32_t* slots, int32_t n, void* stream);
 
+/* Guided decode (entry points added under ABI 50, no struct changes): the attention window's centre
+ * comes from a table instead of from the previous step's argmax.
+ * dv3_attn_step_guided_f32 -- dv3_attn_step_f32 in per-utterance mode, except that item b at step t centres its window
+ *   on  la = guide[b * guide_bs + min(t, steps[b] - 1)]  (guide: DEVICE int32 rows of stride guide_bs, steps: DEVICE
+ *   int32[B]; the row index is clamped into [0, guide_bs) and la into the item's own keys [0, key_len[b])): the keys
+ *   [la - win_back, la + win_ahead) clamped by the same two-sided rule (deepvoice3.py:150-156), with the descriptor's
+ *   win_back / win_ahead.  last_attended is neither read nor written (it may be NULL) and no argmax is taken; scores,
+ *   softmax, stored rows (attn, attn_seq), context and the key_len handling are those of dv3_attn_step_f32.
+ *   Requires key_len != NULL and t_off == NULL (slot mode is refused: a slot's step is t - t_off[b], the table has one
+ *   step axis for the batch), win_back >= 0, win_ahead >= 1, and -- what the host can check without reading the
+ *   device -- guide_bs >= t_value + 1 when the step travels in t_value (guide_bs >= 1 with a device counter).
+ * dv3_decode_program_launch_guided -- dv3_decode_program_launch with the guided kernel for EVERY attention entry (all
+ *   share the one table); conv entries are launched as they are.  The same requirements for every attention entry,
+ *   no conv entry in slot mode, and guide_bs >= t0 + n_steps.  dv3_decode_program_run has no guided form.
+ * dv3_guide_from_durations_i32 -- the table from per-key step counts.  dur: DEVICE int32 rows of stride dur_bs >= Tk,
+ *   item b's first key_len[b] entries (clamped to [1, Tk]) are read.  With cum the inclusive running sum, key n owns
+ *   steps [cum[n-1], cum[n]); a key of duration 0 owns none.  steps[b] = min(sum, T); guide[b * guide_bs + t] for
+ *   t < T: the owner of step t, and for t >= steps[b] the last key that owns a step -- bit for bit
+ *   np.repeat(np.arange(key_len), dur)[:T], continued by its last entry.  flags[b] is a bit set of DV3_GUIDE_*:
+ *   NEGATIVE a duration below 0 (counted as 0), EMPTY sum 0 (steps = 0, a row of zeros), OVER sum above T (cut at T).
+ *   One wave per item, integers only.  Refused: a null pointer, B outside [1, 65535], Tk outside [1, DV3_GUIDE_MAX_TK],
+ *   T outside [1, DV3_GUIDE_MAX_T], dur_bs < Tk, guide_bs < T. */
+#define DV3_GUIDE_NEGATIVE 1
+#define DV3_GUIDE_EMPTY 2
+#define DV3_GUIDE_OVER 4
+#define DV3_GUIDE_MAX_TK 2048
+#define DV3_GUIDE_MAX_T 1048576
+int dv3_attn_step_guided_f32(const dv3_attn_step_desc* d, const int32_t* guide, int64_t guide_bs,
+                             const int32_t* steps, void* stream);
+int dv3_decode_program_launch_guided(const dv3_decode_program* prog, const int32_t* guide, int64_t guide_bs,
+                                     const int32_t* steps, void* stream);
+int dv3_guide_from_durations_i32(const int32_t* dur, int64_t dur_bs, const int32_t* key_len, int32_t B, int32_t Tk,
+                                 int32_t T, int32_t* guide, int64_t guide_bs, int32_t* steps, int32_t* flags, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Audio inverse (audio.py:37-43, synthesis.py:64-71): linear spectrogram -> waveform on the
  * device.  The reference calls the third-party `lws` package for phase reconstruction (not
