@@ -47,7 +47,10 @@ synthesis.join_utterances builds a document of several utterances on them.  Off 
 Loudness (csrc/loudness.hip): Mastering(level="lufs") levels to a LUFS target under a sample-peak or
 true-peak ceiling.  wave_loudness measures ITU-R BS.1770 integrated loudness and the 4x true peak of spans or groups of
 spans on the device (k_weighting and true_peak_table make its float64 coefficients and its interpolator on the host),
-loudness_gains turns its rows into gains.
+loudness_gains turns its rows into gains.  Mastering(limiter=Limiter()) (csrc/limiter.hip) holds the
+ceiling with a look-ahead limiter instead of the static gain, so that the target is met where one loud syllable sets
+the peak: limit_spans is the kernel's wrapper, master_source what master_items and join_utterances take their source
+and gains from.
 """
 import numpy as np
 import torch
@@ -1509,6 +1512,38 @@ def _db(v, what, lo, hi):
     return float(v)
 
 
+class Limiter(object):
+    """A look-ahead peak limiter for Mastering(limiter=) (limit_spans; csrc/limiter.hip): the gain is
+    turned down lookahead_ms before a peak that would pass the ceiling, over a box of that length, held while the peak
+    lasts, and released exponentially with the time constant release_ms; passes: how often the loudness target is
+    re-aimed from the limited result (1 .. 4; more than one needs level="lufs").  lookahead_ms >= 0, release_ms > 0.
+    The defaults are starting points, not measurements: nothing here was heard on a trained voice.
+    Refused by value (ValueError naming it)."""
+
+    def __init__(self, lookahead_ms=1.5, release_ms=50.0, passes=1):
+        num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and \
+            np.isfinite(float(v))
+        if not num(lookahead_ms) or float(lookahead_ms) < 0.0:
+            raise ValueError("Limiter: lookahead_ms=%r must be a finite number >= 0" % (lookahead_ms,))
+        if not num(release_ms) or float(release_ms) <= 0.0:
+            raise ValueError("Limiter: release_ms=%r must be a finite number > 0" % (release_ms,))
+        if isinstance(passes, bool) or not isinstance(passes, (int, np.integer)) or not 1 <= int(passes) <= 4:
+            raise ValueError("Limiter: passes=%r must be an integer in [1, 4]" % (passes,))
+        self.lookahead_ms, self.release_ms, self.passes = float(lookahead_ms), float(release_ms), int(passes)
+
+    def lookahead(self, sample_rate):
+        """A = floor(lookahead_ms * sample_rate / 1000 + 0.5) samples; ValueError above DV3_LIMIT_MAX_LOOKAHEAD"""
+        A = int(np.floor(self.lookahead_ms * float(sample_rate) / 1000.0 + 0.5))
+        if A > _lib.CONSTS["DV3_LIMIT_MAX_LOOKAHEAD"]:
+            raise ValueError("Limiter: lookahead_ms=%r is %d samples at %r Hz, at most %d" % (
+                self.lookahead_ms, A, sample_rate, _lib.CONSTS["DV3_LIMIT_MAX_LOOKAHEAD"]))
+        return A
+
+    def rho(self, sample_rate):
+        """the release factor per sample, exp(-1000 / (release_ms * sample_rate))"""
+        return float(np.exp(-1000.0 / (self.release_ms * float(sample_rate))))
+
+
 class Mastering(object):
     """How synthesised waveforms become deliverable audio (master_items, synthesis.join_utterances).
     level: None (gain 1), "peak" (the largest |x| goes to target_db dBFS), "rms" (the RMS goes to target_db dBFS, but
@@ -1521,11 +1556,15 @@ class Mastering(object):
     "lufs" (EBU R 128); max_gain_db caps the gain of "peak", "rms" and "lufs" (a near-silent item is not blown up); fade_ms: the raised-cosine fade
     at a document's joins and edges (join_utterances; master_items fades nothing); dither, seed: TPDF dither of +-1 LSB
     before the int16 rounding, a function of (seed, sample index); dtype: "int16" or "float32".
+    limiter: None, or a Limiter -- with level None, "rms" or "lufs" the static gain no longer gives way to
+    the ceiling (it is min(target gain, max_gain), or 1): a look-ahead limiter holds every utterance under ceiling_db
+    instead, with the sample-peak or, under true_peak=True, the true-peak detector; "peak" (its target is itself a
+    peak) and "reference" take none, and Limiter(passes > 1) re-aims a loudness target, so it needs "lufs".
     The defaults are starting points, not measurements: nothing here was heard on a trained voice.
     Refused by value (ValueError naming it)."""
 
     def __init__(self, level=None, scope="item", target_db=None, ceiling_db=-1.0, max_gain_db=30.0, fade_ms=5.0,
-                 dither=False, seed=0, dtype="int16", true_peak=False):
+                 dither=False, seed=0, dtype="int16", true_peak=False, limiter=None):
         if level is not None and level != "lufs" and level not in _GAIN_POLICIES:
             raise ValueError("Mastering: level=%r must be None, 'peak', 'rms', 'lufs' or 'reference'" % (level,))
         if not isinstance(true_peak, (bool, np.bool_)):
@@ -1552,6 +1591,16 @@ class Mastering(object):
             raise ValueError("Mastering: dither=True needs dtype='int16'")
         if level == "reference" and (dtype != "int16" or self.dither):
             raise ValueError("Mastering: level='reference' is the reference's save_wav: dtype='int16' and no dither")
+        if limiter is not None:
+            if not isinstance(limiter, Limiter):
+                raise ValueError("Mastering: limiter=%r must be None or an audio.Limiter" % (limiter,))
+            if level in ("peak", "reference"):
+                raise ValueError("Mastering: limiter= goes with level None, 'rms' or 'lufs', not %r (a peak target leaves "
+                                 "a limiter nothing to hold; 'reference' is the reference's save_wav)" % (level,))
+            if limiter.passes > 1 and level != "lufs":
+                raise ValueError("Mastering: Limiter(passes=%d) re-aims a loudness target: it needs level='lufs'"
+                                 % limiter.passes)
+        self.limiter = limiter
 
     def mode(self):
         """the DV3_MASTER_* output mode"""
@@ -1576,11 +1625,16 @@ def check_mastering(mastering, what):
     return mastering
 
 
-def wave_gains(levels, lengths, mastering, groups=None):
+_NO_CEILING = 1e30      # a finite linear ceiling that cannot bind: the gain entries refuse an infinite one
+
+
+def wave_gains(levels, lengths, mastering, groups=None, ceiling=None):
     """Levels -> the per-item values the master launch takes, float32 (B,) on the device: levels (B, 5) from wave_levels,
     lengths int64 (B,) on the device, mastering.level the policy ("peak", "rms": a multiplier; "reference": the divisor
     max(0.01, peak)), groups: None (mastering.scope decides: every item alone, or all of them one group) or the group
-    offsets, ascending host ints from 0 to B.  fp64 on the device, rounded once (include/dv3hip.h: dv3_wave_gains_f32)."""
+    offsets, ascending host ints from 0 to B.  ceiling: None (mastering.ceiling_db) or a LINEAR ceiling in its place (a
+    limiter's pre-gain takes one that cannot bind).  fp64 on the device, rounded once (include/dv3hip.h:
+    dv3_wave_gains_f32)."""
     if mastering.level is None:
         raise ValueError("wave_gains: mastering.level is None (the gain is 1: nothing to compute)")
     if mastering.level == "lufs":
@@ -1600,8 +1654,9 @@ def wave_gains(levels, lengths, mastering, groups=None):
     gain = torch.empty(B, dtype=torch.float32, device=dev)
     lin = lambda db: 10.0 ** (db / 20.0)
     _lib.call("dv3_wave_gains_f32", _c(levels).data_ptr(), _c(lengths).data_ptr(), goff_d.data_ptr(), B, goff.size - 1,
-              _lib.CONSTS[_GAIN_POLICIES[mastering.level]], lin(mastering.target_db), lin(mastering.ceiling_db),
-              lin(mastering.max_gain_db), gain.data_ptr(), _stream())
+              _lib.CONSTS[_GAIN_POLICIES[mastering.level]], lin(mastering.target_db),
+              lin(mastering.ceiling_db) if ceiling is None else float(ceiling), lin(mastering.max_gain_db), gain.data_ptr(),
+              _stream())
     return gain
 
 
@@ -1723,10 +1778,12 @@ def wave_loudness(wav_flat, starts, lengths, sample_rate, groups=None, true_peak
     return rows
 
 
-def loudness_gains(rows, groups, mastering):
+def loudness_gains(rows, groups, mastering, ceiling=None, max_gain=None):
     """wave_loudness' rows -> float32 (B,) gains on the device, B = groups[-1]: group g (items groups[g] ..
     groups[g + 1] - 1) gets g = min(10^((target_db - lufs) / 20), ceiling / peak, max_gain), 1 when it is silent; float64
-    on the device, rounded once (include/dv3hip.h: dv3_loudness_gains_f32).  mastering: a Mastering("lufs")."""
+    on the device, rounded once (include/dv3hip.h: dv3_loudness_gains_f32).  mastering: a Mastering("lufs"); ceiling,
+    max_gain: None (the Mastering's) or LINEAR values in their place (a limiter's pre-gain takes a ceiling that cannot
+    bind)."""
     if not isinstance(mastering, Mastering) or mastering.level != "lufs":
         raise ValueError("loudness_gains: a Mastering with level='lufs' expected")
     G = int(rows.shape[0]) if torch.is_tensor(rows) and rows.dim() == 2 else -1
@@ -1741,22 +1798,104 @@ def loudness_gains(rows, groups, mastering):
     gain = torch.empty(B, dtype=torch.float32, device=dev)
     lin = lambda db: 10.0 ** (db / 20.0)
     _lib.call("dv3_loudness_gains_f32", _c(rows).data_ptr(), goff_d.data_ptr(), B, G, float(mastering.target_db),
-              lin(mastering.ceiling_db), lin(mastering.max_gain_db), gain.data_ptr(), _stream())
+              lin(mastering.ceiling_db) if ceiling is None else float(ceiling),
+              lin(mastering.max_gain_db) if max_gain is None else float(max_gain), gain.data_ptr(), _stream())
     return gain
 
 
-def span_gains(wav_flat, starts_d, lengths_d, max_len, mastering, sample_rate=None):
+def span_gains(wav_flat, starts_d, lengths_d, max_len, mastering, sample_rate=None, ceiling=None):
     """the gains of B spans (int64 device tensors and a bound on the lengths) under a Mastering with a level: wave_levels
-    and wave_gains, or under "lufs" wave_levels (the ceiling's sample peak), wave_loudness and loudness_gains"""
+    and wave_gains, or under "lufs" wave_levels (the ceiling's sample peak), wave_loudness and loudness_gains; ceiling:
+    None, or the LINEAR ceiling wave_gains / loudness_gains take in the Mastering's place"""
     if mastering.level != "lufs":
-        return wave_gains(wave_levels(wav_flat, starts_d, lengths_d, max_len), lengths_d, mastering)
+        return wave_gains(wave_levels(wav_flat, starts_d, lengths_d, max_len), lengths_d, mastering, ceiling=ceiling)
     levels = None if mastering.true_peak else wave_levels(wav_flat, starts_d, lengths_d, max_len)
     if sample_rate is None:
         raise ValueError("Mastering: level='lufs' needs a sample rate")
     B = int(starts_d.numel())
     groups = list(range(B + 1)) if mastering.scope == "item" else [0, B]
     rows = wave_loudness(wav_flat, starts_d, lengths_d, sample_rate, groups, mastering.true_peak, max_len, levels)
-    return loudness_gains(rows, groups, mastering)
+    return loudness_gains(rows, groups, mastering, ceiling=ceiling)
+
+
+# ---- look-ahead peak limiter (csrc/limiter.hip; DESIGN.md 3.6n) -----------------------------------------------------------
+LIMITER_COLUMNS = ("gain_min", "over_samples")
+
+
+def rho_powers(rho):
+    """rho^(2^i), i = 0 .. log2(DV3_LIMIT_TILE), each one float64 pow (repeated squaring would double the relative error
+    at every step): what dv3_wave_limit_f32 takes"""
+    return np.array([float(rho) ** (2 ** i) for i in range(_lib.CONSTS["DV3_LIMIT_RHO_POWERS"])], dtype=np.float64)
+
+
+def limit_spans(wav_flat, starts_d, lengths_d, max_len, gain, ceiling, lookahead, rho, true_peak=False):
+    """The look-ahead limiter over B spans of a flat float32 device tensor (spans as wave_levels takes them: host
+    integers, or int64 device tensors with max_len): span b times gain[b] (a float32 (B,) device tensor, or one number),
+    held under `ceiling` (LINEAR) by a gain that turns down `lookahead` samples ahead of a peak and releases by the
+    factor `rho` per sample; true_peak: the detector also reads the 4x interpolants (true_peak_table).  -> (a float32
+    buffer of wav_flat's layout: the span samples limited, zeros elsewhere; float64 (B, 2) on the device, columns
+    LIMITER_COLUMNS: the smallest gain the limiter applied and the number of samples that demanded a reduction).
+    include/dv3hip.h (dv3_wave_limit_f32) states every step; tests/limiter_ref.py restates it.  No host read."""
+    import ctypes
+    wav_flat = _c(_chk(wav_flat, "wav_flat")).reshape(-1)
+    starts_d, lengths_d, B, max_len = _span_tables(wav_flat, starts_d, lengths_d, max_len, "limit_spans")
+    if not 1 <= B <= 65535:
+        raise ValueError("limit_spans: %d spans, at most 65535 per call" % B)
+    if max_len > 2 ** 30:
+        raise ValueError("limit_spans: max_len=%d, at most 2^30 samples per span" % max_len)
+    dev = wav_flat.device
+    if not torch.is_tensor(gain):
+        gain = torch.full((B,), float(gain), dtype=torch.float32, device=dev)
+    if gain.numel() != B or gain.dtype != torch.float32 or not gain.is_cuda:
+        raise ValueError("limit_spans: gain must be a number or a float32 device tensor of %d values" % B)
+    T = _lib.CONSTS["DV3_LIMIT_TILE"]
+    scratch = torch.empty(max(B * -(-max_len // T) * (T + 3), 1), dtype=torch.float64, device=dev)
+    out = torch.zeros_like(wav_flat)
+    report = torch.empty((B, len(LIMITER_COLUMNS)), dtype=torch.float64, device=dev)
+    powers = (ctypes.c_double * _lib.CONSTS["DV3_LIMIT_RHO_POWERS"])(*rho_powers(rho).tolist())
+    table = (ctypes.c_float * 36)(*true_peak_table().reshape(-1).tolist()) if true_peak else None
+    _lib.call("dv3_wave_limit_f32", wav_flat.data_ptr(), starts_d.data_ptr(), lengths_d.data_ptr(), B, max_len,
+              _c(gain).data_ptr(), float(ceiling), int(lookahead), ctypes.addressof(powers),
+              ctypes.addressof(table) if true_peak else None, scratch.data_ptr(), out.data_ptr(), report.data_ptr(),
+              _stream())
+    return out, report
+
+
+def master_source(wav_flat, starts_d, lengths_d, max_len, mastering, sample_rate=None):
+    """What the master launch reads under a Mastering: -> (source buffer, per-span gains or None).  Without a limiter
+    that is (wav_flat, span_gains(...)) -- None when the level is None.  With mastering.limiter the pre-gain drops the
+    ceiling term (min(target gain, max_gain), or 1), limit_spans holds the spans under the ceiling, and the limited
+    buffer comes back; Limiter(passes=P): P - 1 times the limited spans are measured by wave_loudness with the same
+    groups, each group's pre-gain is multiplied by 10^((target - L) / 20) (capped at max_gain; a silent group's stays) and
+    the ORIGINAL samples are limited again.  Under the true-peak detector the gain varies across an interpolant's 12 taps,
+    so the limited buffer's true peak is measured once more and the gains are the trim min(1, ceiling / peak); under the
+    sample-peak one they are None.  No host read."""
+    lim = mastering.limiter
+    if lim is None:
+        if mastering.level is None:
+            return wav_flat, None
+        return wav_flat, span_gains(wav_flat, starts_d, lengths_d, max_len, mastering, sample_rate)
+    if sample_rate is None:
+        raise ValueError("Mastering: limiter= needs a sample rate (its look-ahead and release are times)")
+    A, rho = lim.lookahead(sample_rate), lim.rho(sample_rate)
+    lin = lambda db: 10.0 ** (db / 20.0)
+    c, cap = lin(mastering.ceiling_db), lin(mastering.max_gain_db)
+    B = int(starts_d.numel())
+    if mastering.level is None:
+        pre = torch.ones(B, dtype=torch.float32, device=wav_flat.device)
+    else:
+        pre = span_gains(wav_flat, starts_d, lengths_d, max_len, mastering, sample_rate, ceiling=_NO_CEILING)
+    out, _ = limit_spans(wav_flat, starts_d, lengths_d, max_len, pre, c, A, rho, mastering.true_peak)
+    groups = list(range(B + 1)) if mastering.scope == "item" else [0, B]
+    for _ in range(lim.passes - 1):
+        rows = wave_loudness(out, starts_d, lengths_d, sample_rate, groups, False, max_len)
+        step = loudness_gains(rows, groups, mastering, ceiling=_NO_CEILING, max_gain=_NO_CEILING)
+        pre = torch.clamp(pre * step, max=cap)
+        out, _ = limit_spans(wav_flat, starts_d, lengths_d, max_len, pre, c, A, rho, mastering.true_peak)
+    if not mastering.true_peak:
+        return out, None
+    peak = wave_loudness(out, starts_d, lengths_d, sample_rate, None, True, max_len)[:, LOUDNESS_COLUMNS.index("true_peak")]
+    return out, torch.clamp(c / peak, max=1.0).to(torch.float32)
 
 
 _FADE_CACHE = {}
@@ -1845,7 +1984,7 @@ def master_items(wavs, samples, mastering, sample_rate=None):
     them (a view of a buffer whose rows are padded to 16 bytes).  Levels, gains (they stay on the device) and one master
     launch; with dither one master launch per item, each counting its samples from 0, so that an item's bits do not
     depend on what shares its batch.  No fades: fade_ms is for join_utterances.  sample_rate: needed by level "lufs"
-    alone (span_gains)."""
+    and by a limiter (master_source, which gives the launch its source and gains)."""
     mastering = check_mastering(mastering, "master_items")
     if mastering is None:
         raise ValueError("master_items: mastering is None")
@@ -1861,9 +2000,11 @@ def master_items(wavs, samples, mastering, sample_rate=None):
     gain = None
     if mastering.level == "lufs" and sample_rate is None:
         raise ValueError("master_items: level='lufs' needs sample_rate= (the loudness measure is defined per sample rate)")
-    if mastering.level is not None:
+    if mastering.limiter is not None and sample_rate is None:
+        raise ValueError("master_items: limiter= needs sample_rate= (its look-ahead and release are times)")
+    if mastering.level is not None or mastering.limiter is not None:
         starts_d, lengths_d, _, max_len = _span_tables(flat, starts, samples, None, "master_items")
-        gain = span_gains(flat, starts_d, lengths_d, max_len, mastering, sample_rate)
+        flat, gain = master_source(flat, starts_d, lengths_d, max_len, mastering, sample_rate)
     Lp = -(-L // 8) * 8
     kw = dict(dtype=mastering.dtype, reference=mastering.level == "reference", seed=mastering.seed)
     if not mastering.dither:

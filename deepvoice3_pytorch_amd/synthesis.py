@@ -71,7 +71,8 @@ device waveforms into one document -- silence trimmed, levelled, sentences cross
 quantised, in one launch after one host read --, and tts_document speaks a text longer than one utterance, sentence by
 sentence, with every token's span on the document's time axis.  Mastering("lufs") levels to a BS.1770 loudness target
 (DESIGN.md 3.6l): per utterance, or with scope="document" from the pooled blocks of all sentences; the entry points
-pass their audio_cfg.sample_rate.
+pass their audio_cfg.sample_rate.  Mastering(..., limiter=audio.Limiter()) holds the ceiling with a look-ahead limiter
+instead of the static gain: every utterance is limited alone, before any join.
 
     wav, spans = synthesis.tts_document(model, [seq0, seq1, ...], mastering=audio.Mastering("rms", "document"))
     audio.save_wav("document.wav", wav, 22050)
@@ -871,10 +872,10 @@ def join_utterances(wavs, sample_rate, pauses=0.25, trim_db=40.0, mastering=None
     F = mastering.fade_samples(sample_rate)
     table, N = plan_document(lens, sample_rate, pauses, F, starts=src, lead=lead, tail=tail)
     gain = None
-    if mastering.level is not None:
+    if mastering.level is not None or mastering.limiter is not None:
         sl = torch.from_numpy(np.concatenate([src, lens])).to(flat.device, non_blocking=True)
         S = src.size
-        gain = audio.span_gains(flat, sl[:S], sl[S:], int(lens.max()), mastering, sample_rate)
+        flat, gain = audio.master_source(flat, sl[:S], sl[S:], int(lens.max()), mastering, sample_rate)
     doc = audio.wave_master(flat, table["src"], table["len"], table["dst"], gain, table["flags"], N, F, mastering.dtype,
                             mastering.level == "reference", mastering.dither, mastering.seed)
     sr = float(sample_rate)

@@ -1852,6 +1852,65 @@ int dv3_loudness_gate_f64(const double* energy, const int64_t* lengths, const in
 int dv3_loudness_gains_f32(const double* rows, const int32_t* goff, int32_t B, int32_t G, double target_lufs,
                            double ceiling, double max_gain, float* gain, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Look-ahead peak limiter: a time-varying gain that holds every span under a ceiling, so that a loudness target is met
+ * where one static gain would give way to the loudest syllable (audio.limit_spans, audio.Limiter,
+ * Mastering(limiter=); csrc/limiter.hip).  The reference has no counterpart.  One new entry point with
+ * plain arguments, no struct added or changed, so the version stays 50.
+ *
+ * dv3_wave_limit_f32: x, starts, lengths, B, max_len as dv3_wave_loudness_f64 takes them (span b is x[starts[b] ..
+ * starts[b] + L), L = lengths[b] clamped into [0, max_len]; max_len <= 2^30).  Per span: the pre-gain g = gain[b] (device
+ * float[B]), the ceiling c > 0 (LINEAR), the look-ahead A samples, 0 <= A <= DV3_LIMIT_MAX_LOOKAHEAD, the release factor
+ * rho in [0, 1), and the detector: the sample peak (peak_table NULL) or the true peak (peak_table: a HOST array of 3 x 12
+ * floats, audio.true_peak_table(), as dv3_wave_loudness_f64 takes it).  Everything between the first and the last line is
+ * fp64:
+ *     y[n]  = fmul(g, x[n])                                 fp32 product, rounded once, then widened; y is 0 outside [0, L)
+ *     e[n]  = |y[n]|                                        sample-peak detector
+ *             true-peak detector: i_p[m] = sum over j = 0 .. 11 of table[p - 1][j] y[m + 6 - j], p = 1 .. 3, m = -1 .. L - 1
+ *             (the interpolant at m + p / 4; summed from 0 in ascending j, each step one fma),
+ *             e[n] = max(|y[n]|, max_p |i_p[n]|, max_p |i_p[n - 1]|)     an interpolant counts for both of its neighbours
+ *     dr[n] = e[n] > c ? 1 - c / e[n] : 0                   the gain reduction this sample demands
+ *     dm[n] = max over j in [n, min(n + A, L - 1)] of dr[j] look-ahead
+ *     dq[n] = max(dm[n], rho dq[n - 1]),  dq[-1] = 0        instant hold, exponential release
+ *     ds[n] = (1 / (A + 1)) * sum over k in [n - A, n] of dq[max(k, 0)]       attack: a box of the look-ahead's length
+ *     s[n]  = 1 - ds[n]
+ *     out[n] = fmul(y[n], (float) s[n])                     fp32, rounded once
+ * Consequences.  ds[n] >= dr[n]: every dq[k] of the box has n inside its look-ahead window (k <= n <= k + A), and the
+ * clamp max(k, 0) keeps that true for the first A samples; so under the sample-peak detector |out[n]| <= c (1 + 2^-22),
+ * one rounding of s and one of the product.  Under the true-peak detector the gain varies across an interpolant's 12
+ * taps, so the true peak of out may pass c by a little: measure it (dv3_wave_loudness_f64) and trim.  Where nothing
+ * exceeds c every table is 0, s is exactly 1 and out[n] = fmul(g, x[n]), the bits dv3_wave_master_f32 makes from x and g.
+ * Nothing depends on B, on where the span lies in the flat buffer (any 4-byte alignment) or on the launch geometry.
+ *
+ * How the device evaluates it.  The span is cut into tiles of DV3_LIMIT_TILE samples from its own first sample.  The
+ * release is evaluated as dq[n] = max over k <= n of dm[k] rho^(n - k): the same recursion, associative, different only
+ * in rounding.  rho_pow (a HOST array of DV3_LIMIT_RHO_POWERS doubles) holds rho^(2^i), i = 0 .. log2(DV3_LIMIT_TILE), made
+ * by the caller in fp64, each one pow rounded once; rho_pow[0] is rho.  Pass A runs the recursion inside a tile from a zero
+ * state (steps v[n] = max(v[n], v[n - d] rho^d), d = 1, 2, 4, ..), pass B carries the tiles' end values along the span,
+ * carry' = max(end, carry rho^T), and pass C takes dq[n] = max(dq_local[n], carry rho^(i + 1)), i = n mod T, rho^(i + 1)
+ * the product of the powers of i + 1's binary digits in ascending order.  The box sum adds the sums of the power-of-two
+ * windows that W = A + 1 decomposes into (lowest digit first, the window ending at n; each window's sum built by
+ * doubling, S_2d[n] = S_d[n] + S_d[n - d]): non-negative terms only, nothing cancels, and A = 0 gives ds = dq exactly.
+ * The fp64 tables hold to 1e-12 absolute against the sequential form; tests/limiter_ref.py restates both.
+ *
+ * report double[B][DV3_LIMIT_COLUMNS]: (gain_min, over_samples) = (the smallest s[n] of the span, the number of samples
+ * with dr[n] > 0); (1, 0) for an empty span.  out float[] of x's layout: only span samples are written.  scratch:
+ * B * ceil(max_len / DV3_LIMIT_TILE) * (DV3_LIMIT_TILE + 3) doubles the call may overwrite (NULL allowed when max_len is
+ * 0).  Four launches; no atomics; every read of x is guarded by the span, whatever the tables hold; two calls give
+ * bit-equal output.  Refused (DV3_EINVAL, "wave_limit:", nothing launched): a null x, starts, lengths, gain, rho_pow, out
+ * or report; a null scratch with max_len > 0; B outside [1, 65535]; max_len outside [0, 2^30]; lookahead outside
+ * [0, DV3_LIMIT_MAX_LOOKAHEAD]; a ceiling that is no positive finite number; rho_pow[0] outside [0, 1), or a later entry
+ * that is negative, not a number or above its predecessor; out == x; scratch, report, starts or lengths not 8-byte
+ * aligned, x, out or gain not 4-byte aligned; an entry of peak_table that is not finite.
+ * ------------------------------------------------------------------------------------ */
+#define DV3_LIMIT_TILE 1024
+#define DV3_LIMIT_MAX_LOOKAHEAD 512
+#define DV3_LIMIT_RHO_POWERS 11
+#define DV3_LIMIT_COLUMNS 2
+int dv3_wave_limit_f32(const float* x, const int64_t* starts, const int64_t* lengths, int32_t B, int64_t max_len,
+                       const float* gain, double ceiling, int32_t lookahead, const double* rho_pow,
+                       const float* peak_table /* or NULL */, double* scratch, float* out, double* report, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
